@@ -11,10 +11,13 @@ plonk/prover.py:89,113,136), inputs already resident in HBM:
 
 `value` = commits/sec = polynomials committed per second over the whole job (all ranks).  N > 1: one
 process per GPU, every rank commits its own polynomials against a replicated SRS -- the path shards by
-polynomial with no data-path collective, so scaling is "weak".  The last step's
-commitments are checked against the trapdoor identity commit(ck, p) = p(tau) G1 after the clock stops.
+polynomial with no data-path collective, so scaling is "weak".
 
-The same JSON line also carries
+A plain run does only what that figure needs: set-up, warm-up, the timed steps, --dump-outputs DIR if given
+(the last step's commitments and a seeded sample of its coefficients, as .npy, for comparing two builds output
+for output), and one JSON line.  Everything else below runs with --full only.  With --full the last step's
+commitments are checked against the trapdoor identity commit(ck, p) = p(tau) G1 after the clock stops, and
+the same JSON line also carries
   * ntt_elements_per_s + roofline_ntt   the NTT half of BASELINE.json's metric, timed alone;
   * roofline                             the dominant kernel (msm_accumulate), HIP events on its stream;
   * open                                 KZG.open of k = 6 polynomials of 2^20 (plonk/prover.py:184): opens/s,
@@ -32,7 +35,8 @@ The same JSON line also carries
                                          algorithms on 1 core, and a multi-threaded Montgomery + Pippenger
                                          CPU implementation on all host cores.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--curve bls12_381]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--curve bls12_381] [--full]
+                    [--dump-outputs DIR]
 
 --gpus N > 1 without a launcher (no WORLD_SIZE in the environment) starts N child processes, one per
 GPU, before this process has touched HIP; under torch.distributed.run it uses the ranks it is given
@@ -98,9 +102,21 @@ def parse_args(argv=None):
                     help="launcher self-test without a GPU: the ranks rendezvous over gloo, all-gather one record "
                          "each and rank 0 prints one JSON line")
     ap.add_argument("--mode", default="all", choices=("all", "batch", "range"),
-                    help="all (default): headline + every section; batch: headline only; range: the config-4 "
-                         "section only, printed as its own line")
-    return ap.parse_args(argv)
+                    help="all (default): headline + every section (with --full); batch: headline only; range: the "
+                         "config-4 section only, printed as its own line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the last step's trapdoor "
+                         "check, per-kernel spans and rooflines, the NTT and the accumulate kernel timed alone, the "
+                         "sections of --mode all and the CPU baselines (off: the headline loop only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0) to DIR/<name>.npy: the "
+                         "commitments and a fixed, seeded sample of the coefficient vectors, as float64")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.mode == "range":
+        ap.error("--dump-outputs writes the headline path's outputs; --mode range has none")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -257,6 +273,35 @@ def cpu_baseline_optimised(curve, log_n, omega):
         "ntt_elements_per_s": n / t_ntt,
         "cpu_model": cpu_model(),
     }
+
+
+# ------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ------------------------------------------------------------------------------------------------
+
+DUMP_SAMPLE = 1 << 18          # coefficients written of the B x 2^log_n (16 MiB as float64 words)
+
+
+def dump_outputs(dirname, xy, inf, coeffs):
+    """What the last timed step handed its caller, as float64 (every value is a 32-bit word or a flag, exact in a
+    double): the B commitments -- affine x and y as little-endian 32-bit words, [B, 2, words], and the infinity
+    flags -- and a fixed, seeded sample of the B coefficient vectors its INTTs left in the work buffer (all of them
+    would be B x 2^log_n x 32 bytes), with each sampled element's flat index p * 2^log_n + i."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    flat = coeffs.reshape(-1, 4)
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=min(flat.shape[0], DUMP_SAMPLE),
+                                                  replace=False))
+    sample = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+    arrays = {
+        "commitments_xy": xy.view(np.uint32).reshape(xy.shape[0], 2, -1),
+        "commitments_infinity": inf,
+        "coefficients_sample": sample.view(np.uint32),
+        "coefficients_sample_index": idx,
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -709,7 +754,7 @@ def main(argv=None):
     for i in range(args.warmup):
         step(i)
     ctx.commit_flush()
-    ctx.prof_enable(True)
+    ctx.prof_enable(args.full)                              # the per-kernel spans of the timed loop: --full
     ctx.prof_reset()
     env.barrier()
     t0 = time.perf_counter()
@@ -720,6 +765,34 @@ def main(argv=None):
     elapsed = time.perf_counter() - t0
     ctx.prof_enable(False)
     elapsed = env.max_over_ranks(elapsed)
+    last = args.steps - 1
+    if args.dump_outputs and rank == 0:                     # before anything below reuses the work buffers
+        dump_outputs(args.dump_outputs, *results[last], works[last & 1])
+    headline = {
+        "metric": "KZG G1 commits/sec (INTT 2^%d + commit 2^%d, BLS12-381)" % (log_n, log_n)
+        if args.curve == "bls12_381" else "KZG G1 commits/sec (INTT + commit, BN254)",
+        "value": world * args.steps * B / elapsed,
+        "unit": "commits/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": DTYPE,
+        "data": "synthetic",
+        "config": {"workload": f"degree-2^{log_n} INTT + KZG commit, {args.curve}, 2^{log_n}-point SRS, "
+                               f"uniform Fr scalars, batch of {B} polynomials per GPU per step",
+                   "log_n": log_n, "curve": args.curve, "batch": B, "window_bits": 20 if n >= (1 << 18) else 16,
+                   "sharding": "independent polynomials per rank, replicated SRS"},
+    }
+    if not args.full:
+        coll_info = env.collectives_info()      # a collective: every rank takes part
+        if rank == 0:
+            print(json.dumps({**headline, "collectives": coll_info, "srs_setup_s": t_srs}), flush=True)
+        return finish(0)
+
     spans_main = {name: ctx.prof_read(name) for name in
                   ("msm_partition1", "msm_partition2", "msm_order", "msm_accumulate", "msm_finalize", "msm_reduce")}
     mhz_pipelined = ctx.prof_read("msm_accumulate_shader_mhz")[0]
@@ -727,7 +800,6 @@ def main(argv=None):
     # ---- the timed loop's own results, checked (outside the timed region): the coefficients of the last
     # step are still in its work buffer; commit(ck, p) must be p(tau) G1 for each of its B polynomials,
     # and no earlier step may have produced infinity or the zero record
-    last = args.steps - 1
     ok_headline = all(int(inf.sum()) == 0 and xy.any(axis=1).all() for xy, inf in results.values())
     if args.steps > 0:
         xy_last, inf_last = results[last]
@@ -814,23 +886,7 @@ def main(argv=None):
         ntt_bytes = 2 * n * 32                              # read + write every element once
         acc_alone_s = acc_alone[0] / max(acc_alone[1], 1) * 1e-3
         out = {
-            "metric": "KZG G1 commits/sec (INTT 2^%d + commit 2^%d, BLS12-381)" % (log_n, log_n)
-            if args.curve == "bls12_381" else "KZG G1 commits/sec (INTT + commit, BN254)",
-            "value": world * args.steps * B / elapsed,
-            "unit": "commits/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": DTYPE,
-            "data": "synthetic",
-            "config": {"workload": f"degree-2^{log_n} INTT + KZG commit, {args.curve}, 2^{log_n}-point SRS, "
-                                   f"uniform Fr scalars, batch of {B} polynomials per GPU per step",
-                       "log_n": log_n, "curve": args.curve, "batch": B, "window_bits": 20 if n >= (1 << 18) else 16,
-                       "sharding": "independent polynomials per rank, replicated SRS"},
+            **headline,
             "verified": {"last_step_commit_trapdoor": ok_headline},
             # what the process group really was (a SCALE record then shows that RCCL saw N ranks, one GPU each)
             "collectives": coll_info,

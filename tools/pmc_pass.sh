@@ -7,7 +7,7 @@ OUT=$PWD/gpurun_out/pmc_$NAME
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 [ -n "$LIB" ] && export KZG_MI355X_LIB=$LIB
-rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d $OUT -o p -- python3 bench.py --mode batch --steps 3 --warmup 1 --no-cpu-baseline --no-isolated > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d $OUT -o p -- python3 bench.py --full --mode batch --steps 3 --warmup 1 --no-cpu-baseline --no-isolated > $OUT/bench.log 2>&1
 python3 - "$OUT" <<'PY' | tee $OUT.txt
 import collections, csv, glob, re, sys
 out = sys.argv[1]

@@ -9,7 +9,7 @@ OUT=$REPO/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 cd $REPO
-BENCH="python3 bench.py --mode batch --no-cpu-baseline --no-isolated"
+BENCH="python3 bench.py --full --mode batch --no-cpu-baseline --no-isolated"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $BENCH --steps 5 --warmup 2 > $OUT/trace_bench.log 2>&1
 echo "trace done"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o fetch -- $BENCH --steps 3 --warmup 1 > $OUT/pmc_fetch.log 2>&1
