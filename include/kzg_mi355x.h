@@ -205,6 +205,34 @@ int kzg_open_device_async(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys,
                           size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf,
                           uint64_t* eval_out);
 
+/* ---- evaluation form: keys in the Lagrange basis, openings from values ----------------------------
+ * Domain H = {w^i, i < n}, n = 2^log_n (1 <= log_n <= 24), w a primitive n-th root of unity given by the caller (the
+ * `w` of fft_ff); w^(n/2) != -1 is KZG_ERR_ARG.  Values are in natural order: vals[i] = p(w^i).
+ * A Lagrange key holds [L_i(tau)] G1, L_i the Lagrange polynomial of point w^i, so kzg_commit* on a Lagrange key
+ * commits VALUES: the result equals the coefficient commitment of their interpolant.  kzg_srs_export, kzg_srs_size
+ * and kzg_srs_free work on either basis.
+ *   kzg_srs_generate_lagrange  from the secret: L_i(tau) = (tau^n - 1)/n * w^i / (tau - w^i) on the device, then the
+ *                              fixed-base table of kzg_srs_generate
+ *   kzg_srs_lagrange           from the first n points of a monomial key (generated, loaded or read from a file; no
+ *                              tau needed): an inverse NTT over G1.  KZG_ERR_ARG for a key shorter than n or one that
+ *                              is itself a Lagrange key. */
+int kzg_srs_generate_lagrange(kzg_ctx* ctx, const uint64_t tau[4], uint32_t log_n, const uint64_t w[4],
+                              kzg_srs** out);
+int kzg_srs_lagrange(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_n, const uint64_t w[4], kzg_srs** out);
+/* KZG.open from values: k value vectors, `stride` elements apart, vector j having lens[j] <= n values (missing values
+ * read as zero; lens[j] > n is KZG_ERR_DEGREE).  combined = sum_j xi^(j+1) vals_j, its value y at z by the
+ * barycentric formula, the quotient (combined - y)/(X - z) on H -- z in H included (the within-domain formula of
+ * EIP-4844) -- committed against the Lagrange key `srs` (a monomial key is KZG_ERR_ARG).  Parameters, outputs and the
+ * pipelined form's slot rules are those of kzg_open / kzg_open_device / kzg_open_device_async; the proof equals
+ * kzg_open's on the interpolants, and eval_out receives y. */
+int kzg_open_evals(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* vals, const size_t* lens, size_t k, size_t stride,
+                   const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out);
+int kzg_open_evals_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_vals, const size_t* lens, size_t k,
+                          size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf,
+                          uint64_t* eval_out);
+int kzg_open_evals_device_async(kzg_ctx* ctx, const kzg_srs* srs, const void* d_vals, const size_t* lens, size_t k,
+                                size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy,
+                                uint8_t* out_inf, uint64_t* eval_out);
 /* ---- KZG.open on ONE polynomial set partitioned by coefficient range across GPUs ----------------
  * Rank g holds coefficients [lo_g, hi_g) of every polynomial (the same ranges for all) and a key
  * shard.  kzg_open_shard_begin combines the slices (sum xi^(i+1) p_i) and returns the slice
@@ -248,11 +276,16 @@ int kzg_fr_vec_inverse(kzg_ctx* ctx, size_t n, const void* d_a, void* d_out);
 int kzg_fr_vec_prefix_product(kzg_ctx* ctx, size_t n, const void* d_a, void* d_out);
 int kzg_fr_poly_eval(kzg_ctx* ctx, size_t n, const void* d_a, const uint64_t z[4], uint64_t out[4]);
 
+/* Barycentric evaluation of one value vector over H = {w^i} (len <= 2^log_n values, missing ones zero; longer is
+ * KZG_ERR_DEGREE) at z, z in H included: p(z) of the interpolant.  Device-resident values; synchronises. */
+int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size_t len, const void* d_vals,
+                         const uint64_t z[4], uint64_t out[4]);
 /* ---- measurement hooks (bench.py) -----------------------------------------------------------
  * When enabled, the library brackets its kernels with HIP events on the stream each one runs on.
  * Span names: "ntt_pass", "msm_partition1", "msm_partition2", "msm_order", "msm_accumulate",
  * "msm_finalize", "msm_reduce", "open_poly" (ONE span per kzg_open*: combination, scan and division),
- * "open_shard_poly" (one per kzg_open_shard_begin and one per _finish).  kzg_prof_read synchronises the
+ * "open_shard_poly" (one per kzg_open_shard_begin and one per _finish), "srs_lagrange" (one per Lagrange key
+ * built), "open_evals_poly" (ONE per kzg_open_evals*: combination, value and quotient).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.
  * Two names are not spans: "msm_accumulate_shader_mhz" and "ntt_pass_shader_mhz" return (in *total_ms) the shader
  * clock in MHz the accumulate / NTT kernel ran at since the last reset -- s_memtime over s_memrealtime ticks of its

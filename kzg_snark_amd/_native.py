@@ -77,6 +77,14 @@ SIGNATURES = {
     "kzg_open_device_async": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
     "kzg_g1_sum": (ctypes.c_int, [ctypes.c_int, _vp, _vp, ctypes.c_size_t, _vp, _vp]),
     "kzg_open_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    "kzg_srs_generate_lagrange": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, ctypes.POINTER(_vp)]),
+    "kzg_srs_lagrange": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, ctypes.POINTER(_vp)]),
+    "kzg_open_evals": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    "kzg_open_evals_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp, _vp,
+                                             _vp]),
+    "kzg_open_evals_device_async": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp,
+                                                   _vp, _vp]),
+    "kzg_fr_eval_lagrange": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
 }
 
 
@@ -294,6 +302,53 @@ class Context:
                                                    outer_stride, ctypes.byref(h)))
         return Srs(self, h, n)
 
+    # ---- evaluation form (Lagrange keys over the domain {w^i}, n = 2^log_n)
+    def srs_generate_lagrange(self, tau_words, log_n, w):
+        """[L_i(tau) G1], i < 2^log_n: the Lagrange key from the secret."""
+        h = ctypes.c_void_p()
+        self._check(lib().kzg_srs_generate_lagrange(self._h, _as_vp(tau_words), int(log_n),
+                                                    _as_vp(int_to_words(int(w))), ctypes.byref(h)))
+        return Srs(self, h, 1 << int(log_n), basis=(int(log_n), int(w)))
+
+    def srs_lagrange(self, monomial, log_n, w):
+        """The Lagrange key from the first 2^log_n points of a monomial key (inverse NTT over G1)."""
+        h = ctypes.c_void_p()
+        self._check(lib().kzg_srs_lagrange(self._h, monomial._h, int(log_n), _as_vp(int_to_words(int(w))),
+                                           ctypes.byref(h)))
+        return Srs(self, h, 1 << int(log_n), basis=(int(log_n), int(w)))
+
+    def open_evals(self, srs, vals, lens, stride, z_words, xi_words, device=False):
+        """Opening from value vectors (uint64[k, stride, 4] host array, or a device pointer with device=True)
+        against a Lagrange key: (out_xy, out_inf, eval)."""
+        k = len(lens)
+        lens_a = np.asarray(lens, dtype=np.uint64)
+        out_xy = np.zeros(2 * self.fp_limbs, dtype=np.uint64)
+        out_inf = np.zeros(1, dtype=np.uint8)
+        ev = np.zeros(4, dtype=np.uint64)
+        fn = lib().kzg_open_evals_device if device else lib().kzg_open_evals
+        self._check(fn(self._h, srs._h, _as_vp(vals), _as_vp(lens_a), k, stride, _as_vp(z_words),
+                       _as_vp(xi_words), _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev)))
+        return out_xy, out_inf, ev
+
+    def open_evals_device_async(self, srs, d_vals, lens, stride, z_words, xi_words, out_xy, out_inf, eval_out):
+        """Pipelined opening from values: the outputs (numpy arrays the caller keeps alive) are filled by the time
+        commit_flush() returns -- the slot rules of open_device_async."""
+        lens_a = np.asarray(lens, dtype=np.uint64)
+        _check_out(out_xy, np.uint64, 2 * self.fp_limbs, "out_xy")
+        _check_out(out_inf, np.uint8, 1, "out_inf")
+        _check_out(eval_out, np.uint64, 4, "eval_out")
+        self._check(lib().kzg_open_evals_device_async(self._h, srs._h, _as_vp(d_vals), _as_vp(lens_a), len(lens),
+                                                      stride, _as_vp(z_words), _as_vp(xi_words), _as_vp(out_xy),
+                                                      _as_vp(out_inf), _as_vp(eval_out)))
+        self._inflight.append((srs, out_xy, out_inf, eval_out))
+
+    def eval_lagrange(self, log_n, w, n, d_vals, z):
+        """p(z) of the interpolant of n device-resident values over {w^i} (barycentric, z in the domain included)."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(lib().kzg_fr_eval_lagrange(self._h, int(log_n), _as_vp(int_to_words(int(w))), n, _as_vp(d_vals),
+                                               _as_vp(int_to_words(int(z))), _as_vp(out)))
+        return int.from_bytes(out.tobytes(), "little")
+
     # ---- commit / open on host buffers
     def commit(self, srs, scalars, lens, stride):
         """scalars: uint64[n_polys, stride, 4]; lens: per-polynomial coefficient counts."""
@@ -404,12 +459,14 @@ class Context:
 
 
 class Srs:
-    """Device-resident commitment key (kzg_srs): the reference's `ck` list."""
+    """Device-resident commitment key (kzg_srs): the reference's `ck` list.  basis: None for a monomial key
+    ([tau^i] G1), (log_n, w) for a Lagrange key over the domain {w^i} ([L_i(tau)] G1)."""
 
-    def __init__(self, ctx, h, n):
+    def __init__(self, ctx, h, n, basis=None):
         self.ctx = ctx
         self._h = h
         self.n = n
+        self.basis = basis
 
     def export(self, start=0, count=None):
         count = self.n - start if count is None else count

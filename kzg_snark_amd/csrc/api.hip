@@ -160,6 +160,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
   hipFree(c->io.p);
   hipFree(c->clk_probe);
   hipFree(c->scan_tmp.p);
+  hipFree(c->lagr_tmp.p);
   for (auto& b : c->poly_tmp) hipFree(b.p);
   for (auto s : c->aux_streams) hipStreamDestroy(s);
   for (auto e : c->aux_events) hipEventDestroy(e);
@@ -527,6 +528,66 @@ int kzg_open_shard_finish(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t z[4],
   return commit_device(c, srs->s, d_vec, &len, 1, len ? len : 1, out_xy, out_inf);
 }
 
+int kzg_srs_generate_lagrange(kzg_ctx* ctx, const uint64_t tau[4], uint32_t log_n, const uint64_t w[4],
+                              kzg_srs** out) {
+  if (!ctx || !tau || !w || !out) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  *out = nullptr;
+  KZG_HIP(c, hipSetDevice(c->device));
+  Srs* s = nullptr;
+  int rc = srs_generate_lagrange(c, reinterpret_cast<const uint32_t*>(tau), log_n, reinterpret_cast<const uint32_t*>(w),
+                                 &s);
+  if (rc) return rc;
+  *out = new kzg_srs{s};
+  return KZG_OK;
+}
+
+int kzg_srs_lagrange(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_n, const uint64_t w[4], kzg_srs** out) {
+  if (!ctx || !monomial || !w || !out) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  *out = nullptr;
+  KZG_HIP(c, hipSetDevice(c->device));
+  Srs* s = nullptr;
+  int rc = srs_lagrange(c, monomial->s, log_n, reinterpret_cast<const uint32_t*>(w), &s);
+  if (rc) return rc;
+  *out = new kzg_srs{s};
+  return KZG_OK;
+}
+
+int kzg_open_evals_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_vals, const size_t* lens, size_t k,
+                          size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf,
+                          uint64_t* eval_out) {
+  if (!ctx || !srs || !z || !xi || !out_xy || !out_inf || (k && (!lens || !d_vals))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return open_evals_device(c, srs->s, static_cast<const uint32_t*>(d_vals), lens, k, stride,
+                           reinterpret_cast<const uint32_t*>(z), reinterpret_cast<const uint32_t*>(xi), out_xy, out_inf,
+                           eval_out, /*sync=*/true);
+}
+
+int kzg_open_evals_device_async(kzg_ctx* ctx, const kzg_srs* srs, const void* d_vals, const size_t* lens, size_t k,
+                                size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy,
+                                uint8_t* out_inf, uint64_t* eval_out) {
+  if (!ctx || !srs || !z || !xi || !out_xy || !out_inf || !eval_out || (k && (!lens || !d_vals))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return open_evals_device(c, srs->s, static_cast<const uint32_t*>(d_vals), lens, k, stride,
+                           reinterpret_cast<const uint32_t*>(z), reinterpret_cast<const uint32_t*>(xi), out_xy, out_inf,
+                           eval_out, /*sync=*/false);
+}
+
+int kzg_open_evals(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* vals, const size_t* lens, size_t k, size_t stride,
+                   const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
+  if (!ctx || !srs || !z || !xi || !out_xy || !out_inf || (k && (!lens || !vals))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  const size_t bytes = k * stride * 32;
+  int rc = ensure_buf(c, c->io, bytes ? bytes : 32);
+  if (rc) return rc;
+  if (bytes) KZG_HIP(c, hipMemcpyAsync(c->io.p, vals, bytes, hipMemcpyHostToDevice, c->stream));
+  return kzg_open_evals_device(ctx, srs, c->io.p, lens, k, stride, z, xi, out_xy, out_inf, eval_out);
+}
+
 #define KZG_VEC_ENTER()                          \
   if (!ctx) return KZG_ERR_ARG;                  \
   Ctx* c = &ctx->c;                              \
@@ -572,6 +633,14 @@ int kzg_fr_poly_eval(kzg_ctx* ctx, size_t n, const void* d_a, const uint64_t z[4
   KZG_VEC_ENTER();
   if (!z || !out || (n && !d_a)) return KZG_ERR_ARG;
   return fr_poly_eval(c, n, static_cast<const uint32_t*>(d_a), reinterpret_cast<const uint32_t*>(z), out);
+}
+
+int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size_t len, const void* d_vals,
+                         const uint64_t z[4], uint64_t out[4]) {
+  KZG_VEC_ENTER();
+  if (!w || !z || !out || (len && !d_vals)) return KZG_ERR_ARG;
+  return fr_eval_lagrange(c, log_n, reinterpret_cast<const uint32_t*>(w), len, static_cast<const uint32_t*>(d_vals),
+                          reinterpret_cast<const uint32_t*>(z), out);
 }
 
 int kzg_prof_enable(kzg_ctx* ctx, int on) {

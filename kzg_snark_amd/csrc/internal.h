@@ -61,6 +61,7 @@ struct Ctx {
   DevBuf io;              // staging for the host-pointer entry points
   DevBuf poly_tmp[4];     // open(): combined polynomial + suffix values; scratch of the vector primitives
   DevBuf scan_tmp;        // open(): chunk values, tile aggregates, power tables (kept between the shard calls)
+  DevBuf lagr_tmp;        // lagrange.hip: combined values, denominators, inverses, quotient, partial sums
   size_t open_shard_n = 0;                // slice length between kzg_open_shard_begin / _finish
   uint32_t open_shard_tb = 0;             // tile width the slice's aggregates were formed with
   // kzg_ctx_set_tuning: 0 = the library's own choice

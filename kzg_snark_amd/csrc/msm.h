@@ -12,7 +12,15 @@ struct Srs {
   int win_bits = 16;          // Pippenger window c: 20 for keys of >= 2^18 points, else 16
   int nwin = 16;              // ceil(256 / c) table windows
   uint32_t* recs = nullptr;   // [nwin][n] records of Curve::REC_WORDS words
+  // basis of the key: monomial ([tau^i] G) or Lagrange over the domain {w^i} of n = 2^log_n points
+  // ([L_i(tau)] G, lagrange.hip); a commit against a Lagrange key commits values
+  int basis = 0;              // SRS_MONOMIAL | SRS_LAGRANGE
+  uint32_t log_n = 0;         // Lagrange keys: domain size and root (canonical words)
+  uint32_t w[8] = {0};
+  uint32_t* d_wpow = nullptr; // Lagrange keys: w^i, i < n (canonical words, 32 B each)
 };
+constexpr int SRS_MONOMIAL = 0;
+constexpr int SRS_LAGRANGE = 1;
 
 int srs_load(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, Srs** out);
 // run_len = 0: the contiguous range tau^(start + i); otherwise record i = tau^(start + (i / run_len) * outer_stride +
@@ -21,6 +29,20 @@ int srs_generate(Ctx* c, const uint64_t* tau, size_t start, size_t n, Srs** out,
                  size_t inner_stride = 1, size_t outer_stride = 0);
 int srs_export(Ctx* c, const Srs* s, size_t start, size_t count, uint64_t* xy, uint8_t* inf);
 void srs_free(Srs* s);
+// record i = scalars[i] * G1 (device vector of n canonical scalars), windows built; synchronises
+int srs_generate_scalars(Ctx* c, const uint32_t* d_scalars, size_t n, Srs** out);
+// an n-point key whose window-0 records the caller fills, then srs_finish_windows (synchronises)
+int srs_create(Ctx* c, size_t n, Srs** out);
+int srs_finish_windows(Ctx* c, Srs* s);
+
+// lagrange.hip: evaluation-form keys and openings
+int srs_lagrange(Ctx* c, const Srs* mono, uint32_t log_n, const uint32_t* w_words, Srs** out);
+int srs_generate_lagrange(Ctx* c, const uint32_t* tau_words, uint32_t log_n, const uint32_t* w_words, Srs** out);
+int open_evals_device(Ctx* c, const Srs* s, const uint32_t* d_vals, const size_t* lens, size_t k, size_t stride,
+                      const uint32_t* z_words, const uint32_t* xi_words, uint64_t* out_xy, uint8_t* out_inf,
+                      uint64_t* eval_out, bool sync);
+int fr_eval_lagrange(Ctx* c, uint32_t log_n, const uint32_t* w_words, size_t len, const uint32_t* d_vals,
+                     const uint32_t* z_words, uint64_t* out);
 
 // One MSM per polynomial; scalars device-resident, results to host memory (synchronises).
 // drain = false leaves up to four polynomials in flight; their outputs are written when their

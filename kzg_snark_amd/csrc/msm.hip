@@ -35,6 +35,7 @@
 #include "ec.h"
 #include "msm.h"
 #include "msm_prep.h"
+#include "srs_rec.h"
 
 namespace kzg {
 
@@ -53,55 +54,6 @@ struct Win {
   static constexpr int NPART = HI + LO + 1;                   // points handed to the host
 };
 constexpr int MAX_NPART = 24;
-
-template <class C> struct Rec {
-  static constexpr int WORDS = C::REC_WORDS;
-  static constexpr int N = C::Fp::N;
-  static constexpr int FLAG = 2 * N;   // word index of the flags (bit 0: infinity)
-};
-
-// x, y and the flag word of a record (bit 0: point at infinity)
-template <class C>
-__device__ __forceinline__ uint32_t load_rec(const uint32_t* recs, size_t idx, Fe<typename C::Fp>& x,
-                                             Fe<typename C::Fp>& y) {
-  constexpr int N = C::Fp::N;
-  const uint32_t* p = recs + idx * Rec<C>::WORDS;
-  uint32_t flag;
-  constexpr int Q = (2 * N + 3) / 4;                 // 16-byte loads covering x and y
-  uint32_t w[4 * Q];
-  if constexpr (4 * Q <= Rec<C>::WORDS && (Rec<C>::WORDS % 4) == 0) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-#pragma unroll
-    for (int i = 0; i < Q; ++i) {
-      const uint4 v = q[i];
-      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
-    if constexpr (Rec<C>::FLAG < 4 * Q) flag = w[Rec<C>::FLAG]; else flag = p[Rec<C>::FLAG];
-  } else {
-    const uint2* q = reinterpret_cast<const uint2*>(p);
-#pragma unroll
-    for (int i = 0; i < (2 * N) / 2; ++i) {
-      const uint2 v = q[i];
-      w[2 * i] = v.x; w[2 * i + 1] = v.y;
-    }
-    flag = p[Rec<C>::FLAG];
-  }
-#pragma unroll
-  for (int j = 0; j < N; ++j) { x.l[j] = w[j]; y.l[j] = w[N + j]; }
-  return flag;
-}
-
-template <class C>
-__device__ __forceinline__ void store_rec(uint32_t* recs, size_t idx, const Fe<typename C::Fp>& x,
-                                          const Fe<typename C::Fp>& y, bool inf) {
-  constexpr int N = C::Fp::N;
-  uint32_t* p = recs + idx * Rec<C>::WORDS;
-#pragma unroll
-  for (int j = 0; j < N; ++j) { p[j] = inf ? 0u : x.l[j]; p[N + j] = inf ? 0u : y.l[j]; }
-#pragma unroll
-  for (int j = 2 * N; j < Rec<C>::WORDS; ++j) p[j] = 0;
-  p[Rec<C>::FLAG] = inf ? 1u : 0u;
-}
 
 // XYZZ points are 4*N words = a whole number of 16-byte quads; every array of them is 16-byte aligned
 template <class C>
@@ -228,29 +180,35 @@ __global__ __launch_bounds__(256) void gen_table_kernel(const uint32_t* g_rec, u
 }
 
 // SRS generation (kzg.py:70-72): record i = tau^i * G by fixed-base windows of 8 bits.
-// powers: canonical words of tau^i (computed by pow kernel below)
+// scalars != null: record i = scalars[i] * G instead (canonical words; the Lagrange key of lagrange.hip)
 template <class C>
 __global__ __launch_bounds__(128) void srs_generate_kernel(const uint32_t* tab, const uint32_t* tau_mont,
                                                            uint32_t* recs, size_t start, size_t n, size_t run_len,
-                                                           size_t inner_stride, size_t outer_stride) {
+                                                           size_t inner_stride, size_t outer_stride,
+                                                           const uint32_t* scalars) {
   using F = typename C::Fp;
   using Fr = typename C::Fr;
   using Fd = Field<F>;
   using Frd = Field<Fr>;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  // s = tau^i (square-and-multiply on the index bits), canonical words
-  Fe<Fr> b, acc = Frd::one();
-#pragma unroll
-  for (int j = 0; j < Fr::N; ++j) b.l[j] = tau_mont[j];
-  // record i holds tau^e, e = start + (i / run_len) * outer_stride + (i % run_len) * inner_stride
-  // (a contiguous range: run_len = n, inner_stride = 1)
-  for (size_t bits = start + (i / run_len) * outer_stride + (i % run_len) * inner_stride; bits; bits >>= 1) {
-    if (bits & 1u) acc = Frd::mul(acc, b);
-    b = Frd::mul(b, b);
-  }
   uint32_t s[Fr::NW];
-  Frd::to_words(Frd::from_mont(acc), s);
+  if (scalars) {
+#pragma unroll
+    for (int j = 0; j < Fr::NW; ++j) s[j] = scalars[i * Fr::NW + j];
+  } else {
+    // s = tau^i (square-and-multiply on the index bits), canonical words
+    Fe<Fr> b, acc = Frd::one();
+#pragma unroll
+    for (int j = 0; j < Fr::N; ++j) b.l[j] = tau_mont[j];
+    // record i holds tau^e, e = start + (i / run_len) * outer_stride + (i % run_len) * inner_stride
+    // (a contiguous range: run_len = n, inner_stride = 1)
+    for (size_t bits = start + (i / run_len) * outer_stride + (i % run_len) * inner_stride; bits; bits >>= 1) {
+      if (bits & 1u) acc = Frd::mul(acc, b);
+      b = Frd::mul(b, b);
+    }
+    Frd::to_words(Frd::from_mont(acc), s);
+  }
   XYZZ<C> p = Ec<C>::infinity();
   for (int j = 0; j < 32; ++j) {
     const uint32_t d = (s[j >> 2] >> (8 * (j & 3))) & 0xffu;
@@ -624,7 +582,8 @@ static int srs_load_t(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, 
 
 template <class C>
 static int srs_generate_t(Ctx* c, const uint32_t* tau_words, size_t start, size_t n, const uint64_t* gen_xy,
-                          Srs** out, size_t run_len, size_t inner_stride, size_t outer_stride) {
+                          Srs** out, size_t run_len, size_t inner_stride, size_t outer_stride,
+                          const uint32_t* d_scalars = nullptr) {
   using F = typename C::Fp;
   using Fr = typename C::Fr;
   if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, "kzg_srs_generate: bad size");
@@ -648,7 +607,7 @@ static int srs_generate_t(Ctx* c, const uint32_t* tau_words, size_t start, size_
                      (size_t)1, d_bad);
   hipLaunchKernelGGL(gen_table_kernel<C>, dim3(32), dim3(256), 0, c->stream, d_g, d_tab);
   hipLaunchKernelGGL(srs_generate_kernel<C>, dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, c->stream, d_tab, d_tau,
-                     s->recs, start, n, run_len, inner_stride, outer_stride);
+                     s->recs, start, n, run_len, inner_stride, outer_stride, d_scalars);
   e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, "srs generate", e));
   cleanup();
@@ -675,9 +634,27 @@ int srs_generate(Ctx* c, const uint64_t* tau, size_t start, size_t n, Srs** out,
   return c->curve == 0 ? srs_generate_t<Bn254>(c, t, start, n, GEN_BN254, out, run_len, inner_stride, outer_stride)
                        : srs_generate_t<Bls12_381>(c, t, start, n, GEN_BLS, out, run_len, inner_stride, outer_stride);
 }
+int srs_generate_scalars(Ctx* c, const uint32_t* d_scalars, size_t n, Srs** out) {
+  static const uint32_t zero[8] = {0};
+  return c->curve == 0 ? srs_generate_t<Bn254>(c, zero, 0, n, GEN_BN254, out, n ? n : 1, 1, 0, d_scalars)
+                       : srs_generate_t<Bls12_381>(c, zero, 0, n, GEN_BLS, out, n ? n : 1, 1, 0, d_scalars);
+}
+int srs_create(Ctx* c, size_t n, Srs** out) {
+  const size_t rb = c->curve == 0 ? rec_bytes<Bn254>() : rec_bytes<Bls12_381>();
+  if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, "SRS: bad size");
+  Srs* s = srs_alloc(c, n);
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->recs), (size_t)s->nwin * n * rb);
+  if (e != hipSuccess) { delete s; return set_err(c, KZG_ERR_ALLOC, "hipMalloc(SRS table)", e); }
+  *out = s;
+  return KZG_OK;
+}
+int srs_finish_windows(Ctx* c, Srs* s) {
+  return c->curve == 0 ? srs_build_windows<Bn254>(c, s) : srs_build_windows<Bls12_381>(c, s);
+}
 void srs_free(Srs* s) {
   if (!s) return;
   hipFree(s->recs);
+  hipFree(s->d_wpow);
   delete s;
 }
 

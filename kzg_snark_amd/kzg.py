@@ -64,6 +64,17 @@ class CommitmentKey(Sequence):
         return self._cache[i]
 
 
+class LagrangeKey(CommitmentKey):
+    """A commitment key in the Lagrange basis of the domain {w^i, i < n}: the points [L_i(tau)] G1.  A Sequence of
+    points like CommitmentKey; commit_evaluations / open_evaluations take VALUES f[i] = p(w^i) against it."""
+
+    def __init__(self, ctx, srs, n, w):
+        super().__init__(ctx, srs)
+        self.n = int(n)
+        self.w = int(w)
+        self.log_n = self.n.bit_length() - 1
+
+
 class KZG:
     def __init__(self, curve_type="bn254"):
         if curve_type not in _curve.CURVES:
@@ -326,3 +337,99 @@ class KZG:
             rhs.append(self.multiply(proof, int(weight)))
             weight *= rho
         return self.pairing(self.G2, self._sum_g1(lhs)) == self.pairing(rk, self._sum_g1(rhs))
+
+    # ---- evaluation form (Lagrange-basis keys): commit to and open value vectors f[i] = p(w^i) -------------------
+    def _domain(self, n, w):
+        """Validate (n, w) on the host: n a power of two >= 2, w a primitive n-th root (w^(n/2) = -1).  -> (log_n, w)."""
+        n = int(n)
+        if n < 2 or n & (n - 1):
+            raise ValueError(f"domain size {n} is not a power of two >= 2")
+        r = self.curve_order
+        if (r - 1) % n:
+            raise ValueError(f"the scalar field has no {n}-th roots of unity")
+        w = int(self.Fq.root_of_unity(n)) if w is None else int(w) % r
+        if pow(w, n // 2, r) != r - 1:
+            raise ValueError(f"w is not a primitive {n}-th root of unity")
+        return n.bit_length() - 1, w
+
+    def _value_lists(self, value_lists, n):
+        out = []
+        for v in value_lists:
+            m = len(v) if hasattr(v, "__len__") else len(v.list())
+            if m > n:
+                raise ValueError(f"{m} values exceed the domain size {n}")
+            c = self._coeffs(v)          # canonical ints (or a uint64[m, 4] buffer); trailing zero values dropped
+            if len(c) > n:
+                raise ValueError(f"{len(c)} values exceed the domain size {n}")
+            out.append(c)
+        return out
+
+    def setup_lagrange(self, n, tau=None, w=None):
+        """setup() in the Lagrange basis of {w^i}, i < n: (LagrangeKey [L_i(tau) G1], tau G2).  w defaults to
+        Fq.root_of_unity(n), the root of plonk/encoder.py:49."""
+        log_n, w = self._domain(n, w)
+        if tau is None:
+            tau = self.Fq.random_element()
+        tau = int(tau) % self.curve_order
+        ctx = self._context()
+        srs = ctx.srs_generate_lagrange(_native.int_to_words(tau), log_n, w)
+        return LagrangeKey(ctx, srs, 1 << log_n, w), self.multiply(self.G2, tau)
+
+    def lagrange_key(self, ck, n, w=None):
+        """The Lagrange key of the first n points of a monomial key (CommitmentKey or list of points): an inverse
+        NTT over G1 on the device, no tau needed."""
+        log_n, w = self._domain(n, w)
+        if len(ck) < (1 << log_n):
+            raise ValueError(f"commitment key of {len(ck)} points is shorter than the domain ({1 << log_n})")
+        key = self._key(ck)
+        ctx = self._context()
+        return LagrangeKey(ctx, ctx.srs_lagrange(key.srs, log_n, w), 1 << log_n, w)
+
+    def commit_evaluations(self, lk, value_lists):
+        """Commitments to value vectors: equal to commit(ck, [interpolant]) for the same tau."""
+        if not isinstance(lk, LagrangeKey):
+            raise TypeError("commit_evaluations needs a LagrangeKey (setup_lagrange / lagrange_key)")
+        vals = self._value_lists(value_lists, lk.n)
+        if not vals:
+            return []
+        arr, lens, stride = self._pack(vals)
+        xy, inf = self._context().commit(lk.srs, arr, lens, stride)
+        return self._points(xy, inf)
+
+    def open_evaluations(self, lk, value_lists, z, xi):
+        """open() from value vectors: the same proof as open(ck, [interpolants], z, xi), z in the domain included."""
+        if not isinstance(lk, LagrangeKey):
+            raise TypeError("open_evaluations needs a LagrangeKey (setup_lagrange / lagrange_key)")
+        vals = self._value_lists(value_lists, lk.n)
+        z = int(self.Fq(z))
+        xi = int(self.Fq(xi))
+        arr, lens, stride = self._pack(vals)
+        xy, inf, _ = self._context().open_evals(lk.srs, arr, lens, stride, _native.int_to_words(z),
+                                                _native.int_to_words(xi))
+        return self._points(xy, inf)[0]
+
+    def evaluate_evaluations(self, lk_or_w, values, z):
+        """p(z) for the interpolant of values over {w^i} (barycentric, on the device; z in the domain included).
+        lk_or_w: a LagrangeKey, or the root w itself (the domain size is then its multiplicative order)."""
+        if isinstance(lk_or_w, LagrangeKey):
+            log_n, w = lk_or_w.log_n, lk_or_w.w
+        else:
+            r = self.curve_order
+            w = int(lk_or_w) % r
+            n, x = 1, w
+            while x != 1 and n < (1 << 40):
+                x = x * x % r
+                n *= 2
+            if x != 1:
+                raise ValueError("w is not a root of unity of power-of-two order")
+            log_n, w = self._domain(n, w)
+        vals = self._value_lists([values], 1 << log_n)[0]
+        z = int(self.Fq(z))
+        if not len(vals):
+            return self.Fq(0)
+        import torch
+        ctx = self._context()
+        arr = np.ascontiguousarray(vals if isinstance(vals, np.ndarray) else _native.ints_to_limbs(vals))
+        d = torch.from_numpy(arr.view(np.int64)).to(f"cuda:{ctx.device}", non_blocking=False)
+        torch.cuda.synchronize(ctx.device)
+        return self.Fq(ctx.eval_lagrange(log_n, w, len(vals), d.data_ptr(), z))
