@@ -51,6 +51,7 @@ extern "C" {
 
 typedef struct kzg_ctx kzg_ctx;
 typedef struct kzg_srs kzg_srs;
+typedef struct kzg_domain_table kzg_domain_table;
 
 /* ABI version of this header (bumped on incompatible change). */
 int kzg_abi_version(void);
@@ -78,7 +79,8 @@ int kzg_ctx_synchronize(kzg_ctx* ctx);
  * depend on it).  value 0 restores the library's choice.  Keys:
  *   "ntt_tile_log"       log2 of the transform's LDS tile, 8..12 (default: 11 alone, 10 beside an accumulate kernel)
  *   "open_tile_threads"  threads per tile of the opening's scan, 128 | 256 (default: 256 alone, 128 beside one)
- *   "open_direct_tiles"  tile count up to which every tile sums all tile aggregates above it (default 1024) */
+ *   "open_direct_tiles"  tile count up to which every tile sums all tile aggregates above it (default 1024)
+ *   "open_domain_chunk"  vectors per chunk of kzg_open_domain*, 1..1024 (default: as many as ~2 GiB of scratch holds) */
 int kzg_ctx_set_tuning(kzg_ctx* ctx, const char* key, int64_t value);
 
 /* ---- NTT: replaces fft_ff (fft_ff.py:3-37) and ifft_ff (fft_ff.py:39-58) -------------
@@ -233,6 +235,26 @@ int kzg_open_evals_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_vals, 
 int kzg_open_evals_device_async(kzg_ctx* ctx, const kzg_srs* srs, const void* d_vals, const size_t* lens, size_t k,
                                 size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy,
                                 uint8_t* out_inf, uint64_t* eval_out);
+/* ---- every proof on a domain at once: FK20 (Feist-Khovratovich, "Fast amortized KZG proofs", 2020) -----------
+ * For b coefficient vectors p_j of degree < n = 2^log_n (1 <= log_n <= 20) and a primitive n-th root w, all n proofs
+ * pi_j[i] = kzg_open(p_j, z = w^i, xi = 1) (kzg.py:122-159) in O(n log n) group work and no MSM: the forward G1 DFT of
+ * h_m = sum_(t>m) c_t [tau^(t-m-1)] G1, whose Toeplitz product runs as a circular convolution of size 2n against a
+ * table built once per key and n.
+ *   kzg_domain_table_create  the table from the first n points of a monomial key (KZG_ERR_ARG for a Lagrange key, a
+ *                            key of another curve or shorter than n, log_n outside [1, 20]): 2n affine points.
+ *   kzg_open_domain          vectors `stride` elements apart, vector j having lens[j] <= n coefficients (KZG_ERR_DEGREE
+ *                            above n, KZG_ERR_ARG for lens[j] > stride or a w that is not a primitive n-th root).
+ *                            out_xy / out_inf: [b][n] proofs in kzg_open's point format; eval_out ([b][n][4] limbs, may
+ *                            be NULL) receives y_j[i] = p_j(w^i).  The vectors run in chunks that bound the scratch
+ *                            (tuning key "open_domain_chunk").  Synchronises; the commit pipeline is not touched. */
+int kzg_domain_table_create(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_n, kzg_domain_table** out);
+size_t kzg_domain_table_size(const kzg_domain_table* t);
+void kzg_domain_table_free(kzg_domain_table* t);
+int kzg_open_domain(kzg_ctx* ctx, const kzg_domain_table* t, const uint64_t* polys, const size_t* lens, size_t b,
+                    size_t stride, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out);
+int kzg_open_domain_device(kzg_ctx* ctx, const kzg_domain_table* t, const void* d_polys, const size_t* lens, size_t b,
+                           size_t stride, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf,
+                           uint64_t* eval_out);
 /* ---- KZG.open on ONE polynomial set partitioned by coefficient range across GPUs ----------------
  * Rank g holds coefficients [lo_g, hi_g) of every polynomial (the same ranges for all) and a key
  * shard.  kzg_open_shard_begin combines the slices (sum xi^(i+1) p_i) and returns the slice
@@ -285,7 +307,8 @@ int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size
  * Span names: "ntt_pass", "msm_partition1", "msm_partition2", "msm_order", "msm_accumulate",
  * "msm_finalize", "msm_reduce", "open_poly" (ONE span per kzg_open*: combination, scan and division),
  * "open_shard_poly" (one per kzg_open_shard_begin and one per _finish), "srs_lagrange" (one per Lagrange key
- * built), "open_evals_poly" (ONE per kzg_open_evals*: combination, value and quotient).  kzg_prof_read synchronises the
+ * built), "open_evals_poly" (ONE per kzg_open_evals*: combination, value and quotient), "domain_table" (one per
+ * kzg_domain_table_create), "open_domain" (ONE per kzg_open_domain*: every chunk, transform and copy).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.
  * Two names are not spans: "msm_accumulate_shader_mhz" and "ntt_pass_shader_mhz" return (in *total_ms) the shader
  * clock in MHz the accumulate / NTT kernel ran at since the last reset -- s_memtime over s_memrealtime ticks of its

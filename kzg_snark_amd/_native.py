@@ -85,6 +85,12 @@ SIGNATURES = {
     "kzg_open_evals_device_async": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp,
                                                    _vp, _vp]),
     "kzg_fr_eval_lagrange": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "kzg_domain_table_create": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.POINTER(_vp)]),
+    "kzg_domain_table_size": (ctypes.c_size_t, [_vp]),
+    "kzg_domain_table_free": (None, [_vp]),
+    "kzg_open_domain": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
+    "kzg_open_domain_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp,
+                                              _vp]),
 }
 
 
@@ -349,6 +355,27 @@ class Context:
                                                _as_vp(int_to_words(int(z))), _as_vp(out)))
         return int.from_bytes(out.tobytes(), "little")
 
+    # ---- every proof on a domain (FK20)
+    def domain_table(self, monomial, log_n):
+        """The FK20 table of the first 2^log_n points of a monomial key."""
+        h = ctypes.c_void_p()
+        self._check(lib().kzg_domain_table_create(self._h, monomial._h, int(log_n), ctypes.byref(h)))
+        return DomainTable(self, h, 1 << int(log_n))
+
+    def open_domain(self, table, polys, lens, stride, w, device=False, evals=True):
+        """All n proofs of each of len(lens) coefficient vectors (uint64[b, stride, 4] host array, or a device pointer
+        with device=True) at w^i: (out_xy uint64[b, n, 2*fp_limbs], out_inf uint8[b, n], evals uint64[b, n, 4] or
+        None)."""
+        b, n = len(lens), table.n
+        lens_a = np.asarray(lens, dtype=np.uint64)
+        out_xy = np.zeros((b, n, 2 * self.fp_limbs), dtype=np.uint64)
+        out_inf = np.zeros((b, n), dtype=np.uint8)
+        ev = np.zeros((b, n, 4), dtype=np.uint64) if evals else None
+        fn = lib().kzg_open_domain_device if device else lib().kzg_open_domain
+        self._check(fn(self._h, table._h, _as_vp(polys), _as_vp(lens_a), b, stride, _as_vp(int_to_words(int(w))),
+                       _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev) if evals else None))
+        return out_xy, out_inf, ev
+
     # ---- commit / open on host buffers
     def commit(self, srs, scalars, lens, stride):
         """scalars: uint64[n_polys, stride, 4]; lens: per-polynomial coefficient counts."""
@@ -478,6 +505,26 @@ class Srs:
     def close(self):
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
             lib().kzg_srs_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DomainTable:
+    """FK20 table of one monomial key and domain size n (kzg_domain_table): 2n affine points on the device."""
+
+    def __init__(self, ctx, h, n):
+        self.ctx = ctx
+        self._h = h
+        self.n = n
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            lib().kzg_domain_table_free(self._h)
         self._h = None
 
     def __del__(self):

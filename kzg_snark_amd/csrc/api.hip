@@ -13,6 +13,9 @@ struct kzg_ctx {
 struct kzg_srs {
   kzg::Srs* s;
 };
+struct kzg_domain_table {
+  kzg::DomainTable* t;
+};
 
 namespace kzg {
 int device_any_nonzero(Ctx* c, const uint32_t* d_words, size_t from, size_t to, bool* out);   // poly.hip
@@ -161,6 +164,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
   hipFree(c->clk_probe);
   hipFree(c->scan_tmp.p);
   hipFree(c->lagr_tmp.p);
+  hipFree(c->dom_tmp.p);
   for (auto& b : c->poly_tmp) hipFree(b.p);
   for (auto s : c->aux_streams) hipStreamDestroy(s);
   for (auto e : c->aux_events) hipEventDestroy(e);
@@ -213,6 +217,9 @@ int kzg_ctx_set_tuning(kzg_ctx* ctx, const char* key, int64_t value) {
   } else if (k == "open_direct_tiles") {
     if (value < 0 || value > (1 << 20)) return set_err(c, KZG_ERR_ARG, "open_direct_tiles: 0 .. 2^20");
     c->tune_open_direct_max = (int)value;
+  } else if (k == "open_domain_chunk") {
+    if (value < 0 || value > 1024) return set_err(c, KZG_ERR_ARG, "open_domain_chunk: 0 .. 1024");
+    c->tune_open_domain_chunk = (int)value;
   } else {
     return set_err(c, KZG_ERR_ARG, "kzg_ctx_set_tuning: unknown key");
   }
@@ -586,6 +593,45 @@ int kzg_open_evals(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* vals, const
   if (rc) return rc;
   if (bytes) KZG_HIP(c, hipMemcpyAsync(c->io.p, vals, bytes, hipMemcpyHostToDevice, c->stream));
   return kzg_open_evals_device(ctx, srs, c->io.p, lens, k, stride, z, xi, out_xy, out_inf, eval_out);
+}
+
+int kzg_domain_table_create(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_n, kzg_domain_table** out) {
+  if (!ctx || !monomial || !out) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  *out = nullptr;
+  KZG_HIP(c, hipSetDevice(c->device));
+  DomainTable* t = nullptr;
+  int rc = domain_table_create(c, monomial->s, log_n, &t);
+  if (rc) return rc;
+  *out = new kzg_domain_table{t};
+  return KZG_OK;
+}
+
+size_t kzg_domain_table_size(const kzg_domain_table* t) { return t ? domain_table_size(t->t) : 0; }
+
+void kzg_domain_table_free(kzg_domain_table* t) {
+  if (!t) return;
+  domain_table_free(t->t);
+  delete t;
+}
+
+int kzg_open_domain_device(kzg_ctx* ctx, const kzg_domain_table* t, const void* d_polys, const size_t* lens, size_t b,
+                           size_t stride, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf,
+                           uint64_t* eval_out) {
+  if (!ctx || !t || !w || (b && (!lens || !d_polys || !out_xy || !out_inf))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return open_domain(c, t->t, static_cast<const uint32_t*>(d_polys), /*host_polys=*/false, lens, b, stride,
+                     reinterpret_cast<const uint32_t*>(w), out_xy, out_inf, eval_out);
+}
+
+int kzg_open_domain(kzg_ctx* ctx, const kzg_domain_table* t, const uint64_t* polys, const size_t* lens, size_t b,
+                    size_t stride, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
+  if (!ctx || !t || !w || (b && (!lens || !polys || !out_xy || !out_inf))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return open_domain(c, t->t, reinterpret_cast<const uint32_t*>(polys), /*host_polys=*/true, lens, b, stride,
+                     reinterpret_cast<const uint32_t*>(w), out_xy, out_inf, eval_out);
 }
 
 #define KZG_VEC_ENTER()                          \

@@ -1,0 +1,476 @@
+// domain.hip -- all n KZG proofs on a domain H = {w^i, i < n} at once (Feist-Khovratovich, "Fast amortized KZG
+// proofs", 2020: FK20), n = 2^log_n, on gfx950.  Each proof equals kzg_open's at z = w^i (kzg.py:122-159).
+//
+// For p(X) = sum_(j<n) c_j X^j and the monomial key s_t = [tau^t] G1, the quotient at z is sum_(m<n) z^m Q_m(X) with
+//     pi(z) = sum_(m<n) h_m z^m,    h_m = sum_(j=m+1)^(n-1) c_j s_(j-m-1)    (h_(n-1) = 0),
+// so pi(w^k), k < n, is the forward G1 DFT of h with the caller's root w.  h is a Toeplitz product, taken as a
+// circular convolution of size N = 2n with the library's primitive N-th root omega (g^((r-1)/N), g the smallest
+// primitive root of Fr -- any primitive root gives the same h):
+//   table (once per key and n)   s^_u = s_(n-2-u) for u <= n-2, O above;  S = DFT_G1,N(s^)  ->  N compact affine points
+//   per polynomial               c^ = DFT_Fr,N(c zero-padded)           (ntt_run_device, batched)
+//                                u^_i = (c^_i / N) * S_i                 (one scalar times one fixed affine point)
+//                                u = DFT_G1,N(u^) with omega^-1          (no 1/N: it rode on the scalars)
+//                                h_m = u_(n-1+m), m <= n-2; h_(n-1) = O  (the linear convolution has 2n-2 < N terms)
+//                                pi = DFT_G1,n(h) with w, natural order
+// The G1 DFTs are radix 2, decimation in time, in XYZZ: a bit-reversed load (folded into the Hadamard pass and the
+// extraction), one launch per level over every vector of the batch, a pass to affine.  As in lagrange.hip's
+// g1_intt_level_kernel, butterfly t of a vector takes twiddle index k = t / (len / 2h): the lanes of a wave share a
+// twiddle wherever >= 64 butterflies do, so the double-and-add branches are wave-uniform on all but the last six
+// levels, and twiddle index 0 only adds and subtracts.
+// Every kernel: vector stores only, no scratch, <= 256 VGPRs, one instantiation per curve.
+#include <cstring>
+#include <algorithm>
+#include <vector>
+#include "internal.h"
+#include "ec.h"
+#include "msm.h"
+#include "srs_rec.h"
+
+namespace kzg {
+
+namespace {
+
+struct DomFr {                    // one Fr element (Montgomery limbs) as a kernel argument
+  uint32_t l[9];
+};
+
+// compact affine record of the table: x[NW] y[NW] canonical words, flag word (bit 0: infinity), pad to 16 bytes
+template <class C>
+struct Tbl {
+  static constexpr int NW = C::Fp::NW;
+  static constexpr int WORDS = 2 * NW + 4;       // 20 (BN254) / 28 (BLS12-381) words
+  static constexpr int Q = WORDS / 4;
+};
+
+// the table point as XYZZ (Montgomery)
+template <class C>
+__device__ __forceinline__ XYZZ<C> ld_tbl(const uint32_t* tbl, size_t idx) {
+  using Fd = Field<typename C::Fp>;
+  constexpr int NW = C::Fp::NW;
+  const uint4* p = reinterpret_cast<const uint4*>(tbl + idx * Tbl<C>::WORDS);
+  uint32_t w[Tbl<C>::WORDS];
+#pragma unroll
+  for (int q = 0; q < Tbl<C>::Q; ++q) {
+    const uint4 v = p[q];
+    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+  }
+  Affine<C> a;
+  a.inf = (w[2 * NW] & 1u) != 0;
+  a.x = Fd::to_mont(Fd::from_words(w));
+  a.y = Fd::to_mont(Fd::from_words(w + NW));
+  return Ec<C>::from_affine(a);
+}
+
+template <class C>
+__device__ __forceinline__ void st_tbl(uint32_t* tbl, size_t idx, const Affine<C>& a) {
+  using Fd = Field<typename C::Fp>;
+  constexpr int NW = C::Fp::NW;
+  uint32_t w[Tbl<C>::WORDS];
+  if (a.inf) {
+#pragma unroll
+    for (int q = 0; q < 2 * NW; ++q) w[q] = 0;
+  } else {
+    Fd::to_words(Fd::from_mont(a.x), w);
+    Fd::to_words(Fd::from_mont(a.y), w + NW);
+  }
+  w[2 * NW] = a.inf ? 1u : 0u;
+#pragma unroll
+  for (int q = 2 * NW + 1; q < Tbl<C>::WORDS; ++q) w[q] = 0;
+  uint4* p = reinterpret_cast<uint4*>(tbl + idx * Tbl<C>::WORDS);
+#pragma unroll
+  for (int q = 0; q < Tbl<C>::Q; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+}
+
+template <class C>
+__device__ __forceinline__ XYZZ<C> dom_ld(const uint32_t* base, size_t idx) {
+  constexpr int N = C::Fp::N;
+  const uint4* p = reinterpret_cast<const uint4*>(base + idx * 4 * N);
+  uint32_t w[4 * N];
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    const uint4 v = p[q];
+    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+  }
+  XYZZ<C> r;
+#pragma unroll
+  for (int j = 0; j < N; ++j) { r.x.l[j] = w[j]; r.y.l[j] = w[N + j]; r.zz.l[j] = w[2 * N + j]; r.zzz.l[j] = w[3 * N + j]; }
+  return r;
+}
+template <class C>
+__device__ __forceinline__ void dom_st(uint32_t* base, size_t idx, const XYZZ<C>& v) {
+  constexpr int N = C::Fp::N;
+  uint32_t w[4 * N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) { w[j] = v.x.l[j]; w[N + j] = v.y.l[j]; w[2 * N + j] = v.zz.l[j]; w[3 * N + j] = v.zzz.l[j]; }
+  uint4* p = reinterpret_cast<uint4*>(base + idx * 4 * N);
+#pragma unroll
+  for (int q = 0; q < N; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+}
+
+template <class F>
+__device__ __forceinline__ Fe<F> dom_arg(const DomFr& a) {
+  Fe<F> r;
+#pragma unroll
+  for (int j = 0; j < F::N; ++j) r.l[j] = a.l[j];
+  return r;
+}
+
+__device__ __forceinline__ uint32_t bitrev(uint32_t i, uint32_t log_len) {
+  return log_len ? __brev(i) >> (32 - log_len) : 0u;
+}
+
+// ---- kernels -----------------------------------------------------------------------------------------------------
+
+// table input: buf[bitrev_N(u)] = s_(n-2-u) (window-0 record of the monomial key) for u <= n-2, O for u >= n-1
+template <class C>
+__global__ __launch_bounds__(128) void dom_load_key_kernel(const uint32_t* recs, uint32_t n, uint32_t log_nn,
+                                                           uint32_t* buf) {
+  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= (1u << log_nn)) return;
+  Affine<C> a;
+  if (u + 2 <= n) {
+    a.inf = load_rec<C>(recs, n - 2 - u, a.x, a.y) & 1u;
+  } else {
+    a.inf = true;
+  }
+  dom_st<C>(buf, bitrev(u, log_nn), Ec<C>::from_affine(a));
+}
+
+// one radix-2 level of half-size h = 2^s over `nvec` vectors of 2^log_len points each (vector j at j << log_len):
+// butterfly t pairs i0 = b*2h + k and i0 + h with twiddle root^(k * len/(2h)), k = t / (len/(2h)), b = t mod
+// (len/(2h)).  root in Montgomery form.
+template <class C>
+__global__ __launch_bounds__(64) void dom_level_kernel(uint32_t* buf, uint32_t nvec, uint32_t log_len, uint32_t s,
+                                                       DomFr root) {
+  using Fr = typename C::Fr;
+  using Frd = Field<Fr>;
+  using Fd = Field<typename C::Fp>;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t lh = log_len - 1;
+  if (g >= (nvec << lh)) return;
+  const uint32_t j = g >> lh, t = g & ((1u << lh) - 1);
+  const uint32_t lnb = lh - s;                            // log2 of the butterflies per twiddle
+  const uint32_t k = t >> lnb, b = t & ((1u << lnb) - 1);
+  const size_t base = (size_t)j << log_len;
+  const size_t i0 = base + ((size_t)b << (s + 1)) + k, i1 = i0 + ((size_t)1 << s);
+  XYZZ<C> B = dom_ld<C>(buf, i1);
+  if (k) {
+    Fe<Fr> pw = dom_arg<Fr>(root), acc = Frd::one();
+    for (uint32_t bits = k << lnb; bits; bits >>= 1) {
+      if (bits & 1u) acc = Frd::mul(acc, pw);
+      pw = Frd::sqr(pw);
+    }
+    uint32_t e[8];
+    Frd::to_words(Frd::from_mont(acc), e);
+    XYZZ<C> r = Ec<C>::infinity();
+#pragma unroll 1
+    for (int q = 7; q >= 0; --q) {
+      const uint32_t word = e[q];
+#pragma unroll 1
+      for (int bit = 31; bit >= 0; --bit) {
+        r = Ec<C>::dbl(r);
+        if ((word >> bit) & 1u) r = Ec<C>::add(r, B);
+      }
+    }
+    B = r;
+  }
+  const XYZZ<C> A = dom_ld<C>(buf, i0);
+  dom_st<C>(buf, i0, Ec<C>::add(A, B));
+  B.y = Fd::neg(B.y);
+  dom_st<C>(buf, i1, Ec<C>::add(A, B));
+}
+
+// Hadamard step: buf[j][bitrev_N(i)] = (chat_j[i] * N^-1) * S_i -- chat: [nvec][N] canonical Fr words (the forward
+// transform of the zero-padded coefficients), S: the table's points.  Double-and-add from the top bit (ec.h: exact
+// for every input); the scalars differ per lane, so unlike the levels' twiddles the branches diverge.
+template <class C>
+__global__ __launch_bounds__(64) void dom_hadamard_kernel(const uint32_t* chat, const uint32_t* tbl, uint32_t nvec,
+                                                          uint32_t log_nn, DomFr ninv, uint32_t* buf) {
+  using Fr = typename C::Fr;
+  using Frd = Field<Fr>;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (nvec << log_nn)) return;
+  const uint32_t j = g >> log_nn, i = g & ((1u << log_nn) - 1);
+  const XYZZ<C> P = ld_tbl<C>(tbl, i);
+  const uint4* cp = reinterpret_cast<const uint4*>(chat + (size_t)g * 8);
+  const uint4 lo = cp[0], hi = cp[1];
+  const uint32_t cw[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  uint32_t e[8];
+  Frd::to_words(Frd::reduce(Frd::mul(Frd::from_words(cw), dom_arg<Fr>(ninv))), e);     // standard * Montgomery
+  XYZZ<C> r = Ec<C>::infinity();
+#pragma unroll 1
+  for (int q = 7; q >= 0; --q) {
+    const uint32_t word = e[q];
+#pragma unroll 1
+    for (int bit = 31; bit >= 0; --bit) {
+      r = Ec<C>::dbl(r);
+      if ((word >> bit) & 1u) r = Ec<C>::add(r, P);
+    }
+  }
+  dom_st<C>(buf, ((size_t)j << log_nn) + bitrev(i, log_nn), r);
+}
+
+// extraction into the bit-reversed input of the size-n transform: dst[j][bitrev_n(m)] = src[j][n-1+m] for m <= n-2,
+// O for m = n-1 (src: [nvec][2n], dst: [nvec][n])
+template <class C>
+__global__ __launch_bounds__(64) void dom_extract_kernel(const uint32_t* src, uint32_t nvec, uint32_t log_n,
+                                                         uint32_t* dst) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (nvec << log_n)) return;
+  const uint32_t n = 1u << log_n;
+  const uint32_t j = g >> log_n, m = g & (n - 1);
+  const XYZZ<C> v = m + 1 < n ? dom_ld<C>(src, ((size_t)j << (log_n + 1)) + n - 1 + m) : Ec<C>::infinity();
+  dom_st<C>(dst, ((size_t)j << log_n) + bitrev(m, log_n), v);
+}
+
+// table record i = buf[i] as compact affine
+template <class C>
+__global__ __launch_bounds__(64) void dom_finish_table_kernel(const uint32_t* buf, uint32_t count, uint32_t* tbl) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  st_tbl<C>(tbl, i, Ec<C>::to_affine(dom_ld<C>(buf, i)));
+}
+
+// proofs: buf[i] as canonical affine words x[NW] y[NW] (kzg_open's point format) and a flag byte
+template <class C>
+__global__ __launch_bounds__(64) void dom_finish_proofs_kernel(const uint32_t* buf, uint32_t count, uint32_t* out_xy,
+                                                               uint8_t* out_inf) {
+  using F = typename C::Fp;
+  using Fd = Field<F>;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const Affine<C> a = Ec<C>::to_affine(dom_ld<C>(buf, i));
+  uint32_t w[2 * F::NW];
+  if (a.inf) {
+#pragma unroll
+    for (int q = 0; q < 2 * F::NW; ++q) w[q] = 0;
+  } else {
+    Fd::to_words(Fd::from_mont(a.x), w);
+    Fd::to_words(Fd::from_mont(a.y), w + F::NW);
+  }
+  uint4* p = reinterpret_cast<uint4*>(out_xy + (size_t)i * 2 * F::NW);
+#pragma unroll
+  for (int q = 0; q < 2 * F::NW / 4; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  out_inf[i] = a.inf ? 1 : 0;
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------
+
+constexpr uint32_t DOM_MAX_LOG = 20;
+// scratch of one call: chunks of vectors are sized to stay below this (kzg_ctx_set_tuning "open_domain_chunk" forces
+// the chunk instead)
+constexpr size_t DOM_SCRATCH_BYTES = (size_t)2 << 30;
+constexpr uint32_t DOM_MAX_CHUNK = 1024;       // keeps every launch below 2^31 threads (N <= 2^21)
+
+template <class F>
+DomFr dom_fr(const Fe<F>& v) {
+  DomFr a;
+  memcpy(a.l, v.l, sizeof(a.l));
+  return a;
+}
+
+// small integer -> Montgomery element
+template <class F>
+Fe<F> fr_small(uint32_t v) {
+  uint32_t w[8] = {v, 0, 0, 0, 0, 0, 0, 0};
+  return Field<F>::to_mont(Field<F>::from_words(w));
+}
+
+template <class F>
+Fe<F> fr_pow_words(const Fe<F>& base, const uint32_t* e) {
+  using Fd = Field<F>;
+  Fe<F> acc = Fd::one();
+  for (int k = 7; k >= 0; --k)
+    for (int b = 31; b >= 0; --b) {
+      acc = Fd::sqr(acc);
+      if ((e[k] >> b) & 1u) acc = Fd::mul(acc, base);
+    }
+  return acc;
+}
+
+// w^(2^(log_len-1)) = -1 (w canonical words; Montgomery arithmetic)
+template <class F>
+bool dom_primitive(const Fe<F>& w_mont, uint32_t log_len) {
+  using Fd = Field<F>;
+  Fe<F> x = w_mont;
+  for (uint32_t q = 1; q < log_len; ++q) x = Fd::sqr(x);
+  return Fd::eq(x, Fd::neg(Fd::one()));
+}
+
+// the library's primitive 2^log_len-th root: g^((r-1) / 2^log_len), g = 5 (BN254) / 7 (BLS12-381), Montgomery
+template <class C>
+Fe<typename C::Fr> dom_omega(uint32_t log_len) {
+  using F = typename C::Fr;
+  uint32_t e[8];
+  for (int k = 0; k < 8; ++k) e[k] = F::PW[k];
+  e[0] -= 1;                                           // r - 1 (r is odd)
+  for (int k = 0; k < 8; ++k) {                        // >> log_len (< 32)
+    const uint32_t hi = k + 1 < 8 ? e[k + 1] : 0u;
+    e[k] = (e[k] >> log_len) | (log_len ? hi << (32 - log_len) : 0u);
+  }
+  return fr_pow_words<F>(fr_small<F>(C::ID == 0 ? 5u : 7u), e);
+}
+
+template <class C>
+int launch_levels(Ctx* c, uint32_t* buf, uint32_t nvec, uint32_t log_len, const Fe<typename C::Fr>& root) {
+  const size_t threads = (size_t)nvec << (log_len - 1);
+  const uint32_t blocks = (uint32_t)((threads + 63) / 64);
+  for (uint32_t lv = 0; lv < log_len; ++lv)
+    hipLaunchKernelGGL(dom_level_kernel<C>, dim3(blocks), dim3(64), 0, c->stream, buf, nvec, log_len, lv,
+                       dom_fr<typename C::Fr>(root));
+  KZG_HIP(c, hipGetLastError());
+  return KZG_OK;
+}
+
+template <class C>
+size_t xyzz_bytes() { return (size_t)4 * C::Fp::N * 4; }
+
+}  // namespace
+
+// A table of one monomial key and one domain size: N = 2n compact affine points DFT_G1,N(s^) with root omega.
+struct DomainTable {
+  int curve = 0;
+  uint32_t log_n = 0;
+  size_t n = 0;
+  uint32_t* d_tbl = nullptr;
+};
+
+namespace {
+
+template <class C>
+int domain_table_t(Ctx* c, const Srs* mono, uint32_t log_n, DomainTable** out) {
+  using F = typename C::Fr;
+  if (mono->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
+  if (mono->basis != SRS_MONOMIAL) return set_err(c, KZG_ERR_ARG, "kzg_domain_table_create: the key must be monomial");
+  if (log_n < 1 || log_n > DOM_MAX_LOG) return set_err(c, KZG_ERR_ARG, "kzg_domain_table_create: log_n must be in [1, 20]");
+  const uint32_t n = 1u << log_n, log_nn = log_n + 1, nn = 2 * n;
+  if (mono->n < n) return set_err(c, KZG_ERR_ARG, "kzg_domain_table_create: monomial key shorter than the domain");
+  const Fe<F> omega = dom_omega<C>(log_nn);
+  if (!dom_primitive<F>(omega, log_nn)) return set_err(c, KZG_ERR_ARG, "kzg_domain_table_create: no 2n-th root");
+  DomainTable* t = new DomainTable();
+  t->curve = c->curve;
+  t->log_n = log_n;
+  t->n = n;
+  uint32_t* d_buf = nullptr;
+  auto fail = [&](int code) { hipFree(d_buf); hipFree(t->d_tbl); delete t; return code; };
+  if (hipMalloc(reinterpret_cast<void**>(&t->d_tbl), (size_t)nn * Tbl<C>::WORDS * 4) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&d_buf), (size_t)nn * xyzz_bytes<C>()) != hipSuccess)
+    return fail(set_err(c, KZG_ERR_ALLOC, "hipMalloc(domain table)"));
+  {
+    ProfScope ps(c, "domain_table");
+    hipLaunchKernelGGL(dom_load_key_kernel<C>, dim3((nn + 127) / 128), dim3(128), 0, c->stream, mono->recs, n, log_nn,
+                       d_buf);
+    int rc = launch_levels<C>(c, d_buf, 1, log_nn, omega);
+    if (rc) return fail(rc);
+    hipLaunchKernelGGL(dom_finish_table_kernel<C>, dim3((nn + 63) / 64), dim3(64), 0, c->stream, d_buf, nn,
+                       t->d_tbl);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, "domain table", e));
+  }
+  hipError_t e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, "domain table", e));
+  hipFree(d_buf);
+  d_buf = nullptr;
+  *out = t;
+  return KZG_OK;
+}
+
+// polys: device coefficient vectors (host_polys: host memory, staged per vector); outputs in host memory
+template <class C>
+int open_domain_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_polys, const size_t* lens, size_t b,
+                  size_t stride, const uint32_t* w_words, uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
+  using F = typename C::Fr;
+  using Fd = Field<F>;
+  using Fp = typename C::Fp;
+  if (t->curve != c->curve) return set_err(c, KZG_ERR_ARG, "domain table belongs to another curve");
+  const uint32_t log_n = t->log_n, log_nn = log_n + 1;
+  const size_t n = t->n, nn = 2 * n;
+  if (!dom_primitive<F>(Fd::to_mont(Fd::from_words(w_words)), log_n))
+    return set_err(c, KZG_ERR_ARG, "kzg_open_domain: w is not a primitive n-th root of unity");
+  for (size_t j = 0; j < b; ++j) {
+    if (lens[j] > n) return set_err(c, KZG_ERR_DEGREE, "polynomial longer than the domain");
+    if (lens[j] > stride) return set_err(c, KZG_ERR_ARG, "kzg_open_domain: lens[j] > stride");
+  }
+  if (b == 0) return KZG_OK;
+  // per vector: the size-N XYZZ buffer (later the proofs' output), the size-n XYZZ buffer, N Fr elements
+  const size_t per_vec = nn * xyzz_bytes<C>() + n * xyzz_bytes<C>() + nn * 32;
+  size_t chunk = c->tune_open_domain_chunk > 0 ? (size_t)c->tune_open_domain_chunk
+                                               : std::max<size_t>(1, DOM_SCRATCH_BYTES / per_vec);
+  chunk = std::min<size_t>({chunk, b, DOM_MAX_CHUNK});
+  int rc = ensure_buf(c, c->dom_tmp, chunk * per_vec);
+  if (rc) return rc;
+  uint32_t* d_big = static_cast<uint32_t*>(c->dom_tmp.p);                              // [chunk][N] XYZZ
+  uint32_t* d_small = d_big + chunk * nn * 4 * Fp::N;                                  // [chunk][n] XYZZ
+  uint32_t* d_fr = d_small + chunk * n * 4 * Fp::N;                                    // [chunk][N] Fr words
+  uint32_t* d_oxy = d_big;                                                             // [chunk][n][2 NW] words
+  uint8_t* d_oinf = reinterpret_cast<uint8_t*>(d_big + chunk * n * 2 * Fp::NW);        // [chunk][n] flags
+
+  const Fe<F> omega = dom_omega<C>(log_nn);
+  const Fe<F> omega_inv = Fd::inv(omega);
+  uint32_t omega_words[8], nw[8] = {0};
+  Fd::to_words(Fd::from_mont(omega), omega_words);
+  nw[log_nn >> 5] = 1u << (log_nn & 31);
+  const Fe<F> ninv = Fd::reduce(Fd::inv(Fd::to_mont(Fd::from_words(nw))));
+  const Fe<F> w = Fd::to_mont(Fd::from_words(w_words));
+  const hipMemcpyKind kind = host_polys ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+
+  ProfScope ps(c, "open_domain");
+  for (size_t j0 = 0; j0 < b; j0 += chunk) {
+    const uint32_t m = (uint32_t)std::min(chunk, b - j0);
+    // c^ = DFT_N(c), zero-padded
+    KZG_HIP(c, hipMemsetAsync(d_fr, 0, (size_t)m * nn * 32, c->stream));
+    for (uint32_t j = 0; j < m; ++j)
+      if (lens[j0 + j])
+        KZG_HIP(c, hipMemcpyAsync(d_fr + (size_t)j * nn * 8, polys + (j0 + j) * stride * 8, lens[j0 + j] * 32, kind,
+                                  c->stream));
+    if ((rc = ntt_run_device(c, d_fr, log_nn, omega_words, 0, m))) return rc;
+    const size_t big = (size_t)m * nn, small = (size_t)m * n;
+    hipLaunchKernelGGL(dom_hadamard_kernel<C>, dim3((uint32_t)((big + 63) / 64)), dim3(64), 0, c->stream, d_fr,
+                       t->d_tbl, m, log_nn, dom_fr<F>(ninv), d_big);
+    KZG_HIP(c, hipGetLastError());
+    if ((rc = launch_levels<C>(c, d_big, m, log_nn, omega_inv))) return rc;
+    hipLaunchKernelGGL(dom_extract_kernel<C>, dim3((uint32_t)((small + 63) / 64)), dim3(64), 0, c->stream, d_big, m,
+                       log_n, d_small);
+    KZG_HIP(c, hipGetLastError());
+    if ((rc = launch_levels<C>(c, d_small, m, log_n, w))) return rc;
+    hipLaunchKernelGGL(dom_finish_proofs_kernel<C>, dim3((uint32_t)((small + 63) / 64)), dim3(64), 0, c->stream,
+                       d_small, (uint32_t)small, d_oxy, d_oinf);
+    KZG_HIP(c, hipGetLastError());
+    const size_t pt_words = 2 * Fp::NW;
+    KZG_HIP(c, hipMemcpyAsync(out_xy + j0 * n * pt_words / 2, d_oxy, small * pt_words * 4, hipMemcpyDeviceToHost,
+                              c->stream));
+    KZG_HIP(c, hipMemcpyAsync(out_inf + j0 * n, d_oinf, small, hipMemcpyDeviceToHost, c->stream));
+    if (eval_out) {   // y = DFT_n(c) with w, in the Fr buffer the Hadamard step has consumed
+      KZG_HIP(c, hipMemsetAsync(d_fr, 0, small * 32, c->stream));
+      for (uint32_t j = 0; j < m; ++j)
+        if (lens[j0 + j])
+          KZG_HIP(c, hipMemcpyAsync(d_fr + (size_t)j * n * 8, polys + (j0 + j) * stride * 8, lens[j0 + j] * 32, kind,
+                                    c->stream));
+      if ((rc = ntt_run_device(c, d_fr, log_n, w_words, 0, m))) return rc;
+      KZG_HIP(c, hipMemcpyAsync(eval_out + j0 * n * 4, d_fr, small * 32, hipMemcpyDeviceToHost, c->stream));
+    }
+    // the next chunk overwrites the buffers the copies read
+    KZG_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return KZG_OK;
+}
+
+}  // namespace
+
+int domain_table_create(Ctx* c, const Srs* mono, uint32_t log_n, DomainTable** out) {
+  return c->curve == 0 ? domain_table_t<Bn254>(c, mono, log_n, out) : domain_table_t<Bls12_381>(c, mono, log_n, out);
+}
+void domain_table_free(DomainTable* t) {
+  if (!t) return;
+  hipFree(t->d_tbl);
+  delete t;
+}
+size_t domain_table_size(const DomainTable* t) { return t ? t->n : 0; }
+int open_domain(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_polys, const size_t* lens, size_t b,
+                size_t stride, const uint32_t* w_words, uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
+  return c->curve == 0
+             ? open_domain_t<Bn254>(c, t, polys, host_polys, lens, b, stride, w_words, out_xy, out_inf, eval_out)
+             : open_domain_t<Bls12_381>(c, t, polys, host_polys, lens, b, stride, w_words, out_xy, out_inf, eval_out);
+}
+
+}  // namespace kzg

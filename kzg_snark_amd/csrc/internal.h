@@ -62,12 +62,14 @@ struct Ctx {
   DevBuf poly_tmp[4];     // open(): combined polynomial + suffix values; scratch of the vector primitives
   DevBuf scan_tmp;        // open(): chunk values, tile aggregates, power tables (kept between the shard calls)
   DevBuf lagr_tmp;        // lagrange.hip: combined values, denominators, inverses, quotient, partial sums
+  DevBuf dom_tmp;         // domain.hip: G1 transform buffers and the Fr vectors of one chunk of kzg_open_domain
   size_t open_shard_n = 0;                // slice length between kzg_open_shard_begin / _finish
   uint32_t open_shard_tb = 0;             // tile width the slice's aggregates were formed with
   // kzg_ctx_set_tuning: 0 = the library's own choice
   int tune_ntt_tile_log = 0;              // LDS tile of the transform (8..12)
   int tune_open_tb = 0;                   // threads per tile of the opening's scan (128 | 256)
   int tune_open_direct_max = 0;           // tiles up to which every tile sums all aggregates above it
+  int tune_open_domain_chunk = 0;         // vectors per chunk of kzg_open_domain
   int last_ntt_tile_log = 0;              // what the last transform used (kzg_prof_read "ntt_tile_log")
   void* msm_work = nullptr;               // MsmWork (msm.hip)
   bool prof_on = false;

@@ -44,6 +44,14 @@ int open_evals_device(Ctx* c, const Srs* s, const uint32_t* d_vals, const size_t
 int fr_eval_lagrange(Ctx* c, uint32_t log_n, const uint32_t* w_words, size_t len, const uint32_t* d_vals,
                      const uint32_t* z_words, uint64_t* out);
 
+// domain.hip: all n proofs on a domain (FK20).  A table holds DFT_G1,2n of the reversed monomial key.
+struct DomainTable;
+int domain_table_create(Ctx* c, const Srs* mono, uint32_t log_n, DomainTable** out);
+void domain_table_free(DomainTable* t);
+size_t domain_table_size(const DomainTable* t);
+int open_domain(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_polys, const size_t* lens, size_t b,
+                size_t stride, const uint32_t* w_words, uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out);
+
 // One MSM per polynomial; scalars device-resident, results to host memory (synchronises).
 // drain = false leaves up to four polynomials in flight; their outputs are written when their
 // slot is recycled by a later call or by commit_flush().

@@ -75,6 +75,20 @@ class LagrangeKey(CommitmentKey):
         self.log_n = self.n.bit_length() - 1
 
 
+class DomainTable:
+    """The FK20 table of one monomial key and domain size n (KZG.domain_table): what open_domain needs to compute all
+    n proofs on a domain at once.  Holds 2n affine points on the device."""
+
+    def __init__(self, ctx, table, n):
+        self._ctx = ctx
+        self.table = table
+        self.n = int(n)
+        self.log_n = self.n.bit_length() - 1
+
+    def __len__(self):
+        return self.n
+
+
 class KZG:
     def __init__(self, curve_type="bn254"):
         if curve_type not in _curve.CURVES:
@@ -96,6 +110,7 @@ class KZG:
         self.X = self.R.gen()
         self._ctx = None
         self._loaded = {}          # id(list ck) -> (CommitmentKey, fingerprint); at most _KEY_CACHE entries, LRU
+        self._tables = {}          # (id(CommitmentKey), n) -> (CommitmentKey, DomainTable); at most _TABLE_CACHE, LRU
 
     # ---- py_ecc-shaped single-point operations (host; used by the verifiers) ------
     def _grp(self, pt):
@@ -124,6 +139,7 @@ class KZG:
             self._ctx = _native.get_context(self.curve_type)
         return self._ctx
 
+    _TABLE_CACHE = 2               # FK20 tables kept per (key, n) (2^20: 235 MB on BLS12-381)
     _KEY_CACHE = 2                 # device tables kept for list-form keys (a 2^20-point table is 1.7 GiB)
 
     @staticmethod
@@ -433,3 +449,89 @@ class KZG:
         d = torch.from_numpy(arr.view(np.int64)).to(f"cuda:{ctx.device}", non_blocking=False)
         torch.cuda.synchronize(ctx.device)
         return self.Fq(ctx.eval_lagrange(log_n, w, len(vals), d.data_ptr(), z))
+
+    # ---- every proof on a domain at once (FK20: Feist-Khovratovich, "Fast amortized KZG proofs", 2020) -------------
+    _DOMAIN_MAX = 1 << 20
+
+    def domain_table(self, ck, n):
+        """The FK20 table of the first n points of a monomial key (CommitmentKey or list of points) for domain size n
+        (a power of two, 2 <= n <= 2^20).  Built on the device; tables of a CommitmentKey are cached per (key, n)."""
+        if isinstance(ck, (LagrangeKey, DomainTable)):
+            raise TypeError("domain_table needs a monomial key (setup / load_key / a list of points)")
+        n = int(n)
+        if n < 2 or n & (n - 1) or n > self._DOMAIN_MAX:
+            raise ValueError(f"domain size {n} is not a power of two in [2, 2^20]")
+        if len(ck) < n:
+            raise ValueError(f"commitment key of {len(ck)} points is shorter than the domain ({n})")
+        key = self._key(ck)
+        hit = self._tables.get((id(key), n))
+        if hit and hit[0] is key:
+            self._tables[(id(key), n)] = self._tables.pop((id(key), n))     # most recently used last
+            return hit[1]
+        ctx = self._context()
+        table = DomainTable(ctx, ctx.domain_table(key.srs, n.bit_length() - 1), n)
+        self._tables.pop((id(key), n), None)
+        while len(self._tables) >= self._TABLE_CACHE:
+            old = next(iter(self._tables))
+            self._tables.pop(old)[1].table.close()
+        self._tables[(id(key), n)] = (key, table)
+        return table
+
+    def _domain_call(self, ck_or_table, polynomials, n, w):
+        """Host-side checks shared by open_domain / open_domain_each, before any device work: -> (coefficient lists,
+        n, w).  n defaults to the smallest power of two >= the longest polynomial (setup_lagrange's rule)."""
+        if isinstance(ck_or_table, LagrangeKey):
+            raise TypeError("open_domain needs a monomial key or a DomainTable, not a LagrangeKey")
+        coeffs = [self._coeffs(p) for p in polynomials]
+        longest = max((len(c) for c in coeffs), default=0)
+        if isinstance(ck_or_table, DomainTable):
+            if n is not None and int(n) != ck_or_table.n:
+                raise ValueError(f"n = {n} differs from the table's domain size {ck_or_table.n}")
+            n = ck_or_table.n
+        elif n is None:
+            n = 2
+            while n < longest:
+                n *= 2
+        n = int(n)
+        if n < 2 or n & (n - 1) or n > self._DOMAIN_MAX:
+            raise ValueError(f"domain size {n} is not a power of two in [2, 2^20]")
+        if longest > n:
+            raise ValueError(f"polynomial of {longest} coefficients exceeds the domain size {n}")
+        if not isinstance(ck_or_table, DomainTable) and len(ck_or_table) < n:
+            raise ValueError(f"commitment key of {len(ck_or_table)} points is shorter than the domain ({n})")
+        _, w = self._domain(n, w)
+        return coeffs, n, w
+
+    def open_domain(self, ck_or_table, polynomials, xi, n=None, w=None):
+        """open(ck, polynomials, w^i, xi) for every i < n at once: a list of n proofs.  The xi^(j+1) combination runs
+        on the device (as in open), then FK20 on the combined polynomial.  w defaults to Fq.root_of_unity(n)."""
+        coeffs, n, w = self._domain_call(ck_or_table, polynomials, n, w)
+        xi = int(self.Fq(xi))
+        table = ck_or_table if isinstance(ck_or_table, DomainTable) else self.domain_table(ck_or_table, n)
+        ctx = self._context()
+        r = self.curve_order
+        arr, lens, stride = self._pack(coeffs)
+        length = max(max(lens, default=0), 1)
+        import torch
+        dev = f"cuda:{ctx.device}"
+        d_in = torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).to(dev, non_blocking=False)
+        d_comb = torch.zeros((length, 4), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(ctx.device)
+        ptrs = [d_in.data_ptr() + j * stride * 32 for j in range(len(coeffs))]
+        scalars, x = [], xi
+        for _ in coeffs:
+            scalars.append(x)                                                  # xi^(j+1): kzg.py:148-150
+            x = x * xi % r
+        ctx.vec_lincomb(length, ptrs, lens, scalars, d_comb.data_ptr())
+        xy, inf, _ = ctx.open_domain(table.table, d_comb.data_ptr(), [length], length, w, device=True, evals=False)
+        return self._points(xy[0], inf[0])
+
+    def open_domain_each(self, ck_or_table, polynomials, n=None, w=None):
+        """All n proofs of each polynomial on its own: result[j][i] == open(ck, [polynomials[j]], w^i, 1)."""
+        coeffs, n, w = self._domain_call(ck_or_table, polynomials, n, w)
+        if not coeffs:
+            return []
+        table = ck_or_table if isinstance(ck_or_table, DomainTable) else self.domain_table(ck_or_table, n)
+        arr, lens, stride = self._pack(coeffs)
+        xy, inf, _ = self._context().open_domain(table.table, np.ascontiguousarray(arr), lens, stride, w, evals=False)
+        return [self._points(xy[j], inf[j]) for j in range(len(coeffs))]
