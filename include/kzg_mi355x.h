@@ -80,7 +80,8 @@ int kzg_ctx_synchronize(kzg_ctx* ctx);
  *   "ntt_tile_log"       log2 of the transform's LDS tile, 8..12 (default: 11 alone, 10 beside an accumulate kernel)
  *   "open_tile_threads"  threads per tile of the opening's scan, 128 | 256 (default: 256 alone, 128 beside one)
  *   "open_direct_tiles"  tile count up to which every tile sums all tile aggregates above it (default 1024)
- *   "open_domain_chunk"  vectors per chunk of kzg_open_domain*, 1..1024 (default: as many as ~2 GiB of scratch holds) */
+ *   "open_domain_chunk"  vectors per chunk of kzg_open_domain*, 1..1024 (default: as many as ~2 GiB of scratch holds)
+ *   "open_cosets_chunk"  vectors per chunk of kzg_open_cosets*, 1..1024 (default: as many as ~2 GiB of scratch holds) */
 int kzg_ctx_set_tuning(kzg_ctx* ctx, const char* key, int64_t value);
 
 /* ---- NTT: replaces fft_ff (fft_ff.py:3-37) and ifft_ff (fft_ff.py:39-58) -------------
@@ -255,6 +256,46 @@ int kzg_open_domain(kzg_ctx* ctx, const kzg_domain_table* t, const uint64_t* pol
 int kzg_open_domain_device(kzg_ctx* ctx, const kzg_domain_table* t, const void* d_polys, const size_t* lens, size_t b,
                            size_t stride, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf,
                            uint64_t* eval_out);
+/* ---- coset openings: the values at l = 2^log_l points with ONE proof (FK20's multi-reveal) ----------------------
+ * A coset (h, zeta): zeta a primitive l-th root of unity (zeta = 1 for l = 1), h != 0, the points x_k = h zeta^k
+ * (k < l), vanishing polynomial Z = X^l - a with a = h^l.  For p(X) = sum_(t<n) c_t X^t the remainder is
+ * rho = p mod Z, rho_j = sum_s c_(sl+j) a^s (j < l), the quotient q = (p - rho) / Z, and the proof pi = [q(tau)] G1
+ * (l = 1: kzg_open at z = h).  Check: e([p(tau)] - [rho(tau)], G2) = e(pi, [tau^l] G2 - a G2); the verifier recovers
+ * rho from the values y_k = p(x_k) as rho_j = h^-j l^-1 sum_k y_k zeta^(-jk).
+ *   kzg_coset_table_create  the table of a monomial key for n = 2^log_n (1 <= log_n <= 20) and l = 2^log_l
+ *                           (0 <= log_l <= log_n - 1): l sub-tables of 2m points, m = n/l -- 2n affine points for
+ *                           every l.  KZG_ERR_ARG as for kzg_domain_table_create.  A table from
+ *                           kzg_domain_table_create is the l = 1 table; kzg_domain_table_size / _free apply to both;
+ *                           kzg_open_domain* refuses a table with l > 1 (KZG_ERR_ARG).
+ *   kzg_open_cosets         every coset of a domain {w^t, t < N}, N = 2^log_N (log_n <= log_N <= min(log_n + 2, 21)),
+ *                           w a primitive N-th root: coset i < N/l is (h = w^i, zeta = w^(N/l)), its value k is
+ *                           p(w^(i + k N/l)).  Vectors `stride` elements apart, vector j having lens[j] <= n
+ *                           coefficients (KZG_ERR_DEGREE above n; KZG_ERR_ARG for lens[j] > stride, a w that is not a
+ *                           primitive N-th root, log_N out of range).  out_xy / out_inf: [b][N/l] proofs in
+ *                           kzg_open's point format; eval_out ([b][N/l][l][4] limbs, may be NULL) the values.
+ *                           The l Toeplitz products of size m are summed before one inverse G1 DFT of size 2m, and
+ *                           the final G1 DFT has size N/l (root w^l).  Chunks bound the scratch (tuning key
+ *                           "open_cosets_chunk").  Synchronises; the commit pipeline is not touched.
+ *   kzg_open_coset          ONE coset (0 <= log_l <= 12) of the combination sum_j xi^(j+1) p_j of k <= 64 polynomials
+ *                           (kzg_open's rule): the quotient by X^l - a on the device, then one MSM against a
+ *                           monomial key (KZG_ERR_ARG for a Lagrange key, a zeta that is not a primitive l-th root or
+ *                           h = 0; KZG_ERR_DEGREE for lens[j] above the key, before any work is queued).  eval_out
+ *                           ([l][4] limbs, may be NULL) receives the combination's values at h zeta^k.  Synchronises
+ *                           like kzg_open; pending kzg_commit_device_async results stay correct. */
+int kzg_coset_table_create(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_n, uint32_t log_l,
+                           kzg_domain_table** out);
+int kzg_open_cosets(kzg_ctx* ctx, const kzg_domain_table* t, const uint64_t* polys, const size_t* lens, size_t b,
+                    size_t stride, uint32_t log_N, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf,
+                    uint64_t* eval_out);
+int kzg_open_cosets_device(kzg_ctx* ctx, const kzg_domain_table* t, const void* d_polys, const size_t* lens, size_t b,
+                           size_t stride, uint32_t log_N, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf,
+                           uint64_t* eval_out);
+int kzg_open_coset(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* polys, const size_t* lens, size_t k,
+                   size_t stride, uint32_t log_l, const uint64_t h[4], const uint64_t zeta[4], const uint64_t xi[4],
+                   uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out);
+int kzg_open_coset_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,
+                          size_t stride, uint32_t log_l, const uint64_t h[4], const uint64_t zeta[4],
+                          const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out);
 /* ---- KZG.open on ONE polynomial set partitioned by coefficient range across GPUs ----------------
  * Rank g holds coefficients [lo_g, hi_g) of every polynomial (the same ranges for all) and a key
  * shard.  kzg_open_shard_begin combines the slices (sum xi^(i+1) p_i) and returns the slice
@@ -308,7 +349,9 @@ int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size
  * "msm_finalize", "msm_reduce", "open_poly" (ONE span per kzg_open*: combination, scan and division),
  * "open_shard_poly" (one per kzg_open_shard_begin and one per _finish), "srs_lagrange" (one per Lagrange key
  * built), "open_evals_poly" (ONE per kzg_open_evals*: combination, value and quotient), "domain_table" (one per
- * kzg_domain_table_create), "open_domain" (ONE per kzg_open_domain*: every chunk, transform and copy).  kzg_prof_read synchronises the
+ * kzg_domain_table_create), "open_domain" (ONE per kzg_open_domain*: every chunk, transform and copy), "coset_table"
+ * (one per kzg_coset_table_create), "open_cosets" (ONE per kzg_open_cosets*), "open_coset_poly" (ONE per
+ * kzg_open_coset*: combination, division and remainder).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.
  * Two names are not spans: "msm_accumulate_shader_mhz" and "ntt_pass_shader_mhz" return (in *total_ms) the shader
  * clock in MHz the accumulate / NTT kernel ran at since the last reset -- s_memtime over s_memrealtime ticks of its

@@ -91,6 +91,15 @@ SIGNATURES = {
     "kzg_open_domain": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
     "kzg_open_domain_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp,
                                               _vp]),
+    "kzg_coset_table_create": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp)]),
+    "kzg_open_cosets": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, _vp, _vp,
+                                       _vp, _vp]),
+    "kzg_open_cosets_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32,
+                                              _vp, _vp, _vp, _vp]),
+    "kzg_open_coset": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, _vp, _vp,
+                                      _vp, _vp, _vp, _vp]),
+    "kzg_open_coset_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32,
+                                             _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -376,6 +385,42 @@ class Context:
                        _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev) if evals else None))
         return out_xy, out_inf, ev
 
+    # ---- coset openings (FK20 multi-reveal, and one coset by division)
+    def coset_table(self, monomial, log_n, log_l):
+        """The coset table of the first 2^log_n points of a monomial key for cosets of 2^log_l points."""
+        h = ctypes.c_void_p()
+        self._check(lib().kzg_coset_table_create(self._h, monomial._h, int(log_n), int(log_l), ctypes.byref(h)))
+        return DomainTable(self, h, 1 << int(log_n), 1 << int(log_l))
+
+    def open_cosets(self, table, polys, lens, stride, log_N, w, device=False, evals=True):
+        """The N/l coset proofs of each of len(lens) coefficient vectors (uint64[b, stride, 4] host array, or a device
+        pointer with device=True) on the domain {w^t, t < N = 2^log_N}: (out_xy uint64[b, N/l, 2*fp_limbs],
+        out_inf uint8[b, N/l], evals uint64[b, N/l, l, 4] or None)."""
+        b, l = len(lens), table.l
+        cosets = (1 << int(log_N)) // l
+        lens_a = np.asarray(lens, dtype=np.uint64)
+        out_xy = np.zeros((b, cosets, 2 * self.fp_limbs), dtype=np.uint64)
+        out_inf = np.zeros((b, cosets), dtype=np.uint8)
+        ev = np.zeros((b, cosets, l, 4), dtype=np.uint64) if evals else None
+        fn = lib().kzg_open_cosets_device if device else lib().kzg_open_cosets
+        self._check(fn(self._h, table._h, _as_vp(polys), _as_vp(lens_a), b, stride, int(log_N),
+                       _as_vp(int_to_words(int(w))), _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev) if evals else None))
+        return out_xy, out_inf, ev
+
+    def open_coset(self, srs, polys, lens, stride, log_l, h, zeta, xi, device=False):
+        """One coset proof of the xi-combination of len(lens) polynomials at h * zeta^k, k < 2^log_l:
+        (out_xy uint64[2*fp_limbs], out_inf uint8[1], values uint64[l, 4])."""
+        k = len(lens)
+        lens_a = np.asarray(lens, dtype=np.uint64)
+        out_xy = np.zeros(2 * self.fp_limbs, dtype=np.uint64)
+        out_inf = np.zeros(1, dtype=np.uint8)
+        ev = np.zeros((1 << int(log_l), 4), dtype=np.uint64)
+        fn = lib().kzg_open_coset_device if device else lib().kzg_open_coset
+        self._check(fn(self._h, srs._h, _as_vp(polys), _as_vp(lens_a), k, stride, int(log_l),
+                       _as_vp(int_to_words(int(h))), _as_vp(int_to_words(int(zeta))), _as_vp(int_to_words(int(xi))),
+                       _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev)))
+        return out_xy, out_inf, ev
+
     # ---- commit / open on host buffers
     def commit(self, srs, scalars, lens, stride):
         """scalars: uint64[n_polys, stride, 4]; lens: per-polynomial coefficient counts."""
@@ -515,12 +560,14 @@ class Srs:
 
 
 class DomainTable:
-    """FK20 table of one monomial key and domain size n (kzg_domain_table): 2n affine points on the device."""
+    """FK20 table of one monomial key, domain size n and coset size l (kzg_domain_table; l = 1 from domain_table):
+    2n affine points on the device."""
 
-    def __init__(self, ctx, h, n):
+    def __init__(self, ctx, h, n, l=1):
         self.ctx = ctx
         self._h = h
         self.n = n
+        self.l = l
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):

@@ -220,6 +220,9 @@ int kzg_ctx_set_tuning(kzg_ctx* ctx, const char* key, int64_t value) {
   } else if (k == "open_domain_chunk") {
     if (value < 0 || value > 1024) return set_err(c, KZG_ERR_ARG, "open_domain_chunk: 0 .. 1024");
     c->tune_open_domain_chunk = (int)value;
+  } else if (k == "open_cosets_chunk") {
+    if (value < 0 || value > 1024) return set_err(c, KZG_ERR_ARG, "open_cosets_chunk: 0 .. 1024");
+    c->tune_open_cosets_chunk = (int)value;
   } else {
     return set_err(c, KZG_ERR_ARG, "kzg_ctx_set_tuning: unknown key");
   }
@@ -632,6 +635,73 @@ int kzg_open_domain(kzg_ctx* ctx, const kzg_domain_table* t, const uint64_t* pol
   KZG_HIP(c, hipSetDevice(c->device));
   return open_domain(c, t->t, reinterpret_cast<const uint32_t*>(polys), /*host_polys=*/true, lens, b, stride,
                      reinterpret_cast<const uint32_t*>(w), out_xy, out_inf, eval_out);
+}
+
+int kzg_coset_table_create(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_n, uint32_t log_l,
+                           kzg_domain_table** out) {
+  if (!ctx || !monomial || !out) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  *out = nullptr;
+  KZG_HIP(c, hipSetDevice(c->device));
+  DomainTable* t = nullptr;
+  int rc = coset_table_create(c, monomial->s, log_n, log_l, &t);
+  if (rc) return rc;
+  *out = new kzg_domain_table{t};
+  return KZG_OK;
+}
+
+int kzg_open_cosets_device(kzg_ctx* ctx, const kzg_domain_table* t, const void* d_polys, const size_t* lens, size_t b,
+                           size_t stride, uint32_t log_N, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf,
+                           uint64_t* eval_out) {
+  if (!ctx || !t || !w || (b && (!lens || !d_polys || !out_xy || !out_inf))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return open_cosets(c, t->t, static_cast<const uint32_t*>(d_polys), /*host_polys=*/false, lens, b, stride, log_N,
+                     reinterpret_cast<const uint32_t*>(w), out_xy, out_inf, eval_out);
+}
+
+int kzg_open_cosets(kzg_ctx* ctx, const kzg_domain_table* t, const uint64_t* polys, const size_t* lens, size_t b,
+                    size_t stride, uint32_t log_N, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf,
+                    uint64_t* eval_out) {
+  if (!ctx || !t || !w || (b && (!lens || !polys || !out_xy || !out_inf))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return open_cosets(c, t->t, reinterpret_cast<const uint32_t*>(polys), /*host_polys=*/true, lens, b, stride, log_N,
+                     reinterpret_cast<const uint32_t*>(w), out_xy, out_inf, eval_out);
+}
+
+int kzg_open_coset_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,
+                          size_t stride, uint32_t log_l, const uint64_t h[4], const uint64_t zeta[4],
+                          const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
+  if (!ctx || !srs || !h || !zeta || !xi || !out_xy || !out_inf || (k && (!lens || !d_polys))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  if (srs->s->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
+  if (srs->s->basis != SRS_MONOMIAL) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: the key must be monomial");
+  uint32_t* d_quot = nullptr;
+  size_t qlen = 0;
+  int rc = open_coset_quotient_device(c, static_cast<const uint32_t*>(d_polys), lens, k, stride, log_l,
+                                      reinterpret_cast<const uint32_t*>(h), reinterpret_cast<const uint32_t*>(zeta),
+                                      reinterpret_cast<const uint32_t*>(xi), srs->s->n, &d_quot, &qlen, eval_out);
+  if (rc) return rc;
+  return commit_device(c, srs->s, d_quot, &qlen, 1, qlen ? qlen : 1, out_xy, out_inf);
+}
+
+int kzg_open_coset(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* polys, const size_t* lens, size_t k,
+                   size_t stride, uint32_t log_l, const uint64_t h[4], const uint64_t zeta[4], const uint64_t xi[4],
+                   uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
+  if (!ctx || !srs || !h || !zeta || !xi || !out_xy || !out_inf || (k && (!lens || !polys))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  if (srs->s->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
+  if (srs->s->basis != SRS_MONOMIAL) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: the key must be monomial");
+  int rc = open_coset_check(c, lens, k, stride, log_l, reinterpret_cast<const uint32_t*>(h),
+                            reinterpret_cast<const uint32_t*>(zeta), srs->s->n);     // before anything is queued
+  if (rc) return rc;
+  const size_t bytes = k * stride * 32;
+  if ((rc = ensure_buf(c, c->io, bytes ? bytes : 32))) return rc;
+  if (bytes) KZG_HIP(c, hipMemcpyAsync(c->io.p, polys, bytes, hipMemcpyHostToDevice, c->stream));
+  return kzg_open_coset_device(ctx, srs, c->io.p, lens, k, stride, log_l, h, zeta, xi, out_xy, out_inf, eval_out);
 }
 
 #define KZG_VEC_ENTER()                          \

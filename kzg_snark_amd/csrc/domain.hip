@@ -121,19 +121,21 @@ __device__ __forceinline__ uint32_t bitrev(uint32_t i, uint32_t log_len) {
 
 // ---- kernels -----------------------------------------------------------------------------------------------------
 
-// table input: buf[bitrev_N(u)] = s_(n-2-u) (window-0 record of the monomial key) for u <= n-2, O for u >= n-1
+// table input of sub-table j < l (l = 2^log_l, m = n/l, 2m = 2^log_mm): buf[j][bitrev_2m(u)] = s_((m-2-u) l + j)
+// (window-0 record of the monomial key) for u <= m-2, O for u >= m-1.  l = 1 is open_domain's single table.
 template <class C>
-__global__ __launch_bounds__(128) void dom_load_key_kernel(const uint32_t* recs, uint32_t n, uint32_t log_nn,
-                                                           uint32_t* buf) {
-  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-  if (u >= (1u << log_nn)) return;
+__global__ __launch_bounds__(128) void dom_load_key_kernel(const uint32_t* recs, uint32_t m, uint32_t log_l,
+                                                           uint32_t log_mm, uint32_t* buf) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (1u << (log_l + log_mm))) return;
+  const uint32_t j = g >> log_mm, u = g & ((1u << log_mm) - 1);
   Affine<C> a;
-  if (u + 2 <= n) {
-    a.inf = load_rec<C>(recs, n - 2 - u, a.x, a.y) & 1u;
+  if (u + 2 <= m) {
+    a.inf = load_rec<C>(recs, ((size_t)(m - 2 - u) << log_l) + j, a.x, a.y) & 1u;
   } else {
     a.inf = true;
   }
-  dom_st<C>(buf, bitrev(u, log_nn), Ec<C>::from_affine(a));
+  dom_st<C>(buf, ((size_t)j << log_mm) + bitrev(u, log_mm), Ec<C>::from_affine(a));
 }
 
 // one radix-2 level of half-size h = 2^s over `nvec` vectors of 2^log_len points each (vector j at j << log_len):
@@ -210,17 +212,117 @@ __global__ __launch_bounds__(64) void dom_hadamard_kernel(const uint32_t* chat, 
   dom_st<C>(buf, ((size_t)j << log_nn) + bitrev(i, log_nn), r);
 }
 
-// extraction into the bit-reversed input of the size-n transform: dst[j][bitrev_n(m)] = src[j][n-1+m] for m <= n-2,
-// O for m = n-1 (src: [nvec][2n], dst: [nvec][n])
+// extraction into the bit-reversed input of the final transform: dst[j][bitrev(u)] = src[j][m-1+u] for u <= m-2, O
+// for m-1 <= u < 2^log_dst (src: [nvec][2^log_src], dst: [nvec][2^log_dst]).  open_domain: m = n, src 2n, dst n;
+// open_cosets: m = n/l, src 2m, dst N/l >= m (O-padded).
 template <class C>
-__global__ __launch_bounds__(64) void dom_extract_kernel(const uint32_t* src, uint32_t nvec, uint32_t log_n,
-                                                         uint32_t* dst) {
+__global__ __launch_bounds__(64) void dom_extract_kernel(const uint32_t* src, uint32_t nvec, uint32_t log_src,
+                                                         uint32_t m, uint32_t log_dst, uint32_t* dst) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (nvec << log_n)) return;
-  const uint32_t n = 1u << log_n;
-  const uint32_t j = g >> log_n, m = g & (n - 1);
-  const XYZZ<C> v = m + 1 < n ? dom_ld<C>(src, ((size_t)j << (log_n + 1)) + n - 1 + m) : Ec<C>::infinity();
-  dom_st<C>(dst, ((size_t)j << log_n) + bitrev(m, log_n), v);
+  if (g >= (nvec << log_dst)) return;
+  const uint32_t j = g >> log_dst, u = g & ((1u << log_dst) - 1);
+  const XYZZ<C> v = u + 2 <= m ? dom_ld<C>(src, ((size_t)j << log_src) + m - 1 + u) : Ec<C>::infinity();
+  dom_st<C>(dst, ((size_t)j << log_dst) + bitrev(u, log_dst), v);
+}
+
+// ---- coset openings (open_cosets) ---------------------------------------------------------------------------------
+
+// de-interleave: dst[v][j][s] = src[v][s l + j] for s < m, 0 for m <= s < 2m (src: [nvec][n] zero-padded canonical
+// words, dst: [nvec][l][2m]) -- the inputs a^(j) of the l size-2m transforms
+__global__ __launch_bounds__(256) void dom_deinterleave_kernel(const uint32_t* src, uint32_t nvec, uint32_t log_l,
+                                                               uint32_t log_mm, uint32_t* dst) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t log_nn = log_l + log_mm;                  // l * 2m = 2n
+  if (g >= (nvec << log_nn)) return;
+  const uint32_t v = g >> log_nn, j = (g >> log_mm) & ((1u << log_l) - 1), s = g & ((1u << log_mm) - 1);
+  uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+  if (s < (1u << (log_mm - 1))) {
+    const uint4* p = reinterpret_cast<const uint4*>(src + (((size_t)v << (log_nn - 1)) + ((size_t)s << log_l) + j) * 8);
+    lo = p[0];
+    hi = p[1];
+  }
+  uint4* q = reinterpret_cast<uint4*>(dst + (size_t)g * 8);
+  q[0] = lo;
+  q[1] = hi;
+}
+
+// in place: x[i] <- x[i] * 2m^-1 (canonical words; ninv Montgomery) -- the scalars of the Hadamard sum
+template <class F>
+__global__ __launch_bounds__(256) void dom_scale_kernel(uint32_t* x, uint32_t count, DomFr ninv) {
+  using Fd = Field<F>;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  uint4* p = reinterpret_cast<uint4*>(x + (size_t)i * 8);
+  const uint4 lo = p[0], hi = p[1];
+  const uint32_t cw[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  uint32_t e[8];
+  Fd::to_words(Fd::reduce(Fd::mul(Fd::from_words(cw), dom_arg<F>(ninv))), e);      // standard * Montgomery
+  p[0] = make_uint4(e[0], e[1], e[2], e[3]);
+  p[1] = make_uint4(e[4], e[5], e[6], e[7]);
+}
+
+// Hadamard sum over one group of G = 2^log_g sub-tables, Straus style (one doubling chain for the G terms):
+//   r = sum_(jj < G) e_(j0 + jj) * S^(j0 + jj)_i,   j0 = grp G,   e_j = chat[v][j][i] (already scaled by 2m^-1)
+// Thread (v, grp, i), i fastest.  With one group (G = l) r is u^_i itself and goes to dst[v][bitrev_2m(i)];
+// otherwise to part[v][i][grp] for dom_group_sum_kernel.  A scalar word is re-read per bit (L1 hits: four lanes share
+// a line) and a table point per addition, so the chain holds one accumulator and one addend; the bits differ per
+// lane, so, as in dom_hadamard_kernel, the addition runs almost always.
+template <class C>
+__global__ __launch_bounds__(64) void dom_hadsum_kernel(const uint32_t* chat, const uint32_t* tbl, uint32_t nvec,
+                                                        uint32_t log_l, uint32_t log_mm, uint32_t log_g,
+                                                        uint32_t* dst) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t log_ng = log_l - log_g;
+  if (g >= (nvec << (log_mm + log_ng))) return;
+  const uint32_t i = g & ((1u << log_mm) - 1), grp = (g >> log_mm) & ((1u << log_ng) - 1), v = g >> (log_mm + log_ng);
+  const uint32_t G = 1u << log_g, j0 = grp << log_g;
+  const uint32_t* e0 = chat + (((((size_t)v << log_l) + j0) << log_mm) + i) * 8;     // e_j0; e_(j0+jj): + jj 2m
+  const size_t estep = (size_t)8 << log_mm;
+  const size_t t0 = ((size_t)j0 << log_mm) + i;                                    // S^(j0)_i; S^(j0+jj)_i: + jj 2m
+  XYZZ<C> r = Ec<C>::infinity();
+#pragma unroll 1
+  for (int q = 7; q >= 0; --q) {
+#pragma unroll 1
+    for (int bit = 31; bit >= 0; --bit) {
+      r = Ec<C>::dbl(r);
+#pragma unroll 1
+      for (uint32_t jj = 0; jj < G; ++jj) {
+        const uint32_t word = e0[jj * estep + q];
+        if ((word >> bit) & 1u) r = Ec<C>::add(r, ld_tbl<C>(tbl, t0 + ((size_t)jj << log_mm)));
+      }
+    }
+  }
+  if (log_ng == 0)
+    dom_st<C>(dst, ((size_t)v << log_mm) + bitrev(i, log_mm), r);
+  else
+    dom_st<C>(dst, ((((size_t)v << log_mm) + i) << log_ng) + grp, r);
+}
+
+// u^[v][bitrev_2m(i)] = sum_grp part[v][i][grp]
+template <class C>
+__global__ __launch_bounds__(64) void dom_group_sum_kernel(const uint32_t* part, uint32_t nvec, uint32_t log_mm,
+                                                           uint32_t log_ng, uint32_t* dst) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (nvec << log_mm)) return;
+  const uint32_t v = g >> log_mm, i = g & ((1u << log_mm) - 1);
+  const size_t base = (size_t)g << log_ng;
+  XYZZ<C> r = dom_ld<C>(part, base);
+#pragma unroll 1
+  for (uint32_t k = 1; k < (1u << log_ng); ++k) r = Ec<C>::add(r, dom_ld<C>(part, base + k));
+  dom_st<C>(dst, ((size_t)v << log_mm) + bitrev(i, log_mm), r);
+}
+
+// the values of every coset: dst[v][i][k] = src[v][i + k N/l] (src: [nvec][N] = DFT_N(p) with w, dst: [nvec][N/l][l])
+__global__ __launch_bounds__(256) void dom_coset_values_kernel(const uint32_t* src, uint32_t nvec, uint32_t log_nn,
+                                                               uint32_t log_l, uint32_t* dst) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (nvec << log_nn)) return;
+  const uint32_t v = g >> log_nn, i = (g & ((1u << log_nn) - 1)) >> log_l, k = g & ((1u << log_l) - 1);
+  const uint4* p =
+      reinterpret_cast<const uint4*>(src + (((size_t)v << log_nn) + i + ((size_t)k << (log_nn - log_l))) * 8);
+  uint4* q = reinterpret_cast<uint4*>(dst + (size_t)g * 8);
+  q[0] = p[0];
+  q[1] = p[1];
 }
 
 // table record i = buf[i] as compact affine
@@ -327,10 +429,13 @@ size_t xyzz_bytes() { return (size_t)4 * C::Fp::N * 4; }
 
 }  // namespace
 
-// A table of one monomial key and one domain size: N = 2n compact affine points DFT_G1,N(s^) with root omega.
+// A table of one monomial key, one domain size n and one coset size l = 2^log_l (1 for kzg_domain_table_create):
+// l sub-tables [l][2m], m = n/l, of compact affine points S^(j) = DFT_G1,2m(s^(j)) with root omega_2m -- 2n points
+// for every l.
 struct DomainTable {
   int curve = 0;
   uint32_t log_n = 0;
+  uint32_t log_l = 0;
   size_t n = 0;
   uint32_t* d_tbl = nullptr;
 };
@@ -338,18 +443,22 @@ struct DomainTable {
 namespace {
 
 template <class C>
-int domain_table_t(Ctx* c, const Srs* mono, uint32_t log_n, DomainTable** out) {
+int domain_table_t(Ctx* c, const Srs* mono, uint32_t log_n, uint32_t log_l, const char* fn, const char* span,
+                   DomainTable** out) {
   using F = typename C::Fr;
   if (mono->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
-  if (mono->basis != SRS_MONOMIAL) return set_err(c, KZG_ERR_ARG, "kzg_domain_table_create: the key must be monomial");
-  if (log_n < 1 || log_n > DOM_MAX_LOG) return set_err(c, KZG_ERR_ARG, "kzg_domain_table_create: log_n must be in [1, 20]");
-  const uint32_t n = 1u << log_n, log_nn = log_n + 1, nn = 2 * n;
-  if (mono->n < n) return set_err(c, KZG_ERR_ARG, "kzg_domain_table_create: monomial key shorter than the domain");
-  const Fe<F> omega = dom_omega<C>(log_nn);
-  if (!dom_primitive<F>(omega, log_nn)) return set_err(c, KZG_ERR_ARG, "kzg_domain_table_create: no 2n-th root");
+  if (mono->basis != SRS_MONOMIAL) return set_err(c, KZG_ERR_ARG, (std::string(fn) + ": the key must be monomial").c_str());
+  if (log_n < 1 || log_n > DOM_MAX_LOG) return set_err(c, KZG_ERR_ARG, (std::string(fn) + ": log_n must be in [1, 20]").c_str());
+  if (log_l >= log_n) return set_err(c, KZG_ERR_ARG, (std::string(fn) + ": log_l must be in [0, log_n - 1]").c_str());
+  const uint32_t n = 1u << log_n, nn = 2 * n;
+  const uint32_t m = n >> log_l, log_mm = log_n - log_l + 1;
+  if (mono->n < n) return set_err(c, KZG_ERR_ARG, (std::string(fn) + ": monomial key shorter than the domain").c_str());
+  const Fe<F> omega = dom_omega<C>(log_mm);
+  if (!dom_primitive<F>(omega, log_mm)) return set_err(c, KZG_ERR_ARG, (std::string(fn) + ": no 2m-th root").c_str());
   DomainTable* t = new DomainTable();
   t->curve = c->curve;
   t->log_n = log_n;
+  t->log_l = log_l;
   t->n = n;
   uint32_t* d_buf = nullptr;
   auto fail = [&](int code) { hipFree(d_buf); hipFree(t->d_tbl); delete t; return code; };
@@ -357,10 +466,10 @@ int domain_table_t(Ctx* c, const Srs* mono, uint32_t log_n, DomainTable** out) {
       hipMalloc(reinterpret_cast<void**>(&d_buf), (size_t)nn * xyzz_bytes<C>()) != hipSuccess)
     return fail(set_err(c, KZG_ERR_ALLOC, "hipMalloc(domain table)"));
   {
-    ProfScope ps(c, "domain_table");
-    hipLaunchKernelGGL(dom_load_key_kernel<C>, dim3((nn + 127) / 128), dim3(128), 0, c->stream, mono->recs, n, log_nn,
-                       d_buf);
-    int rc = launch_levels<C>(c, d_buf, 1, log_nn, omega);
+    ProfScope ps(c, span);
+    hipLaunchKernelGGL(dom_load_key_kernel<C>, dim3((nn + 127) / 128), dim3(128), 0, c->stream, mono->recs, m, log_l,
+                       log_mm, d_buf);
+    int rc = launch_levels<C>(c, d_buf, 1u << log_l, log_mm, omega);
     if (rc) return fail(rc);
     hipLaunchKernelGGL(dom_finish_table_kernel<C>, dim3((nn + 63) / 64), dim3(64), 0, c->stream, d_buf, nn,
                        t->d_tbl);
@@ -383,6 +492,7 @@ int open_domain_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
   using Fd = Field<F>;
   using Fp = typename C::Fp;
   if (t->curve != c->curve) return set_err(c, KZG_ERR_ARG, "domain table belongs to another curve");
+  if (t->log_l) return set_err(c, KZG_ERR_ARG, "kzg_open_domain: a coset table (l > 1) needs kzg_open_cosets");
   const uint32_t log_n = t->log_n, log_nn = log_n + 1;
   const size_t n = t->n, nn = 2 * n;
   if (!dom_primitive<F>(Fd::to_mont(Fd::from_words(w_words)), log_n))
@@ -430,7 +540,7 @@ int open_domain_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
     KZG_HIP(c, hipGetLastError());
     if ((rc = launch_levels<C>(c, d_big, m, log_nn, omega_inv))) return rc;
     hipLaunchKernelGGL(dom_extract_kernel<C>, dim3((uint32_t)((small + 63) / 64)), dim3(64), 0, c->stream, d_big, m,
-                       log_n, d_small);
+                       log_nn, (uint32_t)n, log_n, d_small);
     KZG_HIP(c, hipGetLastError());
     if ((rc = launch_levels<C>(c, d_small, m, log_n, w))) return rc;
     hipLaunchKernelGGL(dom_finish_proofs_kernel<C>, dim3((uint32_t)((small + 63) / 64)), dim3(64), 0, c->stream,
@@ -455,10 +565,135 @@ int open_domain_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
   return KZG_OK;
 }
 
+// Coset FK20: N/l proofs per vector, coset i = {w^(i + k N/l), k < l}.  The l Toeplitz products of size m = n/l are
+// summed before one inverse G1 DFT (the sum of the Hadamard products is the transform of the sum):
+//   c^(j) = DFT_Fr,2m(a^(j)),  a^(j)_s = c_(s l + j)          one batched NTT over l vectors per polynomial
+//   u^_i  = sum_j (c^(j)_i / 2m) S^(j)_i                      dom_hadsum_kernel (+ dom_group_sum_kernel)
+//   u     = DFT_G1,2m(u^) with omega^-1;  h_u = u_(m-1+u) (u <= m-2), O up to N/l
+//   pi    = DFT_G1,N/l(h) with w^l
+// Buffers of one chunk of vectors (every region a multiple of 32 bytes per vector):
+//   big [2m] XYZZ, part [2m][l/G] XYZZ (only when G < l), small [N/l] XYZZ, fr [l][2m] Fr, stage [n] Fr,
+//   (values) val [N] Fr, valt [N] Fr, (proofs) oxy [N/l][2 NW] words, oinf [N/l] bytes.
+template <class C>
+int open_cosets_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_polys, const size_t* lens, size_t b,
+                  size_t stride, uint32_t log_N, const uint32_t* w_words, uint64_t* out_xy, uint8_t* out_inf,
+                  uint64_t* eval_out) {
+  using F = typename C::Fr;
+  using Fd = Field<F>;
+  using Fp = typename C::Fp;
+  if (t->curve != c->curve) return set_err(c, KZG_ERR_ARG, "domain table belongs to another curve");
+  const uint32_t log_n = t->log_n, log_l = t->log_l;
+  if (log_N < log_n || log_N > std::min<uint32_t>(log_n + 2, DOM_MAX_LOG + 1))
+    return set_err(c, KZG_ERR_ARG, "kzg_open_cosets: log_N must be in [log_n, min(log_n + 2, 21)]");
+  if (!dom_primitive<F>(Fd::to_mont(Fd::from_words(w_words)), log_N))
+    return set_err(c, KZG_ERR_ARG, "kzg_open_cosets: w is not a primitive N-th root of unity");
+  const size_t n = t->n;
+  for (size_t j = 0; j < b; ++j) {
+    if (lens[j] > n) return set_err(c, KZG_ERR_DEGREE, "polynomial longer than the domain table");
+    if (lens[j] > stride) return set_err(c, KZG_ERR_ARG, "kzg_open_cosets: lens[j] > stride");
+  }
+  if (b == 0) return KZG_OK;
+  const uint32_t m = (uint32_t)(n >> log_l), log_mm = log_n - log_l + 1, mm = 2 * m;
+  const uint32_t log_L = log_N - log_l;                      // N/l proofs per vector
+  const size_t L = (size_t)1 << log_L, NN = (size_t)1 << log_N;
+  // Straus group: G = min(l, 16) terms share a doubling chain, fewer while that would leave < 2^16 threads busy
+  uint32_t log_g = std::min<uint32_t>(log_l, 4);
+  while (log_g && ((std::min<size_t>(b, 64) * 2 * n) >> log_g) < ((size_t)1 << 16)) --log_g;
+  const uint32_t log_ng = log_l - log_g;
+  const size_t xb = xyzz_bytes<C>(), pt_words = 2 * Fp::NW;
+  const size_t part_pts = log_ng ? (size_t)mm << log_ng : 0;
+  const size_t oxy_bytes = (L * pt_words * 4 + 31) / 32 * 32, oinf_bytes = (L + 31) / 32 * 32;
+  const size_t per_vec = (mm + part_pts + L) * xb + (2 * n + n) * 32 + (eval_out ? 2 * NN * 32 : 0) + oxy_bytes +
+                         oinf_bytes;
+  size_t chunk = c->tune_open_cosets_chunk > 0 ? (size_t)c->tune_open_cosets_chunk
+                                               : std::max<size_t>(1, DOM_SCRATCH_BYTES / per_vec);
+  chunk = std::min<size_t>({chunk, b, DOM_MAX_CHUNK});
+  int rc = ensure_buf(c, c->dom_tmp, chunk * per_vec + 9 * 256);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->dom_tmp.p);
+  auto region = [&](size_t per) { uint8_t* p = base; base += (chunk * per + 255) / 256 * 256; return p; };
+  uint32_t* d_big = reinterpret_cast<uint32_t*>(region(mm * xb));                 // [chunk][2m] XYZZ
+  uint32_t* d_part = reinterpret_cast<uint32_t*>(region(part_pts * xb));          // [chunk][2m][l/G] XYZZ
+  uint32_t* d_small = reinterpret_cast<uint32_t*>(region(L * xb));                // [chunk][N/l] XYZZ
+  uint32_t* d_fr = reinterpret_cast<uint32_t*>(region(2 * n * 32));               // [chunk][l][2m] Fr
+  uint32_t* d_stage = reinterpret_cast<uint32_t*>(region(n * 32));                // [chunk][n] Fr
+  uint32_t* d_val = reinterpret_cast<uint32_t*>(region(eval_out ? NN * 32 : 0));  // [chunk][N] Fr
+  uint32_t* d_valt = reinterpret_cast<uint32_t*>(region(eval_out ? NN * 32 : 0)); // [chunk][N/l][l] Fr
+  uint32_t* d_oxy = reinterpret_cast<uint32_t*>(region(oxy_bytes));               // [chunk][N/l][2 NW] words
+  uint8_t* d_oinf = region(oinf_bytes);                                           // [chunk][N/l] flags
+
+  const Fe<F> omega = dom_omega<C>(log_mm);
+  const Fe<F> omega_inv = Fd::inv(omega);
+  uint32_t omega_words[8], mw[8] = {0};
+  Fd::to_words(Fd::from_mont(omega), omega_words);
+  mw[log_mm >> 5] = 1u << (log_mm & 31);
+  const Fe<F> mminv = Fd::reduce(Fd::inv(Fd::to_mont(Fd::from_words(mw))));
+  Fe<F> wl = Fd::to_mont(Fd::from_words(w_words));                                // w^l: the final transform's root
+  for (uint32_t q = 0; q < log_l; ++q) wl = Fd::sqr(wl);
+  const hipMemcpyKind kind = host_polys ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+
+  ProfScope ps(c, "open_cosets");
+  for (size_t j0 = 0; j0 < b; j0 += chunk) {
+    const uint32_t mv = (uint32_t)std::min(chunk, b - j0);
+    // the coefficients, zero-padded to n, then de-interleaved into the l zero-padded transforms of size 2m
+    KZG_HIP(c, hipMemsetAsync(d_stage, 0, (size_t)mv * n * 32, c->stream));
+    for (uint32_t j = 0; j < mv; ++j)
+      if (lens[j0 + j])
+        KZG_HIP(c, hipMemcpyAsync(d_stage + (size_t)j * n * 8, polys + (j0 + j) * stride * 8, lens[j0 + j] * 32, kind,
+                                  c->stream));
+    const size_t frs = (size_t)mv * 2 * n;
+    hipLaunchKernelGGL(dom_deinterleave_kernel, dim3((uint32_t)((frs + 255) / 256)), dim3(256), 0, c->stream, d_stage,
+                       mv, log_l, log_mm, d_fr);
+    KZG_HIP(c, hipGetLastError());
+    if ((rc = ntt_run_device(c, d_fr, log_mm, omega_words, 0, mv << log_l))) return rc;
+    hipLaunchKernelGGL(dom_scale_kernel<F>, dim3((uint32_t)((frs + 255) / 256)), dim3(256), 0, c->stream, d_fr,
+                       (uint32_t)frs, dom_fr<F>(mminv));
+    KZG_HIP(c, hipGetLastError());
+    const size_t hs = (size_t)mv * mm << log_ng, big = (size_t)mv * mm, small = (size_t)mv * L;
+    hipLaunchKernelGGL(dom_hadsum_kernel<C>, dim3((uint32_t)((hs + 63) / 64)), dim3(64), 0, c->stream, d_fr,
+                       t->d_tbl, mv, log_l, log_mm, log_g, log_ng ? d_part : d_big);
+    KZG_HIP(c, hipGetLastError());
+    if (log_ng) {
+      hipLaunchKernelGGL(dom_group_sum_kernel<C>, dim3((uint32_t)((big + 63) / 64)), dim3(64), 0, c->stream, d_part,
+                         mv, log_mm, log_ng, d_big);
+      KZG_HIP(c, hipGetLastError());
+    }
+    if ((rc = launch_levels<C>(c, d_big, mv, log_mm, omega_inv))) return rc;
+    hipLaunchKernelGGL(dom_extract_kernel<C>, dim3((uint32_t)((small + 63) / 64)), dim3(64), 0, c->stream, d_big, mv,
+                       log_mm, m, log_L, d_small);
+    KZG_HIP(c, hipGetLastError());
+    if ((rc = launch_levels<C>(c, d_small, mv, log_L, wl))) return rc;
+    hipLaunchKernelGGL(dom_finish_proofs_kernel<C>, dim3((uint32_t)((small + 63) / 64)), dim3(64), 0, c->stream,
+                       d_small, (uint32_t)small, d_oxy, d_oinf);
+    KZG_HIP(c, hipGetLastError());
+    KZG_HIP(c, hipMemcpyAsync(out_xy + j0 * L * pt_words / 2, d_oxy, small * pt_words * 4, hipMemcpyDeviceToHost,
+                              c->stream));
+    KZG_HIP(c, hipMemcpyAsync(out_inf + j0 * L, d_oinf, small, hipMemcpyDeviceToHost, c->stream));
+    if (eval_out) {   // y = DFT_N(c) with w, regrouped per coset
+      KZG_HIP(c, hipMemsetAsync(d_val, 0, (size_t)mv * NN * 32, c->stream));
+      KZG_HIP(c, hipMemcpy2DAsync(d_val, NN * 32, d_stage, n * 32, n * 32, mv, hipMemcpyDeviceToDevice, c->stream));
+      if ((rc = ntt_run_device(c, d_val, log_N, w_words, 0, mv))) return rc;
+      const size_t vals = (size_t)mv * NN;
+      hipLaunchKernelGGL(dom_coset_values_kernel, dim3((uint32_t)((vals + 255) / 256)), dim3(256), 0, c->stream, d_val,
+                         mv, log_N, log_l, d_valt);
+      KZG_HIP(c, hipGetLastError());
+      KZG_HIP(c, hipMemcpyAsync(eval_out + j0 * NN * 4, d_valt, vals * 32, hipMemcpyDeviceToHost, c->stream));
+    }
+    // the next chunk overwrites the buffers the copies read
+    KZG_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return KZG_OK;
+}
+
 }  // namespace
 
 int domain_table_create(Ctx* c, const Srs* mono, uint32_t log_n, DomainTable** out) {
-  return c->curve == 0 ? domain_table_t<Bn254>(c, mono, log_n, out) : domain_table_t<Bls12_381>(c, mono, log_n, out);
+  return c->curve == 0 ? domain_table_t<Bn254>(c, mono, log_n, 0, "kzg_domain_table_create", "domain_table", out)
+                       : domain_table_t<Bls12_381>(c, mono, log_n, 0, "kzg_domain_table_create", "domain_table", out);
+}
+int coset_table_create(Ctx* c, const Srs* mono, uint32_t log_n, uint32_t log_l, DomainTable** out) {
+  return c->curve == 0 ? domain_table_t<Bn254>(c, mono, log_n, log_l, "kzg_coset_table_create", "coset_table", out)
+                       : domain_table_t<Bls12_381>(c, mono, log_n, log_l, "kzg_coset_table_create", "coset_table", out);
 }
 void domain_table_free(DomainTable* t) {
   if (!t) return;
@@ -471,6 +706,14 @@ int open_domain(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_p
   return c->curve == 0
              ? open_domain_t<Bn254>(c, t, polys, host_polys, lens, b, stride, w_words, out_xy, out_inf, eval_out)
              : open_domain_t<Bls12_381>(c, t, polys, host_polys, lens, b, stride, w_words, out_xy, out_inf, eval_out);
+}
+int open_cosets(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_polys, const size_t* lens, size_t b,
+                size_t stride, uint32_t log_N, const uint32_t* w_words, uint64_t* out_xy, uint8_t* out_inf,
+                uint64_t* eval_out) {
+  return c->curve == 0 ? open_cosets_t<Bn254>(c, t, polys, host_polys, lens, b, stride, log_N, w_words, out_xy, out_inf,
+                                              eval_out)
+                       : open_cosets_t<Bls12_381>(c, t, polys, host_polys, lens, b, stride, log_N, w_words, out_xy,
+                                                  out_inf, eval_out);
 }
 
 }  // namespace kzg

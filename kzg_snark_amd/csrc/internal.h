@@ -70,6 +70,7 @@ struct Ctx {
   int tune_open_tb = 0;                   // threads per tile of the opening's scan (128 | 256)
   int tune_open_direct_max = 0;           // tiles up to which every tile sums all aggregates above it
   int tune_open_domain_chunk = 0;         // vectors per chunk of kzg_open_domain
+  int tune_open_cosets_chunk = 0;         // vectors per chunk of kzg_open_cosets
   int last_ntt_tile_log = 0;              // what the last transform used (kzg_prof_read "ntt_tile_log")
   void* msm_work = nullptr;               // MsmWork (msm.hip)
   bool prof_on = false;

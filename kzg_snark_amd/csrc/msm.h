@@ -51,6 +51,11 @@ void domain_table_free(DomainTable* t);
 size_t domain_table_size(const DomainTable* t);
 int open_domain(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_polys, const size_t* lens, size_t b,
                 size_t stride, const uint32_t* w_words, uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out);
+// Coset openings: a table of l sub-tables (l = 2^log_l; l = 1 is kzg_domain_table_create's) and N/l proofs per vector.
+int coset_table_create(Ctx* c, const Srs* mono, uint32_t log_n, uint32_t log_l, DomainTable** out);
+int open_cosets(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_polys, const size_t* lens, size_t b,
+                size_t stride, uint32_t log_N, const uint32_t* w_words, uint64_t* out_xy, uint8_t* out_inf,
+                uint64_t* eval_out);
 
 // One MSM per polynomial; scalars device-resident, results to host memory (synchronises).
 // drain = false leaves up to four polynomials in flight; their outputs are written when their
@@ -68,6 +73,15 @@ void msm_free_work(Ctx* c);
 int open_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                          const uint32_t* z_words, const uint32_t* xi_words, uint32_t** d_quot_out,
                          size_t* quot_len, uint64_t* eval_out, bool sync = true);
+// poly.hip: coset opening.  combined = sum_i xi^(i+1) p_i; quotient (combined - rho) / (X^l - h^l), rho the remainder.
+// d_quot receives max(n - l, 0) coefficients; eval_out ([l][4], may be null) combined(h zeta^k).  Synchronises.
+// open_coset_check: the argument checks alone (log_l <= 12, h != 0, zeta a primitive l-th root, lens, key length).
+int open_coset_check(Ctx* c, const size_t* lens, size_t k, size_t stride, uint32_t log_l, const uint32_t* h_words,
+                     const uint32_t* zeta_words, size_t key_n);
+int open_coset_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
+                               uint32_t log_l, const uint32_t* h_words, const uint32_t* zeta_words,
+                               const uint32_t* xi_words, size_t key_n, uint32_t** d_quot_out, size_t* quot_len,
+                               uint64_t* eval_out);
 
 int open_shard_begin_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                             const uint32_t* z_words, const uint32_t* xi_words, uint64_t* chunk_eval_out);

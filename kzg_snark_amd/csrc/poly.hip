@@ -699,6 +699,177 @@ int open_shard_finish_t(Ctx* c, const uint32_t* z_words, const uint32_t* carry_w
   return KZG_OK;
 }
 
+// =====================================================================================
+// Coset opening: division by Z = X^l - a, a = h^l (l = 2^log_l).  With S_t = c_t + a S_(t+l) (zero beyond the end)
+// the quotient is q_t = S_(t+l) and the remainder rho_j = S_j (j < l).  Read as rows of l coefficients (row s holds
+// c_(s l) .. c_(s l + l - 1)) that is l independent suffix-Horner chains down the rows, all with the multiplier a --
+// the opening's scan with the stride l -- run as a blocked scan over tiles of CS_R rows:
+//   coset_tile_kernel  A[b][j] = sum_(r < R) x[bR + r][j] a^r             (the tile's aggregate, one thread per (b, j))
+//   the same on A with a^R, recursively, until one tile holds every row  (log_R(rows) levels: 5 at 2^20, l = 1)
+//   coset_fill_kernel  x[row][j] <- S, walking the tile's rows down from the carry S at row (b+1)R = A[b+1][j] (now a
+//                      suffix value of the level above), top level first
+// Every launch spreads over ceil(rows / R) * l threads; no host round trip, no power table.  R = 16: a 2^20 scan
+// starts at 2^16 threads.
+// =====================================================================================
+constexpr uint32_t CS_R = 16;
+constexpr uint32_t CS_MAX_LOG_L = 12;
+
+template <class F>
+__global__ __launch_bounds__(256) void coset_tile_kernel(const uint32_t* x, uint32_t rows, uint32_t log_l, FrArg a,
+                                                         uint32_t* agg) {
+  using Fd = Field<F>;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t tiles = (rows + CS_R - 1) / CS_R;
+  if (g >= (tiles << log_l)) return;
+  const uint32_t j = g & ((1u << log_l) - 1), b = g >> log_l;
+  const Fe<F> am = load_limbs<F>(a.l);
+  Fe<F> acc = Fd::zero();
+#pragma unroll 1
+  for (int r = CS_R - 1; r >= 0; --r) {
+    const uint32_t row = b * CS_R + r;
+    if (row < rows) acc = Fd::add(load_words<F>(x + (((size_t)row << log_l) + j) * 8), Fd::mul(acc, am));
+  }
+  store_words<F>(agg + (size_t)g * 8, acc);
+}
+
+// upper: the suffix values of the level above (rows `upper_rows`), null at the top level
+template <class F>
+__global__ __launch_bounds__(256) void coset_fill_kernel(uint32_t* x, uint32_t rows, uint32_t log_l, FrArg a,
+                                                         const uint32_t* upper, uint32_t upper_rows) {
+  using Fd = Field<F>;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t tiles = (rows + CS_R - 1) / CS_R;
+  if (g >= (tiles << log_l)) return;
+  const uint32_t j = g & ((1u << log_l) - 1), b = g >> log_l;
+  const Fe<F> am = load_limbs<F>(a.l);
+  Fe<F> acc = upper && b + 1 < upper_rows ? load_words<F>(upper + ((((size_t)b + 1) << log_l) + j) * 8) : Fd::zero();
+#pragma unroll 1
+  for (int r = CS_R - 1; r >= 0; --r) {
+    const uint32_t row = b * CS_R + r;
+    if (row < rows) {
+      uint32_t* p = x + (((size_t)row << log_l) + j) * 8;
+      acc = Fd::add(load_words<F>(p), Fd::mul(acc, am));
+      store_words<F>(p, acc);
+    }
+  }
+}
+
+// level `lv` of the blocked scan over x (rows x l), multiplier a (Montgomery); tmp: the aggregates of every level
+template <class F>
+int coset_scan_level(Ctx* c, uint32_t* x, uint32_t rows, uint32_t log_l, const Fe<F>& a, uint32_t* tmp) {
+  using Fd = Field<F>;
+  const uint32_t tiles = (rows + CS_R - 1) / CS_R;
+  const uint32_t threads = tiles << log_l;
+  const FrArg aa = fr_arg<F>(a);
+  if (tiles == 1) {
+    hipLaunchKernelGGL(coset_fill_kernel<F>, dim3((threads + 255) / 256), dim3(256), 0, c->stream, x, rows, log_l, aa,
+                       (const uint32_t*)nullptr, 0u);
+    KZG_HIP(c, hipGetLastError());
+    return KZG_OK;
+  }
+  hipLaunchKernelGGL(coset_tile_kernel<F>, dim3((threads + 255) / 256), dim3(256), 0, c->stream, x, rows, log_l, aa,
+                     tmp);
+  KZG_HIP(c, hipGetLastError());
+  Fe<F> aR = a;
+  for (uint32_t r = 1; r < CS_R; r <<= 1) aR = Fd::sqr(aR);                  // a^R
+  int rc = coset_scan_level<F>(c, tmp, tiles, log_l, aR, tmp + ((size_t)tiles << log_l) * 8);
+  if (rc) return rc;
+  hipLaunchKernelGGL(coset_fill_kernel<F>, dim3((threads + 255) / 256), dim3(256), 0, c->stream, x, rows, log_l, aa,
+                     (const uint32_t*)tmp, tiles);
+  KZG_HIP(c, hipGetLastError());
+  return KZG_OK;
+}
+
+template <class F>
+int open_coset_check_t(Ctx* c, const size_t* lens, size_t k, size_t stride, uint32_t log_l, const uint32_t* h_words,
+                       const uint32_t* zeta_words, size_t key_n, size_t* n_out) {
+  using Fd = Field<F>;
+  if (log_l > CS_MAX_LOG_L) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: log_l must be in [0, 12]");
+  if (words_are_zero(h_words)) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: h must be non-zero");
+  Fe<F> x = Fd::to_mont(Fd::from_words(zeta_words));
+  if (log_l == 0) {
+    if (!Fd::eq(x, Fd::one())) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: zeta must be 1 for l = 1");
+  } else {
+    for (uint32_t q = 1; q < log_l; ++q) x = Fd::sqr(x);
+    if (!Fd::eq(x, Fd::neg(Fd::one())))
+      return set_err(c, KZG_ERR_ARG, "kzg_open_coset: zeta is not a primitive l-th root of unity");
+  }
+  int rc = check_open_args<F>(c, lens, k, stride, n_out);
+  if (rc) return rc;
+  if (*n_out > key_n) return set_err(c, KZG_ERR_DEGREE, "polynomial longer than the commitment key");
+  return KZG_OK;
+}
+
+// The combination (kzg_open's xi rule), its remainder mod X^l - h^l and quotient.  d_quot receives max(n - l, 0)
+// coefficients (canonical words); eval_out ([l][4], may be null) the values at h zeta^k: y = DFT_l(rho_j h^j) with
+// zeta, on the host.  ONE "open_coset_poly" span per call; synchronises (the l remainder coefficients come back).
+template <class F>
+int open_coset_quotient_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
+                          uint32_t log_l, const uint32_t* h_words, const uint32_t* zeta_words, const uint32_t* xi_words,
+                          size_t key_n, uint32_t** d_quot_out, size_t* quot_len, uint64_t* eval_out) {
+  using Fd = Field<F>;
+  *quot_len = 0;
+  *d_quot_out = nullptr;
+  size_t n = 0;
+  int rc = open_coset_check_t<F>(c, lens, k, stride, log_l, h_words, zeta_words, key_n, &n);
+  if (rc) return rc;
+  const size_t l = (size_t)1 << log_l;
+  if (eval_out) memset(eval_out, 0, l * 32);
+  if (n == 0) return KZG_OK;     // all polynomials zero: quotient 0, every value 0
+  const uint32_t rows = (uint32_t)((n + l - 1) >> log_l);
+  const size_t padded = (size_t)rows << log_l;
+  if ((rc = ensure_buf(c, c->poly_tmp[0], padded * 32))) return rc;
+  size_t agg = 0;                                             // aggregates of every level of the blocked scan
+  for (uint32_t r = rows; r > 1; r = (r + CS_R - 1) / CS_R) agg += (size_t)((r + CS_R - 1) / CS_R) << log_l;
+  if ((rc = ensure_buf(c, c->scan_tmp, (agg + 1) * 32))) return rc;
+  uint32_t* d_S = static_cast<uint32_t*>(c->poly_tmp[0].p);
+  const Fe<F> h = Fd::to_mont(Fd::from_words(h_words));
+  Fe<F> a = h;
+  for (uint32_t q = 0; q < log_l; ++q) a = Fd::sqr(a);        // a = h^l
+  std::vector<uint32_t> rho(l * 8, 0u);
+  {
+    ProfScope ps(c, "open_coset_poly");
+    if ((rc = launch_lincomb<F>(c, d_polys, lens, k, stride, xi_words, d_S, padded))) return rc;   // zero-padded rows
+    if ((rc = coset_scan_level<F>(c, d_S, rows, log_l, a, static_cast<uint32_t*>(c->scan_tmp.p)))) return rc;
+    KZG_HIP(c, hipMemcpyAsync(rho.data(), d_S, std::min(l, n) * 32, hipMemcpyDeviceToHost, c->stream));
+  }
+  KZG_HIP(c, hipStreamSynchronize(c->stream));
+  if (eval_out) {     // y_k = sum_j rho_j h^j zeta^(jk): radix-2 DFT of size l on the host
+    std::vector<Fe<F>> v(l);
+    Fe<F> hp = Fd::one();
+    for (size_t j = 0; j < l; ++j) {
+      v[j] = Fd::mul(Fd::to_mont(Fd::from_words(&rho[j * 8])), hp);
+      hp = Fd::mul(hp, h);
+    }
+    for (size_t i = 1, j = 0; i < l; ++i) {                   // bit-reversed order
+      size_t bit = l >> 1;
+      for (; j & bit; bit >>= 1) j ^= bit;
+      j ^= bit;
+      if (i < j) std::swap(v[i], v[j]);
+    }
+    const Fe<F> zeta = Fd::to_mont(Fd::from_words(zeta_words));
+    for (size_t len = 2; len <= l; len <<= 1) {
+      Fe<F> wl = zeta;                                        // zeta^(l / len)
+      for (size_t e = len; e < l; e <<= 1) wl = Fd::sqr(wl);
+      for (size_t i = 0; i < l; i += len) {
+        Fe<F> wp = Fd::one();
+        for (size_t j = 0; j < len / 2; ++j) {
+          const Fe<F> u = v[i + j], t = Fd::mul(v[i + j + len / 2], wp);
+          v[i + j] = Fd::add(u, t);
+          v[i + j + len / 2] = Fd::sub(u, t);
+          wp = Fd::mul(wp, wl);
+        }
+      }
+    }
+    for (size_t q = 0; q < l; ++q) Fd::to_words(Fd::from_mont(v[q]), reinterpret_cast<uint32_t*>(eval_out + q * 4));
+  }
+  if (n > l) {
+    *d_quot_out = d_S + l * 8;
+    *quot_len = n - l;
+  }
+  return KZG_OK;
+}
+
 }  // namespace
 
 int open_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
@@ -719,6 +890,22 @@ int open_shard_finish_device(Ctx* c, const uint32_t* z_words, const uint32_t* ca
                              uint32_t** d_vec_out, size_t* vec_len, uint64_t* eval_out) {
   return c->curve == 0 ? open_shard_finish_t<BnFr>(c, z_words, carry_words, first_rank, d_vec_out, vec_len, eval_out)
                        : open_shard_finish_t<BlsFr>(c, z_words, carry_words, first_rank, d_vec_out, vec_len, eval_out);
+}
+
+int open_coset_check(Ctx* c, const size_t* lens, size_t k, size_t stride, uint32_t log_l, const uint32_t* h_words,
+                     const uint32_t* zeta_words, size_t key_n) {
+  size_t n = 0;
+  return c->curve == 0 ? open_coset_check_t<BnFr>(c, lens, k, stride, log_l, h_words, zeta_words, key_n, &n)
+                       : open_coset_check_t<BlsFr>(c, lens, k, stride, log_l, h_words, zeta_words, key_n, &n);
+}
+int open_coset_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
+                               uint32_t log_l, const uint32_t* h_words, const uint32_t* zeta_words,
+                               const uint32_t* xi_words, size_t key_n, uint32_t** d_quot_out, size_t* quot_len,
+                               uint64_t* eval_out) {
+  return c->curve == 0 ? open_coset_quotient_t<BnFr>(c, d_polys, lens, k, stride, log_l, h_words, zeta_words, xi_words,
+                                                      key_n, d_quot_out, quot_len, eval_out)
+                       : open_coset_quotient_t<BlsFr>(c, d_polys, lens, k, stride, log_l, h_words, zeta_words,
+                                                       xi_words, key_n, d_quot_out, quot_len, eval_out);
 }
 
 // true iff any of the elements [from, to) of a canonical-word array is non-zero

@@ -77,13 +77,16 @@ class LagrangeKey(CommitmentKey):
 
 class DomainTable:
     """The FK20 table of one monomial key and domain size n (KZG.domain_table): what open_domain needs to compute all
-    n proofs on a domain at once.  Holds 2n affine points on the device."""
+    n proofs on a domain at once.  Holds 2n affine points on the device.  KZG.coset_table makes one for cosets of l
+    points (open_cosets); domain_table's tables have l = 1."""
 
-    def __init__(self, ctx, table, n):
+    def __init__(self, ctx, table, n, l=1):
         self._ctx = ctx
         self.table = table
         self.n = int(n)
         self.log_n = self.n.bit_length() - 1
+        self.l = int(l)
+        self.log_l = self.l.bit_length() - 1
 
     def __len__(self):
         return self.n
@@ -110,7 +113,7 @@ class KZG:
         self.X = self.R.gen()
         self._ctx = None
         self._loaded = {}          # id(list ck) -> (CommitmentKey, fingerprint); at most _KEY_CACHE entries, LRU
-        self._tables = {}          # (id(CommitmentKey), n) -> (CommitmentKey, DomainTable); at most _TABLE_CACHE, LRU
+        self._tables = {}          # (id(CommitmentKey), n[, l]) -> (CommitmentKey, DomainTable); _TABLE_CACHE, LRU
 
     # ---- py_ecc-shaped single-point operations (host; used by the verifiers) ------
     def _grp(self, pt):
@@ -535,3 +538,255 @@ class KZG:
         arr, lens, stride = self._pack(coeffs)
         xy, inf, _ = self._context().open_domain(table.table, np.ascontiguousarray(arr), lens, stride, w, evals=False)
         return [self._points(xy[j], inf[j]) for j in range(len(coeffs))]
+
+    # ---- coset openings: the values at l = 2^log_l points h zeta^k with ONE proof (FK20's multi-reveal) -------------
+    #      Z = X^l - a, a = h^l; rho = p mod Z; pi = [(p - rho)/Z (tau)] G1; check e(C - [rho(tau)], G2) = e(pi, [tau^l] G2 - a G2).
+    _COSET_MAX_LOG_L = 12          # kzg_open_coset
+
+    def _table_cached(self, key, cache_key, make):
+        hit = self._tables.get(cache_key)
+        if hit and hit[0] is key:
+            self._tables[cache_key] = self._tables.pop(cache_key)           # most recently used last
+            return hit[1]
+        table = make()
+        self._tables.pop(cache_key, None)
+        while len(self._tables) >= self._TABLE_CACHE:
+            old = next(iter(self._tables))
+            self._tables.pop(old)[1].table.close()
+        self._tables[cache_key] = (key, table)
+        return table
+
+    @staticmethod
+    def _log2_exact(v, what):
+        v = int(v)
+        if v < 1 or v & (v - 1):
+            raise ValueError(f"{what} {v} is not a power of two")
+        return v.bit_length() - 1
+
+    def coset_table(self, ck, n, l):
+        """The coset table of the first n points of a monomial key for cosets of l points (powers of two, 2 <= n <=
+        2^20, l <= n/2).  Built on the device; cached per (key, n, l) beside domain_table's tables."""
+        if isinstance(ck, (LagrangeKey, DomainTable)):
+            raise TypeError("coset_table needs a monomial key (setup / load_key / a list of points)")
+        n = int(n)
+        if n < 2 or n & (n - 1) or n > self._DOMAIN_MAX:
+            raise ValueError(f"domain size {n} is not a power of two in [2, 2^20]")
+        log_l = self._log2_exact(l, "coset size")
+        if (1 << log_l) > n // 2:
+            raise ValueError(f"coset size {l} exceeds n/2 = {n // 2}")
+        if len(ck) < n:
+            raise ValueError(f"commitment key of {len(ck)} points is shorter than the domain ({n})")
+        key = self._key(ck)
+        ctx = self._context()
+        return self._table_cached(key, (id(key), n, 1 << log_l), lambda: DomainTable(
+            ctx, ctx.coset_table(key.srs, n.bit_length() - 1, log_l), n, 1 << log_l))
+
+    def _cosets_call(self, ck_or_table, polynomials, l, n, w, N):
+        """Host-side checks of open_cosets / open_cosets_each, before any device work: -> (coefficient lists, n, l,
+        log_N, w).  n defaults as in open_domain (at least 2l), N to n."""
+        if isinstance(ck_or_table, LagrangeKey):
+            raise TypeError("open_cosets needs a monomial key or a coset table, not a LagrangeKey")
+        log_l = self._log2_exact(l, "coset size")
+        l = 1 << log_l
+        coeffs = [self._coeffs(p) for p in polynomials]
+        longest = max((len(c) for c in coeffs), default=0)
+        if isinstance(ck_or_table, DomainTable):
+            if n is not None and int(n) != ck_or_table.n:
+                raise ValueError(f"n = {n} differs from the table's domain size {ck_or_table.n}")
+            if l != ck_or_table.l:
+                raise ValueError(f"l = {l} differs from the table's coset size {ck_or_table.l}")
+            n = ck_or_table.n
+        elif n is None:
+            n = max(2, 2 * l)
+            while n < longest:
+                n *= 2
+        n = int(n)
+        if n < 2 or n & (n - 1) or n > self._DOMAIN_MAX:
+            raise ValueError(f"domain size {n} is not a power of two in [2, 2^20]")
+        if l > n // 2:
+            raise ValueError(f"coset size {l} exceeds n/2 = {n // 2}")
+        if longest > n:
+            raise ValueError(f"polynomial of {longest} coefficients exceeds the domain size {n}")
+        if not isinstance(ck_or_table, DomainTable) and len(ck_or_table) < n:
+            raise ValueError(f"commitment key of {len(ck_or_table)} points is shorter than the domain ({n})")
+        N = n if N is None else int(N)
+        if N < n or N & (N - 1) or N > min(4 * n, 2 * self._DOMAIN_MAX):
+            raise ValueError(f"N = {N} is not a power of two in [n, min(4n, 2^21)]")
+        log_N, w = self._domain(N, w)
+        return coeffs, n, l, log_N, w
+
+    def _coset_table_for(self, ck_or_table, n, l):
+        return ck_or_table if isinstance(ck_or_table, DomainTable) else self.coset_table(ck_or_table, n, l)
+
+    def open_cosets(self, ck_or_table, polynomials, xi, l, n=None, w=None, N=None):
+        """One proof per coset of l points of the domain {w^t, t < N}: coset i is {w^(i + k N/l), k < l}, a list of
+        N/l proofs of the xi^(j+1) combination (combined on the device, as in open_domain).  w defaults to
+        Fq.root_of_unity(N), N to n."""
+        coeffs, n, l, log_N, w = self._cosets_call(ck_or_table, polynomials, l, n, w, N)
+        xi = int(self.Fq(xi))
+        table = self._coset_table_for(ck_or_table, n, l)
+        ctx = self._context()
+        r = self.curve_order
+        arr, lens, stride = self._pack(coeffs)
+        length = max(max(lens, default=0), 1)
+        import torch
+        dev = f"cuda:{ctx.device}"
+        d_in = torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).to(dev, non_blocking=False)
+        d_comb = torch.zeros((length, 4), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(ctx.device)
+        ptrs = [d_in.data_ptr() + j * stride * 32 for j in range(len(coeffs))]
+        scalars, x = [], xi
+        for _ in coeffs:
+            scalars.append(x)                                                  # xi^(j+1): kzg.py:148-150
+            x = x * xi % r
+        ctx.vec_lincomb(length, ptrs, lens, scalars, d_comb.data_ptr())
+        xy, inf, _ = ctx.open_cosets(table.table, d_comb.data_ptr(), [length], length, log_N, w, device=True,
+                                     evals=False)
+        return self._points(xy[0], inf[0])
+
+    def open_cosets_each(self, ck_or_table, polynomials, l, n=None, w=None, N=None, with_values=False):
+        """Every coset proof of each polynomial on its own: result[j][i] == open_coset(ck, [polynomials[j]], w^i, l,
+        1, w^(N/l)).  with_values: (proofs, values), values[j][i][k] = p_j(w^(i + k N/l))."""
+        coeffs, n, l, log_N, w = self._cosets_call(ck_or_table, polynomials, l, n, w, N)
+        if not coeffs:
+            return ([], []) if with_values else []
+        table = self._coset_table_for(ck_or_table, n, l)
+        arr, lens, stride = self._pack(coeffs)
+        xy, inf, ev = self._context().open_cosets(table.table, np.ascontiguousarray(arr), lens, stride, log_N, w,
+                                                  evals=with_values)
+        proofs = [self._points(xy[j], inf[j]) for j in range(len(coeffs))]
+        if not with_values:
+            return proofs
+        cosets = (1 << log_N) // l
+        ints = _native.limbs_to_ints(np.ascontiguousarray(ev).reshape(-1, 4))
+        values = [[[ints[(j * cosets + i) * l + k] for k in range(l)] for i in range(cosets)]
+                  for j in range(len(coeffs))]
+        return proofs, values
+
+    def _coset_root(self, l, zeta):
+        """zeta for cosets of l points: Fq.root_of_unity(l) by default; a given one must be a primitive l-th root."""
+        r = self.curve_order
+        log_l = self._log2_exact(l, "coset size")
+        if (r - 1) % (1 << log_l):
+            raise ValueError(f"the scalar field has no {l}-th roots of unity")
+        zeta = int(self.Fq.root_of_unity(1 << log_l)) if zeta is None else int(zeta) % r
+        if log_l == 0:
+            if zeta != 1:
+                raise ValueError("zeta must be 1 for l = 1")
+        elif pow(zeta, (1 << log_l) // 2, r) != r - 1:
+            raise ValueError(f"zeta is not a primitive {l}-th root of unity")
+        return log_l, zeta
+
+    def open_coset(self, ck, polynomials, h, l, xi, zeta=None, with_values=False):
+        """ONE proof for the values of the xi^(j+1) combination at the l points h zeta^k (zeta defaults to
+        Fq.root_of_unity(l)): the commitment of (p - rho) / (X^l - h^l), rho = p mod (X^l - h^l).  l = 1 is open() at
+        z = h.  with_values: (proof, [combined(h zeta^k) for k < l])."""
+        if isinstance(ck, (LagrangeKey, DomainTable)):
+            raise TypeError("open_coset needs a monomial key (setup / load_key / a list of points)")
+        log_l, zeta = self._coset_root(l, zeta)
+        if log_l > self._COSET_MAX_LOG_L:
+            raise ValueError(f"coset size {l} exceeds 2^{self._COSET_MAX_LOG_L}")
+        h = int(self.Fq(h))
+        if h == 0:
+            raise ValueError("h must be non-zero")
+        xi = int(self.Fq(xi))
+        coeffs = [self._coeffs(p) for p in polynomials]
+        if len(coeffs) > 64:
+            raise ValueError("at most 64 polynomials per opening")
+        longest = max((len(c) for c in coeffs), default=0)
+        if longest > len(ck):
+            raise ValueError(f"Polynomial degree {longest - 1} exceeds maximum allowed degree {len(ck) - 1}")
+        key = self._key(ck)
+        arr, lens, stride = self._pack(coeffs)
+        xy, inf, ev = self._context().open_coset(key.srs, arr, lens, stride, log_l, h, zeta, xi)
+        proof = self._points(xy, inf)[0]
+        if not with_values:
+            return proof
+        return proof, [int(v) for v in _native.limbs_to_ints(np.ascontiguousarray(ev).reshape(-1, 4))]
+
+    # ---- coset verification (host) ---------------------------------------------------------------------------------
+    def coset_verification_key(self, l, tau):
+        """[tau^l] G2, the verifier's key for cosets of l points (l = 1: setup's tau G2)."""
+        self._log2_exact(l, "coset size")
+        return self.multiply(self.G2, pow(int(tau) % self.curve_order, int(l), self.curve_order))
+
+    def _coset_remainder(self, h, values, zeta):
+        """rho_j = h^-j l^-1 sum_k y_k zeta^(-jk): the coefficients of the remainder from its values at h zeta^k."""
+        r, l = self.curve_order, len(values)
+        h, zinv = int(self.Fq(h)), pow(zeta, -1, r)
+        lin, hinv = pow(l, -1, r), pow(h, -1, r)
+        ys = [int(self.Fq(v)) for v in values]
+        out, hp = [], lin
+        for j in range(l):
+            zj = pow(zinv, j, r)
+            acc, zp = 0, 1
+            for y in ys:
+                acc += y * zp
+                zp = zp * zj % r
+            out.append(acc % r * hp % r)
+            hp = hp * hinv % r
+        return out
+
+    def _folded_cosets(self, commitments, evaluations, xi, l):
+        """(sum_j xi^(j+1) C_j as a list of terms, sum_j xi^(j+1) y_j[k] for k < l) -- _folded_claim per value"""
+        r = self.curve_order
+        if len(evaluations) < len(commitments):
+            raise IndexError("list index out of range")
+        weight, parts, folded = xi, [], [0] * l
+        for j, C in enumerate(commitments):
+            ys = list(evaluations[j])
+            if len(ys) != l:
+                raise ValueError(f"{len(ys)} values for a coset of {l} points")
+            parts.append(self.multiply(C, weight))
+            folded = [(f + weight * int(self.Fq(y))) % r for f, y in zip(folded, ys)]
+            weight = weight * xi % r
+        return parts, folded
+
+    def _rho_commitment_terms(self, ck, rho):
+        return [self.multiply(ck[j], c) for j, c in enumerate(rho) if c]
+
+    def check_coset(self, ck, rk_l, commitments, h, evaluations, proof, xi, zeta=None):
+        """Two pairings: e(F - [rho(tau)], G2) = e(pi, rk_l - h^l G2), F = sum_j xi^(j+1) C_j, rho the remainder of the
+        folded values; evaluations[j] holds the l values of polynomial j at h zeta^k."""
+        evaluations = [list(e) for e in evaluations]
+        l = len(evaluations[0]) if evaluations else 1
+        _, zeta = self._coset_root(l, zeta)
+        r = self.curve_order
+        h, xi = int(self.Fq(h)), int(self.Fq(xi))
+        if h == 0 or len(ck) < l:
+            return False
+        parts, folded = self._folded_cosets(commitments, evaluations, xi, l)
+        rho = self._coset_remainder(h, folded, zeta)
+        parts += [self.neg(p) for p in self._rho_commitment_terms(ck, rho)]
+        shifted = self.add(rk_l, self.neg(self.multiply(self.G2, pow(h, l, r))))
+        return self.pairing(self.G2, self._sum_g1(parts)) == self.pairing(shifted, proof)
+
+    def batch_check_cosets(self, ck, rk_l, commitments_list, h_list, evaluations_list, proof_list, xi_list, zeta=None,
+                           r=None):
+        """Every claim e(F_i - [rho_i(tau)] + a_i pi_i, G2) = e(pi_i, rk_l), a_i = h_i^l, weighted rho^(i+1) as in
+        batch_check: two pairings in all, and the weighted remainders fold into ONE polynomial of degree < l, so the
+        interpolants cost one l-term sum."""
+        order = self.curve_order
+        claims = list(zip(commitments_list, h_list, evaluations_list, proof_list, xi_list))
+        if not claims:
+            return True
+        l = len(list(claims[0][2])[0]) if len(list(claims[0][2])) else 1
+        _, zeta = self._coset_root(l, zeta)
+        if len(ck) < l:
+            return False
+        rho_w = int(self.Fq(self.Fq.random_element() if r is None else r))
+        weight, lhs, rhs, rho_sum = rho_w, [], [], [0] * l
+        for commitments, h, evaluations, proof, xi in claims:
+            evaluations = [list(e) for e in evaluations]
+            h = int(self.Fq(h))
+            if h == 0:
+                return False
+            parts, folded = self._folded_cosets(commitments, evaluations, int(self.Fq(xi)), l)
+            rho = self._coset_remainder(h, folded, zeta)
+            rho_sum = [(s + weight * c) % order for s, c in zip(rho_sum, rho)]
+            F = self._sum_g1(parts + [self.multiply(proof, pow(h, l, order))])
+            lhs.append(self.multiply(F, weight))
+            rhs.append(self.multiply(proof, weight))
+            weight = weight * rho_w % order
+        lhs += [self.neg(p) for p in self._rho_commitment_terms(ck, rho_sum)]
+        return self.pairing(self.G2, self._sum_g1(lhs)) == self.pairing(rk_l, self._sum_g1(rhs))
