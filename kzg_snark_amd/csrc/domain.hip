@@ -13,26 +13,21 @@
 //                                h_m = u_(n-1+m), m <= n-2; h_(n-1) = O  (the linear convolution has 2n-2 < N terms)
 //                                pi = DFT_G1,n(h) with w, natural order
 // The G1 DFTs are radix 2, decimation in time, in XYZZ: a bit-reversed load (folded into the Hadamard pass and the
-// extraction), one launch per level over every vector of the batch, a pass to affine.  As in lagrange.hip's
-// g1_intt_level_kernel, butterfly t of a vector takes twiddle index k = t / (len / 2h): the lanes of a wave share a
-// twiddle wherever >= 64 butterflies do, so the double-and-add branches are wave-uniform on all but the last six
-// levels, and twiddle index 0 only adds and subtracts.
+// extraction), one launch per level over every vector of the batch (g1_level_kernel, launch_levels: also the
+// transform of lagrange.hip's key from a key), a pass to affine.  Butterfly t of a vector takes twiddle index
+// k = t / (len / 2h): the lanes of a wave share a twiddle wherever >= 64 butterflies do, so the double-and-add
+// branches are wave-uniform on all but the last six levels, and twiddle index 0 only adds and subtracts.
 // Every kernel: vector stores only, no scratch, <= 256 VGPRs, one instantiation per curve.
-#include <cstring>
 #include <algorithm>
-#include <vector>
 #include "internal.h"
-#include "ec.h"
+#include "fr_util.h"
+#include "g1_util.h"
 #include "msm.h"
 #include "srs_rec.h"
 
 namespace kzg {
 
 namespace {
-
-struct DomFr {                    // one Fr element (Montgomery limbs) as a kernel argument
-  uint32_t l[9];
-};
 
 // compact affine record of the table: x[NW] y[NW] canonical words, flag word (bit 0: infinity), pad to 16 bytes
 template <class C>
@@ -81,44 +76,6 @@ __device__ __forceinline__ void st_tbl(uint32_t* tbl, size_t idx, const Affine<C
   for (int q = 0; q < Tbl<C>::Q; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
 }
 
-template <class C>
-__device__ __forceinline__ XYZZ<C> dom_ld(const uint32_t* base, size_t idx) {
-  constexpr int N = C::Fp::N;
-  const uint4* p = reinterpret_cast<const uint4*>(base + idx * 4 * N);
-  uint32_t w[4 * N];
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-    const uint4 v = p[q];
-    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-  }
-  XYZZ<C> r;
-#pragma unroll
-  for (int j = 0; j < N; ++j) { r.x.l[j] = w[j]; r.y.l[j] = w[N + j]; r.zz.l[j] = w[2 * N + j]; r.zzz.l[j] = w[3 * N + j]; }
-  return r;
-}
-template <class C>
-__device__ __forceinline__ void dom_st(uint32_t* base, size_t idx, const XYZZ<C>& v) {
-  constexpr int N = C::Fp::N;
-  uint32_t w[4 * N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) { w[j] = v.x.l[j]; w[N + j] = v.y.l[j]; w[2 * N + j] = v.zz.l[j]; w[3 * N + j] = v.zzz.l[j]; }
-  uint4* p = reinterpret_cast<uint4*>(base + idx * 4 * N);
-#pragma unroll
-  for (int q = 0; q < N; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-}
-
-template <class F>
-__device__ __forceinline__ Fe<F> dom_arg(const DomFr& a) {
-  Fe<F> r;
-#pragma unroll
-  for (int j = 0; j < F::N; ++j) r.l[j] = a.l[j];
-  return r;
-}
-
-__device__ __forceinline__ uint32_t bitrev(uint32_t i, uint32_t log_len) {
-  return log_len ? __brev(i) >> (32 - log_len) : 0u;
-}
-
 // ---- kernels -----------------------------------------------------------------------------------------------------
 
 // table input of sub-table j < l (l = 2^log_l, m = n/l, 2m = 2^log_mm): buf[j][bitrev_2m(u)] = s_((m-2-u) l + j)
@@ -135,15 +92,15 @@ __global__ __launch_bounds__(128) void dom_load_key_kernel(const uint32_t* recs,
   } else {
     a.inf = true;
   }
-  dom_st<C>(buf, ((size_t)j << log_mm) + bitrev(u, log_mm), Ec<C>::from_affine(a));
+  st_point<C>(buf, ((size_t)j << log_mm) + bitrev(u, log_mm), Ec<C>::from_affine(a));
 }
 
 // one radix-2 level of half-size h = 2^s over `nvec` vectors of 2^log_len points each (vector j at j << log_len):
 // butterfly t pairs i0 = b*2h + k and i0 + h with twiddle root^(k * len/(2h)), k = t / (len/(2h)), b = t mod
 // (len/(2h)).  root in Montgomery form.
 template <class C>
-__global__ __launch_bounds__(64) void dom_level_kernel(uint32_t* buf, uint32_t nvec, uint32_t log_len, uint32_t s,
-                                                       DomFr root) {
+__global__ __launch_bounds__(64) void g1_level_kernel(uint32_t* buf, uint32_t nvec, uint32_t log_len, uint32_t s,
+                                                       FrArg root) {
   using Fr = typename C::Fr;
   using Frd = Field<Fr>;
   using Fd = Field<typename C::Fp>;
@@ -155,31 +112,21 @@ __global__ __launch_bounds__(64) void dom_level_kernel(uint32_t* buf, uint32_t n
   const uint32_t k = t >> lnb, b = t & ((1u << lnb) - 1);
   const size_t base = (size_t)j << log_len;
   const size_t i0 = base + ((size_t)b << (s + 1)) + k, i1 = i0 + ((size_t)1 << s);
-  XYZZ<C> B = dom_ld<C>(buf, i1);
+  XYZZ<C> B = ld_point<C>(buf, i1);
   if (k) {
-    Fe<Fr> pw = dom_arg<Fr>(root), acc = Frd::one();
+    Fe<Fr> pw = arg_fe<Fr>(root), acc = Frd::one();
     for (uint32_t bits = k << lnb; bits; bits >>= 1) {
       if (bits & 1u) acc = Frd::mul(acc, pw);
       pw = Frd::sqr(pw);
     }
     uint32_t e[8];
     Frd::to_words(Frd::from_mont(acc), e);
-    XYZZ<C> r = Ec<C>::infinity();
-#pragma unroll 1
-    for (int q = 7; q >= 0; --q) {
-      const uint32_t word = e[q];
-#pragma unroll 1
-      for (int bit = 31; bit >= 0; --bit) {
-        r = Ec<C>::dbl(r);
-        if ((word >> bit) & 1u) r = Ec<C>::add(r, B);
-      }
-    }
-    B = r;
+    B = g1_mul_words<C>(B, e);
   }
-  const XYZZ<C> A = dom_ld<C>(buf, i0);
-  dom_st<C>(buf, i0, Ec<C>::add(A, B));
+  const XYZZ<C> A = ld_point<C>(buf, i0);
+  st_point<C>(buf, i0, Ec<C>::add(A, B));
   B.y = Fd::neg(B.y);
-  dom_st<C>(buf, i1, Ec<C>::add(A, B));
+  st_point<C>(buf, i1, Ec<C>::add(A, B));
 }
 
 // Hadamard step: buf[j][bitrev_N(i)] = (chat_j[i] * N^-1) * S_i -- chat: [nvec][N] canonical Fr words (the forward
@@ -187,29 +134,16 @@ __global__ __launch_bounds__(64) void dom_level_kernel(uint32_t* buf, uint32_t n
 // for every input); the scalars differ per lane, so unlike the levels' twiddles the branches diverge.
 template <class C>
 __global__ __launch_bounds__(64) void dom_hadamard_kernel(const uint32_t* chat, const uint32_t* tbl, uint32_t nvec,
-                                                          uint32_t log_nn, DomFr ninv, uint32_t* buf) {
+                                                          uint32_t log_nn, FrArg ninv, uint32_t* buf) {
   using Fr = typename C::Fr;
   using Frd = Field<Fr>;
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= (nvec << log_nn)) return;
   const uint32_t j = g >> log_nn, i = g & ((1u << log_nn) - 1);
   const XYZZ<C> P = ld_tbl<C>(tbl, i);
-  const uint4* cp = reinterpret_cast<const uint4*>(chat + (size_t)g * 8);
-  const uint4 lo = cp[0], hi = cp[1];
-  const uint32_t cw[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  uint32_t e[8];
-  Frd::to_words(Frd::reduce(Frd::mul(Frd::from_words(cw), dom_arg<Fr>(ninv))), e);     // standard * Montgomery
-  XYZZ<C> r = Ec<C>::infinity();
-#pragma unroll 1
-  for (int q = 7; q >= 0; --q) {
-    const uint32_t word = e[q];
-#pragma unroll 1
-    for (int bit = 31; bit >= 0; --bit) {
-      r = Ec<C>::dbl(r);
-      if ((word >> bit) & 1u) r = Ec<C>::add(r, P);
-    }
-  }
-  dom_st<C>(buf, ((size_t)j << log_nn) + bitrev(i, log_nn), r);
+  uint32_t e[8];                                                                      // standard * Montgomery
+  Frd::to_words(Frd::reduce(Frd::mul(load_words<Fr>(chat + (size_t)g * 8), arg_fe<Fr>(ninv))), e);
+  st_point<C>(buf, ((size_t)j << log_nn) + bitrev(i, log_nn), g1_mul_words<C>(P, e));
 }
 
 // extraction into the bit-reversed input of the final transform: dst[j][bitrev(u)] = src[j][m-1+u] for u <= m-2, O
@@ -221,8 +155,8 @@ __global__ __launch_bounds__(64) void dom_extract_kernel(const uint32_t* src, ui
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= (nvec << log_dst)) return;
   const uint32_t j = g >> log_dst, u = g & ((1u << log_dst) - 1);
-  const XYZZ<C> v = u + 2 <= m ? dom_ld<C>(src, ((size_t)j << log_src) + m - 1 + u) : Ec<C>::infinity();
-  dom_st<C>(dst, ((size_t)j << log_dst) + bitrev(u, log_dst), v);
+  const XYZZ<C> v = u + 2 <= m ? ld_point<C>(src, ((size_t)j << log_src) + m - 1 + u) : Ec<C>::infinity();
+  st_point<C>(dst, ((size_t)j << log_dst) + bitrev(u, log_dst), v);
 }
 
 // ---- coset openings (open_cosets) ---------------------------------------------------------------------------------
@@ -248,17 +182,12 @@ __global__ __launch_bounds__(256) void dom_deinterleave_kernel(const uint32_t* s
 
 // in place: x[i] <- x[i] * 2m^-1 (canonical words; ninv Montgomery) -- the scalars of the Hadamard sum
 template <class F>
-__global__ __launch_bounds__(256) void dom_scale_kernel(uint32_t* x, uint32_t count, DomFr ninv) {
+__global__ __launch_bounds__(256) void dom_scale_kernel(uint32_t* x, uint32_t count, FrArg ninv) {
   using Fd = Field<F>;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  uint4* p = reinterpret_cast<uint4*>(x + (size_t)i * 8);
-  const uint4 lo = p[0], hi = p[1];
-  const uint32_t cw[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  uint32_t e[8];
-  Fd::to_words(Fd::reduce(Fd::mul(Fd::from_words(cw), dom_arg<F>(ninv))), e);      // standard * Montgomery
-  p[0] = make_uint4(e[0], e[1], e[2], e[3]);
-  p[1] = make_uint4(e[4], e[5], e[6], e[7]);
+  uint32_t* p = x + (size_t)i * 8;
+  store_words<F>(p, Fd::mul(load_words<F>(p), arg_fe<F>(ninv)));      // standard * Montgomery
 }
 
 // Hadamard sum over one group of G = 2^log_g sub-tables, Straus style (one doubling chain for the G terms):
@@ -293,9 +222,9 @@ __global__ __launch_bounds__(64) void dom_hadsum_kernel(const uint32_t* chat, co
     }
   }
   if (log_ng == 0)
-    dom_st<C>(dst, ((size_t)v << log_mm) + bitrev(i, log_mm), r);
+    st_point<C>(dst, ((size_t)v << log_mm) + bitrev(i, log_mm), r);
   else
-    dom_st<C>(dst, ((((size_t)v << log_mm) + i) << log_ng) + grp, r);
+    st_point<C>(dst, ((((size_t)v << log_mm) + i) << log_ng) + grp, r);
 }
 
 // u^[v][bitrev_2m(i)] = sum_grp part[v][i][grp]
@@ -306,10 +235,10 @@ __global__ __launch_bounds__(64) void dom_group_sum_kernel(const uint32_t* part,
   if (g >= (nvec << log_mm)) return;
   const uint32_t v = g >> log_mm, i = g & ((1u << log_mm) - 1);
   const size_t base = (size_t)g << log_ng;
-  XYZZ<C> r = dom_ld<C>(part, base);
+  XYZZ<C> r = ld_point<C>(part, base);
 #pragma unroll 1
-  for (uint32_t k = 1; k < (1u << log_ng); ++k) r = Ec<C>::add(r, dom_ld<C>(part, base + k));
-  dom_st<C>(dst, ((size_t)v << log_mm) + bitrev(i, log_mm), r);
+  for (uint32_t k = 1; k < (1u << log_ng); ++k) r = Ec<C>::add(r, ld_point<C>(part, base + k));
+  st_point<C>(dst, ((size_t)v << log_mm) + bitrev(i, log_mm), r);
 }
 
 // the values of every coset: dst[v][i][k] = src[v][i + k N/l] (src: [nvec][N] = DFT_N(p) with w, dst: [nvec][N/l][l])
@@ -330,7 +259,7 @@ template <class C>
 __global__ __launch_bounds__(64) void dom_finish_table_kernel(const uint32_t* buf, uint32_t count, uint32_t* tbl) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  st_tbl<C>(tbl, i, Ec<C>::to_affine(dom_ld<C>(buf, i)));
+  st_tbl<C>(tbl, i, Ec<C>::to_affine(ld_point<C>(buf, i)));
 }
 
 // proofs: buf[i] as canonical affine words x[NW] y[NW] (kzg_open's point format) and a flag byte
@@ -341,7 +270,7 @@ __global__ __launch_bounds__(64) void dom_finish_proofs_kernel(const uint32_t* b
   using Fd = Field<F>;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  const Affine<C> a = Ec<C>::to_affine(dom_ld<C>(buf, i));
+  const Affine<C> a = Ec<C>::to_affine(ld_point<C>(buf, i));
   uint32_t w[2 * F::NW];
   if (a.inf) {
 #pragma unroll
@@ -364,18 +293,11 @@ constexpr uint32_t DOM_MAX_LOG = 20;
 constexpr size_t DOM_SCRATCH_BYTES = (size_t)2 << 30;
 constexpr uint32_t DOM_MAX_CHUNK = 1024;       // keeps every launch below 2^31 threads (N <= 2^21)
 
-template <class F>
-DomFr dom_fr(const Fe<F>& v) {
-  DomFr a;
-  memcpy(a.l, v.l, sizeof(a.l));
-  return a;
-}
-
 // small integer -> Montgomery element
 template <class F>
 Fe<F> fr_small(uint32_t v) {
   uint32_t w[8] = {v, 0, 0, 0, 0, 0, 0, 0};
-  return Field<F>::to_mont(Field<F>::from_words(w));
+  return mont_from_words<F>(w);
 }
 
 template <class F>
@@ -388,15 +310,6 @@ Fe<F> fr_pow_words(const Fe<F>& base, const uint32_t* e) {
       if ((e[k] >> b) & 1u) acc = Fd::mul(acc, base);
     }
   return acc;
-}
-
-// w^(2^(log_len-1)) = -1 (w canonical words; Montgomery arithmetic)
-template <class F>
-bool dom_primitive(const Fe<F>& w_mont, uint32_t log_len) {
-  using Fd = Field<F>;
-  Fe<F> x = w_mont;
-  for (uint32_t q = 1; q < log_len; ++q) x = Fd::sqr(x);
-  return Fd::eq(x, Fd::neg(Fd::one()));
 }
 
 // the library's primitive 2^log_len-th root: g^((r-1) / 2^log_len), g = 5 (BN254) / 7 (BLS12-381), Montgomery
@@ -414,18 +327,40 @@ Fe<typename C::Fr> dom_omega(uint32_t log_len) {
 }
 
 template <class C>
-int launch_levels(Ctx* c, uint32_t* buf, uint32_t nvec, uint32_t log_len, const Fe<typename C::Fr>& root) {
-  const size_t threads = (size_t)nvec << (log_len - 1);
-  const uint32_t blocks = (uint32_t)((threads + 63) / 64);
-  for (uint32_t lv = 0; lv < log_len; ++lv)
-    hipLaunchKernelGGL(dom_level_kernel<C>, dim3(blocks), dim3(64), 0, c->stream, buf, nvec, log_len, lv,
-                       dom_fr<typename C::Fr>(root));
-  KZG_HIP(c, hipGetLastError());
+size_t xyzz_bytes() { return (size_t)4 * C::Fp::N * 4; }
+
+// d_dst[j] = vector j of polys (lens[j] coefficients, `stride` elements apart) zero-padded to `len` elements, j < m
+int stage_polys(Ctx* c, uint32_t* d_dst, size_t len, const uint32_t* polys, hipMemcpyKind kind, const size_t* lens,
+                size_t stride, uint32_t m) {
+  KZG_HIP(c, hipMemsetAsync(d_dst, 0, (size_t)m * len * 32, c->stream));
+  for (uint32_t j = 0; j < m; ++j)
+    if (lens[j])
+      KZG_HIP(c, hipMemcpyAsync(d_dst + (size_t)j * len * 8, polys + j * stride * 8, lens[j] * 32, kind, c->stream));
   return KZG_OK;
 }
 
+// The tail of a chunk of `nvec` vectors: h from u = d_big (dom_extract_kernel), pi = DFT_G1(h) with `root` in d_small,
+// the 2^log_dst proofs per vector as affine words in d_oxy / d_oinf and on their way to the host (vector 0 of the
+// chunk is vector j0 of the call).
 template <class C>
-size_t xyzz_bytes() { return (size_t)4 * C::Fp::N * 4; }
+int finish_proofs(Ctx* c, const uint32_t* d_big, uint32_t nvec, uint32_t log_src, uint32_t m, uint32_t log_dst,
+                  uint32_t* d_small, const Fe<typename C::Fr>& root, uint32_t* d_oxy, uint8_t* d_oinf, size_t j0,
+                  uint64_t* out_xy, uint8_t* out_inf) {
+  const size_t count = (size_t)nvec << log_dst, pt_words = 2 * C::Fp::NW;
+  const uint32_t blocks = (uint32_t)((count + 63) / 64);
+  hipLaunchKernelGGL(dom_extract_kernel<C>, dim3(blocks), dim3(64), 0, c->stream, d_big, nvec, log_src, m, log_dst,
+                     d_small);
+  KZG_HIP(c, hipGetLastError());
+  int rc = launch_levels(c, d_small, nvec, log_dst, fr_arg<typename C::Fr>(root));
+  if (rc) return rc;
+  hipLaunchKernelGGL(dom_finish_proofs_kernel<C>, dim3(blocks), dim3(64), 0, c->stream, d_small, (uint32_t)count,
+                     d_oxy, d_oinf);
+  KZG_HIP(c, hipGetLastError());
+  KZG_HIP(c, hipMemcpyAsync(out_xy + (j0 << log_dst) * pt_words / 2, d_oxy, count * pt_words * 4,
+                            hipMemcpyDeviceToHost, c->stream));
+  KZG_HIP(c, hipMemcpyAsync(out_inf + (j0 << log_dst), d_oinf, count, hipMemcpyDeviceToHost, c->stream));
+  return KZG_OK;
+}
 
 }  // namespace
 
@@ -454,7 +389,7 @@ int domain_table_t(Ctx* c, const Srs* mono, uint32_t log_n, uint32_t log_l, cons
   const uint32_t m = n >> log_l, log_mm = log_n - log_l + 1;
   if (mono->n < n) return set_err(c, KZG_ERR_ARG, (std::string(fn) + ": monomial key shorter than the domain").c_str());
   const Fe<F> omega = dom_omega<C>(log_mm);
-  if (!dom_primitive<F>(omega, log_mm)) return set_err(c, KZG_ERR_ARG, (std::string(fn) + ": no 2m-th root").c_str());
+  if (!primitive_root<F>(omega, log_mm)) return set_err(c, KZG_ERR_ARG, (std::string(fn) + ": no 2m-th root").c_str());
   DomainTable* t = new DomainTable();
   t->curve = c->curve;
   t->log_n = log_n;
@@ -469,7 +404,7 @@ int domain_table_t(Ctx* c, const Srs* mono, uint32_t log_n, uint32_t log_l, cons
     ProfScope ps(c, span);
     hipLaunchKernelGGL(dom_load_key_kernel<C>, dim3((nn + 127) / 128), dim3(128), 0, c->stream, mono->recs, m, log_l,
                        log_mm, d_buf);
-    int rc = launch_levels<C>(c, d_buf, 1u << log_l, log_mm, omega);
+    int rc = launch_levels(c, d_buf, 1u << log_l, log_mm, fr_arg<F>(omega));
     if (rc) return fail(rc);
     hipLaunchKernelGGL(dom_finish_table_kernel<C>, dim3((nn + 63) / 64), dim3(64), 0, c->stream, d_buf, nn,
                        t->d_tbl);
@@ -495,7 +430,7 @@ int open_domain_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
   if (t->log_l) return set_err(c, KZG_ERR_ARG, "kzg_open_domain: a coset table (l > 1) needs kzg_open_cosets");
   const uint32_t log_n = t->log_n, log_nn = log_n + 1;
   const size_t n = t->n, nn = 2 * n;
-  if (!dom_primitive<F>(Fd::to_mont(Fd::from_words(w_words)), log_n))
+  if (!primitive_root<F>(mont_from_words<F>(w_words), log_n))
     return set_err(c, KZG_ERR_ARG, "kzg_open_domain: w is not a primitive n-th root of unity");
   for (size_t j = 0; j < b; ++j) {
     if (lens[j] > n) return set_err(c, KZG_ERR_DEGREE, "polynomial longer than the domain");
@@ -517,45 +452,28 @@ int open_domain_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
 
   const Fe<F> omega = dom_omega<C>(log_nn);
   const Fe<F> omega_inv = Fd::inv(omega);
-  uint32_t omega_words[8], nw[8] = {0};
+  uint32_t omega_words[8];
   Fd::to_words(Fd::from_mont(omega), omega_words);
-  nw[log_nn >> 5] = 1u << (log_nn & 31);
-  const Fe<F> ninv = Fd::reduce(Fd::inv(Fd::to_mont(Fd::from_words(nw))));
-  const Fe<F> w = Fd::to_mont(Fd::from_words(w_words));
+  const Fe<F> ninv = Fd::reduce(inv_pow2<F>(log_nn));
+  const Fe<F> w = mont_from_words<F>(w_words);
   const hipMemcpyKind kind = host_polys ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
 
   ProfScope ps(c, "open_domain");
   for (size_t j0 = 0; j0 < b; j0 += chunk) {
     const uint32_t m = (uint32_t)std::min(chunk, b - j0);
     // c^ = DFT_N(c), zero-padded
-    KZG_HIP(c, hipMemsetAsync(d_fr, 0, (size_t)m * nn * 32, c->stream));
-    for (uint32_t j = 0; j < m; ++j)
-      if (lens[j0 + j])
-        KZG_HIP(c, hipMemcpyAsync(d_fr + (size_t)j * nn * 8, polys + (j0 + j) * stride * 8, lens[j0 + j] * 32, kind,
-                                  c->stream));
+    if ((rc = stage_polys(c, d_fr, nn, polys + j0 * stride * 8, kind, lens + j0, stride, m))) return rc;
     if ((rc = ntt_run_device(c, d_fr, log_nn, omega_words, 0, m))) return rc;
     const size_t big = (size_t)m * nn, small = (size_t)m * n;
     hipLaunchKernelGGL(dom_hadamard_kernel<C>, dim3((uint32_t)((big + 63) / 64)), dim3(64), 0, c->stream, d_fr,
-                       t->d_tbl, m, log_nn, dom_fr<F>(ninv), d_big);
+                       t->d_tbl, m, log_nn, fr_arg<F>(ninv), d_big);
     KZG_HIP(c, hipGetLastError());
-    if ((rc = launch_levels<C>(c, d_big, m, log_nn, omega_inv))) return rc;
-    hipLaunchKernelGGL(dom_extract_kernel<C>, dim3((uint32_t)((small + 63) / 64)), dim3(64), 0, c->stream, d_big, m,
-                       log_nn, (uint32_t)n, log_n, d_small);
-    KZG_HIP(c, hipGetLastError());
-    if ((rc = launch_levels<C>(c, d_small, m, log_n, w))) return rc;
-    hipLaunchKernelGGL(dom_finish_proofs_kernel<C>, dim3((uint32_t)((small + 63) / 64)), dim3(64), 0, c->stream,
-                       d_small, (uint32_t)small, d_oxy, d_oinf);
-    KZG_HIP(c, hipGetLastError());
-    const size_t pt_words = 2 * Fp::NW;
-    KZG_HIP(c, hipMemcpyAsync(out_xy + j0 * n * pt_words / 2, d_oxy, small * pt_words * 4, hipMemcpyDeviceToHost,
-                              c->stream));
-    KZG_HIP(c, hipMemcpyAsync(out_inf + j0 * n, d_oinf, small, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = launch_levels(c, d_big, m, log_nn, fr_arg<F>(omega_inv)))) return rc;
+    if ((rc = finish_proofs<C>(c, d_big, m, log_nn, (uint32_t)n, log_n, d_small, w, d_oxy, d_oinf, j0, out_xy,
+                               out_inf)))
+      return rc;
     if (eval_out) {   // y = DFT_n(c) with w, in the Fr buffer the Hadamard step has consumed
-      KZG_HIP(c, hipMemsetAsync(d_fr, 0, small * 32, c->stream));
-      for (uint32_t j = 0; j < m; ++j)
-        if (lens[j0 + j])
-          KZG_HIP(c, hipMemcpyAsync(d_fr + (size_t)j * n * 8, polys + (j0 + j) * stride * 8, lens[j0 + j] * 32, kind,
-                                    c->stream));
+      if ((rc = stage_polys(c, d_fr, n, polys + j0 * stride * 8, kind, lens + j0, stride, m))) return rc;
       if ((rc = ntt_run_device(c, d_fr, log_n, w_words, 0, m))) return rc;
       KZG_HIP(c, hipMemcpyAsync(eval_out + j0 * n * 4, d_fr, small * 32, hipMemcpyDeviceToHost, c->stream));
     }
@@ -585,7 +503,7 @@ int open_cosets_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
   const uint32_t log_n = t->log_n, log_l = t->log_l;
   if (log_N < log_n || log_N > std::min<uint32_t>(log_n + 2, DOM_MAX_LOG + 1))
     return set_err(c, KZG_ERR_ARG, "kzg_open_cosets: log_N must be in [log_n, min(log_n + 2, 21)]");
-  if (!dom_primitive<F>(Fd::to_mont(Fd::from_words(w_words)), log_N))
+  if (!primitive_root<F>(mont_from_words<F>(w_words), log_N))
     return set_err(c, KZG_ERR_ARG, "kzg_open_cosets: w is not a primitive N-th root of unity");
   const size_t n = t->n;
   for (size_t j = 0; j < b; ++j) {
@@ -624,11 +542,10 @@ int open_cosets_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
 
   const Fe<F> omega = dom_omega<C>(log_mm);
   const Fe<F> omega_inv = Fd::inv(omega);
-  uint32_t omega_words[8], mw[8] = {0};
+  uint32_t omega_words[8];
   Fd::to_words(Fd::from_mont(omega), omega_words);
-  mw[log_mm >> 5] = 1u << (log_mm & 31);
-  const Fe<F> mminv = Fd::reduce(Fd::inv(Fd::to_mont(Fd::from_words(mw))));
-  Fe<F> wl = Fd::to_mont(Fd::from_words(w_words));                                // w^l: the final transform's root
+  const Fe<F> mminv = Fd::reduce(inv_pow2<F>(log_mm));
+  Fe<F> wl = mont_from_words<F>(w_words);                                         // w^l: the final transform's root
   for (uint32_t q = 0; q < log_l; ++q) wl = Fd::sqr(wl);
   const hipMemcpyKind kind = host_polys ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
 
@@ -636,20 +553,16 @@ int open_cosets_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
   for (size_t j0 = 0; j0 < b; j0 += chunk) {
     const uint32_t mv = (uint32_t)std::min(chunk, b - j0);
     // the coefficients, zero-padded to n, then de-interleaved into the l zero-padded transforms of size 2m
-    KZG_HIP(c, hipMemsetAsync(d_stage, 0, (size_t)mv * n * 32, c->stream));
-    for (uint32_t j = 0; j < mv; ++j)
-      if (lens[j0 + j])
-        KZG_HIP(c, hipMemcpyAsync(d_stage + (size_t)j * n * 8, polys + (j0 + j) * stride * 8, lens[j0 + j] * 32, kind,
-                                  c->stream));
+    if ((rc = stage_polys(c, d_stage, n, polys + j0 * stride * 8, kind, lens + j0, stride, mv))) return rc;
     const size_t frs = (size_t)mv * 2 * n;
     hipLaunchKernelGGL(dom_deinterleave_kernel, dim3((uint32_t)((frs + 255) / 256)), dim3(256), 0, c->stream, d_stage,
                        mv, log_l, log_mm, d_fr);
     KZG_HIP(c, hipGetLastError());
     if ((rc = ntt_run_device(c, d_fr, log_mm, omega_words, 0, mv << log_l))) return rc;
     hipLaunchKernelGGL(dom_scale_kernel<F>, dim3((uint32_t)((frs + 255) / 256)), dim3(256), 0, c->stream, d_fr,
-                       (uint32_t)frs, dom_fr<F>(mminv));
+                       (uint32_t)frs, fr_arg<F>(mminv));
     KZG_HIP(c, hipGetLastError());
-    const size_t hs = (size_t)mv * mm << log_ng, big = (size_t)mv * mm, small = (size_t)mv * L;
+    const size_t hs = (size_t)mv * mm << log_ng, big = (size_t)mv * mm;
     hipLaunchKernelGGL(dom_hadsum_kernel<C>, dim3((uint32_t)((hs + 63) / 64)), dim3(64), 0, c->stream, d_fr,
                        t->d_tbl, mv, log_l, log_mm, log_g, log_ng ? d_part : d_big);
     KZG_HIP(c, hipGetLastError());
@@ -658,17 +571,9 @@ int open_cosets_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
                          mv, log_mm, log_ng, d_big);
       KZG_HIP(c, hipGetLastError());
     }
-    if ((rc = launch_levels<C>(c, d_big, mv, log_mm, omega_inv))) return rc;
-    hipLaunchKernelGGL(dom_extract_kernel<C>, dim3((uint32_t)((small + 63) / 64)), dim3(64), 0, c->stream, d_big, mv,
-                       log_mm, m, log_L, d_small);
-    KZG_HIP(c, hipGetLastError());
-    if ((rc = launch_levels<C>(c, d_small, mv, log_L, wl))) return rc;
-    hipLaunchKernelGGL(dom_finish_proofs_kernel<C>, dim3((uint32_t)((small + 63) / 64)), dim3(64), 0, c->stream,
-                       d_small, (uint32_t)small, d_oxy, d_oinf);
-    KZG_HIP(c, hipGetLastError());
-    KZG_HIP(c, hipMemcpyAsync(out_xy + j0 * L * pt_words / 2, d_oxy, small * pt_words * 4, hipMemcpyDeviceToHost,
-                              c->stream));
-    KZG_HIP(c, hipMemcpyAsync(out_inf + j0 * L, d_oinf, small, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = launch_levels(c, d_big, mv, log_mm, fr_arg<F>(omega_inv)))) return rc;
+    if ((rc = finish_proofs<C>(c, d_big, mv, log_mm, m, log_L, d_small, wl, d_oxy, d_oinf, j0, out_xy, out_inf)))
+      return rc;
     if (eval_out) {   // y = DFT_N(c) with w, regrouped per coset
       KZG_HIP(c, hipMemsetAsync(d_val, 0, (size_t)mv * NN * 32, c->stream));
       KZG_HIP(c, hipMemcpy2DAsync(d_val, NN * 32, d_stage, n * 32, n * 32, mv, hipMemcpyDeviceToDevice, c->stream));
@@ -687,6 +592,19 @@ int open_cosets_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
 
 }  // namespace
 
+// every level of the transform of `nvec` vectors of 2^log_len points (bit-reversed in, natural out), root Montgomery
+int launch_levels(Ctx* c, uint32_t* buf, uint32_t nvec, uint32_t log_len, const FrArg& root) {
+  const size_t threads = (size_t)nvec << (log_len - 1);
+  const dim3 blocks((uint32_t)((threads + 63) / 64));
+  for (uint32_t lv = 0; lv < log_len; ++lv) {
+    if (c->curve == 0)
+      hipLaunchKernelGGL(g1_level_kernel<Bn254>, blocks, dim3(64), 0, c->stream, buf, nvec, log_len, lv, root);
+    else
+      hipLaunchKernelGGL(g1_level_kernel<Bls12_381>, blocks, dim3(64), 0, c->stream, buf, nvec, log_len, lv, root);
+  }
+  KZG_HIP(c, hipGetLastError());
+  return KZG_OK;
+}
 int domain_table_create(Ctx* c, const Srs* mono, uint32_t log_n, DomainTable** out) {
   return c->curve == 0 ? domain_table_t<Bn254>(c, mono, log_n, 0, "kzg_domain_table_create", "domain_table", out)
                        : domain_table_t<Bls12_381>(c, mono, log_n, 0, "kzg_domain_table_create", "domain_table", out);

@@ -4,12 +4,9 @@
 //   key from tau      L_i(tau) = (tau^n - 1)/n * w^i / (tau - w^i)   (e_m when tau = w^m), then the fixed-base
 //                     table of srs_generate_kernel (msm.hip) with the scalar taken from that vector
 //   key from a key    L_i = n^-1 sum_j w^(-ij) P_j over the first n window-0 records of a monomial key: an inverse
-//                     NTT over G1 in XYZZ, radix 2, decimation in time (bit-reversed load, natural output), one
-//                     launch per level; every butterfly multiplies a point by its twiddle (double-and-add over the
-//                     255 bits).  Butterfly t of a level takes twiddle index k = t / (n / 2h): the lanes of a wave
-//                     share a twiddle wherever >= 64 butterflies do, so the double-and-add branches are
-//                     wave-uniform on all but the last six levels.  Level 0 has twiddle 1 (add / subtract only);
-//                     n^-1 is applied once, in the pass that writes the affine records.
+//                     NTT over G1 in XYZZ, radix 2, decimation in time: a bit-reversed load (g1_intt_load_kernel),
+//                     the levels of domain.hip's transform (launch_levels: one vector, root w^-1, natural output),
+//                     and n^-1 applied once, in the pass that writes the affine records (g1_intt_finish_kernel).
 //   open from values  P = sum_j xi^(j+1) f_j (kzg.py:148-150, fr_vec_lincomb), d_i = z - w^i inverted as a batch
 //                     (fr_vec_inverse, 0 -> 0), then ONE reduction pass for three sums over i with d_i != 0
 //                       S = sum P_i w^i / d_i     T = sum w^i / d_i     E = P_m (the i with d_i = 0, if any)
@@ -22,7 +19,8 @@
 #include <algorithm>
 #include <vector>
 #include "internal.h"
-#include "ec.h"
+#include "fr_util.h"
+#include "g1_util.h"
 #include "msm.h"
 #include "srs_rec.h"
 
@@ -31,9 +29,6 @@ namespace kzg {
 namespace {
 
 constexpr int LG_FRN = 9;         // both scalar fields: 9 x 29-bit limbs
-struct LgFr {                     // one Fr element (limbs) as a kernel argument
-  uint32_t l[LG_FRN];
-};
 struct LgWords {                  // one Fr element as canonical words (a scalar multiplier)
   uint32_t w[8];
 };
@@ -42,40 +37,6 @@ constexpr uint32_t SUM_TB = 128;  // threads per workgroup of the reduction pass
 // 32 elements per thread at 2^20: 115 us; 2048: 4 per thread)
 constexpr uint32_t SUM_MAXG = 2048;
 
-template <class F>
-__device__ __forceinline__ Fe<F> ld_words(const uint32_t* p) {
-  const uint4* g = reinterpret_cast<const uint4*>(p);
-  const uint4 lo = g[0], hi = g[1];
-  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  return Field<F>::from_words(w);
-}
-template <class F>
-__device__ __forceinline__ void st_words(uint32_t* p, const Fe<F>& v) {
-  uint32_t w[8];
-  Field<F>::to_words(Field<F>::reduce(v), w);
-  uint4* g = reinterpret_cast<uint4*>(p);
-  g[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  g[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-template <class F>
-__device__ __forceinline__ Fe<F> ld_limbs(const uint32_t* p) {
-  Fe<F> r;
-#pragma unroll
-  for (int j = 0; j < F::N; ++j) r.l[j] = p[j];
-  return r;
-}
-template <class F>
-__device__ __forceinline__ void st_limbs(uint32_t* p, const Fe<F>& v) {
-#pragma unroll
-  for (int j = 0; j < F::N; ++j) p[j] = v.l[j];
-}
-template <class F>
-__device__ __forceinline__ Fe<F> arg_fe(const LgFr& a) {
-  Fe<F> r;
-#pragma unroll
-  for (int j = 0; j < F::N; ++j) r.l[j] = a.l[j];
-  return r;
-}
 template <class F>
 __device__ __forceinline__ Fe<F> shfl_xor_fe(const Fe<F>& v, int mask) {
   Fe<F> r;
@@ -88,7 +49,7 @@ __device__ __forceinline__ Fe<F> shfl_xor_fe(const Fe<F>& v, int mask) {
 
 // out[i] = w^i (canonical words); w in Montgomery form
 template <class F>
-__global__ __launch_bounds__(256) void lagr_wpow_kernel(uint32_t n, LgFr w, uint32_t* out) {
+__global__ __launch_bounds__(256) void lagr_wpow_kernel(uint32_t n, FrArg w, uint32_t* out) {
   using Fd = Field<F>;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -97,30 +58,30 @@ __global__ __launch_bounds__(256) void lagr_wpow_kernel(uint32_t n, LgFr w, uint
     if (bits & 1u) acc = Fd::mul(acc, b);
     b = Fd::sqr(b);
   }
-  st_words<F>(out + (size_t)i * 8, Fd::from_mont(acc));
+  store_words<F>(out + (size_t)i * 8, Fd::from_mont(acc));
 }
 
 // d[i] = z - w^i (z in standard form: the difference of two standard values is one)
 template <class F>
-__global__ __launch_bounds__(256) void lagr_denom_kernel(uint32_t n, const uint32_t* wpow, LgFr z, uint32_t* d) {
+__global__ __launch_bounds__(256) void lagr_denom_kernel(uint32_t n, const uint32_t* wpow, FrArg z, uint32_t* d) {
   using Fd = Field<F>;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  st_words<F>(d + (size_t)i * 8, Fd::sub(arg_fe<F>(z), ld_words<F>(wpow + (size_t)i * 8)));
+  store_words<F>(d + (size_t)i * 8, Fd::sub(arg_fe<F>(z), load_words<F>(wpow + (size_t)i * 8)));
 }
 
 // L_i(tau) from the inverted denominators: inv_i = 0 marks tau = w^i (scalar 1; cz = 0 then zeroes the others)
 template <class F>
 __global__ __launch_bounds__(256) void lagr_basis_scalars_kernel(uint32_t n, const uint32_t* wpow,
-                                                                 const uint32_t* inv, LgFr cz, uint32_t* out) {
+                                                                 const uint32_t* inv, FrArg cz, uint32_t* out) {
   using Fd = Field<F>;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const Fe<F> iv = ld_words<F>(inv + (size_t)i * 8);
+  const Fe<F> iv = load_words<F>(inv + (size_t)i * 8);
   Fe<F> r;
   if (Fd::is_zero(iv)) r = Fd::raw_one();
-  else r = Fd::mul(Fd::mul(arg_fe<F>(cz), Fd::to_mont(ld_words<F>(wpow + (size_t)i * 8))), iv);   // standard form
-  st_words<F>(out + (size_t)i * 8, r);
+  else r = Fd::mul(Fd::mul(arg_fe<F>(cz), Fd::to_mont(load_words<F>(wpow + (size_t)i * 8))), iv);   // standard form
+  store_words<F>(out + (size_t)i * 8, r);
 }
 
 // Per workgroup: S = sum P_i w^i inv_i, T = sum w^i inv_i over inv_i != 0, E = sum P_i over inv_i = 0 (P_i = 0 for
@@ -133,12 +94,12 @@ __global__ __launch_bounds__(SUM_TB) void lagr_sums_kernel(uint32_t n, uint32_t 
   Fe<F> S = Fd::zero(), T = Fd::zero(), E = Fd::zero();
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const Fe<F> iv = ld_words<F>(inv + (size_t)i * 8);
-    const Fe<F> p = i < plen ? Fd::to_mont(ld_words<F>(P + (size_t)i * 8)) : Fd::zero();
+    const Fe<F> iv = load_words<F>(inv + (size_t)i * 8);
+    const Fe<F> p = i < plen ? Fd::to_mont(load_words<F>(P + (size_t)i * 8)) : Fd::zero();
     if (Fd::is_zero(iv)) {
       E = Fd::add(E, p);
     } else {
-      const Fe<F> u = Fd::mul(Fd::to_mont(ld_words<F>(wpow + (size_t)i * 8)), Fd::to_mont(iv));
+      const Fe<F> u = Fd::mul(Fd::to_mont(load_words<F>(wpow + (size_t)i * 8)), Fd::to_mont(iv));
       T = Fd::add(T, u);
       S = Fd::add(S, Fd::mul(p, u));
     }
@@ -151,35 +112,35 @@ __global__ __launch_bounds__(SUM_TB) void lagr_sums_kernel(uint32_t n, uint32_t 
   }
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   if (lane == 0) {
-    st_limbs<F>(&red[wave][0], S);
-    st_limbs<F>(&red[wave][LG_FRN], T);
-    st_limbs<F>(&red[wave][2 * LG_FRN], E);
+    store_limbs<F>(&red[wave][0], S);
+    store_limbs<F>(&red[wave][LG_FRN], T);
+    store_limbs<F>(&red[wave][2 * LG_FRN], E);
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (uint32_t q = 1; q < SUM_TB / 64; ++q) {
-      S = Fd::add(S, ld_limbs<F>(&red[q][0]));
-      T = Fd::add(T, ld_limbs<F>(&red[q][LG_FRN]));
-      E = Fd::add(E, ld_limbs<F>(&red[q][2 * LG_FRN]));
+      S = Fd::add(S, load_limbs<F>(&red[q][0]));
+      T = Fd::add(T, load_limbs<F>(&red[q][LG_FRN]));
+      E = Fd::add(E, load_limbs<F>(&red[q][2 * LG_FRN]));
     }
     uint32_t* o = part + (size_t)blockIdx.x * 3 * LG_FRN;
-    st_limbs<F>(o, S);
-    st_limbs<F>(o + LG_FRN, T);
-    st_limbs<F>(o + 2 * LG_FRN, E);
+    store_limbs<F>(o, S);
+    store_limbs<F>(o + LG_FRN, T);
+    store_limbs<F>(o + 2 * LG_FRN, E);
   }
 }
 
 // One wave: y = cz S + E, q_m = zinv (S - y T).  out: y as canonical words [8], y (Montgomery) [9], q_m [9]
 template <class F>
-__global__ __launch_bounds__(64) void lagr_value_kernel(uint32_t groups, const uint32_t* part, LgFr cz, LgFr zinv,
+__global__ __launch_bounds__(64) void lagr_value_kernel(uint32_t groups, const uint32_t* part, FrArg cz, FrArg zinv,
                                                         uint32_t* out) {
   using Fd = Field<F>;
   Fe<F> S = Fd::zero(), T = Fd::zero(), E = Fd::zero();
   for (uint32_t g = threadIdx.x; g < groups; g += 64) {
     const uint32_t* q = part + (size_t)g * 3 * LG_FRN;
-    S = Fd::add(S, ld_limbs<F>(q));
-    T = Fd::add(T, ld_limbs<F>(q + LG_FRN));
-    E = Fd::add(E, ld_limbs<F>(q + 2 * LG_FRN));
+    S = Fd::add(S, load_limbs<F>(q));
+    T = Fd::add(T, load_limbs<F>(q + LG_FRN));
+    E = Fd::add(E, load_limbs<F>(q + 2 * LG_FRN));
   }
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
@@ -190,9 +151,9 @@ __global__ __launch_bounds__(64) void lagr_value_kernel(uint32_t groups, const u
   if (threadIdx.x != 0) return;
   const Fe<F> y = Fd::reduce(Fd::add(Fd::mul(arg_fe<F>(cz), S), E));
   const Fe<F> qm = Fd::reduce(Fd::mul(arg_fe<F>(zinv), Fd::sub(S, Fd::mul(y, T))));
-  st_words<F>(out, Fd::from_mont(y));
-  st_limbs<F>(out + 8, y);
-  st_limbs<F>(out + 8 + LG_FRN, qm);
+  store_words<F>(out, Fd::from_mont(y));
+  store_limbs<F>(out + 8, y);
+  store_limbs<F>(out + 8 + LG_FRN, qm);
 }
 
 // q_i = (y - P_i) inv_i = (P_i - y)/(w^i - z); q_m (inv_m = 0, z = w^m) from lagr_value_kernel
@@ -202,60 +163,18 @@ __global__ __launch_bounds__(256) void lagr_quotient_kernel(uint32_t n, const ui
   using Fd = Field<F>;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const Fe<F> iv = ld_words<F>(inv + (size_t)i * 8);
+  const Fe<F> iv = load_words<F>(inv + (size_t)i * 8);
   Fe<F> r;
   if (Fd::is_zero(iv)) {
-    r = Fd::from_mont(ld_limbs<F>(val + 8 + LG_FRN));
+    r = Fd::from_mont(load_limbs<F>(val + 8 + LG_FRN));
   } else {
-    const Fe<F> d = Fd::sub(ld_limbs<F>(val + 8), Fd::to_mont(ld_words<F>(P + (size_t)i * 8)));   // Montgomery
+    const Fe<F> d = Fd::sub(load_limbs<F>(val + 8), Fd::to_mont(load_words<F>(P + (size_t)i * 8)));   // Montgomery
     r = Fd::mul(d, iv);                                                                           // standard
   }
-  st_words<F>(q + (size_t)i * 8, r);
+  store_words<F>(q + (size_t)i * 8, r);
 }
 
 // ---- G1 inverse NTT -------------------------------------------------------------------------------
-
-template <class C>
-__device__ __forceinline__ XYZZ<C> ld_point(const uint32_t* base, size_t idx) {
-  constexpr int N = C::Fp::N;
-  const uint4* p = reinterpret_cast<const uint4*>(base + idx * 4 * N);
-  uint32_t w[4 * N];
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-    const uint4 v = p[q];
-    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-  }
-  XYZZ<C> r;
-#pragma unroll
-  for (int j = 0; j < N; ++j) { r.x.l[j] = w[j]; r.y.l[j] = w[N + j]; r.zz.l[j] = w[2 * N + j]; r.zzz.l[j] = w[3 * N + j]; }
-  return r;
-}
-template <class C>
-__device__ __forceinline__ void st_point(uint32_t* base, size_t idx, const XYZZ<C>& v) {
-  constexpr int N = C::Fp::N;
-  uint32_t w[4 * N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) { w[j] = v.x.l[j]; w[N + j] = v.y.l[j]; w[2 * N + j] = v.zz.l[j]; w[3 * N + j] = v.zzz.l[j]; }
-  uint4* p = reinterpret_cast<uint4*>(base + idx * 4 * N);
-#pragma unroll
-  for (int q = 0; q < N; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-}
-
-// e * P by double-and-add from the top bit (e: 8 canonical words).  Exact for every input (ec.h's add / dbl).
-template <class C>
-__device__ __forceinline__ XYZZ<C> g1_mul_words(const XYZZ<C>& p, const uint32_t* e) {
-  XYZZ<C> acc = Ec<C>::infinity();
-#pragma unroll 1
-  for (int k = 7; k >= 0; --k) {
-    const uint32_t word = e[k];
-#pragma unroll 1
-    for (int b = 31; b >= 0; --b) {
-      acc = Ec<C>::dbl(acc);
-      if ((word >> b) & 1u) acc = Ec<C>::add(acc, p);
-    }
-  }
-  return acc;
-}
 
 // buf[bitrev(i)] = record i of window 0
 template <class C>
@@ -266,35 +185,6 @@ __global__ __launch_bounds__(128) void g1_intt_load_kernel(const uint32_t* recs,
   Affine<C> a;
   a.inf = load_rec<C>(recs, i, a.x, a.y) & 1u;
   st_point<C>(buf, __brev(i) >> (32 - log_n), Ec<C>::from_affine(a));
-}
-
-// one radix-2 level of half-size h = 2^s: butterfly t pairs i0 = b*2h + k and i0 + h with twiddle winv^(k * n/(2h)),
-// k = t / (n/(2h)), b = t mod (n/(2h)).  winv in Montgomery form.
-template <class C>
-__global__ __launch_bounds__(64) void g1_intt_level_kernel(uint32_t* buf, uint32_t log_n, uint32_t s, LgFr winv) {
-  using Fr = typename C::Fr;
-  using Frd = Field<Fr>;
-  using Fd = Field<typename C::Fp>;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (1u << (log_n - 1))) return;
-  const uint32_t lnb = log_n - 1 - s;                     // log2 of the butterflies per twiddle
-  const uint32_t k = t >> lnb, b = t & ((1u << lnb) - 1);
-  const size_t i0 = ((size_t)b << (s + 1)) + k, i1 = i0 + ((size_t)1 << s);
-  XYZZ<C> B = ld_point<C>(buf, i1);
-  if (k) {
-    Fe<Fr> base = arg_fe<Fr>(winv), acc = Frd::one();
-    for (uint32_t bits = k << lnb; bits; bits >>= 1) {
-      if (bits & 1u) acc = Frd::mul(acc, base);
-      base = Frd::sqr(base);
-    }
-    uint32_t e[8];
-    Frd::to_words(Frd::from_mont(acc), e);
-    B = g1_mul_words<C>(B, e);
-  }
-  const XYZZ<C> A = ld_point<C>(buf, i0);
-  st_point<C>(buf, i0, Ec<C>::add(A, B));
-  B.y = Fd::neg(B.y);
-  st_point<C>(buf, i1, Ec<C>::add(A, B));
 }
 
 // record i = n^-1 * buf[i], affine canonical (window 0 of the Lagrange key)
@@ -312,24 +202,8 @@ __global__ __launch_bounds__(64) void g1_intt_finish_kernel(const uint32_t* buf,
 // ---- host side --------------------------------------------------------------------------------------
 
 template <class F>
-LgFr lg_arg(const Fe<F>& v) {
-  LgFr a;
-  memcpy(a.l, v.l, sizeof(a.l));
-  return a;
-}
-template <class F>
 void lg_words(const Fe<F>& mont, uint32_t* w) {
   Field<F>::to_words(Field<F>::from_mont(mont), w);
-}
-
-// w (canonical words) is a primitive 2^log_n-th root of unity: w^(n/2) = -1
-template <class F>
-bool primitive_root(const uint32_t* w_words, uint32_t log_n) {
-  using Fd = Field<F>;
-  if (log_n == 0) return false;
-  Fe<F> x = Fd::to_mont(Fd::from_words(w_words));
-  for (uint32_t q = 1; q < log_n; ++q) x = Fd::sqr(x);
-  return Fd::eq(x, Fd::neg(Fd::one()));
 }
 
 // (z^n - 1)/n (Montgomery) and whether z^n = 1 (z in H)
@@ -340,17 +214,15 @@ Fe<F> vanishing_over_n(const Fe<F>& z_mont, uint32_t log_n, bool* in_domain) {
   for (uint32_t q = 0; q < log_n; ++q) zn = Fd::sqr(zn);
   const Fe<F> num = Fd::sub(zn, Fd::one());
   *in_domain = Fd::is_zero(num);
-  uint32_t nw[8] = {0};
-  nw[log_n >> 5] = 1u << (log_n & 31);
-  return Fd::reduce(Fd::mul(num, Fd::inv(Fd::to_mont(Fd::from_words(nw)))));
+  return Fd::reduce(Fd::mul(num, inv_pow2<F>(log_n)));
 }
 
 constexpr int LG_MAX_LOG = 24;
 
 template <class F>
 int launch_wpow(Ctx* c, uint32_t n, const uint32_t* w_words, uint32_t* out) {
-  const Fe<F> w = Field<F>::to_mont(Field<F>::from_words(w_words));
-  hipLaunchKernelGGL(lagr_wpow_kernel<F>, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, lg_arg<F>(w), out);
+  const Fe<F> w = mont_from_words<F>(w_words);
+  hipLaunchKernelGGL(lagr_wpow_kernel<F>, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, fr_arg<F>(w), out);
   KZG_HIP(c, hipGetLastError());
   return KZG_OK;
 }
@@ -370,15 +242,15 @@ int value_pass(Ctx* c, uint32_t log_n, uint32_t plen, const uint32_t* d_P, const
   const Fe<F> cz = vanishing_over_n<F>(zm, log_n, &in_domain);
   const Fe<F> zinv = in_domain ? Fd::reduce(Fd::inv(zm)) : Fd::zero();
   const uint32_t grid = (n + 255) / 256;
-  hipLaunchKernelGGL(lagr_denom_kernel<F>, dim3(grid), dim3(256), 0, c->stream, n, d_wpow, lg_arg<F>(zs), d_den);
+  hipLaunchKernelGGL(lagr_denom_kernel<F>, dim3(grid), dim3(256), 0, c->stream, n, d_wpow, fr_arg<F>(zs), d_den);
   KZG_HIP(c, hipGetLastError());
   int rc = fr_vec_inverse(c, n, d_den, d_inv);
   if (rc) return rc;
   const uint32_t groups = std::min<uint32_t>(SUM_MAXG, (n + SUM_TB - 1) / SUM_TB);
   hipLaunchKernelGGL(lagr_sums_kernel<F>, dim3(groups), dim3(SUM_TB), 0, c->stream, n, plen, d_P, d_wpow, d_inv,
                      d_part);
-  hipLaunchKernelGGL(lagr_value_kernel<F>, dim3(1), dim3(64), 0, c->stream, groups, d_part, lg_arg<F>(cz),
-                     lg_arg<F>(zinv), d_val);
+  hipLaunchKernelGGL(lagr_value_kernel<F>, dim3(1), dim3(64), 0, c->stream, groups, d_part, fr_arg<F>(cz),
+                     fr_arg<F>(zinv), d_val);
   KZG_HIP(c, hipGetLastError());
   if (d_q) {
     hipLaunchKernelGGL(lagr_quotient_kernel<F>, dim3(grid), dim3(256), 0, c->stream, n, d_P, d_inv, d_val, d_q);
@@ -392,7 +264,8 @@ int srs_generate_lagrange_t(Ctx* c, const uint32_t* tau_words, uint32_t log_n, c
   using F = typename C::Fr;
   using Fd = Field<F>;
   if (log_n < 1 || log_n > LG_MAX_LOG) return set_err(c, KZG_ERR_ARG, "Lagrange key: log_n must be in [1, 24]");
-  if (!primitive_root<F>(w_words, log_n)) return set_err(c, KZG_ERR_ARG, "Lagrange key: w is not a primitive root");
+  if (!primitive_root<F>(mont_from_words<F>(w_words), log_n))
+    return set_err(c, KZG_ERR_ARG, "Lagrange key: w is not a primitive root");
   const uint32_t n = 1u << log_n;
   ProfScope ps(c, "srs_lagrange");
   uint32_t *d_wpow = nullptr, *d_tmp = nullptr;
@@ -409,10 +282,10 @@ int srs_generate_lagrange_t(Ctx* c, const uint32_t* tau_words, uint32_t log_n, c
   bool in_domain = false;
   const Fe<F> cz = vanishing_over_n<F>(Fd::to_mont(ts), log_n, &in_domain);
   const uint32_t grid = (n + 255) / 256;
-  hipLaunchKernelGGL(lagr_denom_kernel<F>, dim3(grid), dim3(256), 0, c->stream, n, d_wpow, lg_arg<F>(ts), d_den);
+  hipLaunchKernelGGL(lagr_denom_kernel<F>, dim3(grid), dim3(256), 0, c->stream, n, d_wpow, fr_arg<F>(ts), d_den);
   if ((rc = fr_vec_inverse(c, n, d_den, d_inv))) { cleanup(); return rc; }
   hipLaunchKernelGGL(lagr_basis_scalars_kernel<F>, dim3(grid), dim3(256), 0, c->stream, n, d_wpow, d_inv,
-                     lg_arg<F>(cz), d_sc);
+                     fr_arg<F>(cz), d_sc);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { cleanup(); return set_err(c, KZG_ERR_HIP, "Lagrange scalars", e); }
   Srs* s = nullptr;
@@ -435,7 +308,8 @@ int srs_lagrange_t(Ctx* c, const Srs* mono, uint32_t log_n, const uint32_t* w_wo
   if (log_n < 1 || log_n > LG_MAX_LOG) return set_err(c, KZG_ERR_ARG, "Lagrange key: log_n must be in [1, 24]");
   const uint32_t n = 1u << log_n;
   if (mono->n < n) return set_err(c, KZG_ERR_ARG, "kzg_srs_lagrange: monomial key shorter than the domain");
-  if (!primitive_root<F>(w_words, log_n)) return set_err(c, KZG_ERR_ARG, "Lagrange key: w is not a primitive root");
+  if (!primitive_root<F>(mont_from_words<F>(w_words), log_n))
+    return set_err(c, KZG_ERR_ARG, "Lagrange key: w is not a primitive root");
   Srs* s = nullptr;
   int rc = srs_create(c, n, &s);
   if (rc) return rc;
@@ -447,17 +321,12 @@ int srs_lagrange_t(Ctx* c, const Srs* mono, uint32_t log_n, const uint32_t* w_wo
   {
     ProfScope ps(c, "srs_lagrange");
     if ((rc = launch_wpow<F>(c, n, w_words, s->d_wpow))) return fail(rc);
-    const Fe<F> winv = Fd::inv(Fd::to_mont(Fd::from_words(w_words)));
-    uint32_t nw[8] = {0};
-    nw[log_n >> 5] = 1u << (log_n & 31);
+    const Fe<F> winv = Fd::inv(mont_from_words<F>(w_words));
     LgWords ninv;
-    lg_words<F>(Fd::inv(Fd::to_mont(Fd::from_words(nw))), ninv.w);
+    lg_words<F>(inv_pow2<F>(log_n), ninv.w);
     hipLaunchKernelGGL(g1_intt_load_kernel<C>, dim3((n + 127) / 128), dim3(128), 0, c->stream, mono->recs, n, log_n,
                        d_buf);
-    const uint32_t half = n / 2;
-    for (uint32_t lv = 0; lv < log_n; ++lv)
-      hipLaunchKernelGGL(g1_intt_level_kernel<C>, dim3((half + 63) / 64), dim3(64), 0, c->stream, d_buf, log_n, lv,
-                         lg_arg<F>(winv));
+    if ((rc = launch_levels(c, d_buf, 1, log_n, fr_arg<F>(winv)))) return fail(rc);
     hipLaunchKernelGGL(g1_intt_finish_kernel<C>, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_buf, n, ninv,
                        s->recs);
     hipError_t e = hipGetLastError();
@@ -501,7 +370,7 @@ int open_evals_t(Ctx* c, const Srs* s, const uint32_t* d_vals, const size_t* len
     ProfScope ps(c, "open_evals_poly");
     std::vector<const uint32_t*> ptrs(k);
     std::vector<uint32_t> xw(std::max<size_t>(k, 1) * 8);
-    const Fe<F> xi = Fd::to_mont(Fd::from_words(xi_words));
+    const Fe<F> xi = mont_from_words<F>(xi_words);
     Fe<F> xp = Fd::one();
     for (size_t j = 0; j < k; ++j) {
       ptrs[j] = d_vals + j * stride * 8;
@@ -526,7 +395,8 @@ int fr_eval_lagrange_t(Ctx* c, uint32_t log_n, const uint32_t* w_words, size_t l
                        const uint32_t* z_words, uint64_t* out) {
   memset(out, 0, 32);
   if (log_n < 1 || log_n > LG_MAX_LOG) return set_err(c, KZG_ERR_ARG, "kzg_fr_eval_lagrange: log_n must be in [1, 24]");
-  if (!primitive_root<F>(w_words, log_n)) return set_err(c, KZG_ERR_ARG, "kzg_fr_eval_lagrange: w is not a primitive root");
+  if (!primitive_root<F>(mont_from_words<F>(w_words), log_n))
+    return set_err(c, KZG_ERR_ARG, "kzg_fr_eval_lagrange: w is not a primitive root");
   const size_t n = (size_t)1 << log_n;
   if (len > n) return set_err(c, KZG_ERR_DEGREE, "value vector longer than the domain");
   if (len == 0) return KZG_OK;

@@ -44,6 +44,13 @@ int open_evals_device(Ctx* c, const Srs* s, const uint32_t* d_vals, const size_t
 int fr_eval_lagrange(Ctx* c, uint32_t log_n, const uint32_t* w_words, size_t len, const uint32_t* d_vals,
                      const uint32_t* z_words, uint64_t* out);
 
+// domain.hip: the radix-2 G1 transform in XYZZ, in place, one launch per level: `nvec` vectors of 2^log_len points
+// (vector j at point j << log_len), bit-reversed in, natural out, unscaled; root a primitive 2^log_len-th root of
+// unity in Montgomery form.  log_len <= 24 for one vector, nvec << log_len <= 2^31.
+struct FrArg;   // fr_util.h
+__attribute__((visibility("hidden")))   // library-private: not in the exported symbol list
+int launch_levels(Ctx* c, uint32_t* d_buf, uint32_t nvec, uint32_t log_len, const FrArg& root);
+
 // domain.hip: all n proofs on a domain (FK20).  A table holds DFT_G1,2n of the reversed monomial key.
 struct DomainTable;
 int domain_table_create(Ctx* c, const Srs* mono, uint32_t log_n, DomainTable** out);

@@ -34,6 +34,7 @@
 // the last pass -- brings the value back below 2p, one conditional subtraction makes
 // it canonical.
 #include "internal.h"
+#include "fr_util.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -364,9 +365,7 @@ int build_domain(Ctx* c, NttDomain& d) {
   Fe<F> w = Fd::to_mont(Fd::from_words(d.w));
   if (d.inverse) w = Fd::inv(w);                       // fft_ff.py:53
   // n^-1 (fft_ff.py:57): n as a field element, inverted
-  uint32_t nw[8] = {0};
-  nw[log_n >> 5] = 1u << (log_n & 31);
-  const Fe<F> ninv = Fd::inv(Fd::to_mont(Fd::from_words(nw)));
+  const Fe<F> ninv = inv_pow2<F>(log_n);
 
   const bool two_pass = log_n > (uint32_t)TILE_LOG;
   d.kmax = two_pass ? (log_n + 1) / 2 : log_n;

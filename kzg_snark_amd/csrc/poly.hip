@@ -12,6 +12,7 @@
 // field.h (an asm volatile per multiply-add) would only keep the scheduler from hoisting the next loads.
 #define KZG_NO_CHAIN_PIN 1
 #include "internal.h"
+#include "fr_util.h"
 #include "msm.h"
 #include <algorithm>
 #include <cstdlib>
@@ -37,37 +38,6 @@ struct LincombArgs {              // travels in the kernel arguments (2.6 KB): n
   uint32_t lens[MAXK];
   uint32_t xipow[MAXK * FRN];   // xi^(i+1), Montgomery form
 };
-struct FrArg {                    // one field element (Montgomery limbs) as a kernel argument
-  uint32_t l[FRN];
-};
-
-template <class F>
-__device__ __forceinline__ Fe<F> load_words(const uint32_t* p) {
-  const uint4* g = reinterpret_cast<const uint4*>(p);
-  const uint4 lo = g[0], hi = g[1];
-  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  return Field<F>::from_words(w);
-}
-template <class F>
-__device__ __forceinline__ void store_words(uint32_t* p, const Fe<F>& v) {
-  uint32_t w[8];
-  Field<F>::to_words(Field<F>::reduce(v), w);
-  uint4* g = reinterpret_cast<uint4*>(p);
-  g[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  g[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-template <class F>
-__device__ __forceinline__ Fe<F> load_limbs(const uint32_t* p) {
-  Fe<F> r;
-#pragma unroll
-  for (int j = 0; j < F::N; ++j) r.l[j] = p[j];
-  return r;
-}
-template <class F>
-__device__ __forceinline__ void store_limbs(uint32_t* p, const Fe<F>& v) {
-#pragma unroll
-  for (int j = 0; j < F::N; ++j) p[j] = v.l[j];
-}
 
 // sum over up to DOT_G terms c_g * x_g with ONE Montgomery reduction (Field::dot): 81 multiply-adds per term plus 74
 // for the group, against 155 per term for separate products -- the combination kernels are bound by exactly these
@@ -331,7 +301,7 @@ __device__ __forceinline__ Fe<F> tile_carry_sum(uint32_t b, uint32_t ntiles, con
                                  load_limbs<F>(W + (size_t)((sp << SG_LOG) - b - 1) * F::N)));
   }
   if (has_hv && tid == TB - 1)
-    acc = Fd::add(acc, Fd::mul(load_limbs<F>(hv.l), load_limbs<F>(W + (size_t)(ntiles - b - 1) * F::N)));
+    acc = Fd::add(acc, Fd::mul(arg_fe<F>(hv), load_limbs<F>(W + (size_t)(ntiles - b - 1) * F::N)));
   return block_sum<F, TB>(acc, red);
 }
 
@@ -380,7 +350,7 @@ __global__ __launch_bounds__(TB) void tile_fill_kernel(const uint32_t* comb, uin
   Fe<F> acc = Fd::mul(Fd::add(ex, load_limbs<F>(qsh)), load_limbs<F>(zinv + (size_t)(tid + 1) * F::N));
   const uint32_t j0 = e0 + tid * SC;
   if (j0 < n) {
-    const Fe<F> z = load_limbs<F>(zarg.l);
+    const Fe<F> z = arg_fe<F>(zarg);
     for (uint32_t j = j0 + SC; j-- > j0;) {
       if (j >= n) {                                         // the chunk that holds the end: zero coefficients above it
         if (has_hv) acc = Fd::mul(acc, z);
@@ -429,12 +399,6 @@ struct TilePlan {
   uint32_t *G = nullptr, *H = nullptr, *A = nullptr, *zinv = nullptr, *W = nullptr;
 };
 
-template <class F>
-static FrArg fr_arg(const Fe<F>& v) {
-  FrArg a;
-  memcpy(a.l, v.l, F::N * 4);
-  return a;
-}
 static bool words_are_zero(const uint32_t* w) {
   uint32_t acc = 0;
   for (int i = 0; i < 8; ++i) acc |= w[i];
@@ -722,7 +686,7 @@ __global__ __launch_bounds__(256) void coset_tile_kernel(const uint32_t* x, uint
   const uint32_t tiles = (rows + CS_R - 1) / CS_R;
   if (g >= (tiles << log_l)) return;
   const uint32_t j = g & ((1u << log_l) - 1), b = g >> log_l;
-  const Fe<F> am = load_limbs<F>(a.l);
+  const Fe<F> am = arg_fe<F>(a);
   Fe<F> acc = Fd::zero();
 #pragma unroll 1
   for (int r = CS_R - 1; r >= 0; --r) {
@@ -741,7 +705,7 @@ __global__ __launch_bounds__(256) void coset_fill_kernel(uint32_t* x, uint32_t r
   const uint32_t tiles = (rows + CS_R - 1) / CS_R;
   if (g >= (tiles << log_l)) return;
   const uint32_t j = g & ((1u << log_l) - 1), b = g >> log_l;
-  const Fe<F> am = load_limbs<F>(a.l);
+  const Fe<F> am = arg_fe<F>(a);
   Fe<F> acc = upper && b + 1 < upper_rows ? load_words<F>(upper + ((((size_t)b + 1) << log_l) + j) * 8) : Fd::zero();
 #pragma unroll 1
   for (int r = CS_R - 1; r >= 0; --r) {
@@ -786,13 +750,11 @@ int open_coset_check_t(Ctx* c, const size_t* lens, size_t k, size_t stride, uint
   using Fd = Field<F>;
   if (log_l > CS_MAX_LOG_L) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: log_l must be in [0, 12]");
   if (words_are_zero(h_words)) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: h must be non-zero");
-  Fe<F> x = Fd::to_mont(Fd::from_words(zeta_words));
+  const Fe<F> zeta = mont_from_words<F>(zeta_words);
   if (log_l == 0) {
-    if (!Fd::eq(x, Fd::one())) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: zeta must be 1 for l = 1");
-  } else {
-    for (uint32_t q = 1; q < log_l; ++q) x = Fd::sqr(x);
-    if (!Fd::eq(x, Fd::neg(Fd::one())))
-      return set_err(c, KZG_ERR_ARG, "kzg_open_coset: zeta is not a primitive l-th root of unity");
+    if (!Fd::eq(zeta, Fd::one())) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: zeta must be 1 for l = 1");
+  } else if (!primitive_root<F>(zeta, log_l)) {
+    return set_err(c, KZG_ERR_ARG, "kzg_open_coset: zeta is not a primitive l-th root of unity");
   }
   int rc = check_open_args<F>(c, lens, k, stride, n_out);
   if (rc) return rc;

@@ -467,51 +467,62 @@ class KZG:
         if len(ck) < n:
             raise ValueError(f"commitment key of {len(ck)} points is shorter than the domain ({n})")
         key = self._key(ck)
-        hit = self._tables.get((id(key), n))
-        if hit and hit[0] is key:
-            self._tables[(id(key), n)] = self._tables.pop((id(key), n))     # most recently used last
-            return hit[1]
         ctx = self._context()
-        table = DomainTable(ctx, ctx.domain_table(key.srs, n.bit_length() - 1), n)
-        self._tables.pop((id(key), n), None)
+        return self._table_cached(key, (id(key), n), lambda: DomainTable(
+            ctx, ctx.domain_table(key.srs, n.bit_length() - 1), n))
+
+    def _table_cached(self, key, cache_key, make):
+        hit = self._tables.get(cache_key)
+        if hit and hit[0] is key:
+            self._tables[cache_key] = self._tables.pop(cache_key)           # most recently used last
+            return hit[1]
+        table = make()
+        self._tables.pop(cache_key, None)
         while len(self._tables) >= self._TABLE_CACHE:
             old = next(iter(self._tables))
             self._tables.pop(old)[1].table.close()
-        self._tables[(id(key), n)] = (key, table)
+        self._tables[cache_key] = (key, table)
         return table
 
-    def _domain_call(self, ck_or_table, polynomials, n, w):
-        """Host-side checks shared by open_domain / open_domain_each, before any device work: -> (coefficient lists,
-        n, w).  n defaults to the smallest power of two >= the longest polynomial (setup_lagrange's rule)."""
+    def _fk20_call(self, who, ck_or_table, polynomials, n, w, l=None, N=None):
+        """Host-side checks of open_domain* (l is None) and open_cosets*, `who` in the messages, before any device
+        work: -> (coefficient lists, n, l, log_N, w).  n defaults to the smallest power of two >= the longest
+        polynomial (setup_lagrange's rule; at least 2l for cosets), N to n."""
+        cosets = l is not None
         if isinstance(ck_or_table, LagrangeKey):
-            raise TypeError("open_domain needs a monomial key or a DomainTable, not a LagrangeKey")
+            raise TypeError(f"{who} needs a monomial key or a {'coset table' if cosets else 'DomainTable'}, "
+                            "not a LagrangeKey")
+        if cosets:
+            l = 1 << self._log2_exact(l, "coset size")
         coeffs = [self._coeffs(p) for p in polynomials]
         longest = max((len(c) for c in coeffs), default=0)
         if isinstance(ck_or_table, DomainTable):
             if n is not None and int(n) != ck_or_table.n:
                 raise ValueError(f"n = {n} differs from the table's domain size {ck_or_table.n}")
+            if cosets and l != ck_or_table.l:
+                raise ValueError(f"l = {l} differs from the table's coset size {ck_or_table.l}")
             n = ck_or_table.n
         elif n is None:
-            n = 2
+            n = max(2, 2 * l) if cosets else 2
             while n < longest:
                 n *= 2
         n = int(n)
         if n < 2 or n & (n - 1) or n > self._DOMAIN_MAX:
             raise ValueError(f"domain size {n} is not a power of two in [2, 2^20]")
+        if cosets and l > n // 2:
+            raise ValueError(f"coset size {l} exceeds n/2 = {n // 2}")
         if longest > n:
             raise ValueError(f"polynomial of {longest} coefficients exceeds the domain size {n}")
         if not isinstance(ck_or_table, DomainTable) and len(ck_or_table) < n:
             raise ValueError(f"commitment key of {len(ck_or_table)} points is shorter than the domain ({n})")
-        _, w = self._domain(n, w)
-        return coeffs, n, w
+        N = n if N is None else int(N)
+        if N < n or N & (N - 1) or N > min(4 * n, 2 * self._DOMAIN_MAX):
+            raise ValueError(f"N = {N} is not a power of two in [n, min(4n, 2^21)]")
+        log_N, w = self._domain(N, w)
+        return coeffs, n, l, log_N, w
 
-    def open_domain(self, ck_or_table, polynomials, xi, n=None, w=None):
-        """open(ck, polynomials, w^i, xi) for every i < n at once: a list of n proofs.  The xi^(j+1) combination runs
-        on the device (as in open), then FK20 on the combined polynomial.  w defaults to Fq.root_of_unity(n)."""
-        coeffs, n, w = self._domain_call(ck_or_table, polynomials, n, w)
-        xi = int(self.Fq(xi))
-        table = ck_or_table if isinstance(ck_or_table, DomainTable) else self.domain_table(ck_or_table, n)
-        ctx = self._context()
+    def _combine_on_device(self, ctx, coeffs, xi):
+        """sum_j xi^(j+1) coeffs[j] on the device (as in open): -> (device tensor of canonical words, its length)"""
         r = self.curve_order
         arr, lens, stride = self._pack(coeffs)
         length = max(max(lens, default=0), 1)
@@ -526,12 +537,22 @@ class KZG:
             scalars.append(x)                                                  # xi^(j+1): kzg.py:148-150
             x = x * xi % r
         ctx.vec_lincomb(length, ptrs, lens, scalars, d_comb.data_ptr())
+        return d_comb, length
+
+    def open_domain(self, ck_or_table, polynomials, xi, n=None, w=None):
+        """open(ck, polynomials, w^i, xi) for every i < n at once: a list of n proofs.  The xi^(j+1) combination runs
+        on the device (as in open), then FK20 on the combined polynomial.  w defaults to Fq.root_of_unity(n)."""
+        coeffs, n, _, _, w = self._fk20_call("open_domain", ck_or_table, polynomials, n, w)
+        xi = int(self.Fq(xi))
+        table = ck_or_table if isinstance(ck_or_table, DomainTable) else self.domain_table(ck_or_table, n)
+        ctx = self._context()
+        d_comb, length = self._combine_on_device(ctx, coeffs, xi)
         xy, inf, _ = ctx.open_domain(table.table, d_comb.data_ptr(), [length], length, w, device=True, evals=False)
         return self._points(xy[0], inf[0])
 
     def open_domain_each(self, ck_or_table, polynomials, n=None, w=None):
         """All n proofs of each polynomial on its own: result[j][i] == open(ck, [polynomials[j]], w^i, 1)."""
-        coeffs, n, w = self._domain_call(ck_or_table, polynomials, n, w)
+        coeffs, n, _, _, w = self._fk20_call("open_domain", ck_or_table, polynomials, n, w)
         if not coeffs:
             return []
         table = ck_or_table if isinstance(ck_or_table, DomainTable) else self.domain_table(ck_or_table, n)
@@ -542,19 +563,6 @@ class KZG:
     # ---- coset openings: the values at l = 2^log_l points h zeta^k with ONE proof (FK20's multi-reveal) -------------
     #      Z = X^l - a, a = h^l; rho = p mod Z; pi = [(p - rho)/Z (tau)] G1; check e(C - [rho(tau)], G2) = e(pi, [tau^l] G2 - a G2).
     _COSET_MAX_LOG_L = 12          # kzg_open_coset
-
-    def _table_cached(self, key, cache_key, make):
-        hit = self._tables.get(cache_key)
-        if hit and hit[0] is key:
-            self._tables[cache_key] = self._tables.pop(cache_key)           # most recently used last
-            return hit[1]
-        table = make()
-        self._tables.pop(cache_key, None)
-        while len(self._tables) >= self._TABLE_CACHE:
-            old = next(iter(self._tables))
-            self._tables.pop(old)[1].table.close()
-        self._tables[cache_key] = (key, table)
-        return table
 
     @staticmethod
     def _log2_exact(v, what):
@@ -581,40 +589,6 @@ class KZG:
         return self._table_cached(key, (id(key), n, 1 << log_l), lambda: DomainTable(
             ctx, ctx.coset_table(key.srs, n.bit_length() - 1, log_l), n, 1 << log_l))
 
-    def _cosets_call(self, ck_or_table, polynomials, l, n, w, N):
-        """Host-side checks of open_cosets / open_cosets_each, before any device work: -> (coefficient lists, n, l,
-        log_N, w).  n defaults as in open_domain (at least 2l), N to n."""
-        if isinstance(ck_or_table, LagrangeKey):
-            raise TypeError("open_cosets needs a monomial key or a coset table, not a LagrangeKey")
-        log_l = self._log2_exact(l, "coset size")
-        l = 1 << log_l
-        coeffs = [self._coeffs(p) for p in polynomials]
-        longest = max((len(c) for c in coeffs), default=0)
-        if isinstance(ck_or_table, DomainTable):
-            if n is not None and int(n) != ck_or_table.n:
-                raise ValueError(f"n = {n} differs from the table's domain size {ck_or_table.n}")
-            if l != ck_or_table.l:
-                raise ValueError(f"l = {l} differs from the table's coset size {ck_or_table.l}")
-            n = ck_or_table.n
-        elif n is None:
-            n = max(2, 2 * l)
-            while n < longest:
-                n *= 2
-        n = int(n)
-        if n < 2 or n & (n - 1) or n > self._DOMAIN_MAX:
-            raise ValueError(f"domain size {n} is not a power of two in [2, 2^20]")
-        if l > n // 2:
-            raise ValueError(f"coset size {l} exceeds n/2 = {n // 2}")
-        if longest > n:
-            raise ValueError(f"polynomial of {longest} coefficients exceeds the domain size {n}")
-        if not isinstance(ck_or_table, DomainTable) and len(ck_or_table) < n:
-            raise ValueError(f"commitment key of {len(ck_or_table)} points is shorter than the domain ({n})")
-        N = n if N is None else int(N)
-        if N < n or N & (N - 1) or N > min(4 * n, 2 * self._DOMAIN_MAX):
-            raise ValueError(f"N = {N} is not a power of two in [n, min(4n, 2^21)]")
-        log_N, w = self._domain(N, w)
-        return coeffs, n, l, log_N, w
-
     def _coset_table_for(self, ck_or_table, n, l):
         return ck_or_table if isinstance(ck_or_table, DomainTable) else self.coset_table(ck_or_table, n, l)
 
@@ -622,24 +596,11 @@ class KZG:
         """One proof per coset of l points of the domain {w^t, t < N}: coset i is {w^(i + k N/l), k < l}, a list of
         N/l proofs of the xi^(j+1) combination (combined on the device, as in open_domain).  w defaults to
         Fq.root_of_unity(N), N to n."""
-        coeffs, n, l, log_N, w = self._cosets_call(ck_or_table, polynomials, l, n, w, N)
+        coeffs, n, l, log_N, w = self._fk20_call("open_cosets", ck_or_table, polynomials, n, w, l, N)
         xi = int(self.Fq(xi))
         table = self._coset_table_for(ck_or_table, n, l)
         ctx = self._context()
-        r = self.curve_order
-        arr, lens, stride = self._pack(coeffs)
-        length = max(max(lens, default=0), 1)
-        import torch
-        dev = f"cuda:{ctx.device}"
-        d_in = torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).to(dev, non_blocking=False)
-        d_comb = torch.zeros((length, 4), dtype=torch.int64, device=dev)
-        torch.cuda.synchronize(ctx.device)
-        ptrs = [d_in.data_ptr() + j * stride * 32 for j in range(len(coeffs))]
-        scalars, x = [], xi
-        for _ in coeffs:
-            scalars.append(x)                                                  # xi^(j+1): kzg.py:148-150
-            x = x * xi % r
-        ctx.vec_lincomb(length, ptrs, lens, scalars, d_comb.data_ptr())
+        d_comb, length = self._combine_on_device(ctx, coeffs, xi)
         xy, inf, _ = ctx.open_cosets(table.table, d_comb.data_ptr(), [length], length, log_N, w, device=True,
                                      evals=False)
         return self._points(xy[0], inf[0])
@@ -647,7 +608,7 @@ class KZG:
     def open_cosets_each(self, ck_or_table, polynomials, l, n=None, w=None, N=None, with_values=False):
         """Every coset proof of each polynomial on its own: result[j][i] == open_coset(ck, [polynomials[j]], w^i, l,
         1, w^(N/l)).  with_values: (proofs, values), values[j][i][k] = p_j(w^(i + k N/l))."""
-        coeffs, n, l, log_N, w = self._cosets_call(ck_or_table, polynomials, l, n, w, N)
+        coeffs, n, l, log_N, w = self._fk20_call("open_cosets", ck_or_table, polynomials, n, w, l, N)
         if not coeffs:
             return ([], []) if with_values else []
         table = self._coset_table_for(ck_or_table, n, l)

@@ -7,11 +7,11 @@ import os
 import random
 import re
 import subprocess
-import sys
 
 import pytest
 
 from oracle import py_oracle as O
+from restated import fr_dft, g1_dft, g1_mul, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "kzg_mi355x.h")
@@ -61,30 +61,6 @@ def coset_interpolate(values, h, zeta, r):
     l = len(values)
     zi, hi, li = pow(zeta, -1, r), pow(h, -1, r), pow(l, -1, r)
     return [sum(y * pow(zi, j * k, r) for k, y in enumerate(values)) * li * pow(hi, j, r) % r for j in range(l)]
-
-
-def g1_mul(pt, k, cv):
-    k %= cv.r
-    if O.is_inf(pt) or k == 0:
-        return O.Z1()
-    return pt if k == 1 else O.multiply(pt, k, cv)
-
-
-def g1_dft(points, root, cv):
-    """naive O(len^2) DFT over G1: out[k] = sum_i root^(i k) points[i]"""
-    n, r = len(points), cv.r
-    out = []
-    for k in range(n):
-        acc = O.Z1()
-        for i, p in enumerate(points):
-            acc = O.add(acc, g1_mul(p, pow(root, i * k % n, r), cv), cv)
-        out.append(acc)
-    return out
-
-
-def fr_dft(vals, root, r):
-    n = len(vals)
-    return [sum(v * pow(root, i * k % n, r) for i, v in enumerate(vals)) % r for k in range(n)]
 
 
 def coset_table_restated(ck, n, l, cv):
@@ -288,15 +264,11 @@ def test_facade_rejects_bad_arguments_before_the_device(curve, monkeypatch):
 
 # ---- kernel budget -------------------------------------------------------------------------------------------------
 def test_new_kernels_never_spill_and_fit_256_vgprs(built):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), built],
-                         capture_output=True, text=True, check=True).stdout
+    out, listing = kernel_resources(built)
     rows = {}
-    for line in out.splitlines():
-        m = re.match(r"(\S.*?)\s+vgpr\s+(\d+)\s+agpr\s+(\d+)\s+sgpr\s+(\d+)\s+lds\s+(\d+)\s+scratch\s+(\d+)", line)
-        if m:
-            k = re.search(r"(\w+_kernel)\b", m.group(1))                    # demangled or plain
-            name = k.group(1) if k else m.group(1).strip()
-            rows.setdefault(name, []).append((int(m.group(2)), int(m.group(6))))
+    for raw, vgpr, _, _, _, scratch in listing:
+        k = re.search(r"(\w+_kernel)\b", raw)                             # demangled or plain
+        rows.setdefault(k.group(1) if k else raw, []).append((vgpr, scratch))
     for names, count in ((NEW_KERNELS, 2), (NEW_FR_KERNELS, 1)):
         for name in names:
             assert len(rows.get(name, [])) == count, (name, out)

@@ -4,11 +4,11 @@ persistent accumulate kernel holds 2 waves x 168 VGPRs, the reduce-stage kernels
 silently turns the pipeline back into three serial stages, so the budget is checked on the built code
 object (no GPU needed: the numbers are in the ELF notes)."""
 import os
-import re
-import subprocess
 import sys
 
 import pytest
+
+from restated import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "kzg_snark_amd", "lib", "libkzg_mi355x.so")
@@ -20,13 +20,8 @@ def kernels():
         sys.path.insert(0, ROOT)
         from kzg_snark_amd import build
         build.build(verbose=False)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), LIB],
-                         capture_output=True, text=True, check=True).stdout
-    rows = []
-    for line in out.splitlines():
-        m = re.match(r"(\S.*?)\s+vgpr\s+(\d+)\s+agpr\s+(\d+)\s+sgpr\s+(\d+)\s+lds\s+(\d+)\s+scratch\s+(\d+)", line)
-        if m:
-            rows.append((m.group(1).strip(), int(m.group(2)), int(m.group(5)), int(m.group(6))))
+    out, listing = kernel_resources(LIB)
+    rows = [(name, vgpr, lds, scratch) for name, vgpr, _, _, lds, scratch in listing]
     assert rows, out
     return rows
 

@@ -3,9 +3,10 @@ its domain and value lists on the host; the new kernels fit their register budge
 import os
 import re
 import subprocess
-import sys
 
 import pytest
+
+from restated import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "kzg_mi355x.h")
@@ -64,15 +65,12 @@ def test_facade_validates_the_domain_without_a_gpu(curve):
 
 
 def test_new_kernels_never_spill_and_the_opening_kernels_fit_their_budget(built):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), built],
-                         capture_output=True, text=True, check=True).stdout
+    out, listing = kernel_resources(built)
     rows = {}
-    for line in out.splitlines():
-        m = re.match(r"(\S.*?)\s+vgpr\s+(\d+)\s+agpr\s+(\d+)\s+sgpr\s+(\d+)\s+lds\s+(\d+)\s+scratch\s+(\d+)", line)
-        if m:
-            rows.setdefault(m.group(1).strip(), []).append((int(m.group(2)), int(m.group(5)), int(m.group(6))))
+    for name, vgpr, _, _, lds, scratch in listing:
+        rows.setdefault(name, []).append((vgpr, lds, scratch))
     opening = ["lagr_denom_kernel", "lagr_sums_kernel", "lagr_value_kernel", "lagr_quotient_kernel"]
-    others = ["lagr_wpow_kernel", "lagr_basis_scalars_kernel", "g1_intt_load_kernel", "g1_intt_level_kernel",
+    others = ["lagr_wpow_kernel", "lagr_basis_scalars_kernel", "g1_intt_load_kernel", "g1_level_kernel",
               "g1_intt_finish_kernel"]
     for name in opening + others:
         assert len(rows.get(name, [])) == 2, (name, out)              # one instantiation per curve

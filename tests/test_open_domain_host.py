@@ -7,18 +7,18 @@ import os
 import random
 import re
 import subprocess
-import sys
 
 import pytest
 
 from oracle import py_oracle as O
+from restated import fr_dft, g1_dft, g1_mul, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "kzg_mi355x.h")
 
 NEW_SYMBOLS = ["kzg_domain_table_create", "kzg_domain_table_size", "kzg_domain_table_free", "kzg_open_domain",
                "kzg_open_domain_device"]
-NEW_KERNELS = ["dom_load_key_kernel", "dom_level_kernel", "dom_hadamard_kernel", "dom_extract_kernel",
+NEW_KERNELS = ["dom_load_key_kernel", "g1_level_kernel", "dom_hadamard_kernel", "dom_extract_kernel",
                "dom_finish_table_kernel", "dom_finish_proofs_kernel"]
 CURVES = ["bls12_381", "bn254"]
 TAU = 0x5eed_1234_abcd_0987_6543_21fe_dcba
@@ -46,30 +46,6 @@ def test_new_symbols_are_declared_exported_and_bound(built):
 
 
 # ---- the algorithm restated over the oracle's group law ------------------------------------------------------------
-def g1_mul(pt, k, cv):
-    k %= cv.r
-    if O.is_inf(pt) or k == 0:
-        return O.Z1()
-    return pt if k == 1 else O.multiply(pt, k, cv)
-
-
-def g1_dft(points, root, cv):
-    """naive O(len^2) DFT over G1: out[k] = sum_i root^(i k) points[i]"""
-    n, r = len(points), cv.r
-    out = []
-    for k in range(n):
-        acc = O.Z1()
-        for i, p in enumerate(points):
-            acc = O.add(acc, g1_mul(p, pow(root, i * k % n, r), cv), cv)
-        out.append(acc)
-    return out
-
-
-def fr_dft(vals, root, r):
-    n = len(vals)
-    return [sum(v * pow(root, i * k % n, r) for i, v in enumerate(vals)) % r for k in range(n)]
-
-
 def fk20_restated(coeffs, ck, n, w, cv):
     """all n proofs pi(w^i) of p = sum_j coeffs[j] X^j (len <= n) against the monomial key ck (>= n points)"""
     r, nn = cv.r, 2 * n
@@ -155,13 +131,10 @@ def test_facade_rejects_bad_arguments_before_the_device(curve, monkeypatch):
 
 # ---- kernel budget -------------------------------------------------------------------------------------------------
 def test_new_kernels_never_spill_and_fit_256_vgprs(built):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), built],
-                         capture_output=True, text=True, check=True).stdout
+    out, listing = kernel_resources(built)
     rows = {}
-    for line in out.splitlines():
-        m = re.match(r"(\S.*?)\s+vgpr\s+(\d+)\s+agpr\s+(\d+)\s+sgpr\s+(\d+)\s+lds\s+(\d+)\s+scratch\s+(\d+)", line)
-        if m:
-            rows.setdefault(m.group(1).strip(), []).append((int(m.group(2)), int(m.group(6))))
+    for name, vgpr, _, _, _, scratch in listing:
+        rows.setdefault(name, []).append((vgpr, scratch))
     for name in NEW_KERNELS:
         assert "prep_" not in name
         assert len(rows.get(name, [])) == 2, (name, out)                  # one instantiation per curve
