@@ -296,6 +296,35 @@ int kzg_open_coset(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* polys, cons
 int kzg_open_coset_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,
                           size_t stride, uint32_t log_l, const uint64_t h[4], const uint64_t zeta[4],
                           const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out);
+/* ---- bulk verification: any number of coset claims folded into ONE pairing equation ----------------------------
+ * Claim k < K: the polynomial of commitment C[c_k] takes the l = 2^log_l values y_k[t] at w^(i_k + t N/l), t < l
+ * (N = 2^log_N, coset (h_k = w^(i_k), zeta = w^(N/l)) in kzg_open_cosets' numbering), with proof pi_k.  With
+ * a_k = h_k^l, the remainder I_k(X) = sum_j rho_kj X^j recovered from the values as above, and weights r_k = rho^(k+1)
+ * (the rule of the facade's batch_check / batch_check_cosets; rho is the caller's random element):
+ *     L = sum_j (sum_(k: c_k = j) r_k) C[j]  -  [(sum_k r_k I_k)(tau)] G1  +  sum_k (r_k a_k) pi_k
+ *     R = sum_k r_k pi_k
+ * and every claim holds (up to the soundness error of the random combination) iff e(L, G2) = e(R, [tau^l] G2).  The
+ * library returns the two points (out_xy / out_inf: L, then R, kzg_open's point format); the caller does the two
+ * pairings.  This is verify_cell_kzg_proof_batch of EIP-7594 in this library's conventions; l = 1 checks the proofs of
+ * kzg_open_domain.
+ *   monomial   the monomial key (>= l points; KZG_ERR_ARG for a Lagrange key, a key of another curve, a shorter one)
+ *   comm_xy / comm_inf   n_comm commitments (1 <= n_comm <= 2^16), comm_idx[k] = c_k < n_comm
+ *   coset_idx  i_k < N/l;  values [K][l][4] canonical limbs (reduced by the caller), natural order: what
+ *              kzg_open_cosets' eval_out holds for that coset;  proof_xy / proof_inf: the K proofs
+ * Layouts are those kzg_open_cosets / kzg_open_domain write: for one polynomial, coset_idx = 0 .. N/l - 1 and
+ * comm_idx = 0.  Cells may repeat, come in any order and cover any subset.  Ranges: 0 <= log_l <= 12,
+ * log_l < log_N <= 21, K <= 2^21, K * l <= 2^24; K = 0 is KZG_OK with both points at infinity.  KZG_ERR_ARG, before
+ * any MSM is queued: sizes or an index out of range, a w that is not a primitive N-th root, a proof or commitment
+ * with a coordinate >= p or off the curve.  Membership in the prime-order subgroup is NOT checked (as in the facade's
+ * host verifiers): a caller that takes points from an untrusted party checks it first.
+ * The proofs are used once, so they are not expanded into a key's window multiples: they become window-0 records
+ * only (one record per proof), each scalar is cut into slices of win_bits - 1 bits, and every slice vector runs
+ * through the commit pipeline as one polynomial.  Host pointers in, host results out; synchronises.
+ * Results of kzg_commit_device_async / kzg_open_device_async still pending are delivered as by a later commit. */
+int kzg_verify_cosets(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
+                      const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
+                      const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy,
+                      const uint8_t* proof_inf, size_t K, const uint64_t rho[4], uint64_t* out_xy, uint8_t* out_inf);
 /* ---- KZG.open on ONE polynomial set partitioned by coefficient range across GPUs ----------------
  * Rank g holds coefficients [lo_g, hi_g) of every polynomial (the same ranges for all) and a key
  * shard.  kzg_open_shard_begin combines the slices (sum xi^(i+1) p_i) and returns the slice
@@ -351,12 +380,14 @@ int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size
  * built), "open_evals_poly" (ONE per kzg_open_evals*: combination, value and quotient), "domain_table" (one per
  * kzg_domain_table_create), "open_domain" (ONE per kzg_open_domain*: every chunk, transform and copy), "coset_table"
  * (one per kzg_coset_table_create), "open_cosets" (ONE per kzg_open_cosets*), "open_coset_poly" (ONE per
- * kzg_open_coset*: combination, division and remainder).  kzg_prof_read synchronises the
+ * kzg_open_coset*: combination, division and remainder), "verify_cosets" (ONE per kzg_verify_cosets: the whole call on
+ * the context's stream; its MSMs also report under the msm_* names).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.
  * Two names are not spans: "msm_accumulate_shader_mhz" and "ntt_pass_shader_mhz" return (in *total_ms) the shader
  * clock in MHz the accumulate / NTT kernel ran at since the last reset -- s_memtime over s_memrealtime ticks of its
  * first wave -- and *count = 1 when a launch has reported, 0 otherwise; "ntt_tile_log" returns log2 of the LDS
- * tile the last two-pass transform took. */
+ * tile the last two-pass transform took; "verify_device_bytes" the bytes of device memory the last kzg_verify_cosets
+ * asked for (commit-pipeline slots not included). */
 int kzg_prof_enable(kzg_ctx* ctx, int on);
 int kzg_prof_reset(kzg_ctx* ctx);
 int kzg_prof_read(kzg_ctx* ctx, const char* name, double* total_ms, uint64_t* count);

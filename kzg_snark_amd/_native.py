@@ -100,6 +100,8 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp]),
     "kzg_open_coset_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32,
                                              _vp, _vp, _vp, _vp, _vp, _vp]),
+    "kzg_verify_cosets": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_size_t,
+                                         _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
 }
 
 
@@ -420,6 +422,40 @@ class Context:
                        _as_vp(int_to_words(int(h))), _as_vp(int_to_words(int(zeta))), _as_vp(int_to_words(int(xi))),
                        _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev)))
         return out_xy, out_inf, ev
+
+    # ---- bulk verification
+    def verify_cosets(self, srs, log_N, log_l, w, comm_xy, comm_inf, comm_idx, coset_idx, values, proof_xy, proof_inf,
+                      rho):
+        """The two G1 points (L, R) of the rho-weighted combination of K coset claims: (xy uint64[2, 2*fp_limbs],
+        inf uint8[2]); the claims hold iff e(L, G2) = e(R, [tau^l] G2).  comm_xy uint64[n_comm, 2*fp_limbs] with
+        comm_inf uint8[n_comm] or None; comm_idx / coset_idx uint32[K]; values uint64[K, l, 4]; proof_xy
+        uint64[K, 2*fp_limbs] with proof_inf uint8[K] or None -- the layouts open_cosets / open_domain return."""
+        P = 2 * self.fp_limbs
+        comm_idx = np.ascontiguousarray(comm_idx, dtype=np.uint32).reshape(-1)
+        coset_idx = np.ascontiguousarray(coset_idx, dtype=np.uint32).reshape(-1)
+        K, l = comm_idx.size, 1 << int(log_l)
+        comm_xy = np.ascontiguousarray(comm_xy, dtype=np.uint64).reshape(-1, P)
+        proof_xy = np.ascontiguousarray(proof_xy, dtype=np.uint64).reshape(-1, P)
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        if coset_idx.size != K or proof_xy.shape[0] != K or values.size != K * l * 4:
+            raise ValueError("verify_cosets: comm_idx, coset_idx, values and proofs describe different numbers of cells")
+        if comm_inf is not None:
+            comm_inf = np.ascontiguousarray(comm_inf, dtype=np.uint8).reshape(-1)
+            if comm_inf.size != comm_xy.shape[0]:
+                raise ValueError("verify_cosets: comm_inf and comm_xy differ in length")
+        if proof_inf is not None:
+            proof_inf = np.ascontiguousarray(proof_inf, dtype=np.uint8).reshape(-1)
+            if proof_inf.size != K:
+                raise ValueError("verify_cosets: proof_inf and proof_xy differ in length")
+        out_xy = np.zeros((2, P), dtype=np.uint64)
+        out_inf = np.zeros(2, dtype=np.uint8)
+        self._check(lib().kzg_verify_cosets(self._h, srs._h, int(log_N), int(log_l), _as_vp(int_to_words(int(w))),
+                                            _as_vp(comm_xy), _as_vp(comm_inf), comm_xy.shape[0], _as_vp(comm_idx),
+                                            _as_vp(coset_idx), _as_vp(values), _as_vp(proof_xy), _as_vp(proof_inf), K,
+                                            _as_vp(int_to_words(int(rho))), _as_vp(out_xy), _as_vp(out_inf)))
+        # the library retires every pipeline slot before it returns, as kzg_commit_flush does
+        self._inflight.clear()
+        return out_xy, out_inf
 
     # ---- commit / open on host buffers
     def commit(self, srs, scalars, lens, stride):

@@ -165,6 +165,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
   hipFree(c->scan_tmp.p);
   hipFree(c->lagr_tmp.p);
   hipFree(c->dom_tmp.p);
+  hipFree(c->ver_tmp.p);
   for (auto& b : c->poly_tmp) hipFree(b.p);
   for (auto s : c->aux_streams) hipStreamDestroy(s);
   for (auto e : c->aux_events) hipEventDestroy(e);
@@ -704,6 +705,20 @@ int kzg_open_coset(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* polys, cons
   return kzg_open_coset_device(ctx, srs, c->io.p, lens, k, stride, log_l, h, zeta, xi, out_xy, out_inf, eval_out);
 }
 
+int kzg_verify_cosets(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
+                      const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
+                      const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy,
+                      const uint8_t* proof_inf, size_t K, const uint64_t rho[4], uint64_t* out_xy, uint8_t* out_inf) {
+  if (!ctx || !monomial || !w || !rho || !out_xy || !out_inf || !comm_xy ||
+      (K && (!comm_idx || !coset_idx || !values || !proof_xy)))
+    return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return verify_cosets(c, monomial->s, log_N, log_l, reinterpret_cast<const uint32_t*>(w), comm_xy, comm_inf, n_comm,
+                       comm_idx, coset_idx, values, proof_xy, proof_inf, K, reinterpret_cast<const uint32_t*>(rho),
+                       out_xy, out_inf);
+}
+
 #define KZG_VEC_ENTER()                          \
   if (!ctx) return KZG_ERR_ARG;                  \
   Ctx* c = &ctx->c;                              \
@@ -791,6 +806,11 @@ int kzg_prof_read(kzg_ctx* ctx, const char* name, double* total_ms, uint64_t* co
   *total_ms = 0;
   *count = 0;
   const bool acc_clk = std::string(name) == "msm_accumulate_shader_mhz", ntt_clk = std::string(name) == "ntt_pass_shader_mhz";
+  if (std::string(name) == "verify_device_bytes") {   // not a span: device memory the last kzg_verify_cosets asked for
+    *total_ms = (double)c->ver_last_bytes;
+    *count = c->ver_last_bytes ? 1 : 0;
+    return KZG_OK;
+  }
   if (std::string(name) == "ntt_tile_log") {   // not a span: log2 of the LDS tile the last transform took
     *total_ms = (double)c->last_ntt_tile_log;
     *count = c->last_ntt_tile_log ? 1 : 0;

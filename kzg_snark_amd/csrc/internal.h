@@ -1,5 +1,5 @@
 // internal.h -- library-private declarations shared by the translation units of
-// libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, poly.hip).
+// libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, poly.hip, verify.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,6 +63,9 @@ struct Ctx {
   DevBuf scan_tmp;        // open(): chunk values, tile aggregates, power tables (kept between the shard calls)
   DevBuf lagr_tmp;        // lagrange.hip: combined values, denominators, inverses, quotient, partial sums
   DevBuf dom_tmp;         // domain.hip: G1 transform buffers and the Fr vectors of one chunk of kzg_open_domain
+  DevBuf ver_tmp;         // verify.hip: staged claims, proof records, weights, power tables, partial sums
+  size_t ver_last_bytes = 0;              // what the last kzg_verify_cosets carved out of ver_tmp (kzg_prof_read)
+  uint32_t ver_lds_attr_set = 0;          // per ver_cell_kernel instantiation, as ntt_lds_attr_set
   size_t open_shard_n = 0;                // slice length between kzg_open_shard_begin / _finish
   uint32_t open_shard_tb = 0;             // tile width the slice's aggregates were formed with
   // kzg_ctx_set_tuning: 0 = the library's own choice

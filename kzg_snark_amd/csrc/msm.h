@@ -34,6 +34,11 @@ int srs_generate_scalars(Ctx* c, const uint32_t* d_scalars, size_t n, Srs** out)
 // an n-point key whose window-0 records the caller fills, then srs_finish_windows (synchronises)
 int srs_create(Ctx* c, size_t n, Srs** out);
 int srs_finish_windows(Ctx* c, Srs* s);
+// `out` becomes a key of n points over caller-owned window-0 records and NO further window (nothing is allocated, the
+// caller keeps `recs` alive and never calls srs_free on it): good for commits whose scalars are all below
+// 2^(win_bits - 1), which yield one digit, in window 0 (verify.hip)
+void srs_window0_view(const Ctx* c, uint32_t* recs, size_t n, Srs* out);
+size_t srs_rec_bytes(int curve);
 
 // lagrange.hip: evaluation-form keys and openings
 int srs_lagrange(Ctx* c, const Srs* mono, uint32_t log_n, const uint32_t* w_words, Srs** out);
@@ -89,6 +94,12 @@ int open_coset_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* le
                                uint32_t log_l, const uint32_t* h_words, const uint32_t* zeta_words,
                                const uint32_t* xi_words, size_t key_n, uint32_t** d_quot_out, size_t* quot_len,
                                uint64_t* eval_out);
+
+// verify.hip: the two G1 points (L, R) of a random linear combination of K coset claims
+int verify_cosets(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const uint32_t* w_words,
+                  const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
+                  const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy, const uint8_t* proof_inf,
+                  size_t K, const uint32_t* rho_words, uint64_t* out_xy, uint8_t* out_inf);
 
 int open_shard_begin_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                             const uint32_t* z_words, const uint32_t* xi_words, uint64_t* chunk_eval_out);

@@ -651,6 +651,15 @@ int srs_create(Ctx* c, size_t n, Srs** out) {
 int srs_finish_windows(Ctx* c, Srs* s) {
   return c->curve == 0 ? srs_build_windows<Bn254>(c, s) : srs_build_windows<Bls12_381>(c, s);
 }
+void srs_window0_view(const Ctx* c, uint32_t* recs, size_t n, Srs* out) {
+  *out = Srs();
+  out->n = n;
+  out->curve = c->curve;
+  out->win_bits = pick_win_bits(n);
+  out->nwin = 1;
+  out->recs = recs;
+}
+size_t srs_rec_bytes(int curve) { return curve == 0 ? rec_bytes<Bn254>() : rec_bytes<Bls12_381>(); }
 void srs_free(Srs* s) {
   if (!s) return;
   hipFree(s->recs);

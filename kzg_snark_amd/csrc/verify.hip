@@ -1,0 +1,449 @@
+// verify.hip -- bulk verification on gfx950: K coset claims folded into the two G1 points of ONE pairing equation.
+//
+// Claim k: the polynomial of commitment C[c_k] takes the l values y_k[t] at w^(i_k + t N/l), proof pi_k.  With
+// h_k = w^(i_k), a_k = h_k^l, zeta = w^(N/l), the remainder I_k(X) = sum_j rho_kj X^j,
+// rho_kj = h_k^-j l^-1 sum_t y_k[t] zeta^(-jt), and the weights r_k = rho^(k+1):
+//     L = sum_j (sum_(k: c_k = j) r_k) C[j]  -  [T(tau)] G1  +  sum_k (r_k a_k) pi_k,     T_j = sum_k r_k rho_kj
+//     R = sum_k r_k pi_k                           accept iff e(L, G2) = e(R, [tau^l] G2)       
+//
+//   powers    w^e (e < N <= 2^21) and rho^e (e <= K <= 2^21) come from two-level tables x^e = lo[e & 2047] hi[e >> 11]
+//             (ver_pow_table_kernel, 3073 entries each): one product per power, no per-cell exponentiation
+//   weights   r_k and s_k = r_k a_k as canonical scalars (ver_weights_kernel); the per-commitment sums of r_k over the
+//             cells grouped by commitment (a counting sort of the small indices on the host, ver_commsum_kernel)
+//   values    ver_cell_kernel: tiles of max(l, 256) elements in LDS, a decimation-in-frequency inverse transform per
+//             cell (twiddles from the w table), then r_k l^-1 h_k^-j applied on the way back to memory;
+//             ver_colsum_kernel / ver_colsum_final_kernel add the cells up: T
+//   proofs    imported as window-0 records (ver_import_kernel: coordinates < p, on the curve) of a key that holds NO
+//             other window; every scalar is cut into slices of win_bits - 1 bits (ver_slice_kernel) and each slice
+//             vector goes through the commit pipeline as one polynomial: a slice yields one digit, in window 0, without
+//             a carry.  sum_s 2^(s (win_bits - 1)) P_s is finished on the host.
+//   short     [T(tau)] is a commit of l scalars against the monomial key, the commitment term a commit of n_comm
+//             scalars against a key loaded from the commitments.
+// Fr kernels: <= 128 VGPRs, no scratch; elements travel as 8 canonical words (values in standard form, table entries
+// and factors in Montgomery form, so a product of the two is in standard form again).
+#include <cstring>
+#include <algorithm>
+#include <vector>
+#include "internal.h"
+#include "fr_util.h"
+#include "g1_util.h"
+#include "msm.h"
+#include "srs_rec.h"
+
+namespace kzg {
+
+namespace {
+
+constexpr uint32_t VER_TLOG = 11;                               // x^e = lo[e & 2047] * hi[e >> 11]
+constexpr uint32_t VER_TLO = 1u << VER_TLOG;
+constexpr uint32_t VER_THI = (1u << (21 - VER_TLOG)) + 1;       // exponents up to 2^21 inclusive
+constexpr uint32_t VER_TAB = VER_TLO + VER_THI;
+constexpr uint32_t VER_MIN_TILE_LOG = 8;                        // ver_cell_kernel: tile of max(l, 256) elements
+constexpr uint32_t VER_SUM_THREADS = 1u << 15;                  // ver_colsum_kernel: threads (a multiple of every l)
+constexpr uint32_t VER_COMM_SPLIT = 64;                         // ver_commsum_kernel: workgroups per commitment when few
+
+template <class F>
+__device__ __forceinline__ Fe<F> ver_shfl_xor(const Fe<F>& v, int mask) {
+  Fe<F> r;
+#pragma unroll
+  for (int j = 0; j < F::N; ++j) r.l[j] = __shfl_xor(v.l[j], mask);
+  return r;
+}
+
+// x^e from a two-level table (Montgomery form)
+template <class F>
+__device__ __forceinline__ Fe<F> ver_pow(const uint32_t* tab, uint32_t e) {
+  return Field<F>::mul(load_words<F>(tab + (size_t)(e & (VER_TLO - 1)) * 8),
+                       load_words<F>(tab + (size_t)(VER_TLO + (e >> VER_TLOG)) * 8));
+}
+
+// tab[i] = base^i (i < VER_TLO), tab[VER_TLO + i] = base_hi^i (i < VER_THI), base_hi = base^VER_TLO; Montgomery words
+template <class F>
+__global__ __launch_bounds__(256) void ver_pow_table_kernel(FrArg base, FrArg base_hi, uint32_t* tab) {
+  using Fd = Field<F>;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= VER_TAB) return;
+  Fe<F> b = arg_fe<F>(i < VER_TLO ? base : base_hi), acc = Fd::one();
+  for (uint32_t bits = i < VER_TLO ? i : i - VER_TLO; bits; bits >>= 1) {
+    if (bits & 1u) acc = Fd::mul(acc, b);
+    b = Fd::sqr(b);
+  }
+  store_words<F>(tab + (size_t)i * 8, acc);
+}
+
+// r_k = rho^(k+1) and s_k = r_k w^(i_k l), canonical words
+template <class F>
+__global__ __launch_bounds__(256) void ver_weights_kernel(uint32_t K, uint32_t log_l, const uint32_t* coset_idx,
+                                                          const uint32_t* wtab, const uint32_t* rtab, uint32_t* r_out,
+                                                          uint32_t* s_out) {
+  using Fd = Field<F>;
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K) return;
+  const Fe<F> r = ver_pow<F>(rtab, k + 1);
+  const Fe<F> s = Fd::mul(r, ver_pow<F>(wtab, coset_idx[k] << log_l));     // i_k < N/l: the exponent is below N
+  store_words<F>(r_out + (size_t)k * 8, Fd::from_mont(r));
+  store_words<F>(s_out + (size_t)k * 8, Fd::from_mont(s));
+}
+
+template <class F>
+__device__ __forceinline__ Fe<F> ver_lds_load(const uint32_t* tile, uint32_t pos) {
+  return load_words<F>(tile + (size_t)pos * 8);
+}
+
+// vals[k][j] <- r_k l^-1 h_k^-j sum_t vals[k][t] zeta^(-jt), in place.  A workgroup takes tiles of E = 2^log_e =
+// max(l, 256) consecutive elements (whole cells): decimation in frequency in LDS, natural order in, bit-reversed out,
+// the output j of a cell read from position bitrev(j).  Dynamic LDS: E x 32 bytes.
+template <class F>
+__global__ __launch_bounds__(256) void ver_cell_kernel(uint32_t K, uint32_t log_l, uint32_t log_N, uint32_t log_e,
+                                                       const uint32_t* coset_idx, const uint32_t* wtab,
+                                                       const uint32_t* rtab, FrArg linv, uint32_t* vals) {
+  using Fd = Field<F>;
+  extern __shared__ __attribute__((aligned(16))) uint32_t ver_tile[];
+  const uint32_t E = 1u << log_e, l = 1u << log_l, N = 1u << log_N, tid = threadIdx.x;
+  const size_t M = (size_t)K << log_l;
+  const size_t ntiles = (M + E - 1) >> log_e;
+  for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const size_t base = t << log_e;
+    for (uint32_t p = tid; p < E; p += 256) {
+      uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+      if (base + p < M) {
+        const uint4* g = reinterpret_cast<const uint4*>(vals + (base + p) * 8);
+        lo = g[0];
+        hi = g[1];
+      }
+      uint4* s = reinterpret_cast<uint4*>(ver_tile + (size_t)p * 8);
+      s[0] = lo;
+      s[1] = hi;
+    }
+    __syncthreads();
+    for (uint32_t ll = log_l; ll >= 1; --ll) {         // blocks of 2^ll elements, never across a cell
+      const uint32_t half = 1u << (ll - 1);
+      for (uint32_t b = tid; b < E / 2; b += 256) {
+        const uint32_t i = b & (half - 1);
+        const uint32_t pos = ((b >> (ll - 1)) << ll) + i;
+        const Fe<F> u = ver_lds_load<F>(ver_tile, pos), v = ver_lds_load<F>(ver_tile, pos + half);
+        const uint32_t ex = (N - (N >> ll) * i) & (N - 1);             // (zeta^-1)^(i l / 2^ll) = w^(-i N / 2^ll)
+        store_words<F>(ver_tile + (size_t)pos * 8, Fd::add(u, v));
+        store_words<F>(ver_tile + (size_t)(pos + half) * 8, Fd::mul(Fd::sub(u, v), ver_pow<F>(wtab, ex)));
+      }
+      __syncthreads();
+    }
+    for (uint32_t p = tid; p < E; p += 256) {
+      if (base + p >= M) continue;
+      const uint32_t k = (uint32_t)((base + p) >> log_l), j = p & (l - 1);
+      const Fe<F> x = ver_lds_load<F>(ver_tile, (p & ~(l - 1)) + bitrev(j, log_l));
+      const uint32_t ex = (N - (uint32_t)(((uint64_t)coset_idx[k] * j) & (N - 1))) & (N - 1);   // h_k^-j
+      const Fe<F> f = Fd::mul(Fd::mul(ver_pow<F>(rtab, k + 1), arg_fe<F>(linv)), ver_pow<F>(wtab, ex));
+      store_words<F>(vals + (base + p) * 8, Fd::mul(x, f));
+    }
+    __syncthreads();
+  }
+}
+
+// part[t] = sum of vals[e], e = t mod (number of threads): the thread count is a multiple of l, so every thread stays
+// in one column j = t mod l
+template <class F>
+__global__ __launch_bounds__(256) void ver_colsum_kernel(size_t M, const uint32_t* vals, uint32_t* part) {
+  using Fd = Field<F>;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  Fe<F> acc = Fd::zero();
+  for (size_t e = t; e < M; e += stride) acc = Fd::add(acc, load_words<F>(vals + e * 8));
+  store_words<F>(part + t * 8, acc);
+}
+
+// out[j] = sum_(q < cnt) part[q * cols + j]: one wave per column
+template <class F>
+__global__ __launch_bounds__(64) void ver_colsum_final_kernel(uint32_t cols, uint32_t cnt, const uint32_t* part,
+                                                              uint32_t* out) {
+  using Fd = Field<F>;
+  const uint32_t j = blockIdx.x;
+  Fe<F> acc = Fd::zero();
+  for (uint32_t q = threadIdx.x; q < cnt; q += 64) acc = Fd::add(acc, load_words<F>(part + ((size_t)q * cols + j) * 8));
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) acc = Fd::add(acc, ver_shfl_xor<F>(acc, m));
+  if (threadIdx.x == 0) store_words<F>(out + (size_t)j * 8, acc);
+}
+
+// part[sp][j] = sum of r[perm[q]] over share sp of the cells of commitment j (perm: cells grouped by commitment,
+// off[j] .. off[j + 1])
+template <class F>
+__global__ __launch_bounds__(256) void ver_commsum_kernel(const uint32_t* r, const uint32_t* perm, const uint32_t* off,
+                                                          uint32_t n_comm, uint32_t* part) {
+  using Fd = Field<F>;
+  __shared__ uint32_t red[4][F::N];
+  const uint32_t j = blockIdx.x, sp = blockIdx.y, nsp = gridDim.y;
+  const uint32_t q0 = off[j], len = off[j + 1] - q0;
+  const uint32_t a = q0 + (uint32_t)(((uint64_t)len * sp) / nsp), b = q0 + (uint32_t)(((uint64_t)len * (sp + 1)) / nsp);
+  Fe<F> acc = Fd::zero();
+  for (uint32_t q = a + threadIdx.x; q < b; q += 256) acc = Fd::add(acc, load_words<F>(r + (size_t)perm[q] * 8));
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) acc = Fd::add(acc, ver_shfl_xor<F>(acc, m));
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (lane == 0) store_limbs<F>(red[wave], acc);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (uint32_t q = 1; q < 4; ++q) acc = Fd::add(acc, load_limbs<F>(red[q]));
+    store_words<F>(part + ((size_t)sp * n_comm + j) * 8, acc);
+  }
+}
+
+// out[k] = bits [bit, bit + bits) of the canonical scalar src[k], as a scalar of its own (bits <= 19)
+__global__ __launch_bounds__(256) void ver_slice_kernel(uint32_t K, const uint32_t* src, uint32_t bit, uint32_t bits,
+                                                        uint32_t* out) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K) return;
+  const uint32_t idx = bit >> 5, sh = bit & 31u;
+  const uint64_t lo = src[(size_t)k * 8 + idx], hi = idx + 1 < 8 ? src[(size_t)k * 8 + idx + 1] : 0u;
+  const uint32_t d = (uint32_t)(((hi << 32) | lo) >> sh) & ((1u << bits) - 1);
+  uint4* o = reinterpret_cast<uint4*>(out + (size_t)k * 8);
+  o[0] = make_uint4(d, 0, 0, 0);
+  o[1] = make_uint4(0, 0, 0, 0);
+}
+
+// canonical affine words -> window-0 records, as srs_import_kernel (msm.hip); a coordinate >= p or a point off the
+// curve is counted in *bad
+template <class C>
+__global__ __launch_bounds__(256) void ver_import_kernel(const uint32_t* xy, const uint8_t* inf, uint32_t* recs,
+                                                         size_t n, uint32_t* bad) {
+  using F = typename C::Fp;
+  using Fd = Field<F>;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool is_inf = inf && inf[i];
+  Fe<F> x = Fd::zero(), y = Fd::zero();
+  if (!is_inf) {
+    uint32_t wx[F::NW], wy[F::NW];
+#pragma unroll
+    for (int k = 0; k < F::NW; ++k) { wx[k] = xy[i * 2 * F::NW + k]; wy[k] = xy[i * 2 * F::NW + F::NW + k]; }
+    bool x_lt = false, x_gt = false, y_lt = false, y_gt = false;       // compared with p from the top word down
+#pragma unroll
+    for (int k = F::NW - 1; k >= 0; --k) {
+      const uint32_t pw = F::PW[k];
+      if (!x_lt && !x_gt) { x_lt = wx[k] < pw; x_gt = wx[k] > pw; }
+      if (!y_lt && !y_gt) { y_lt = wy[k] < pw; y_gt = wy[k] > pw; }
+    }
+    x = Fd::reduce(Fd::to_mont(Fd::from_words(wx)));
+    y = Fd::reduce(Fd::to_mont(Fd::from_words(wy)));
+    if (!x_lt || !y_lt || !Ec<C>::on_curve(x, y)) atomicAdd(bad, 1u);
+  }
+  store_rec<C>(recs, i, x, y, is_inf);
+}
+
+// ---- host side --------------------------------------------------------------------------------------
+
+template <class C>
+XYZZ<C> point_from_words(const uint64_t* xy, uint8_t inf) {
+  using Fd = Field<typename C::Fp>;
+  constexpr int NW = C::Fp::NW;
+  if (inf) return Ec<C>::infinity();
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(xy);
+  Affine<C> a;
+  a.x = Fd::reduce(Fd::to_mont(Fd::from_words(w)));
+  a.y = Fd::reduce(Fd::to_mont(Fd::from_words(w + NW)));
+  a.inf = false;
+  return Ec<C>::from_affine(a);
+}
+
+template <class C>
+void point_to_words(const XYZZ<C>& p, uint64_t* xy, uint8_t* inf) {
+  using Fd = Field<typename C::Fp>;
+  constexpr int NW = C::Fp::NW;
+  const Affine<C> a = Ec<C>::to_affine(p);
+  uint32_t* o = reinterpret_cast<uint32_t*>(xy);
+  if (a.inf) {
+    memset(o, 0, 2 * NW * 4);
+    *inf = 1;
+    return;
+  }
+  Fd::to_words(Fd::from_mont(a.x), o);
+  Fd::to_words(Fd::from_mont(a.y), o + NW);
+  *inf = 0;
+}
+
+// sum_s 2^(s * sb) P_s over the slice results, from the top slice down
+template <class C>
+XYZZ<C> recombine_slices(const uint64_t* xy, const uint8_t* inf, uint32_t ns, uint32_t sb) {
+  constexpr size_t PW64 = C::Fp::NW;                // 64-bit words per point (2 coordinates of NW / 2)
+  XYZZ<C> acc = Ec<C>::infinity();
+  for (uint32_t s = ns; s-- > 0;) {
+    for (uint32_t d = 0; d < sb; ++d) acc = Ec<C>::dbl(acc);
+    acc = Ec<C>::add(acc, point_from_words<C>(xy + (size_t)s * PW64, inf[s]));
+  }
+  return acc;
+}
+
+template <class C>
+int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const uint32_t* w_words,
+                    const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
+                    const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy,
+                    const uint8_t* proof_inf, size_t K, const uint32_t* rho_words, uint64_t* out_xy, uint8_t* out_inf) {
+  using F = typename C::Fr;
+  using Fd = Field<F>;
+  using Fp = typename C::Fp;
+  constexpr size_t PW64 = Fp::NW;                   // 64-bit words per affine point
+  constexpr size_t PT_BYTES = 2 * Fp::NW * 4;
+  if (mono->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
+  if (mono->basis != SRS_MONOMIAL) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: the key must be monomial");
+  if (log_l > 12 || log_N <= log_l || log_N > 21)
+    return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: need 0 <= log_l <= 12 and log_l < log_N <= 21");
+  if (K > ((size_t)1 << 21) || (K << log_l) > ((size_t)1 << 24))
+    return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: need K <= 2^21 and K * l <= 2^24");
+  if (n_comm < 1 || n_comm > ((size_t)1 << 16)) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: need 1 <= n_comm <= 2^16");
+  const size_t l = (size_t)1 << log_l;
+  if (mono->n < l) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: the key has fewer than l points");
+  const Fe<F> w = mont_from_words<F>(w_words);
+  if (!primitive_root<F>(w, log_N))
+    return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: w is not a primitive N-th root of unity");
+  memset(out_xy, 0, 2 * PT_BYTES);
+  out_inf[0] = out_inf[1] = 1;
+  if (K == 0) return KZG_OK;
+  // the cells grouped by commitment: a counting sort of the indices (and their range check)
+  const uint32_t n_cosets = 1u << (log_N - log_l);
+  std::vector<uint32_t> off(n_comm + 1, 0), perm(K);
+  for (size_t k = 0; k < K; ++k) {
+    if (comm_idx[k] >= n_comm) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: commitment index out of range");
+    if (coset_idx[k] >= n_cosets) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: coset index out of range");
+    ++off[comm_idx[k] + 1];
+  }
+  for (size_t j = 0; j < n_comm; ++j) off[j + 1] += off[j];
+  {
+    std::vector<uint32_t> cur(off.begin(), off.end() - 1);
+    for (size_t k = 0; k < K; ++k) perm[cur[comm_idx[k]]++] = (uint32_t)k;
+  }
+
+  const size_t M = K << log_l, rb = srs_rec_bytes(c->curve);
+  const uint32_t log_e = std::max(log_l, VER_MIN_TILE_LOG);
+  const uint32_t sum_threads = std::max<uint32_t>((uint32_t)l, VER_SUM_THREADS);
+  const uint32_t nsp = n_comm >= VER_COMM_SPLIT ? 1 : VER_COMM_SPLIT;
+  size_t total = 0;
+  auto reserve = [&](size_t bytes) { const size_t o = total; total += (bytes + 255) / 256 * 256; return o; };
+  const size_t o_pxy = reserve(K * PT_BYTES), o_pinf = reserve(proof_inf ? K : 0), o_cxy = reserve(n_comm * PT_BYTES),
+               o_cinf = reserve(comm_inf ? n_comm : 0), o_recs = reserve(K * rb), o_vals = reserve(M * 32),
+               o_r = reserve(K * 32), o_s = reserve(K * 32), o_slice = reserve(K * 32), o_cidx = reserve(K * 4),
+               o_perm = reserve(K * 4), o_off = reserve((n_comm + 1) * 4), o_wtab = reserve((size_t)VER_TAB * 32),
+               o_rtab = reserve((size_t)VER_TAB * 32), o_part = reserve((size_t)sum_threads * 32),
+               o_cpart = reserve(n_comm * nsp * 32), o_T = reserve(l * 32), o_coef = reserve(n_comm * 32),
+               o_bad = reserve(4);
+  int rc = ensure_buf(c, c->ver_tmp, total);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ver_tmp.p);
+  auto u32 = [&](size_t o) { return reinterpret_cast<uint32_t*>(base + o); };
+  uint32_t *d_pxy = u32(o_pxy), *d_cxy = u32(o_cxy), *d_recs = u32(o_recs), *d_vals = u32(o_vals), *d_r = u32(o_r),
+           *d_s = u32(o_s), *d_slice = u32(o_slice), *d_cidx = u32(o_cidx), *d_perm = u32(o_perm), *d_off = u32(o_off),
+           *d_wtab = u32(o_wtab), *d_rtab = u32(o_rtab), *d_part = u32(o_part), *d_cpart = u32(o_cpart),
+           *d_T = u32(o_T), *d_coef = u32(o_coef), *d_bad = u32(o_bad);
+  uint8_t* d_pinf = proof_inf ? base + o_pinf : nullptr;
+  uint8_t* d_cinf = comm_inf ? base + o_cinf : nullptr;
+
+  Srs* cs = nullptr;                                 // the commitments as a key of their own (all windows)
+  if ((rc = srs_create(c, n_comm, &cs))) return rc;
+  c->ver_last_bytes = total + (size_t)cs->nwin * n_comm * rb;
+  auto fail = [&](int code) { srs_free(cs); return code; };
+#define KZG_VER_HIP(call)                                                        \
+  do {                                                                           \
+    hipError_t e__ = (call);                                                     \
+    if (e__ != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, #call, e__));     \
+  } while (0)
+
+  ProfScope ps(c, "verify_cosets");
+  hipStream_t st = c->stream;
+  KZG_VER_HIP(hipMemcpyAsync(d_pxy, proof_xy, K * PT_BYTES, hipMemcpyHostToDevice, st));
+  if (proof_inf) KZG_VER_HIP(hipMemcpyAsync(d_pinf, proof_inf, K, hipMemcpyHostToDevice, st));
+  KZG_VER_HIP(hipMemcpyAsync(d_cxy, comm_xy, n_comm * PT_BYTES, hipMemcpyHostToDevice, st));
+  if (comm_inf) KZG_VER_HIP(hipMemcpyAsync(d_cinf, comm_inf, n_comm, hipMemcpyHostToDevice, st));
+  KZG_VER_HIP(hipMemsetAsync(d_bad, 0, 4, st));
+  hipLaunchKernelGGL(ver_import_kernel<C>, dim3((uint32_t)((K + 255) / 256)), dim3(256), 0, st, d_pxy, d_pinf, d_recs,
+                     K, d_bad);
+  hipLaunchKernelGGL(ver_import_kernel<C>, dim3((uint32_t)((n_comm + 255) / 256)), dim3(256), 0, st, d_cxy, d_cinf,
+                     cs->recs, n_comm, d_bad);
+  KZG_VER_HIP(hipGetLastError());
+  uint32_t bad = 0;
+  KZG_VER_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+  // the claims travel while the points are checked
+  KZG_VER_HIP(hipMemcpyAsync(d_vals, values, M * 32, hipMemcpyHostToDevice, st));
+  KZG_VER_HIP(hipMemcpyAsync(d_cidx, coset_idx, K * 4, hipMemcpyHostToDevice, st));
+  KZG_VER_HIP(hipMemcpyAsync(d_perm, perm.data(), K * 4, hipMemcpyHostToDevice, st));
+  KZG_VER_HIP(hipMemcpyAsync(d_off, off.data(), (n_comm + 1) * 4, hipMemcpyHostToDevice, st));
+  KZG_VER_HIP(hipStreamSynchronize(st));
+  if (bad) return fail(set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: a proof or commitment has a coordinate >= p or is not on the curve"));
+  if ((rc = srs_finish_windows(c, cs))) return fail(rc);
+
+  // ---- weights and the fold of the values
+  const Fe<F> rho = mont_from_words<F>(rho_words);
+  Fe<F> w_hi = w, rho_hi = rho;
+  for (uint32_t q = 0; q < VER_TLOG; ++q) { w_hi = Fd::sqr(w_hi); rho_hi = Fd::sqr(rho_hi); }
+  const dim3 tab_grid((VER_TAB + 255) / 256), k_grid((uint32_t)((K + 255) / 256));
+  hipLaunchKernelGGL(ver_pow_table_kernel<F>, tab_grid, dim3(256), 0, st, fr_arg<F>(w), fr_arg<F>(w_hi), d_wtab);
+  hipLaunchKernelGGL(ver_pow_table_kernel<F>, tab_grid, dim3(256), 0, st, fr_arg<F>(rho), fr_arg<F>(rho_hi), d_rtab);
+  hipLaunchKernelGGL(ver_weights_kernel<F>, k_grid, dim3(256), 0, st, (uint32_t)K, log_l, d_cidx, d_wtab, d_rtab, d_r,
+                     d_s);
+  KZG_VER_HIP(hipGetLastError());
+  const size_t lds_bytes = (size_t)32 << log_e;
+  if (lds_bytes > 64 * 1024 && !c->ver_lds_attr_set) {   // > 64 KiB of dynamic LDS (gfx950: 160 KiB per CU); per device
+    KZG_VER_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ver_cell_kernel<F>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    c->ver_lds_attr_set = 1;
+  }
+  const size_t ntiles = (M + ((size_t)1 << log_e) - 1) >> log_e;
+  hipLaunchKernelGGL(ver_cell_kernel<F>, dim3((uint32_t)std::min<size_t>(ntiles, 4096)), dim3(256), lds_bytes, st,
+                     (uint32_t)K, log_l, log_N, log_e, d_cidx, d_wtab, d_rtab, fr_arg<F>(Fd::reduce(inv_pow2<F>(log_l))),
+                     d_vals);
+  hipLaunchKernelGGL(ver_colsum_kernel<F>, dim3(sum_threads / 256), dim3(256), 0, st, M, d_vals, d_part);
+  hipLaunchKernelGGL(ver_colsum_final_kernel<F>, dim3((uint32_t)l), dim3(64), 0, st, (uint32_t)l,
+                     sum_threads >> log_l, d_part, d_T);
+  hipLaunchKernelGGL(ver_commsum_kernel<F>, dim3((uint32_t)n_comm, nsp), dim3(256), 0, st, d_r, d_perm, d_off,
+                     (uint32_t)n_comm, d_cpart);
+  hipLaunchKernelGGL(ver_colsum_final_kernel<F>, dim3((uint32_t)n_comm), dim3(64), 0, st, (uint32_t)n_comm, nsp,
+                     d_cpart, d_coef);
+  KZG_VER_HIP(hipGetLastError());
+
+  // ---- the MSMs: 2 x ns slice vectors over the proofs, T over the key, the weights over the commitments
+  Srs pv;
+  srs_window0_view(c, d_recs, K, &pv);
+  const uint32_t sb = (uint32_t)pv.win_bits - 1, ns = (F::BITS + sb - 1) / sb;
+  std::vector<uint64_t> h_xy((size_t)(2 * ns + 2) * PW64);
+  std::vector<uint8_t> h_inf(2 * ns + 2);
+  for (uint32_t v = 0; v < 2 && rc == KZG_OK; ++v) {
+    for (uint32_t s = 0; s < ns && rc == KZG_OK; ++s) {
+      hipLaunchKernelGGL(ver_slice_kernel, k_grid, dim3(256), 0, st, (uint32_t)K, v ? d_s : d_r, s * sb, sb, d_slice);
+      // the pipeline takes its own copy of the scalars in stream order (or holds the stream until they are consumed):
+      // the next slice may overwrite d_slice
+      const size_t idx = (size_t)v * ns + s;
+      rc = commit_device(c, &pv, d_slice, &K, 1, K, h_xy.data() + idx * PW64, h_inf.data() + idx, /*drain=*/false);
+    }
+  }
+  if (rc == KZG_OK)
+    rc = commit_device(c, mono, d_T, &l, 1, l, h_xy.data() + (size_t)2 * ns * PW64, h_inf.data() + 2 * ns, false);
+  if (rc == KZG_OK)
+    rc = commit_device(c, cs, d_coef, &n_comm, 1, n_comm, h_xy.data() + (size_t)(2 * ns + 1) * PW64,
+                       h_inf.data() + 2 * ns + 1, false);
+  const int rc2 = commit_flush(c);                    // also on an error: nothing may point at h_xy afterwards
+  if (rc == KZG_OK) rc = rc2;
+  if (rc) return fail(rc);
+#undef KZG_VER_HIP
+
+  const XYZZ<C> R = recombine_slices<C>(h_xy.data(), h_inf.data(), ns, sb);
+  const XYZZ<C> S = recombine_slices<C>(h_xy.data() + (size_t)ns * PW64, h_inf.data() + ns, ns, sb);
+  XYZZ<C> Tp = point_from_words<C>(h_xy.data() + (size_t)2 * ns * PW64, h_inf[2 * ns]);
+  Tp.y = Field<Fp>::neg(Tp.y);                        // -O = O: y = 0 stays 0
+  const XYZZ<C> Cc = point_from_words<C>(h_xy.data() + (size_t)(2 * ns + 1) * PW64, h_inf[2 * ns + 1]);
+  point_to_words<C>(Ec<C>::add(Ec<C>::add(Cc, Tp), S), out_xy, out_inf);
+  point_to_words<C>(R, out_xy + PW64, out_inf + 1);
+  srs_free(cs);
+  return KZG_OK;
+}
+
+}  // namespace
+
+int verify_cosets(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const uint32_t* w_words,
+                  const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
+                  const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy, const uint8_t* proof_inf,
+                  size_t K, const uint32_t* rho_words, uint64_t* out_xy, uint8_t* out_inf) {
+  return c->curve == 0 ? verify_cosets_t<Bn254>(c, mono, log_N, log_l, w_words, comm_xy, comm_inf, n_comm, comm_idx,
+                                                coset_idx, values, proof_xy, proof_inf, K, rho_words, out_xy, out_inf)
+                       : verify_cosets_t<Bls12_381>(c, mono, log_N, log_l, w_words, comm_xy, comm_inf, n_comm,
+                                                    comm_idx, coset_idx, values, proof_xy, proof_inf, K, rho_words,
+                                                    out_xy, out_inf);
+}
+
+}  // namespace kzg

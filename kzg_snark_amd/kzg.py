@@ -9,6 +9,7 @@ commit and open -- executed by the gfx950 engine through the C ABI.
     open(ck, polynomials, z, xi) -> point            kzg.py:122
     check(rk, commitments, z, evaluations, proof, xi) -> bool            kzg.py:161
     batch_check(rk, commitments_list, z_list, evaluations_list, proof_list, xi_list, r=None)   kzg.py:213
+    verify_cosets / verify_domain: any number of coset (or single-point) claims folded on the device, two pairings
 
 Points are py_ecc-shaped 3-tuples, always normalised: (x, y, 1), infinity (1, 1, 0).
 The reference returns un-normalised projective triples whose representative
@@ -751,3 +752,104 @@ class KZG:
             weight = weight * rho_w % order
         lhs += [self.neg(p) for p in self._rho_commitment_terms(ck, rho_sum)]
         return self.pairing(self.G2, self._sum_g1(lhs)) == self.pairing(rk_l, self._sum_g1(rhs))
+
+    # ---- bulk verification (device): K claims folded into the two G1 points of one pairing equation -----------------
+    _VERIFY_MAX_N = 1 << 21
+
+    def _g1_arrays(self, points, what):
+        """points: a list of point tuples, or (xy uint64[n, 2L], inf uint8[n] | None) in the C layout -> (xy, inf)."""
+        L = (self._cv.p.bit_length() + 63) // 64                  # uint64 limbs per coordinate (kzg_fp_limbs)
+        if isinstance(points, tuple) and len(points) == 2 and isinstance(points[0], np.ndarray):
+            xy = np.ascontiguousarray(points[0], dtype=np.uint64).reshape(-1, 2 * L)
+            inf = None if points[1] is None else np.ascontiguousarray(points[1], dtype=np.uint8).reshape(-1)
+            if inf is not None and inf.size != xy.shape[0]:
+                raise ValueError(f"{what}: {inf.size} infinity flags for {xy.shape[0]} points")
+            return xy, inf
+        points = list(points)
+        n = len(points)
+        inf = np.zeros(n, dtype=np.uint8)
+        coords = []
+        for i, pt in enumerate(points):
+            x, y, z = (int(c) for c in pt)
+            if z == 0:
+                inf[i] = 1
+                x = y = 0
+            elif z != 1:
+                x, y, z = self._g1.normalize((x, y, z))
+            coords += [x, y]
+        xy = _native.ints_to_limbs(coords, L).reshape(n, 2 * L) if n else np.zeros((0, 2 * L), dtype=np.uint64)
+        return np.ascontiguousarray(xy), inf
+
+    def verify_cosets(self, ck, rk_l, commitments, commitment_indices, coset_indices, values, proofs, l, N, w=None,
+                      r=None):
+        """Cell k claims: the polynomial of commitments[commitment_indices[k]] takes the l values values[k][t] at
+        w^(coset_indices[k] + t N/l), t < l, with proof proofs[k] -- open_cosets' numbering; l = 1: single points.
+        All claims are combined with weights r^(k+1) (r sampled when not given, as in batch_check) into two G1 points
+        on the device, then pairing(G2, L) == pairing(rk_l, R) with rk_l = [tau^l] G2 (coset_verification_key).
+        proofs / commitments: lists of point tuples or (xy, inf) arrays in the C layout (what Context.open_cosets
+        returns); values: nested lists or a uint64[K, l, 4] array.  A point off the curve: False.  No claims: True.
+        Membership in the prime-order subgroup is not checked (as in check / batch_check)."""
+        if isinstance(ck, (LagrangeKey, DomainTable)):
+            raise TypeError("verify_cosets needs a monomial key (setup / load_key / a list of points)")
+        l = 1 << self._log2_exact(l, "coset size")
+        N = int(N)
+        if N < 2 or N & (N - 1) or N > self._VERIFY_MAX_N:
+            raise ValueError(f"N = {N} is not a power of two in [2, 2^21]")
+        if l > N // 2:
+            raise ValueError(f"coset size {l} exceeds N/2 = {N // 2}")
+        if l > (1 << self._COSET_MAX_LOG_L):
+            raise ValueError(f"coset size {l} exceeds 2^{self._COSET_MAX_LOG_L}")
+        log_N, w = self._domain(N, w)
+        if len(ck) < l:
+            raise ValueError(f"commitment key of {len(ck)} points is shorter than the coset size {l}")
+        comm_idx = np.ascontiguousarray(commitment_indices, dtype=np.int64).reshape(-1)
+        coset_idx = np.ascontiguousarray(coset_indices, dtype=np.int64).reshape(-1)
+        K = comm_idx.size
+        pxy, pinf = self._g1_arrays(proofs, "proofs")
+        cxy, cinf = self._g1_arrays(commitments, "commitments")
+        if isinstance(values, np.ndarray) and values.dtype == np.uint64:
+            vals = np.ascontiguousarray(values)
+        else:
+            order = self.curve_order
+            rows = [list(v) for v in values]
+            if any(len(v) != l for v in rows):
+                raise ValueError(f"every cell needs {l} values")
+            flat = [int(y) % order for v in rows for y in v]
+            vals = _native.ints_to_limbs(flat) if flat else np.zeros((0, 4), dtype=np.uint64)
+        if coset_idx.size != K or pxy.shape[0] != K or vals.size != K * l * 4:
+            raise ValueError("commitment_indices, coset_indices, values and proofs must describe the same number of "
+                             f"cells of {l} values")
+        if K > (1 << 21) or K * l > (1 << 24):
+            raise ValueError("at most 2^21 cells and 2^24 values per call")
+        if not 1 <= cxy.shape[0] <= (1 << 16):
+            raise ValueError("between 1 and 2^16 commitments per call")
+        if K and (comm_idx.min() < 0 or comm_idx.max() >= cxy.shape[0]):
+            raise ValueError("commitment index out of range")
+        if K and (coset_idx.min() < 0 or coset_idx.max() >= N // l):
+            raise ValueError(f"coset index out of range [0, {N // l})")
+        rho = int(self.Fq(self.Fq.random_element() if r is None else r))
+        if K == 0:
+            return True
+        key = self._key(ck)
+        try:
+            xy, inf = self._context().verify_cosets(key.srs, log_N, l.bit_length() - 1, w, cxy, cinf,
+                                                    comm_idx.astype(np.uint32), coset_idx.astype(np.uint32),
+                                                    vals.reshape(K, l, 4), pxy, pinf, rho)
+        except _native.NativeError as e:
+            if e.code == -1 and "not on the curve" in str(e):
+                return False
+            raise
+        L_pt, R_pt = self._points(xy, inf)
+        return self.pairing(self.G2, L_pt) == self.pairing(rk_l, R_pt)
+
+    def verify_domain(self, ck, rk, commitment, values, proofs, N=None, w=None, r=None):
+        """The whole output of open_domain at once: proofs[i] opens `commitment` to values[i] at w^i, i < N (N defaults
+        to the number of proofs); rk is setup's tau G2.  verify_cosets with l = 1."""
+        if isinstance(values, np.ndarray) and values.dtype == np.uint64:
+            count = values.size // 4
+        else:
+            values = [[v] for v in values]
+            count = len(values)
+        N = count if N is None else int(N)
+        return self.verify_cosets(ck, rk, [commitment], np.zeros(count, dtype=np.int64),
+                                  np.arange(count, dtype=np.int64), values, proofs, 1, N, w=w, r=r)
