@@ -23,8 +23,16 @@
 // Column bound: a 64-bit column absorbs CAP = 2^(64-2L) - 1 products of two L-bit
 // limbs.  A Montgomery row adds two products per column (a_j*b_i and m*p_j), so
 // the sliding window is carry-normalised every CAP/2 rows: never for L = 29, N = 9
-// (CAP = 63), once (after row 7) for L = 30, N = 13 (CAP = 15).  Inputs must have
-// normalised limbs (< 2^L), which every function of this header guarantees.
+// (CAP = 63), once (after row 7) for L = 30, N = 13 (CAP = 15).
+//
+// What the multipliers require of their operands is NOT "limbs < 2^L" but two things:
+//  (1) per column, the product units stay within FIT = 2^(64-2L): a product of two limbs below 2^L is one unit, and
+//      limbs below u*2^L and v*2^L make a product of u*v units.  mul<UNITS_AB> is told the units of one a*b product
+//      and splits a column when nab*UNITS_AB + nmp > FIT.  Every function of this header but add_lazy / sub_lazy4
+//      returns limbs below 2^L; the un-carried outputs of those two (below 2^32 = 8 * 2^29) are legal operands of
+//      the plain mul<1> as long as (1) still holds without a split, which ntt.hip relies on for L = 29, N = 9;
+//  (2) the result range: (sum of the operand-value products + m*p)/R < 2p, i.e. the products sum below R*p.
+// The host-only audit build below (KZG_AUDIT) checks exactly these two, per call.
 #pragma once
 #include <stdint.h>
 #include "curve_constants.h"
@@ -36,6 +44,84 @@
 #define KZG_HD inline __attribute__((always_inline))
 #endif
 
+// ---- audit build (host only) ----------------------------------------------------------------------
+// How to use: compile a HOST translation unit with -DKZG_AUDIT, run any code of field.h / ec.h, then read
+// kzg::audit::state(): `count` violated pre/postconditions, and the function, line and text of the first one.
+// state().lift = true makes every multiplier return the representative in [p, 2p) (the top of its documented
+// range), so the range tables of the callers are exercised at their stated bounds.  tests/shim/bounds_shim.cpp.
+#if defined(KZG_AUDIT) && !defined(__HIP_DEVICE_COMPILE__)
+#define KZG_AUDIT_ON 1
+namespace kzg {
+namespace audit {
+struct State {
+  unsigned long long count;
+  const char* fn;
+  const char* what;
+  int line;
+  bool lift;
+};
+inline State& state() {
+  static State s = {0, "", "", 0, false};
+  return s;
+}
+inline void fail(const char* fn, int line, const char* what) {
+  State& s = state();
+  if (s.count++ == 0) { s.fn = fn; s.line = line; s.what = what; }
+}
+// little multi-word integers for the range checks: 512 bits hold 13 limbs of 30 bits with 32-bit excess
+struct Big {
+  uint64_t w[8];
+};
+inline Big big_zero() { Big r; for (int i = 0; i < 8; ++i) r.w[i] = 0; return r; }
+inline void big_add_shifted(Big& r, uint64_t v, int bit) {      // r += v * 2^bit
+  const int k = bit >> 6, sh = bit & 63;
+  unsigned __int128 c = (unsigned __int128)v << sh;
+  for (int i = k; i < 8 && c; ++i) {
+    c += r.w[i];
+    r.w[i] = (uint64_t)c;
+    c >>= 64;
+  }
+}
+inline int big_cmp(const Big& a, const Big& b) {
+  for (int i = 7; i >= 0; --i)
+    if (a.w[i] != b.w[i]) return a.w[i] < b.w[i] ? -1 : 1;
+  return 0;
+}
+template <class F>
+inline Big value(const uint32_t* l) {                            // sum l[j] 2^(L j), limbs taken as unsigned 32-bit
+  Big r = big_zero();
+  for (int j = 0; j < F::N; ++j) big_add_shifted(r, l[j], F::L * j);
+  return r;
+}
+template <class F>
+inline Big kp(uint32_t k) {                                      // k * p
+  Big r = big_zero();
+  for (int j = 0; j < F::N; ++j) big_add_shifted(r, (uint64_t)k * F::P[j], F::L * j);
+  return r;
+}
+template <class F>
+inline Big value_plus_kp(const uint32_t* l, uint32_t k) {        // value(l) + k * p
+  Big r = value<F>(l);
+  for (int j = 0; j < F::N; ++j) big_add_shifted(r, (uint64_t)k * F::P[j], F::L * j);
+  return r;
+}
+template <class F>
+inline bool below_kp(const uint32_t* l, uint32_t k) { return big_cmp(value<F>(l), kp<F>(k)) < 0; }
+template <class F>
+inline bool at_most_kp(const uint32_t* l, uint32_t k) { return big_cmp(value<F>(l), kp<F>(k)) <= 0; }
+template <class F>
+inline bool normalised(const uint32_t* l) {                      // lower limbs below 2^L
+  for (int j = 0; j < F::N - 1; ++j)
+    if (l[j] >> F::L) return false;
+  return true;
+}
+}  // namespace audit
+}  // namespace kzg
+#define KZG_AUDIT_CHECK(cond, what) do { if (!(cond)) ::kzg::audit::fail(__func__, __LINE__, what); } while (0)
+#else
+#define KZG_AUDIT_CHECK(cond, what) ((void)0)
+#endif
+
 namespace kzg {
 
 // c + a*b: one v_mad_u64_u32.  On the device every partial sum is also shown to an EMPTY asm statement as an input:
@@ -45,6 +131,9 @@ namespace kzg {
 // draws no hazard nops.
 static KZG_HD uint64_t mad_wide(uint32_t a, uint32_t b, uint64_t c) {
   const uint64_t r = c + (uint64_t)a * b;
+#ifdef KZG_AUDIT_ON
+  if ((((unsigned __int128)a * b + c) >> 64) != 0) audit::fail(__func__, __LINE__, "column carries out of 64 bits");
+#endif
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(KZG_NO_CHAIN_PIN)
   asm volatile("" ::"v"(r));
 #endif
@@ -81,6 +170,28 @@ struct Field {
       w[j + 1] += c;
     }
   }
+
+#ifdef KZG_AUDIT_ON
+  // postcondition of every multiplier: weak-normal.  With audit::state().lift the representative in [p, 2p).
+  static void audit_product(E& r, const char* fn, int line) {
+    if (!audit::normalised<F>(r.l) || !audit::below_kp<F>(r.l, 2)) audit::fail(fn, line, "product not weak-normal (< 2p, limbs < 2^L)");
+    if (audit::state().lift && audit::below_kp<F>(r.l, 1)) {
+      uint32_t c = 0;
+      for (int j = 0; j < N; ++j) {
+        const uint32_t t = r.l[j] + F::P[j] + c;
+        if (j < N - 1) { r.l[j] = t & MASK; c = t >> L; } else { r.l[j] = t; }
+      }
+    }
+  }
+  // true (unwrapped) value of a limb formed as a + (k - b) + c must fit an unsigned 32-bit word
+  static bool audit_limb_ok(uint32_t a, uint32_t k, uint32_t b, uint32_t c) {
+    const int64_t t = (int64_t)a + (int64_t)k - (int64_t)b + (int64_t)c;
+    return t >= 0 && t < ((int64_t)1 << 32);
+  }
+#define KZG_AUDIT_PRODUCT(r) audit_product(r, __func__, __LINE__)
+#else
+#define KZG_AUDIT_PRODUCT(r) ((void)0)
+#endif
 
   static KZG_HD E zero() {
     E r;
@@ -124,6 +235,7 @@ struct Field {
   }
   // limbs -> canonical words.  Requires a canonical element (reduce() first).
   static KZG_HD void to_words(const E& a, uint32_t* w) {
+    KZG_AUDIT_CHECK(audit::normalised<F>(a.l) && audit::below_kp<F>(a.l, 1), "input not canonical");
 #pragma unroll
     for (int k = 0; k < NW; ++k) {
       // word k covers bits [32k, 32k+32)
@@ -183,6 +295,7 @@ struct Field {
       if (split) acc += upper;
     }
     r.l[N - 1] = (uint32_t)acc;
+    KZG_AUDIT_PRODUCT(r);
     return r;
   }
   // Montgomery square: off-diagonal products once, against the doubled operand.
@@ -219,6 +332,7 @@ struct Field {
       if (split) acc += upper;
     }
     r.l[N - 1] = (uint32_t)acc;
+    KZG_AUDIT_PRODUCT(r);
     return r;
   }
 
@@ -256,16 +370,17 @@ struct Field {
       if (split1 || split2) acc += upper;
     }
     r.l[N - 1] = (uint32_t)acc;
+    KZG_AUDIT_PRODUCT(r);
     return r;
   }
 
   // sum_{t<K} a[t]*b[t] with ONE Montgomery reduction: K*N^2 + N^2 + N multiply-adds instead of K*(2N^2 + N) --
   // the linear combinations of KZG.open (kzg.py:148-150) and of the prover's r(X).  Weak-normal (< 2p) in and out:
-  // (K*4p^2 + m*p)/R < 2p needs 4K*p <= R.  A column takes the a*b products of one term after the other and is cut
+  // (K*4p^2 + m*p)/R < 2p needs 4K*p <= R (the static_assert rounds K up to a power of two, 16 at the most).  A column takes the a*b products of one term after the other and is cut
   // (low L bits stay in the chain, the rest joins the outgoing carry) whenever the next group would pass its capacity.
   template <int K>
   static KZG_HD E dot(const E* a, const E* b) {
-    static_assert(K >= 1 && F::BITS + 2 + (K > 8 ? 4 : K > 4 ? 3 : K > 2 ? 2 : K > 1 ? 1 : 0) <= L * N, "dot needs 4K*p <= R");
+    static_assert(K >= 1 && K <= 16 && F::BITS + 2 + (K > 8 ? 4 : K > 4 ? 3 : K > 2 ? 2 : K > 1 ? 1 : 0) <= L * N, "dot needs 4K*p <= R");
     uint32_t m[N];
     E r;
     uint64_t acc = 0;
@@ -297,6 +412,7 @@ struct Field {
       acc += upper;
     }
     r.l[N - 1] = (uint32_t)acc;
+    KZG_AUDIT_PRODUCT(r);
     return r;
   }
 
@@ -356,15 +472,26 @@ struct Field {
   static KZG_HD E add_lazy(const E& a, const E& b) {
     E r;
 #pragma unroll
-    for (int j = 0; j < N; ++j) r.l[j] = a.l[j] + b.l[j];
+    for (int j = 0; j < N; ++j) {
+      KZG_AUDIT_CHECK((uint64_t)a.l[j] + b.l[j] < (1ull << 32), "a limb wraps 32 bits");
+      r.l[j] = a.l[j] + b.l[j];
+    }
     return r;
   }
   // a - b + 4p limb-wise, for a normalised b < 2p (e.g. a mul() output): every limb of the
   // redistributed constant P4R dominates the matching limb of b, so no limb goes negative.
+  // A normalised b between 2p and a + 4p is also taken (ntt.hip's first_step has one below 4p in pass 2): its lower
+  // limbs are still dominated, and the top limb, formed modulo 2^32, is right as soon as the result is carried
+  // (carry(), as put_out does) -- such a result must not go to a multiplier un-carried.
   static KZG_HD E sub_lazy4(const E& a, const E& b) {
+    KZG_AUDIT_CHECK(audit::big_cmp(audit::value<F>(b.l), audit::value_plus_kp<F>(a.l, 4)) <= 0, "a - b + 4p is negative");
     E r;
 #pragma unroll
-    for (int j = 0; j < N; ++j) r.l[j] = a.l[j] + (F::P4R[j] - b.l[j]);
+    for (int j = 0; j < N; ++j) {
+      KZG_AUDIT_CHECK(j == N - 1 || F::P4R[j] >= b.l[j], "a limb of 4p does not dominate the subtrahend's");
+      KZG_AUDIT_CHECK(j == N - 1 || (uint64_t)a.l[j] + (F::P4R[j] - b.l[j]) < (1ull << 32), "a limb wraps 32 bits");
+      r.l[j] = a.l[j] + (F::P4R[j] - b.l[j]);
+    }
     return r;
   }
   // carry propagation: limbs back below 2^L (the top limb absorbs the excess), value unchanged
@@ -373,6 +500,7 @@ struct Field {
     uint32_t c = 0;
 #pragma unroll
     for (int j = 0; j < N - 1; ++j) {
+      KZG_AUDIT_CHECK((uint64_t)a.l[j] + c < (1ull << 32), "a limb wraps 32 bits");
       const uint32_t t = a.l[j] + c;
       r.l[j] = t & MASK;
       c = t >> L;
@@ -400,14 +528,18 @@ struct Field {
   template <int K>
   static KZG_HD E sub_carry(const E& a, const E& b) {
     const uint32_t* kp = pkr<K>();
+    KZG_AUDIT_CHECK(audit::at_most_kp<F>(b.l, K), "subtrahend above K*p");
+    KZG_AUDIT_CHECK(audit::normalised<F>(a.l) && audit::normalised<F>(b.l), "operand limbs not normalised");
     E r;
     uint32_t c = 0;
 #pragma unroll
     for (int j = 0; j < N - 1; ++j) {
+      KZG_AUDIT_CHECK(audit_limb_ok(a.l[j], kp[j], b.l[j], c), "a limb of K*p does not dominate / wraps");
       const uint32_t t = a.l[j] + (kp[j] - b.l[j]) + c;
       r.l[j] = t & MASK;
       c = t >> L;
     }
+    KZG_AUDIT_CHECK(audit_limb_ok(a.l[N - 1], kp[N - 1], b.l[N - 1], c), "top limb negative or above 2^32");
     r.l[N - 1] = a.l[N - 1] + (kp[N - 1] - b.l[N - 1]) + c;
     return r;
   }
@@ -416,11 +548,17 @@ struct Field {
   template <int K>
   static KZG_HD E sub_carry_cneg(const E& a, bool neg, const E& b) {
     const uint32_t* kp = pkr<K>();
+    KZG_AUDIT_CHECK(audit::at_most_kp<F>(b.l, K), "subtrahend above K*p");
+    KZG_AUDIT_CHECK(audit::normalised<F>(a.l) && audit::normalised<F>(b.l), "operand limbs not normalised");
+    KZG_AUDIT_CHECK(audit::below_kp<F>(a.l, 2), "first operand not below 2p");
     E r;
     uint32_t c = 0;
 #pragma unroll
     for (int j = 0; j < N; ++j) {
+      KZG_AUDIT_CHECK(!neg || j == N - 1 || F::P2R[j] >= a.l[j], "a limb of 2p does not dominate the negated operand's");
       const uint32_t aj = neg ? F::P2R[j] - a.l[j] : a.l[j];
+      KZG_AUDIT_CHECK(audit_limb_ok(neg ? F::P2R[j] : a.l[j], kp[j], (neg ? a.l[j] : 0u) + b.l[j], c),
+                      j < N - 1 ? "a limb of K*p does not dominate / wraps" : "top limb negative or above 2^32");
       const uint32_t t = aj + (kp[j] - b.l[j]) + c;
       if (j < N - 1) { r.l[j] = t & MASK; c = t >> L; } else { r.l[j] = t; }
     }
@@ -432,10 +570,12 @@ struct Field {
     uint32_t c = 0;
 #pragma unroll
     for (int j = 0; j < N - 1; ++j) {
+      KZG_AUDIT_CHECK((uint64_t)a.l[j] + 2 * (uint64_t)b.l[j] + c < (1ull << 32), "a limb wraps 32 bits");
       const uint32_t t = a.l[j] + 2 * b.l[j] + c;
       r.l[j] = t & MASK;
       c = t >> L;
     }
+    KZG_AUDIT_CHECK((uint64_t)a.l[N - 1] + 2 * (uint64_t)b.l[N - 1] + c < (1ull << 32), "the top limb wraps 32 bits");
     r.l[N - 1] = a.l[N - 1] + 2 * b.l[N - 1] + c;
     return r;
   }
@@ -445,6 +585,7 @@ struct Field {
 
   // [0, 2p) -> [0, p)
   static KZG_HD E reduce(const E& a) {
+    KZG_AUDIT_CHECK(audit::below_kp<F>(a.l, 2), "input not below 2p");
     E t;
     int32_t ct = 0;
 #pragma unroll
@@ -472,6 +613,7 @@ struct Field {
     constexpr uint64_t PTOP1 = (uint64_t)F::P[N - 1] + 1;
     constexpr uint64_t M = (1ull << 52) / PTOP1;
     static_assert(PTOP1 > (1ull << 20), "top limb of p too small for the 52-bit reciprocal");
+    KZG_AUDIT_CHECK(audit::normalised<F>(a.l) && (a.l[N - 1] >> L) == 0, "limbs not normalised");
     const uint32_t q = (uint32_t)(((uint64_t)a.l[N - 1] * M) >> 52);
     E r;
     int64_t c = 0;
@@ -481,7 +623,9 @@ struct Field {
       r.l[j] = (uint32_t)t & MASK;
       c = t >> L;
     }
+    KZG_AUDIT_CHECK((int64_t)a.l[N - 1] - (int64_t)((uint64_t)q * F::P[N - 1]) + c >= 0, "quotient estimate above floor(x / p)");
     r.l[N - 1] = (uint32_t)((int64_t)a.l[N - 1] - (int64_t)((uint64_t)q * F::P[N - 1]) + c);
+    KZG_AUDIT_CHECK(audit::below_kp<F>(r.l, 2), "quotient estimate leaves 2p or more");
     return reduce(r);
   }
   static KZG_HD bool is_zero(const E& a) {
@@ -495,6 +639,7 @@ struct Field {
   // zero test without the reduction: a weak-normal value is 0 mod p iff it is the integer 0 or
   // the integer p, and normalised limbs represent an integer uniquely
   static KZG_HD bool is_zero_weak(const E& a) {
+    KZG_AUDIT_CHECK(audit::normalised<F>(a.l) && audit::below_kp<F>(a.l, 2), "input not weak-normal");
     uint32_t z = 0, q = 0;
 #pragma unroll
     for (int j = 0; j < N; ++j) { z |= a.l[j]; q |= a.l[j] ^ F::P[j]; }
@@ -513,6 +658,7 @@ struct Field {
   }
   // flag ? p - a : a  for CANONICAL a (table coordinates): result weak-normal in [0, p]
   static KZG_HD E cneg_canonical(const E& a, bool flag) {
+    KZG_AUDIT_CHECK(audit::normalised<F>(a.l) && audit::below_kp<F>(a.l, 1), "input not canonical");
     E r;
     int32_t c = 0;
 #pragma unroll

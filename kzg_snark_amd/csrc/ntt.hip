@@ -136,6 +136,10 @@ __device__ __forceinline__ void radix4_step(uint32_t* lds, const Tw3<F>& tw, uin
   const Fe<F> x0 = lds_get<F>(lds, a0_), x2 = lds_get<F>(lds, a2_);
   const Fe<F> t1 = Fd::mul(lds_get<F>(lds, a1_), tw.a), t3 = Fd::mul(lds_get<F>(lds, a3_), tw.a);
   const Fe<F> b0 = Fd::add_lazy(x0, t1), b1 = Fd::sub_lazy4(x0, t1);                               // level s
+  // The operands of these two products are NOT carried: x2 is normalised (put_out) and t3 a product, so the limbs of
+  // x2 + t3 are below 2 * 2^29 and those of x2 + (P4R - t3) below 3 * 2^29 (a limb of P4R is below 2^30).  A column of
+  // mul<1> then holds at most 9 * 3 + 9 = 36 of the FIT = 64 product units of L = 29 (field.h, header): no split needed.
+  // The values stay below 49p + 4p, far below R = 2^261.  tests/test_field_bounds_host.py audits both claims.
   const Fe<F> u2 = Fd::mul(Fd::add_lazy(x2, t3), tw.b), u3 = Fd::mul(Fd::sub_lazy4(x2, t3), tw.c);
   put_out<F>(lds, a0_, Fd::add_lazy(b0, u2));                                                // level s+1
   put_out<F>(lds, a2_, Fd::sub_lazy4(b0, u2));
