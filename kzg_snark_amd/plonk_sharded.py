@@ -28,8 +28,10 @@ Per round (reference lines in brackets):
 All ranks see the same points and evaluations after every exchange, hence the same challenges and the same proof.
 
 The algebra is a BACKEND (GpuShardBackend below: the engine through DeviceAlgebra; tests inject the oracle on CPU so that
-the choreography runs under gloo without a GPU).  G must be a power of two with n/G >= 8; other world sizes keep
-ProofSharding's dealt MSMs (make_prover)."""
+the choreography runs under gloo without a GPU).  G must be a power of two that divides n, with n/G >= 8 and
+2^ceil(log2(4n)/2) >= 4G (can_shard_vectors: round 2's shift by four rows must stay within one rank's rows of the 4n
+matrix; 8 ranks need n >= 128, 16 ranks n >= 512) -- _prove refuses anything else before its first collective; other
+world sizes keep ProofSharding's dealt MSMs (make_prover)."""
 import numpy as np
 import torch
 
@@ -41,6 +43,29 @@ from .sharding import (FR_BYTES, POINT_BYTES, ShardedTransforms, all_gather_byte
 from .transcript import Transcript
 
 TAIL = 6                      # coefficients above X^n a polynomial of the proof can carry (t_hi: n + 6 in all)
+
+
+def can_shard_vectors(n, world):
+    """Whether an n-gate proof can be vector-sharded over `world` ranks:
+      * world a power of two that divides n (the radix-2 transforms, contiguous ranges);
+      * n / world >= 8 (a rank's range holds the blinding terms and the tail that the sharded opening carries);
+      * N1 >= 4 world, N1 = 2^ceil(log2(4n) / 2) the row count of the 4n-point four-step matrix: z(g X) on the coset
+        is a shift by four rows of the transposed layout, which must lie within the R1 = N1 / world rows of the next
+        rank (ShardedTransforms.T_shift).  Up to four ranks the second condition implies it; eight ranks need
+        n >= 128 and sixteen n >= 512."""
+    n, world = int(n), int(world)
+    if world < 1 or world & (world - 1) or n < 1 or n % world or n // world < 8:
+        return False
+    log4 = (4 * n - 1).bit_length()                      # ceil(log2(4n))
+    return (1 << ((log4 + 1) // 2)) >= 4 * world
+
+
+def min_sharded_gates(world):
+    """the smallest power-of-two gate count that can_shard_vectors accepts for a power-of-two `world`"""
+    n = 8 * world
+    while not can_shard_vectors(n, world):
+        n *= 2
+    return n
 
 
 class SPoly:
@@ -381,8 +406,12 @@ class ShardedProver:
         r, G, g_rank = kzg.curve_order, self.world, self.rank
         sub = ipk["subgroups"]
         n, g, k1, k2 = sub["n"], sub["g"], int(sub["k1"]), int(sub["k2"])
-        if G & (G - 1) or n % G or n // G < 8:
-            raise ValueError("the vector-sharded prover needs a power-of-two world size with n / G >= 8")
+        if not can_shard_vectors(n, G):                 # before any collective or commit: every rank raises alike
+            if G & (G - 1):
+                raise ValueError(f"the vector-sharded prover needs a power-of-two world size, not {G}")
+            raise ValueError(f"the vector-sharded prover cannot split n = {n} gates over {G} ranks: it needs G | n, "
+                             f"n / G >= 8 and 2^ceil(log2(4n) / 2) >= 4 G; the smallest n for {G} ranks is "
+                             f"{min_sharded_gates(G)}")
         m = n // G
         lo = g_rank * m
         log_n = n.bit_length() - 1

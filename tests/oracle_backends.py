@@ -25,7 +25,9 @@ def put(t, vals):
 
 
 class OracleNttOps:
-    """Local halves of the distributed NTT on Python ints (the oracle's fft_ff)."""
+    """Local halves of the distributed NTT on Python ints (the oracle's fft_ff), pass by pass what
+    include/kzg_mi355x.h states for the device's: the n^-1 of an inverse transform rides on the twist (columns,
+    rows_twist); the passes that follow a twist (rows_exchange, columns_plain) are bare transforms."""
 
     def __init__(self, log_n, w, r, inverse):
         self.k1 = (log_n + 1) // 2
@@ -46,7 +48,7 @@ class OracleNttOps:
         for c in range(W):
             col = O.fft_ff([vals[t * W + c] for t in range(N1)], root, self.r)
             for t in range(N1):
-                out[t * W + c] = col[t] * pow(self.w, t * (col_base + c), self.r) % self.r
+                out[t * W + c] = col[t] * pow(self.w, t * (col_base + c), self.r) % self.r * self.scale % self.r
         put(M, out)
 
     def rows_exchange(self, recv, out, world, blocked):
@@ -60,7 +62,7 @@ class OracleNttOps:
         res = [0] * (R1 * N2)
         for t in range(R1):
             row = [vals[(v // W) * R1 * W + t * W + (v % W)] for v in range(N2)]
-            tr = [v * self.scale % self.r for v in O.fft_ff(row, root, self.r)]
+            tr = O.fft_ff(row, root, self.r)
             for b in range(N2):
                 if blocked:
                     res[(b // W) * R1 * W + t * W + (b % W)] = tr[b]

@@ -144,13 +144,16 @@ def test_facade_signatures(native):
         fft_ff_interpolation(vals, F.root_of_unity(8), F)  # fft_ff.py:78
 
 
-@pytest.mark.parametrize("curve,log_n,world", [("bls12_381", 14, 2), ("bls12_381", 16, 4), ("bn254", 13, 2)])
+@pytest.mark.parametrize("curve,log_n,world", [("bls12_381", 14, 2), ("bls12_381", 16, 4), ("bn254", 13, 2),
+                                               ("bls12_381", 13, 8), ("bn254", 14, 8)])
 def test_distributed_ntt_rehearsal_on_one_gpu(native, curve, log_n, world):
     """kzg_ntt_columns_device / kzg_ntt_rows_exchange_device under kzg_snark_amd.sharding.DistributedNTT:
     `world` Python threads play the ranks (one engine context each, all on cuda:0) and exchange
     through an in-process all-to-all.  The result must equal the single-GPU transform and, for a
     slice, the oracle -- forward, inverse and with a w that is not a primitive root; in natural
-    order (three exchanges) and in the transposed layout (two).  The coefficients of the inverse
+    order (three exchanges) and in the transposed layout (two).  Eight ranks -- the machine's world size -- at 2^13
+    (odd split) and 2^14 leave a rank 8 or 16 columns and rows: tiles of 1024 / 2048 elements where the lines per tile
+    are bounded by the rank's share, and exchange blocks of 8 / 16 elements.  The coefficients of the inverse
     transform are then committed where they lie, against key shards generated in the same order
     (kzg_srs_generate_strided): the partial points must add up to p(tau) G1."""
     import threading
@@ -429,8 +432,9 @@ def test_transform_beside_a_commit_in_flight(native, curve):
 def test_transposed_to_natural_passes(native, curve):
     """kzg_ntt_rows_twist_device + kzg_ntt_columns_plain_device: the four-step taken the other way round -- input in
     the transposed layout (row rho holds the elements b N1 + rho), output in natural order -- equals the whole
-    transform (fft_ff.py:15-37 / :39-58) for a primitive root, forward and inverse, 2^13 (odd split) and 2^16; on a
-    row range with its base; a w that is not a primitive root is refused."""
+    transform (fft_ff.py:15-37 / :39-58) for a primitive root, forward and inverse, 2^13 (odd split) and 2^16; on two
+    row ranges with their bases and on eight, as two and eight ranks would run it (at 2^13 eight ranks hold 16 rows and
+    8 columns each); a w that is not a primitive root is refused."""
     import torch
     cv = O.curve(curve)
     ctx = native.get_context(curve)
@@ -455,6 +459,114 @@ def test_transposed_to_natural_passes(native, curve):
             ctx.ntt_columns_plain_device(M.data_ptr(), log_n, ww, inverse, N2)
             ctx.synchronize()
             assert np.array_equal(M.cpu().numpy().view(np.uint64).reshape(n, 4), want), (log_n, inverse)
+            # the same as eight ranks would run it: eight row ranges of N1 / 8 rows, each with its base, and the
+            # column pass over each rank's N2 / 8 columns of its own [N1][W] matrix
+            T8 = x.view(N2, N1, 4).permute(1, 0, 2).contiguous()
+            torch.cuda.synchronize()
+            R1, W = N1 // 8, N2 // 8
+            for g in range(8):
+                ctx.ntt_rows_twist_device(T8.data_ptr() + g * R1 * N2 * 32, log_n, ww, inverse, R1, g * R1)
+            ctx.synchronize()
+            cols = [T8.view(N1, 8, W, 4)[:, g].contiguous() for g in range(8)]           # rank g's columns, whole
+            torch.cuda.synchronize()
+            for Mg in cols:
+                ctx.ntt_columns_plain_device(Mg.data_ptr(), log_n, ww, inverse, W)
+            ctx.synchronize()
+            got8 = torch.stack(cols, dim=1).cpu().numpy().view(np.uint64).reshape(n, 4)
+            assert np.array_equal(got8, want), (log_n, inverse, "eight ranges")
     with pytest.raises(native.NativeError):
         t = torch.zeros((1 << 13, 4), dtype=torch.int64, device="cuda:0")
         ctx.ntt_rows_twist_device(t.data_ptr(), 13, native.int_to_words(12345), False, 128, 0)
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_partial_passes_match_the_restatement(native, curve):
+    """The four local halves of the distributed transform -- kzg_ntt_columns_device, _rows_exchange_device,
+    _rows_twist_device, _columns_plain_device (ntt_partial_t in csrc/ntt.hip) -- called on their own at the shapes one
+    of EIGHT ranks hands them at the smallest sizes (2^13: odd split, N1 = 128, N2 = 64; 2^14: N1 = N2 = 128), against
+    tests/oracle_backends.OracleNttOps on a host copy of the same tensor: Python ints, the stated meaning of each pass.
+    The passes that end a transform (rows_exchange, columns_plain) leave canonical words: equality of the words.  The
+    passes that end with the twist multiplication (columns, rows_twist) hand their partner weakly normalised values
+    (ntt.hip: below 2r is enough between the passes; on an MI355X a few hundred of this test's values lie at or above
+    r): there every word must be below 2r and its residue equal to the restatement's.
+
+    Lines per call: 8 and 16 (a rank's share of 2^13 / 2^14 over eight ranks) and 1 and 2 (the least the argument check
+    admits: a tile of 64 or 128 elements on 64 threads) -- in all of them the lines per tile are bounded by the count
+    and not by the 4096-element tile; the first line is global line 0 or the LAST rank's (7 x count where that fits,
+    else the top of the range), which is what the twist is indexed by.  The rows-exchange pass reads blocks of N2 / 8
+    elements (eight ranks) and of one element (world = N2), and writes blocked or plain.  Forward and inverse; the
+    column and rows-exchange passes also with a w that is no root of unity (they hold for any w; rows_twist refuses
+    one, see test_transposed_to_natural_passes)."""
+    import sys
+    import os
+    import torch
+    here = os.path.dirname(os.path.abspath(__file__))
+    if here not in sys.path:
+        sys.path.insert(0, here)
+    import oracle_backends as OB
+    cv = O.curve(curve)
+    ctx = native.get_context(curve)
+    rs = np.random.RandomState(58)
+
+    def fresh(shape):
+        """device tensor of edge-planted values over [0, r) and its host copy"""
+        m = int(np.prod(shape))
+        raw = _plant_edge_values(_uniform_below_r(rs, m, cv.r), cv.r, native)
+        host = torch.from_numpy(raw.view(np.int64)).view(*shape, 4)
+        dev = host.to("cuda:0")
+        torch.cuda.synchronize()             # torch's stream wrote it; the context runs on a stream of its own
+        return dev, host.clone()
+
+    def same(dev, host, what, weak=False):
+        """weak: a pass that ends with the twist multiplication leaves its values weakly normalised -- the right
+        residue, below 2r, not necessarily below r (ntt.hip: "weak-normal is enough between the passes"; the header
+        calls the halves meaningful only as a pair); the passes that end a transform leave canonical words"""
+        ctx.synchronize()
+        got = dev.cpu()
+        if weak and not torch.equal(got, host):
+            g = native.limbs_to_ints(got.numpy().view(np.uint64).reshape(-1, 4))
+            h = native.limbs_to_ints(host.numpy().view(np.uint64).reshape(-1, 4))
+            assert all(v < 2 * cv.r for v in g), what
+            assert [v % cv.r for v in g] == h, what
+        else:
+            assert torch.equal(got, host), what
+
+    for log_n in (13, 14):
+        n = 1 << log_n
+        k1 = (log_n + 1) // 2
+        N1, N2 = 1 << k1, 1 << (log_n - k1)
+        root = cv.root_of_unity(n)
+        for w, inverse in ((root, False), (root, True), (0x1234567 % cv.r, False)):
+            ww = native.int_to_words(w)
+            spec = OB.OracleNttOps(log_n, w, cv.r, inverse)
+            primitive = w == root
+            for count in (1, 2, 8, 16):
+                for base in sorted({0, min(7 * count, N2 - count)}):
+                    # columns + twist: [N1][count], first column = global column `base`
+                    dev, host = fresh((N1, count))
+                    ctx.ntt_columns_device(dev.data_ptr(), log_n, ww, inverse, count, base)
+                    spec.columns(host, base)
+                    same(dev, host, ("columns", log_n, inverse, primitive, count, base), weak=True)
+                if primitive:
+                    # columns without twist: [N1][count]
+                    dev, host = fresh((N1, count))
+                    ctx.ntt_columns_plain_device(dev.data_ptr(), log_n, ww, inverse, count)
+                    spec.columns_plain(host)
+                    same(dev, host, ("columns_plain", log_n, inverse, count))
+                    for base in sorted({0, min(7 * count, N1 - count)}):
+                        # rows + twist by (global row) x (output index): [count][N2], first row = global row `base`
+                        dev, host = fresh((count, N2))
+                        ctx.ntt_rows_twist_device(dev.data_ptr(), log_n, ww, inverse, count, base)
+                        spec.rows_twist(host, base)
+                        same(dev, host, ("rows_twist", log_n, inverse, count, base), weak=True)
+                for world in (8, N2):
+                    for blocked in (True, False):
+                        # rows, exchange form: [world][count][N2 / world] in, the same blocked shape or [count][N2] out
+                        dev, host = fresh((world, count, N2 // world))
+                        out = torch.full_like(dev, -1)
+                        want = torch.empty_like(host)
+                        torch.cuda.synchronize()
+                        ctx.ntt_rows_exchange_device(dev.data_ptr(), out.data_ptr(), log_n, ww, inverse, count, world,
+                                                     blocked)
+                        spec.rows_exchange(host, want, world, blocked)
+                        same(out, want, ("rows_exchange", log_n, inverse, primitive, count, world, blocked))

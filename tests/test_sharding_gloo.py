@@ -1,6 +1,8 @@
-"""World-size-2 gloo tests (CPU) of the multi-GPU exchange logic (kzg_snark_amd/sharding.py).
-The per-rank commit is the oracle's CPU commit standing in for the GPU MSM -- the exchange
-(round-robin ownership, all-gather, host-side point addition) is what is under test."""
+"""gloo tests (CPU) of the multi-GPU exchange logic (kzg_snark_amd/sharding.py, plonk_sharded.py) at world sizes
+2, 3, 4 and 8 -- eight being the machine's.  The per-rank commit, transform and opening are the oracle's (Python ints,
+tests/oracle_backends.py) standing in for the engine: the exchanges (round-robin ownership, all-gathers, the
+all-to-alls of the four-step transforms, carries, the quotient's re-partition) and the index arithmetic that depends on
+the world size are what is under test."""
 import os
 import random
 import socket
@@ -144,7 +146,7 @@ def _oracle_backends():
     return oracle_backends
 
 
-def _ntt_worker(rank, world, port, q):
+def _ntt_worker(rank, world, port, q, log_n=7):
     import numpy as np
     import torch
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -153,7 +155,6 @@ def _ntt_worker(rank, world, port, q):
     try:
         from kzg_snark_amd.sharding import DistributedNTT
         cv = O.BLS12_381
-        log_n = 7
         n = 1 << log_n
         rng = random.Random(99)
         x = [rng.randrange(cv.r) for _ in range(n)]
@@ -184,6 +185,14 @@ def test_two_rank_distributed_ntt():
     oracle as the local transform."""
     res = _run_ranks(_ntt_worker, 2, 180)
     assert sorted(res) == [(0, "ok"), (1, "ok")], res
+
+
+@pytest.mark.parametrize("log_n", [6, 7])
+def test_eight_rank_distributed_ntt(log_n):
+    """The same at the machine's world size.  2^6 over eight ranks is the degenerate split (N1 = N2 = 8: every rank
+    holds ONE row and ONE column, R1 = W = 1), 2^7 the odd one (N1 = 16, N2 = 8: two rows, one column)."""
+    res = _run_ranks(_ntt_worker, 8, 180, (log_n,))
+    assert sorted(res) == [(r, "ok") for r in range(8)], res
 
 
 def test_two_rank_exchange():
@@ -307,7 +316,15 @@ def _proof_key(proof):
             sorted((k, int(v)) for k, v in proof["evaluations"].items()))
 
 
-def _sharded_worker(rank, world, port, q, case):
+def _digests_agree(proof):
+    """every rank's proof -- commitments, openings AND evaluations -- through one all-gather of a SHA-256"""
+    import hashlib
+    from kzg_snark_amd.sharding import all_gather_bytes
+    digests = all_gather_bytes(hashlib.sha256(repr(_proof_key(proof)).encode()).digest())
+    assert len(set(digests)) == 1, "ranks ended with different proofs"
+
+
+def _sharded_worker(rank, world, port, q, case, gates=64):
     """One rank of a PLONK proof whose VECTORS are split over `world` ranks (plonk_sharded.ShardedProver), the oracle
     standing in for the engine (tests/oracle_backends.py): distributed INTTs and coset NTTs through the all-to-alls,
     accumulator carries, quotient re-partition, range-sharded commitments and openings."""
@@ -328,17 +345,33 @@ def _sharded_worker(rank, world, port, q, case):
             blinders = [int(v, 16) for v in gp["blinders"]]
         else:
             curve, tau = "bn254", 0x7a75
-            circuit = plonk.synthetic_circuit(64, GF(O.curve(curve).r), seed=3)
+            circuit = plonk.synthetic_circuit(gates, GF(O.curve(curve).r), seed=3)
             blinders = list(range(101, 112))
+        mine = blinders if rank == 0 else [b + 1 + rank for b in blinders]       # only rank 0's count
+        if world == 8:
+            # 64 gates pass the guard this prover used to have (n / G >= 8) and are one size too small for eight ranks:
+            # refused by every rank BEFORE the first exchange, so the group is as it was -- the proof below runs
+            # through it
+            assert gates == 128
+            small = plonk.synthetic_circuit(gates // 2, GF(O.curve(curve).r), seed=3)
+            idx0 = plonk.Indexer(curve)
+            idx0.kzg = TP.oracle_backed(curve)
+            ipk0, _ = idx0.preprocess(*small[:6], tau=tau)
+            sp0 = plonk_sharded.ShardedProver(curve, OB.OracleShardBackend(curve))
+            with pytest.raises(ValueError, match=rf"smallest n for {world} ranks is {gates}\b"):
+                sp0.prove(_sharded_ipk(ipk0, OB), small[6], small[7], blinders=mine)
+            assert sp0.exchanges == 0 and sp0.tf.exchanges == 0
         idx = plonk.Indexer(curve)
         idx.kzg = TP.oracle_backed(curve)
         ipk, ivk = idx.preprocess(*circuit[:6], tau=tau)
         sp = plonk_sharded.ShardedProver(curve, OB.OracleShardBackend(curve))
-        mine = blinders if rank == 0 else [b + 1 + rank for b in blinders]       # only rank 0's count
         proof = sp.prove(_sharded_ipk(ipk, OB), circuit[6], circuit[7], blinders=mine)
+        _digests_agree(proof)
         if case == "frozen":
             _check_frozen_proof(proof, gp)
-        else:           # the unsharded host prover with the same blinders: the same proof, and the verifier accepts it
+        elif world < 8 or rank == 0:
+            # the unsharded host prover with the same blinders: the same proof, and the verifier accepts it (at eight
+            # ranks on rank 0 alone: the digest above ties the other seven to it)
             ref = plonk.Prover(curve)
             ref.kzg = TP.oracle_backed(curve)
             want = ref.prove(ipk, circuit[6], circuit[7], blinders=blinders)
@@ -348,20 +381,153 @@ def _sharded_worker(rank, world, port, q, case):
                 assert ver.verify(ivk, circuit[6], proof)
         assert sp.tf.exchanges > 0 and sp.exchanges > 0
         q.put((rank, "ok"))
-    except Exception as e:  # noqa: BLE001
+    except BaseException as e:  # noqa: BLE001  (pytest.raises fails with a BaseException)
         import traceback
         q.put((rank, repr(e) + traceback.format_exc()))
     finally:
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,case", [(2, "frozen"), (2, "synthetic"), (4, "synthetic")])
-def test_vector_sharded_proof_over_ranks(world, case):
+@pytest.mark.parametrize("world,case,gates", [
+    pytest.param(2, "frozen", 16, id="2-frozen"), pytest.param(2, "synthetic", 64, id="2-synthetic"),
+    pytest.param(4, "synthetic", 64, id="4-synthetic"), pytest.param(8, "synthetic", 128, id="8-synthetic-128")])
+def test_vector_sharded_proof_over_ranks(world, case, gates):
     """BASELINE config 5 with the vector work split over the ranks (plonk/prover.py:83-85, 243-264, 297-316 on range /
     transposed shards; commitments and openings against key shards): two ranks reproduce
-    tests/golden/plonk_proof_n16.json bit for bit (n = 16 leaves a rank the minimum of 8 rows); two and four ranks
-    reproduce the unsharded host prover's proof of a 64-gate circuit, which the verifier accepts."""
-    res = _run_ranks(_sharded_worker, world, 600, (case,))
+    tests/golden/plonk_proof_n16.json bit for bit (n = 16 leaves a rank the minimum of 8 rows); two, four and eight
+    ranks reproduce the unsharded host prover's proof of a 64-gate (eight ranks: 128-gate) circuit, which the verifier
+    accepts, and every rank ends with the same proof.  128 gates is the least eight ranks can split
+    (plonk_sharded.can_shard_vectors): the 64-gate circuit is refused first, with no exchange issued, and the proof
+    then runs through the same process group.  At eight ranks the quotient's re-partition takes its one-slot form
+    (plonk_sharded._split_quotient: cap = 1, the tail on rank 6, ranks 6 and 7 sending nothing)."""
+    res = _run_ranks(_sharded_worker, world, 600, (case, gates))
+    assert sorted(res) == [(r, "ok") for r in range(world)], res
+
+
+def test_which_sizes_can_be_vector_sharded():
+    """plonk_sharded.can_shard_vectors against what each transform of the prover asks for, stated directly: a rank's
+    range of at least 8 coefficients; ShardedTransforms.t_index: G | N1; T_shift by the four rows of z(g X):
+    4 <= R1 = N1 / G -- N1 the row count of the 4n-point four-step matrix, here the least power of two whose square
+    reaches 4n.  min_sharded_gates is the least accepted power of two."""
+    from kzg_snark_amd import plonk_sharded
+    table = {}
+    for log_n in range(3, 13):
+        n = 1 << log_n
+        N1 = 1
+        while N1 * N1 < 4 * n:
+            N1 *= 2
+        for G in (1, 2, 4, 8, 16):
+            need = n % G == 0 and n // G >= 8 and N1 % G == 0 and 0 < 4 <= N1 // G
+            table[n, G] = need
+            assert plonk_sharded.can_shard_vectors(n, G) == need, (n, G)
+    for G in (1, 2, 4, 8, 16):
+        least = min(n for (n, g), ok in table.items() if g == G and ok)
+        assert plonk_sharded.min_sharded_gates(G) == least, G
+        assert all(table[n, G] for n in (1 << k for k in range(3, 13)) if n >= least), G     # monotone above it
+    assert [plonk_sharded.min_sharded_gates(G) for G in (1, 2, 4, 8, 16)] == [8, 16, 32, 128, 512]
+    assert table[64, 8] is False and table[256, 16] is False          # the old guard (n / G >= 8 alone) let these in
+    for G in (0, 3, 6, 12):
+        assert not plonk_sharded.can_shard_vectors(1 << 12, G), G
+    assert not plonk_sharded.can_shard_vectors(24 * 8 + 4, 8)          # G does not divide n
+
+
+def _transforms_worker(rank, world, port, q):
+    """sharding.ShardedTransforms, each method on its own against the oracle's whole transform (Python ints)."""
+    import torch
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=_PG_TIMEOUT)
+    try:
+        OB = _oracle_backends()
+        from kzg_snark_amd.sharding import ShardedTransforms, transposed_index
+        cv = O.BLS12_381
+        r, G, g = cv.r, world, rank
+        be = OB.OracleShardBackend("bls12_381")
+        tf = ShardedTransforms(be.ntt_ops, be.full_ntt, min_log=2)
+        rng = random.Random(4242)                         # the same vectors on every rank
+
+        def vector(n):
+            v = [rng.randrange(r) for _ in range(n)]
+            v[0], v[-1] = r - 1, 0
+            return v
+
+        def did(count, what):
+            """the transform just run issued `count` exchanges"""
+            nonlocal seen
+            assert tf.exchanges - seen == count, (what, tf.exchanges - seen, count)
+            seen = tf.exchanges
+
+        seen = 0
+        padded_branches = set()
+        for log_n in (6, 7, 8, 9):
+            n = 1 << log_n
+            m = n // G
+            lo, hi = g * m, (g + 1) * m
+            w = cv.root_of_unity(n)
+            # natural_batch: three vectors through ONE set of all-to-alls (the stacked exchange)
+            xs = [vector(n) for _ in range(3)]
+            for inverse in (False, True):
+                got = tf.natural_batch([OB.tensor_of(x[lo:hi]) for x in xs], log_n, w, inverse)
+                did(3, "natural_batch")
+                for x, t in zip(xs, got):
+                    want = O.ifft_ff(x, w, r) if inverse else O.fft_ff(x, w, r)
+                    assert OB.ints_of(t) == want[lo:hi], ("natural_batch", log_n, inverse)
+            # T_to_natural: this rank's shard of the transposed layout in, its contiguous range out
+            x = xs[0]
+            xT = OB.tensor_of([x[transposed_index(log_n, G, g, i)] for i in range(m)])
+            for inverse in (False, True):
+                keep = xT.clone()
+                got = tf.T_to_natural(xT, log_n, w, inverse)
+                did(2, "T_to_natural")
+                want = O.ifft_ff(x, w, r) if inverse else O.fft_ff(x, w, r)
+                assert OB.ints_of(got) == want[lo:hi], ("T_to_natural", log_n, inverse)
+                assert torch.equal(xT, keep), "T_to_natural must leave its input alone"
+            # padded_to_T_batch: n coefficients of a zero-padded 4n vector -> its transform in the transposed layout
+            log_big = log_n + 2
+            big = 4 * n
+            w_big = cv.root_of_unity(big)
+            kb = (log_big + 1) // 2
+            N1b, N2b = 1 << kb, 1 << (log_big - kb)
+            R1b = N1b // G
+            got = tf.padded_to_T_batch([OB.tensor_of(x[lo:hi]) for x in xs[:2]], log_n, log_big, w_big)
+            two_exchanges = m % N2b == 0            # whole rows of the big matrix per rank; else gather and transform
+            did(2 if two_exchanges else 1, ("padded_to_T_batch", log_n))
+            padded_branches.add(two_exchanges)
+            for x, t in zip(xs[:2], got):
+                want = O.fft_ff(x + [0] * (big - n), w_big, r)
+                assert OB.ints_of(t) == [want[transposed_index(log_big, G, g, i)] for i in range(big // G)], \
+                    ("padded_to_T_batch", log_n)
+            # T_shift: y[i] = full[(i + s) mod 4n] in the transposed layout; the last rank's rows wrap into the next b
+            full = vector(big)
+            idx = [transposed_index(log_big, G, g, i) for i in range(big // G)]
+            assert idx == [int(v) for v in tf.t_index(log_big, "cpu")]
+            fT = OB.tensor_of([full[i] for i in idx])
+            for s in sorted({1, 4, R1b} - ({4} if R1b < 4 else set())):
+                got = tf.T_shift(fT, log_big, s)
+                did(1, "T_shift")
+                assert OB.ints_of(got) == [full[(i + s) % big] for i in idx], ("T_shift", log_n, s)
+            for s in (0, R1b + 1):
+                with pytest.raises(ValueError):
+                    tf.T_shift(fT, log_big, s)
+                did(0, "T_shift refusing")
+        want_branches = {True, False} if G == 8 else {True}         # 2^6 over eight ranks: m = 8 < N2' = 16
+        assert padded_branches == want_branches, padded_branches
+        q.put((rank, "ok"))
+    except BaseException as e:  # noqa: BLE001
+        import traceback
+        q.put((rank, repr(e) + traceback.format_exc()))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 4, 8])
+def test_sharded_transforms_over_ranks(world):
+    """The four transforms of the vector-sharded prover called directly, 2^6 .. 2^9 elements over 2, 4 and 8 ranks,
+    every output element against the oracle's fft_ff / ifft_ff of the whole vector: natural_batch (three vectors, one
+    set of all-to-alls), T_to_natural, padded_to_T_batch into a 4n-point domain -- the two-exchange path, and at eight
+    ranks and 2^6 the gather fallback, told apart by the exchange count -- and T_shift by 1, 4 and a rank's whole row
+    count, whose last rank wraps around; shifts of 0 and of more than a rank's rows are refused."""
+    res = _run_ranks(_transforms_worker, world, 300)
     assert sorted(res) == [(r, "ok") for r in range(world)], res
 
 
@@ -387,9 +553,10 @@ def test_plonk_proof_dealt_over_ranks_is_the_frozen_proof(world):
     _run_plonk_ranks(world, device=False, timeout=300)
 
 
-def _sharded_gpu_worker(rank, world, port, q):
+def _sharded_gpu_worker(rank, world, port, q, parts=("frozen", 12, 13)):
     """The vector-sharded prover on the engine (plonk_sharded.GpuShardBackend), `world` ranks sharing the test box's
-    GPU over gloo (tensors make the round trip through the host in the exchanges)."""
+    GPU over gloo (tensors make the round trip through the host in the exchanges).  parts: "frozen" = the 16-gate
+    instance, 12 / 13 = the synthetic proofs of 2^12 / 2^13 gates."""
     import hashlib
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -403,24 +570,25 @@ def _sharded_gpu_worker(rank, world, port, q):
         from kzg_snark_amd import plonk, plonk_device, plonk_sharded
         from kzg_snark_amd.field import GF
         from kzg_snark_amd.sharding import ProofSharding, all_gather_bytes
-        # 1. the frozen 16-gate proof (every transform below the distributed sizes: gather, transform, keep a share)
-        gp = _golden("plonk_proof_n16.json")
-        circuit = TP.fixture_instance()
-        curve, tau = gp["curve"], int(gp["tau"], 16)
-        blinders = [int(v, 16) for v in gp["blinders"]]
-        idx = plonk_device.DeviceIndexer(curve)
-        ipk, ivk = idx.preprocess(*circuit[:6], tau=tau)
-        prv = plonk_sharded.make_prover(curve, idx.alg, ProofSharding(shard_vectors=True))
-        assert type(prv).__name__ == "ShardedProver"
-        mine = blinders if rank == 0 else [b + 1 + rank for b in blinders]
-        proof = prv.prove(ipk, circuit[6], circuit[7], blinders=mine)
-        _check_frozen_proof(proof, gp)
-        assert plonk.Verifier(curve).verify(ivk, circuit[6], proof)
+        if "frozen" in parts:
+            # 1. the frozen 16-gate proof (every transform below the distributed sizes: gather, transform, keep a share)
+            gp = _golden("plonk_proof_n16.json")
+            circuit = TP.fixture_instance()
+            curve, tau = gp["curve"], int(gp["tau"], 16)
+            blinders = [int(v, 16) for v in gp["blinders"]]
+            idx = plonk_device.DeviceIndexer(curve)
+            ipk, ivk = idx.preprocess(*circuit[:6], tau=tau)
+            prv = plonk_sharded.make_prover(curve, idx.alg, ProofSharding(shard_vectors=True))
+            assert type(prv).__name__ == "ShardedProver"
+            mine = blinders if rank == 0 else [b + 1 + rank for b in blinders]
+            proof = prv.prove(ipk, circuit[6], circuit[7], blinders=mine)
+            _check_frozen_proof(proof, gp)
+            assert plonk.Verifier(curve).verify(ivk, circuit[6], proof)
         # 2. 2^12 and 2^13 gates on BLS12-381: the 4n-point (and at 2^13 the n-point) transforms go through the
         # all-to-alls and the device's column / row passes; same blinders as the unsharded device prover -> the same
         # proof on every rank, and the verifier accepts it
         F = GF(O.BLS12_381.r)
-        for log_gates in (12, 13):
+        for log_gates in (p for p in parts if p != "frozen"):
             big = plonk.synthetic_circuit(1 << log_gates, F, seed=log_gates)
             idx2 = plonk_device.DeviceIndexer("bls12_381")
             ipk2, ivk2 = idx2.preprocess(*big[:6], tau=0x1234567)
@@ -444,12 +612,16 @@ def _sharded_gpu_worker(rank, world, port, q):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [1, 2])
+@pytest.mark.parametrize("world", [1, 2, 8])
 def test_vector_sharded_device_prover_on_one_gpu(world):
     """plonk_sharded.ShardedProver on the engine: one rank (every exchange degenerate, the shard logic alone) and two
     ranks sharing the GPU over gloo.  The frozen 16-gate proof bit for bit; 2^12- and 2^13-gate proofs identical to
-    the unsharded device prover's for the same blinders, accepted by the verifier, the same on every rank."""
-    res = _run_ranks(_sharded_gpu_worker, world, 900)
+    the unsharded device prover's for the same blinders, accepted by the verifier, the same on every rank.
+    Eight ranks -- the machine's world size, eight processes on the one GPU -- prove the 2^13 gates only: the least size
+    at which both the n-point and the 4n-point transforms take the distributed passes (8 and 16 columns and rows of
+    them per rank), and the frozen 16 gates cannot be split eight ways (plonk_sharded.can_shard_vectors)."""
+    parts = (13,) if world == 8 else ("frozen", 12, 13)
+    res = _run_ranks(_sharded_gpu_worker, world, 900, (parts,))
     assert sorted(res) == [(r, "ok") for r in range(world)], res
 
 
