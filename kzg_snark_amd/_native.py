@@ -632,10 +632,7 @@ def g1_sum(curve_type, points):
     rc = lib().kzg_g1_sum(cid, _as_vp(np.ascontiguousarray(xy)), _as_vp(inf), n, _as_vp(out_xy), _as_vp(out_inf))
     if rc != 0:
         raise NativeError(rc, "kzg_g1_sum: a coordinate is not reduced or a point is not on the curve")
-    if out_inf[0]:
-        return (1, 1, 0)
-    v = limbs_to_ints(out_xy.reshape(2, L))
-    return (v[0], v[1], 1)
+    return limbs_to_points(out_xy, out_inf)[0]
 
 
 _contexts = {}
@@ -710,6 +707,19 @@ def limbs_to_ints(arr):
         return _pyconv.bytes_to_ints(a.reshape(-1).view(np.uint8), nb)
     raw = a.tobytes()
     return [int.from_bytes(raw[i:i + nb], "little") for i in range(0, len(raw), nb)]
+
+
+def limbs_to_points(xy, inf):
+    """affine G1 points in the C layout (x | y limbs per row, one infinity flag each; a single row and flag too) ->
+    facade tuples (x, y, 1), infinity (1, 1, 0)"""
+    out = []
+    for row, f in zip(np.atleast_2d(xy), np.atleast_1d(inf)):
+        if f:
+            out.append((1, 1, 0))
+        else:
+            v = limbs_to_ints(row.reshape(2, -1))
+            out.append((v[0], v[1], 1))
+    return out
 
 
 def int_to_words(v, limbs=4):

@@ -40,13 +40,6 @@ class CommitmentKey(Sequence):
     def __len__(self):
         return self.srs.n
 
-    def _point(self, xy_row, inf):
-        if inf:
-            return (1, 1, 0)
-        L = self._ctx.fp_limbs
-        v = _native.limbs_to_ints(xy_row.reshape(2, L))
-        return (v[0], v[1], 1)
-
     def __getitem__(self, i):
         if isinstance(i, slice):
             idx = range(*i.indices(len(self)))
@@ -60,8 +53,7 @@ class CommitmentKey(Sequence):
             start = (i // 1024) * 1024
             count = min(1024, n - start)
             xy, inf = self.srs.export(start, count)
-            for j in range(count):
-                self._cache[start + j] = self._point(xy[j], inf[j])
+            self._cache.update(enumerate(_native.limbs_to_points(xy, inf), start))
         return self._cache[i]
 
 
@@ -220,16 +212,7 @@ class KZG:
                 arr[i, :len(c)] = c if isinstance(c, np.ndarray) else _native.ints_to_limbs(c)
         return arr, [len(c) for c in coeff_lists], stride
 
-    def _points(self, xy, inf):
-        L = self._context().fp_limbs
-        out = []
-        for row, f in zip(np.atleast_2d(xy), np.atleast_1d(inf)):
-            if f:
-                out.append(self.Z1)
-            else:
-                v = _native.limbs_to_ints(row.reshape(2, L))
-                out.append((v[0], v[1], 1))
-        return out
+    _points = staticmethod(_native.limbs_to_points)
 
     # ---- the scheme -----------------------------------------------------------------
     def setup(self, max_degree, tau=None):

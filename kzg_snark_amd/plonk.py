@@ -12,6 +12,7 @@ Polynomial algebra here is the host shim (schoolbook products): fine for the ref
 fixture and the small synthetic circuits of the tests.  The n = 2^20 round runs in
 plonk_device.py, where the quotient is computed on the device (coset NTTs of size 4n instead of
 dense products); both provers share this module's Verifier."""
+from . import plonk_rounds
 from .fft_ff import fft_ff_interpolation
 from .kzg import KZG
 from .transcript import Transcript
@@ -55,8 +56,7 @@ class Domain:
         return fft_ff_interpolation(list(values), self.g, self.Fq)
 
     def lagrange_1_at(self, x):
-        n = self.n
-        return (x ** n - 1) / (self.Fq(n) * (x - 1))
+        return plonk_rounds.lagrange_1_at(self.Fq, self.n, x)
 
     def public_input_at(self, x, zeta):
         """PI(zeta) = -sum_i x_i L_i(zeta) with L_i(X) = g^i (X^n - 1) / (n (X - g^i)): what the verifier needs

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _native
+from . import plonk_rounds as rounds
 from .kzg import KZG, CommitmentKey
 from .plonk import Domain
 from .transcript import Transcript
@@ -85,6 +86,17 @@ class DeviceAlgebra:
             out = torch.zeros((n, 4), dtype=torch.int64, device=self.dev)
             out[:t.shape[0]] = t
             return out
+
+    def pack(self, tensors):
+        """pad to a common stride and stack, as the commit / open entry points take a batch: (pack, lens, stride)"""
+        stride = max(t.shape[0] for t in tensors)
+        return (torch.stack([self.padded(t, stride) for t in tensors]).contiguous(), [t.shape[0] for t in tensors],
+                stride)
+
+    def result_buffers(self, k, evals=False):
+        """host arrays a pipelined commit of k polynomials (or, with evals, one opening: k = 1) fills by the flush"""
+        out = (np.zeros((k, 2 * self.ctx.fp_limbs), dtype=np.uint64), np.zeros(k, dtype=np.uint8))
+        return out + (np.zeros(4, dtype=np.uint64),) if evals else out
 
     # ---- element-wise
     def op(self, kind, a, b):
@@ -204,11 +216,9 @@ class DeviceProver:
             ones4 = alg.const(N4, 1)
             xs = alg.mul_powers(ones4, w4, K)                                     # the coset points
             xn = alg.mul_powers(ones4, pow(w4, n, r), pow(K, n, r))               # x^n: four distinct values
-            zh = alg.sub(xn, ones4)
             cache.clear()                                                          # one domain at a time (N4-sized vectors)
-            cache[key] = {"ones": ones, "idH": alg.mul_powers(ones, g), "ones4": ones4, "xs": xs,
-                          "zh_inv": alg.inverse(zh), "w4": w4, "K": K, "e0": alg.const(1, 1),
-                          "l1": alg.mul(zh, alg.inverse(alg.lincomb(N4, [(n, xs), (-n, ones4)])))}
+            cache[key] = {"ones": ones, "idH": alg.mul_powers(ones, g), "ones4": ones4, "xs": xs, "w4": w4, "K": K,
+                          "e0": alg.const(1, 1), **rounds.coset_constants(alg, N4, n, xs, xn, ones4)}
         return cache[key]
 
     def _circuit_cosets(self, ipk, on_coset):
@@ -221,7 +231,7 @@ class DeviceProver:
         return cache
 
     def _commit(self, ck, tensors):
-        return self._commit_end(self._commit_begin(ck, tensors)), None
+        return self._commit_end(self._commit_begin(ck, tensors))
 
     def _commit_begin(self, ck, tensors):
         """Queue the commitments of a round on the library's pipeline and return at once: whatever the prover
@@ -232,12 +242,9 @@ class DeviceProver:
         mine = list(range(k)) if sh is None else sh.mine(k)
         if not mine:
             return None, None, None, mine, k
-        own = [tensors[i] for i in mine]
-        stride = max(t.shape[0] for t in own)
-        pack = torch.stack([alg.padded(t, stride) for t in own]).contiguous()
-        xy = np.zeros((len(own), 2 * alg.ctx.fp_limbs), dtype=np.uint64)
-        inf = np.zeros(len(own), dtype=np.uint8)
-        alg.ctx.commit_device_async(ck.srs, pack.data_ptr(), [t.shape[0] for t in own], stride, xy, inf)
+        pack, lens, stride = alg.pack([tensors[i] for i in mine])
+        xy, inf = alg.result_buffers(len(mine))
+        alg.ctx.commit_device_async(ck.srs, pack.data_ptr(), lens, stride, xy, inf)
         return pack, xy, inf, mine, k
 
     def _commit_end(self, handle):
@@ -263,16 +270,7 @@ class DeviceProver:
         """plonk/prover.py:24-212.  `blinders` (tests only) fixes b1..b11 of plonk/prover.py:72-75 and
         :346 in the reference's order; `trace`, when a dict, receives the challenges and the device
         tensors of every intermediate polynomial so a test can compare them with the oracle."""
-        try:
-            return self._prove(ipk, x, w, blinders, trace)
-        except BaseException:
-            # a proof that fails half way (an assert of the protocol, an allocation) must not leave commitments of
-            # its rounds queued in the library's pipeline: drain it before the error travels on
-            try:
-                self.alg.ctx.commit_flush()
-            except Exception:
-                pass
-            raise
+        return rounds.prove_flushing(self.alg.ctx.commit_flush, self._prove, ipk, x, w, blinders, trace)
 
     def _prove(self, ipk, x, w, blinders, trace):
         kzg, Fq, alg = self.kzg, self.kzg.Fq, self.alg
@@ -282,29 +280,10 @@ class DeviceProver:
         sub = ipk["subgroups"]
         n, g, k1, k2 = sub["n"], sub["g"], sub["k1"], sub["k2"]
         assert isinstance(ck, CommitmentKey)
-        dom = Domain.__new__(Domain)                 # reuse lagrange_1_at without rebuilding H
-        dom.Fq, dom.n, dom.g = Fq, n, g
         tr = Transcript("plonk-proof", Fq)
         tr.append_message("public-inputs", x)
-        x_limbs = _native.ints_to_limbs([int(v) % r for v in x]).reshape(-1, 4)
-        if isinstance(w, np.ndarray):                # witness already in limb form: no per-element Python work
-            w_limbs = np.ascontiguousarray(w, dtype=np.uint64).reshape(-1, 4)
-        else:
-            w_limbs = _native.ints_to_limbs([int(v) % r for v in w]).reshape(-1, 4)
-        nx = x_limbs.shape[0]
-        assert nx + w_limbs.shape[0] == 3 * n
-
-        def column(i):
-            """rows [i n, (i+1) n) of x ++ w, uploaded piecewise (no host-side copy of the 96 n bytes)."""
-            lo, hi = i * n, (i + 1) * n
-            parts = []
-            if lo < nx:
-                parts.append(x_limbs[lo:min(hi, nx)])
-            if hi > nx:
-                parts.append(w_limbs[max(lo, nx) - nx:hi - nx])
-            return alg.upload_parts(n, parts)
-        b = [int(Fq.random_element()) for _ in range(11)] if blinders is None else [int(v) % r for v in blinders]
-        assert len(b) == 11
+        wit = rounds.Witness(x, w, n, r)
+        b = rounds.draw_blinders(Fq, blinders)
         if sh is not None and sh.active:
             b = sh.shared_scalars(b)                                          # drawn once, by rank 0
         dealt = sh is not None and sh.active and sh.deal_transforms
@@ -312,10 +291,10 @@ class DeviceProver:
         ones, idH = D["ones"], D["idH"]                                       # 1 and g^i on H
 
         # round 1
-        vals = [column(i) for i in range(3)]
+        vals = [alg.upload_parts(n, wit.column_parts(i)) for i in range(3)]     # piecewise: no host copy of x ++ w
         pi = alg.zeros(n)                                                    # PI values: -x_i on the first rows
-        if len(x):
-            pi[:len(x)] = alg.upload([(-int(v)) % r for v in x])
+        if wit.nx:
+            pi[:wit.nx] = alg.upload(wit.public_inputs())
         if dealt:   # the four independent INTTs of the round, each on its owner, results broadcast
             srcs = vals + [pi]
             co = sh.dealt_tensors([(n, 4)] * 4, lambda i: alg.ntt(srcs[i].clone(), g, True), vals[0])
@@ -340,44 +319,29 @@ class DeviceProver:
         else:
             E = {k: on_coset(v) for k, v in r1}
         E.update(self._circuit_cosets(ipk, on_coset))
-        gate = alg.add(alg.add(alg.mul(alg.mul(E["a"], E["b"]), E["qM"]), alg.mul(E["a"], E["qL"])),
-                       alg.add(alg.mul(E["b"], E["qR"]), alg.mul(E["c"], E["qO"])))
-        gate = alg.add(gate, alg.add(E["PI"], E["qC"]))
+        gate = rounds.gate_constraint(alg, E)
         wire_comms = self._commit_end(h1)
         tr.append_message("round1-commitments", wire_comms)
         beta, gamma = int(tr.get_challenge("beta")), int(tr.get_challenge("gamma"))
 
         # round 2: z_i = prod_{j<i} num_j / den_j
-        S = ipk["sigma_values"]
-        num = den = None
-        for v, shift, sig in ((vals[0], 1, S["S_sigma1"]), (vals[1], int(k1), S["S_sigma2"]), (vals[2], int(k2), S["S_sigma3"])):
-            fn = alg.lincomb(n, [(1, v), (beta * shift, idH), (gamma, ones)])
-            fd = alg.lincomb(n, [(1, v), (beta, sig), (gamma, ones)])
-            num = fn if num is None else alg.mul(num, fn)
-            den = fd if den is None else alg.mul(den, fd)
-        z_vals = alg.prefix_product(alg.mul(num, alg.inverse(den)))
+        z_vals = alg.prefix_product(rounds.accumulator_ratios(alg, n, vals, ipk["sigma_values"], idH, ones,
+                                                              beta, gamma, k1, k2))
         z_c = self._blind(alg.ntt(z_vals, g, True), n, [b[8], b[7], b[6]])
         h2 = self._commit_begin(ck, [z_c])
         # queued behind the round-2 MSM: everything of the quotient that needs beta and gamma but not alpha
         E["z"] = on_coset(z_c)
         ones4, xs = D["ones4"], D["xs"]                                       # 1 and the coset points
         zw = torch.roll(E["z"], shifts=-4, dims=0).contiguous()              # z(g * x): g = w4^4
-        p1 = p2 = None
-        for key, shift, sig in (("a", 1, "S_sigma1"), ("b", int(k1), "S_sigma2"), ("c", int(k2), "S_sigma3")):
-            f1 = alg.lincomb(N4, [(1, E[key]), (beta * shift, xs), (gamma, ones4)])
-            f2 = alg.lincomb(N4, [(1, E[key]), (beta, E[sig]), (gamma, ones4)])
-            p1 = f1 if p1 is None else alg.mul(p1, f1)
-            p2 = f2 if p2 is None else alg.mul(p2, f2)
-        perm = alg.sub(alg.mul(p1, E["z"]), alg.mul(p2, zw))
+        perm = rounds.permutation_constraint(alg, N4, E, zw, xs, ones4, beta, gamma, k1, k2)
         # Z_H(x) = x^n - 1 and L1(x) = Z_H(x) / (n (x - 1)) on the coset: domain constants
-        l1t = alg.mul(alg.sub(E["z"], ones4), D["l1"])
+        l1t = rounds.l1_term(alg, E, ones4, D["l1"])
         z_comm = self._commit_end(h2)[0]
         tr.append_message("round2-commitment", z_comm)
         alpha = int(tr.get_challenge("alpha"))
 
         # round 3: combine with alpha, divide by Z_H, back to coefficients
-        numer = alg.lincomb(N4, [(1, gate), (alpha, perm), (alpha * alpha, l1t)])
-        t_ev = alg.mul(numer, D["zh_inv"])
+        t_ev = rounds.quotient_evaluations(alg, N4, gate, perm, l1t, alpha, D["zh_inv"])
         t_c = alg.mul_powers(alg.ntt(t_ev, w4, True), pow(K, -1, r))          # back to coefficients
         # the quotient must have degree <= 3n + 5: its tail is fetched behind the work queued so far and
         # looked at once the round's commitments have come back (no extra wait)
@@ -391,7 +355,7 @@ class DeviceProver:
         alg.set_entries(t_lo, [(n, b[9])])
         alg.set_entries(t_mid, [(0, -b[9]), (n, b[10])])
         alg.set_entries(t_hi, [(0, -b[10])])
-        t_comms, _ = self._commit(ck, [t_lo, t_mid, t_hi])
+        t_comms = self._commit(ck, [t_lo, t_mid, t_hi])
         assert not bool(tail_host.any()), "constraint system is not satisfied (quotient has a remainder)"
         tr.append_message("round3-commitments", t_comms)
         zeta = int(tr.get_challenge("zeta"))
@@ -401,46 +365,32 @@ class DeviceProver:
               "s_sigma1": alg.eval(C["S_sigma1"], zeta), "s_sigma2": alg.eval(C["S_sigma2"], zeta),
               "z_omega": alg.eval(z_c, zeta * int(g) % r)}
         evF = {k: Fq(v) for k, v in ev.items()}
-        tr.append_message("round4-evaluations", [evF[k] for k in ("a", "b", "c", "s_sigma1", "s_sigma2", "z_omega")])
+        tr.append_message("round4-evaluations", [evF[k] for k in rounds.EVALUATIONS])
         v = int(tr.get_challenge("v"))
 
         # round 5: r(X) as a scalar combination of coefficient vectors
-        za, zb, zc, s1, s2, zo = (ev[k] for k in ("a", "b", "c", "s_sigma1", "s_sigma2", "z_omega"))
-        zn = pow(zeta, n, r)
-        L1z = int(dom.lagrange_1_at(Fq(zeta)))
+        L1z = int(rounds.lagrange_1_at(Fq, n, Fq(zeta)))
         PIz = alg.eval(PI_c, zeta)
-        f1 = (za + beta * zeta + gamma) * (zb + beta * int(k1) * zeta + gamma) * (zc + beta * int(k2) * zeta + gamma) % r
-        f2 = (za + beta * s1 + gamma) * (zb + beta * s2 + gamma) * zo % r
-        e0 = D["e0"]
-        const = (PIz - alpha * f2 * (zc + gamma) - alpha * alpha * L1z) % r
-        r_c = alg.lincomb(n + 6, [
-            (za * zb, C["qM"]), (za, C["qL"]), (zb, C["qR"]), (zc, C["qO"]), (1, C["qC"]), (const, e0),
-            (alpha * f1 + alpha * alpha * L1z, z_c), (-alpha * f2 * beta, C["S_sigma3"]),
-            (-(zn - 1), t_lo), (-(zn - 1) * zn, t_mid), (-(zn - 1) * zn * zn, t_hi)])
+        s, const = rounds.linearisation(ev, beta, gamma, alpha, zeta, n, k1, k2, L1z, PIz, r)
+        P = dict(C, z=z_c, t_lo=t_lo, t_mid=t_mid, t_hi=t_hi)
+        r_c = alg.lincomb(n + 6, [(s[k], P[k]) for k in rounds.LINEARISED] + [(const, D["e0"])])
         assert alg.eval(r_c, zeta) == 0, "r(zeta) should be zero"                       # plonk/prover.py:171
         if trace is not None:
             trace.update(beta=beta, gamma=gamma, alpha=alpha, zeta=zeta, v=v, evaluations=dict(ev),
                          a=a_c, b=b_c, c=c_c, z=z_c, PI=PI_c, t=t_c[:3 * n + 6], t_lo=t_lo, t_mid=t_mid,
                          t_hi=t_hi, r=r_c)
-        polys = [r_c, a_c, b_c, c_c, C["S_sigma1"], C["S_sigma2"]]
-        stride = n + 6
-        pack = torch.stack([alg.padded(p, stride) for p in polys]).contiguous()
+        pack, lens, stride = alg.pack([r_c, a_c, b_c, c_c, C["S_sigma1"], C["S_sigma2"]])    # stride: r_c's n + 6
         zw_ = _native.int_to_words
         # the two openings (plonk/prover.py:184-185) are independent: both go through the pipelined entry point
         # and their witness MSMs overlap; results arrive at the flush
-        L = alg.ctx.fp_limbs
-        o1 = (np.zeros(2 * L, dtype=np.uint64), np.zeros(1, dtype=np.uint8), np.zeros(4, dtype=np.uint64))
-        o2 = (np.zeros(2 * L, dtype=np.uint64), np.zeros(1, dtype=np.uint8), np.zeros(4, dtype=np.uint64))
+        o1, o2 = alg.result_buffers(1, evals=True), alg.result_buffers(1, evals=True)
         mine = [0, 1] if sh is None else sh.mine(2)                          # with several ranks: one opening each
         if 0 in mine:
-            alg.ctx.open_device_async(ck.srs, pack.data_ptr(), [p.shape[0] for p in polys], stride, zw_(zeta), zw_(v), *o1)
+            alg.ctx.open_device_async(ck.srs, pack.data_ptr(), lens, stride, zw_(zeta), zw_(v), *o1)
         zpack = alg.padded(z_c, stride)
         if 1 in mine:
             alg.ctx.open_device_async(ck.srs, zpack.data_ptr(), [z_c.shape[0]], stride, zw_(zeta * int(g) % r), zw_(v), *o2)
         alg.ctx.commit_flush()
         local = {i: kzg._points(o[0], o[1])[0] for i, o in ((0, o1), (1, o2)) if i in mine}
         W_z, W_zw = (local[0], local[1]) if sh is None else sh.gather_points(local, 2)
-        return {"commitments": dict(zip(("a", "b", "c"), wire_comms), z=z_comm,
-                                    t_lo=t_comms[0], t_mid=t_comms[1], t_hi=t_comms[2]),
-                "evaluations": evF,
-                "kzg_proofs": {"W_z": W_z, "W_zw": W_zw}}
+        return rounds.proof_dict(wire_comms, z_comm, t_comms, evF, W_z, W_zw)
