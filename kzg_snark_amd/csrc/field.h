@@ -20,19 +20,29 @@
 // Montgomery radix R = 2^(L*N); 4p < R for all four fields, so mul() maps
 // weak-normal inputs to a weak-normal output:  (ab + mp)/R < 4p^2/R + p < 2p.
 //
-// Column bound: a 64-bit column absorbs CAP = 2^(64-2L) - 1 products of two L-bit
-// limbs.  A Montgomery row adds two products per column (a_j*b_i and m*p_j), so
-// the sliding window is carry-normalised every CAP/2 rows: never for L = 29, N = 9
-// (CAP = 63), once (after row 7) for L = 30, N = 13 (CAP = 15).
+// Column bound: a 64-bit column absorbs FIT = 2^(64-2L) products of two L-bit limbs next to a carry (64 for L = 29,
+// 16 for L = 30).  A Montgomery column adds up to 2N products, so N = 9, L = 29 never gets near it and N = 13, L = 30
+// does: there the multiply-add chain of a column is CUT where it could carry out (plan_columns() below decides
+// where, at compile time).  BLS12-381 Fp declares TOP_LIMB_BOUND = 2^26 and is planned by magnitudes -- half of a
+// column's products are m_i * P[j] with the real, often small, limbs of p, and the top limb of an operand is far below
+// 2^30 -- which needs 3 cuts per mul / sqr (columns 10, 11, 12) and 14 per mul2, where counting products needed 9
+// and 24.  A cut costs two VALU instructions (a move and a multiply-add on the chain's high word) where shift, mask
+// and 64-bit addition cost three: 21 VALU instructions fewer per mul / sqr, 44 per mul2, 9450 -> 9136 instructions
+// in msm_accumulate_kernel<Bls12_381, 20> (tools/isa_histogram.py, profiles/r05_isa_histograms.txt); measured,
+// 0.892 -> 0.849 G VALU wave-instructions per accumulate launch; +3.8 % commits/s on the box of the A/B
+// (EXPERIMENTS.md E1, round 5).
 //
-// What the multipliers require of their operands is NOT "limbs < 2^L" but two things:
+// What the multipliers require of their operands is NOT "limbs < 2^L" but three things:
 //  (1) per column, the product units stay within FIT = 2^(64-2L): a product of two limbs below 2^L is one unit, and
 //      limbs below u*2^L and v*2^L make a product of u*v units.  mul<UNITS_AB> is told the units of one a*b product
-//      and splits a column when nab*UNITS_AB + nmp > FIT.  Every function of this header but add_lazy / sub_lazy4
+//      and plans its columns with them.  Every function of this header but add_lazy / sub_lazy4
 //      returns limbs below 2^L; the un-carried outputs of those two (below 2^32 = 8 * 2^29) are legal operands of
-//      the plain mul<1> as long as (1) still holds without a split, which ntt.hip relies on for L = 29, N = 9;
-//  (2) the result range: (sum of the operand-value products + m*p)/R < 2p, i.e. the products sum below R*p.
-// The host-only audit build below (KZG_AUDIT) checks exactly these two, per call.
+//      the plain mul<1> as long as (1) still holds without a cut, which ntt.hip relies on for L = 29, N = 9;
+//  (2) the result range: (sum of the operand-value products + m*p)/R < 2p, i.e. the products sum below R*p;
+//  (3) in a field that declares TOP_LIMB_BOUND (BLS12-381 Fp: 2^26, any normalised value up to 39p; (2) already caps
+//      operands near 25p and ec.h passes nothing above 10p): top limb below the bound, the other limbs below
+//      UNITS_AB * 2^L.  The columns of such a field are planned with these magnitudes, not with (1)'s count.
+// The host-only audit build below (KZG_AUDIT) checks exactly these, per call.
 #pragma once
 #include <stdint.h>
 #include "curve_constants.h"
@@ -145,6 +155,97 @@ struct Fe {
   uint32_t l[F::N];
 };
 
+// ---- column bound ------------------------------------------------------------------------------------
+// A field may declare F::TOP_LIMB_BOUND: the top limb of every operand of its multipliers stays below it.
+template <class F, class = void>
+struct TopLimb {
+  static constexpr bool declared = false;
+  static constexpr uint32_t bound = 0;
+};
+template <class F>
+struct TopLimb<F, decltype((void)F::TOP_LIMB_BOUND)> {
+  static constexpr bool declared = true;
+  static constexpr uint32_t bound = F::TOP_LIMB_BOUND;
+  static_assert(bound >= 1 && bound <= (1u << F::L), "the top limb is a limb");
+};
+
+// Where the 64-bit multiply-add chains of a product-scanning Montgomery multiplier are cut.  Column k takes NG groups
+// of products in turn -- the operand products of each of the NG - 1 terms, then m*p -- on top of the carry of column
+// k - 1.  plan_columns() follows the worst case of every chain with 128-bit integers and cuts (greedily) right before
+// the first group that could carry it out of 64 bits.  A cut sets the HIGH WORD of the chain aside: 2^32 is a multiple
+// of 2^L, so the low L bits (all that m_k and the result limb read) are untouched, the chain goes on from its low
+// word, and the word joins the outgoing carry as hi * 2^(32-L).  After a cut the walk goes on from 2^32 - 1, the
+// largest low word any chain value can leave (the worst-case VALUE may well leave a small one), beside the largest
+// high word: both are upper bounds, so every later decision, `fits` and the carry are.
+//   magnitudes, for a field that declares TOP_LIMB_BOUND: operand limbs 0..N-2 <= UNITS * 2^L - 1 (see precondition
+//     (1) in the header), top limb <= TOP_LIMB_BOUND - 1, m_i <= 2^L - 1 against the REAL limbs of p;
+//   otherwise every limb of the operands and of p counts as 2^L - 1: the count rule -- FIT products and a carry fit.
+template <int NCOL, int NG>
+struct ColumnPlan {
+  bool cut[NCOL][NG];        // cut[k][g]: set the high word aside before group g of column k
+  int cuts;                  // how many
+  bool fits;                 // no chain reaches 2^64
+  uint64_t carry_max;        // the largest carry a column hands on
+};
+
+template <class F, int K, int UNITS, bool SQUARE>
+constexpr ColumnPlan<2 * F::N - 1, K + 1> plan_columns() {
+  typedef unsigned __int128 u128;
+  constexpr int L = F::L, N = F::N;
+  constexpr bool mag = TopLimb<F>::declared;
+  const u128 LIMIT = (((u128)1) << 64) - 1;
+  const u128 one = F::MASK;                                                   // a normalised limb
+  const u128 low = (((u128)UNITS) << L) - 1;                                  // a lower operand limb of u <= UNITS units
+  const u128 low2 = (((u128)UNITS) << (2 * L)) - (((u128)2) << L) + 1;        // (u 2^L - 1)(v 2^L - 1) with u v <= UNITS
+  const u128 top = mag ? (u128)TopLimb<F>::bound - 1 : one;
+  ColumnPlan<2 * N - 1, K + 1> plan = {};
+  plan.fits = true;
+  u128 carry = 0;
+  for (int k = 0; k < 2 * N - 1; ++k) {
+    const int lo = k < N ? 0 : k - N + 1, hi = k < N ? k : N - 1;
+    u128 chain = carry, aside = 0;
+    for (int g = 0; g <= K; ++g) {
+      u128 group = 0;
+      for (int i = lo; i <= hi; ++i) {
+        const int j = k - i;
+        if (g < K) {
+          const bool ti = mag && i == N - 1, tj = mag && j == N - 1;
+          const u128 ab = ti && tj ? top * top : ti || tj ? top * low : low2;
+          group += !SQUARE ? ab : i < j ? 2 * ab : i == j ? ab : 0;          // sqr: off-diagonal once, doubled
+        } else if (i < k || k >= N) {
+          group += one * (mag ? (u128)F::P[j] : one);
+        }
+      }
+      if (g == K && k < N) group += one * (mag ? (u128)F::P[0] : one);        // m_k p_0
+      if (chain + group > LIMIT) {
+        plan.cut[k][g] = true;
+        ++plan.cuts;
+        aside += chain >> 32;                        // the largest high word ...
+        chain = 0xffffffffu;                         // ... and the largest LOW word: not the low word of the largest value
+      }
+      chain += group;
+      if (chain > LIMIT) plan.fits = false;
+    }
+    carry = (chain >> L) + (aside << (32 - L));
+    if (carry > LIMIT) plan.fits = false;
+    else if ((uint64_t)carry > plan.carry_max) plan.carry_max = (uint64_t)carry;
+  }
+  return plan;
+}
+template <class F, int K, int UNITS, bool SQUARE>
+struct Columns {
+  static constexpr ColumnPlan<2 * F::N - 1, K + 1> plan = plan_columns<F, K, UNITS, SQUARE>();
+  static_assert(plan.fits, "a column carries out of 64 bits even with its cuts");
+  // no cut before the first group of a column: the carry and one term's products fit (mul, sqr, mul2 rely on it and
+  // have no code for such a cut; dot<K> could take one but never needs it either)
+  static constexpr bool first_group_fits() {
+    for (int k = 0; k < 2 * F::N - 1; ++k)
+      if (plan.cut[k][0]) return false;
+    return true;
+  }
+  static_assert(first_group_fits(), "the carry and the first group of products do not fit one 64-bit chain");
+};
+
 template <class F>
 struct Field {
   static constexpr int L = F::L;
@@ -170,6 +271,49 @@ struct Field {
       w[j + 1] += c;
     }
   }
+
+  // A cut (ColumnPlan): the chain goes on from its low word, the high word waits for the outgoing carry, which it
+  // joins by ONE multiply-add, hi * 2^(32-L) + carry.  The weight reaches that multiply-add through an empty asm
+  // statement (an s_mov_b32 per cut): a factor the optimiser can see is turned into
+  // ((acc >> L) & ~(2^(32-L) - 1)) + carry -- a 64-bit shift, two ands and a 64-bit addition per cut, more than
+  // the cut by shift and mask that this replaces.  One definition per cut, not per product: a weight that stays
+  // live costs the 168-VGPR reduce kernels a spilled dword (tools/kernel_resources.py).  The per-cut s_mov_b32 and
+  // s_nop are not free -- the per-product form measured +8 % where this one gives +3.8 % (EXPERIMENTS.md E1).
+  static KZG_HD uint32_t peel(uint64_t& acc) {
+    const uint32_t h = (uint32_t)(acc >> 32);
+    acc = (uint32_t)acc;
+    return h;
+  }
+  static KZG_HD uint64_t unpeel(uint32_t h, uint64_t carry) {
+    uint32_t weight = 1u << (32 - L);
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(KZG_NO_CHAIN_PIN)
+    asm volatile("" : "+s"(weight));
+#endif
+    return mad_wide(h, weight, carry);
+  }
+
+#ifdef KZG_AUDIT_ON
+  // precondition (3) of the multipliers of a field that declares TOP_LIMB_BOUND
+  static void audit_operand(const E& a, uint32_t units, const char* fn, int line) {
+    if (!TopLimb<F>::declared) return;
+    bool ok = a.l[N - 1] < TopLimb<F>::bound;
+    for (int j = 0; j < N - 1; ++j) ok = ok && a.l[j] < ((uint64_t)units << L);
+    if (!ok) audit::fail(fn, line, "operand limbs above the column bound (top limb < TOP_LIMB_BOUND, others < units * 2^L)");
+  }
+  // ... and of (1) as the plan takes it: limbs below u * 2^L and v * 2^L with u * v <= units
+  static void audit_units(const E& a, const E& b, uint32_t units, const char* fn, int line) {
+    if (!TopLimb<F>::declared) return;
+    uint32_t ma = 0, mb = 0;
+    for (int j = 0; j < N - 1; ++j) { ma = a.l[j] > ma ? a.l[j] : ma; mb = b.l[j] > mb ? b.l[j] : mb; }
+    const uint64_t u = (ma >> L) + 1, v = (mb >> L) + 1;
+    if (u <= units && v <= units && u * v > units) audit::fail(fn, line, "operand limbs above the column bound (u * v product units above UNITS_AB)");
+  }
+#define KZG_AUDIT_OPERAND(a, units) audit_operand(a, units, __func__, __LINE__)
+#define KZG_AUDIT_UNITS(a, b, units) audit_units(a, b, units, __func__, __LINE__)
+#else
+#define KZG_AUDIT_OPERAND(a, units) ((void)0)
+#define KZG_AUDIT_UNITS(a, b, units) ((void)0)
+#endif
 
 #ifdef KZG_AUDIT_ON
   // postcondition of every multiplier: weak-normal.  With audit::state().lift the representative in [p, 2p).
@@ -262,26 +406,24 @@ struct Field {
   // added last -- one v_lshl_add_u64 per column remains; forcing a single chain with inline-asm
   // multiply-adds was worth another 0.4 % and was not kept)
   //
-  // Column capacity: products of two L-bit limbs are < 2^(2L); a 64-bit column holds FIT of them
-  // next to the carry.  Columns with more products (L = 30, N = 13: the 9 middle ones) are split:
-  // the partial sum is cut into its low L bits (which stay in the chain) and its upper part (added
-  // to the outgoing carry).  `UA` = how many units one a*b product may take (operands with limbs
-  // up to 2^(L+1) from add_lazy count 2 or 4).
+  // Column capacity: a chain that could carry out of 64 bits is cut where Columns<...>::plan says (plan_columns()
+  // above): its high word is set aside and joins the outgoing carry, the low word stays in the chain.  `UNITS_AB` =
+  // how many units one a*b product may take (operands with limbs up to 2^(L+1) from add_lazy count 2 or 4).
   template <int UNITS_AB = 1>
   static KZG_HD E mul(const E& a, const E& b) {
+    using Col = Columns<F, 1, UNITS_AB, false>;
+    KZG_AUDIT_OPERAND(a, UNITS_AB); KZG_AUDIT_OPERAND(b, UNITS_AB); KZG_AUDIT_UNITS(a, b, UNITS_AB);
     uint32_t m[N];
     E r;
     uint64_t acc = 0;
 #pragma unroll
     for (int k = 0; k < 2 * N - 1; ++k) {
       const int lo = k < N ? 0 : k - N + 1, hi = k < N ? k : N - 1;
-      const int nab = hi - lo + 1;                       // a*b products of this column
-      const int nmp = k < N ? k + 1 : nab;               // m*p products (incl. m_k p_0 in the low half)
-      const bool split = nab * UNITS_AB + nmp > FIT;
-      uint64_t upper = 0;
+      const bool cut = Col::plan.cut[k][1];              // before m*p (the carry and the a*b products always fit)
+      uint32_t aside = 0;
 #pragma unroll
       for (int i = lo; i <= hi; ++i) acc = mad_wide(a.l[i], b.l[k - i], acc);
-      if (split) { upper = acc >> L; acc &= (uint64_t)MASK; }
+      if (cut) aside = peel(acc);
 #pragma unroll
       for (int i = lo; i <= hi; ++i)
         if (i < k || k >= N) acc = mad_wide(m[i], F::P[k - i], acc);
@@ -292,7 +434,7 @@ struct Field {
         r.l[k - N] = (uint32_t)acc & MASK;
       }
       acc >>= L;
-      if (split) acc += upper;
+      if (cut) acc = unpeel(aside, acc);
     }
     r.l[N - 1] = (uint32_t)acc;
     KZG_AUDIT_PRODUCT(r);
@@ -300,6 +442,8 @@ struct Field {
   }
   // Montgomery square: off-diagonal products once, against the doubled operand.
   static KZG_HD E sqr(const E& a) {
+    using Col = Columns<F, 1, 1, true>;
+    KZG_AUDIT_OPERAND(a, 1);
     uint32_t m[N], a2[N];
 #pragma unroll
     for (int j = 0; j < N; ++j) a2[j] = a.l[j] << 1;
@@ -308,17 +452,15 @@ struct Field {
 #pragma unroll
     for (int k = 0; k < 2 * N - 1; ++k) {
       const int lo = k < N ? 0 : k - N + 1, hi = k < N ? k : N - 1;
-      const int nab = hi - lo + 1;                       // units: a doubled product counts twice
-      const int nmp = k < N ? k + 1 : nab;
-      const bool split = nab + nmp > FIT;
-      uint64_t upper = 0;
+      const bool cut = Col::plan.cut[k][1];
+      uint32_t aside = 0;
 #pragma unroll
       for (int i = lo; i <= hi; ++i) {
         const int j = k - i;
         if (i < j) acc = mad_wide(a.l[i], a2[j], acc);
         else if (i == j) acc = mad_wide(a.l[i], a.l[i], acc);
       }
-      if (split) { upper = acc >> L; acc &= (uint64_t)MASK; }
+      if (cut) aside = peel(acc);
 #pragma unroll
       for (int i = lo; i <= hi; ++i)
         if (i < k || k >= N) acc = mad_wide(m[i], F::P[k - i], acc);
@@ -329,7 +471,7 @@ struct Field {
         r.l[k - N] = (uint32_t)acc & MASK;
       }
       acc >>= L;
-      if (split) acc += upper;
+      if (cut) acc = unpeel(aside, acc);
     }
     r.l[N - 1] = (uint32_t)acc;
     KZG_AUDIT_PRODUCT(r);
@@ -340,23 +482,23 @@ struct Field {
   // needs 8p < R, true for all four fields).
   static KZG_HD E mul2(const E& a, const E& b, const E& c, const E& d) {
     static_assert(F::BITS + 3 <= L * N, "mul2 needs 8p < R");
+    using Col = Columns<F, 2, 1, false>;
+    KZG_AUDIT_OPERAND(a, 1); KZG_AUDIT_OPERAND(b, 1); KZG_AUDIT_OPERAND(c, 1); KZG_AUDIT_OPERAND(d, 1);
     uint32_t m[N];
     E r;
     uint64_t acc = 0;
 #pragma unroll
     for (int k = 0; k < 2 * N - 1; ++k) {
       const int lo = k < N ? 0 : k - N + 1, hi = k < N ? k : N - 1;
-      const int nab = hi - lo + 1;
-      const int nmp = k < N ? k + 1 : nab;
-      const bool split1 = 2 * nab > FIT;                 // between a*b and c*d
-      const bool split2 = (split1 ? nab : 2 * nab) + nmp > FIT;       // before m*p
-      uint64_t upper = 0;
+      const bool cut1 = Col::plan.cut[k][1];             // between a*b and c*d
+      const bool cut2 = Col::plan.cut[k][2];             // before m*p
+      uint32_t aside1 = 0, aside2 = 0;
 #pragma unroll
       for (int i = lo; i <= hi; ++i) acc = mad_wide(a.l[i], b.l[k - i], acc);
-      if (split1) { upper = acc >> L; acc &= (uint64_t)MASK; }
+      if (cut1) aside1 = peel(acc);
 #pragma unroll
       for (int i = lo; i <= hi; ++i) acc = mad_wide(c.l[i], d.l[k - i], acc);
-      if (split2) { upper += acc >> L; acc &= (uint64_t)MASK; }
+      if (cut2) aside2 = peel(acc);
 #pragma unroll
       for (int i = lo; i <= hi; ++i)
         if (i < k || k >= N) acc = mad_wide(m[i], F::P[k - i], acc);
@@ -367,7 +509,8 @@ struct Field {
         r.l[k - N] = (uint32_t)acc & MASK;
       }
       acc >>= L;
-      if (split1 || split2) acc += upper;
+      if (cut1) acc = unpeel(aside1, acc);
+      if (cut2) acc = unpeel(aside2, acc);
     }
     r.l[N - 1] = (uint32_t)acc;
     KZG_AUDIT_PRODUCT(r);
@@ -377,28 +520,28 @@ struct Field {
   // sum_{t<K} a[t]*b[t] with ONE Montgomery reduction: K*N^2 + N^2 + N multiply-adds instead of K*(2N^2 + N) --
   // the linear combinations of KZG.open (kzg.py:148-150) and of the prover's r(X).  Weak-normal (< 2p) in and out:
   // (K*4p^2 + m*p)/R < 2p needs 4K*p <= R (the static_assert rounds K up to a power of two, 16 at the most).  A column takes the a*b products of one term after the other and is cut
-  // (low L bits stay in the chain, the rest joins the outgoing carry) whenever the next group would pass its capacity.
+  // (the low word stays in the chain, the high word joins the outgoing carry) before a group that could carry it out.
   template <int K>
   static KZG_HD E dot(const E* a, const E* b) {
     static_assert(K >= 1 && K <= 16 && F::BITS + 2 + (K > 8 ? 4 : K > 4 ? 3 : K > 2 ? 2 : K > 1 ? 1 : 0) <= L * N, "dot needs 4K*p <= R");
+    using Col = Columns<F, K, 1, false>;
+#ifdef KZG_AUDIT_ON
+    for (int t = 0; t < K; ++t) { KZG_AUDIT_OPERAND(a[t], 1); KZG_AUDIT_OPERAND(b[t], 1); }
+#endif
     uint32_t m[N];
     E r;
     uint64_t acc = 0;
 #pragma unroll
     for (int k = 0; k < 2 * N - 1; ++k) {
       const int lo = k < N ? 0 : k - N + 1, hi = k < N ? k : N - 1;
-      const int nab = hi - lo + 1;                       // a*b products of ONE term in this column
-      const int nmp = k < N ? k + 1 : nab;
-      uint64_t upper = 0;
-      int used = 1;                                      // the incoming carry (< 2^(64-L)) counts as one product
+      uint32_t aside[K + 1] = {};
 #pragma unroll
       for (int t = 0; t < K; ++t) {
-        if (used + nab > FIT) { upper += acc >> L; acc &= (uint64_t)MASK; used = 1; }
+        if (Col::plan.cut[k][t]) aside[t] = peel(acc);
 #pragma unroll
         for (int i = lo; i <= hi; ++i) acc = mad_wide(a[t].l[i], b[t].l[k - i], acc);
-        used += nab;
       }
-      if (used + nmp > FIT) { upper += acc >> L; acc &= (uint64_t)MASK; used = 1; }
+      if (Col::plan.cut[k][K]) aside[K] = peel(acc);
 #pragma unroll
       for (int i = lo; i <= hi; ++i)
         if (i < k || k >= N) acc = mad_wide(m[i], F::P[k - i], acc);
@@ -409,7 +552,9 @@ struct Field {
         r.l[k - N] = (uint32_t)acc & MASK;
       }
       acc >>= L;
-      acc += upper;
+#pragma unroll
+      for (int t = 0; t <= K; ++t)
+        if (Col::plan.cut[k][t]) acc = unpeel(aside[t], acc);
     }
     r.l[N - 1] = (uint32_t)acc;
     KZG_AUDIT_PRODUCT(r);
