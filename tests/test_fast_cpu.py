@@ -33,6 +33,27 @@ def test_ntt_matches_the_reference_recursion(curve):
 
 
 @pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
+@pytest.mark.parametrize("log_n", [13, 19])
+@pytest.mark.parametrize("inverse", [False, True])
+def test_ntt_matches_the_c_oracle_at_size(curve, log_n, inverse):
+    """FC.ntt == CO.fft (oracle/kzg_oracle.c: the recursion of fft_ff.py:15-37 / :51-58 as written) at 2^13 and 2^19,
+    for a primitive root and an arbitrary w, on one thread and on several, over inputs that span [0, r) with the
+    values next to r planted.  tests/test_ntt_plans_gpu.py takes FC.ntt as its reference above 2^19, where the C
+    oracle needs many seconds; it may only because of this test (the test above stops at 2^10)."""
+    from kzg_snark_amd import _native       # int <-> limb marshalling only: no library is loaded
+    from oracle import c_oracle as CO
+    from ntt_helpers import edge_vector
+    cv = O.curve(curve)
+    n = 1 << log_n
+    raw = edge_vector(np.random.RandomState(19 + log_n), n, cv.r, _native)
+    for w in (cv.root_of_unity(n), 0x123456789abcdef0fedcba9876543210f00dfeed % cv.r):
+        want = CO.fft(curve, raw.copy(), w, inverse=inverse)
+        for threads in (1, min(max(FC.max_threads(), 2), 16)):
+            got = FC.ntt(curve, raw.copy(), w, inverse=inverse, threads=threads)
+            assert np.array_equal(got, want), (curve, log_n, inverse, hex(w)[:12], threads)
+
+
+@pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
 def test_setup_and_msm_match_the_oracle(curve):
     cv = O.curve(curve)
     L = 4 if curve == "bn254" else 6

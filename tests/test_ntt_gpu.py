@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import py_oracle as O
+from ntt_helpers import plant_edge_values as _plant_edge_values, uniform_below_r as _uniform_below_r
 
 pytestmark = pytest.mark.gpu
 
@@ -305,25 +306,6 @@ def test_ragged_lengths_at_size(native, curve, n):
         want = raw.copy()
         CO.fft(curve, want, w, inverse=inverse)
         assert np.array_equal(got, want), (n, inverse)
-
-
-def _uniform_below_r(rs, n, r):
-    """uint64[n,4] limbs of values spread over the WHOLE range [0, r): random 256-bit words with the top limb
-    folded below r's top limb (+1 where the lower limbs allow it), so near-r values occur -- the at-size inputs
-    of the older tests stop at 2^253."""
-    raw = rs.randint(0, 1 << 63, size=(n, 4), dtype=np.int64).astype(np.uint64) * np.uint64(2) \
-        + rs.randint(0, 2, size=(n, 4)).astype(np.uint64)
-    top = r >> 192
-    raw[:, 3] %= np.uint64(top)                      # value < top * 2^192 <= r
-    return raw
-
-
-def _plant_edge_values(raw, r, native):
-    n = raw.shape[0]
-    edge = [r - 1, r - 2, 0, 1, r - (1 << 20), (r - 1) // 2, (r + 1) // 2, r - 1]
-    pos = [0, 1, 2, 3, n // 2, n // 2 + 1, n - 2, n - 1]
-    raw[pos] = native.ints_to_limbs(edge)
-    return raw
 
 
 @pytest.mark.parametrize("curve,log_n", [("bls12_381", 20), ("bn254", 20), ("bls12_381", 24)])

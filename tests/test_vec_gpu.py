@@ -95,3 +95,54 @@ def test_poly_eval_at_the_tile_boundaries(native, curve):
                     assert ctx.poly_eval(n, da.data_ptr(), z) == want, (n, z, direct)
     finally:
         ctx.set_tuning("open_direct_tiles", 0)
+
+
+KZG_ERR_ARG = -1
+
+
+@pytest.mark.parametrize("curve", ["bls12_381", "bn254"])
+@pytest.mark.parametrize("n", [33, 1025])
+def test_lincomb_at_the_group_boundaries(native, curve, n):
+    """kzg_fr_vec_lincomb sums its terms in groups of DOT_G = 6 that share one Montgomery reduction (dot_upto in
+    csrc/poly.hip), up to MAXK = 64 terms: k = 1, 5, 6, 7, 12, 13, 63, 64 -- one short group, one and two full ones,
+    full ones followed by a single term, the limit and the limit less one.  Per k two calls against Python integers:
+      * mixed: scalars 0, 1, r-1 among random ones; lengths n, n - 1, n / 2, 1 and (from k = 5 on) one 0, so that
+        terms drop out of a group at different elements;
+      * extremes: every scalar r-1 and every vector r-1 at elements 0, 31, 32 and n-1, all lengths n -- each group,
+        the full ones of six included, then reduces the largest sum of products it can meet.
+    One term more than MAXK is refused with KZG_ERR_ARG."""
+    import torch
+    r = O.curve(curve).r
+    ctx = native.get_context(curve)
+    rng = random.Random(6400 + n)
+    kmax = 64
+    vecs = [[rng.randrange(r) for _ in range(n)] for _ in range(kmax)]
+    for v in vecs[1::3]:
+        v[0], v[1], v[n - 1] = r - 1, 0, 1
+    top = [list(v) for v in vecs]
+    for v in top:
+        for i in (0, 31, 32, n - 1):
+            v[i] = r - 1
+    d_vecs = [dev(native, v) for v in vecs]
+    d_top = [dev(native, v) for v in top]
+    out = torch.empty_like(d_vecs[0])
+    torch.cuda.synchronize()                 # torch's stream wrote them; the context runs on a stream of its own
+    len_cycle = [n, n // 2, n - 1, 0, n, 1, n]
+    for k in (1, 5, 6, 7, 12, 13, 63, 64):
+        lens = [len_cycle[j % len(len_cycle)] for j in range(k)]
+        sc = [(0, 1, r - 1, rng.randrange(r), rng.randrange(r))[(j + k) % 5] for j in range(k)]
+        ctx.vec_lincomb(n, [d.data_ptr() for d in d_vecs[:k]], lens, sc, out.data_ptr())
+        ctx.synchronize()
+        want = [sum(sc[j] * vecs[j][i] for j in range(k) if i < lens[j]) % r for i in range(n)]
+        assert host(native, out) == want, ("mixed", k)
+        ctx.vec_lincomb(n, [d.data_ptr() for d in d_top[:k]], [n] * k, [r - 1] * k, out.data_ptr())
+        ctx.synchronize()
+        want = [(r - 1) * sum(top[j][i] for j in range(k)) % r for i in range(n)]
+        assert host(native, out) == want, ("extremes", k)
+    before = host(native, out)
+    with pytest.raises(native.NativeError) as e:
+        ctx.vec_lincomb(n, [d_vecs[j % kmax].data_ptr() for j in range(kmax + 1)], [n] * (kmax + 1), [1] * (kmax + 1),
+                        out.data_ptr())
+    assert e.value.code == KZG_ERR_ARG
+    ctx.synchronize()
+    assert host(native, out) == before
