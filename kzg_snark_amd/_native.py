@@ -6,10 +6,10 @@ import ctypes
 import os
 from operator import methodcaller as _methodcaller
 
-# The commit pipeline runs three internal streams beside the caller's; HIP multiplexes streams
-# onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue serialise.
-# Must be in the environment before the HIP runtime initialises (import this module -- or set
-# the variable -- before the first torch.cuda / HIP call).
+# HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues per stream priority (default 4) and streams that share
+# a queue serialise.  The commit pipeline no longer depends on this (csrc/msm.hip: two internal streams, the long kernel
+# on a queue of the high-priority pool; measured equal at 4 and 8, EXPERIMENTS E3), and the line has no effect where
+# the variable is already set or the HIP runtime already runs: it only spreads the CALLER's streams over more queues.
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np  # noqa: E402

@@ -10,7 +10,7 @@
 //     multiples precomputed ALL windows feed ONE set of 2^(c-1) buckets: no
 //     per-window bucket sets, no doublings between windows at commit time.
 //     c = 20 (13 windows, 2^19 buckets) for keys of >= 2^18 points, else c = 16.
-//   commit, three stages on three internal streams (prep(p+1) | accumulate(p) | reduce(p-1) share
+//   commit, three stages on two internal streams (prep(p+1) | accumulate(p) | reduce(p-1) share
 //   the GPU; see "Commit pipeline" below and DESIGN.md 4.2):
 //     P prep        msm_prep.hip: scalar -> W signed c-bit digits (zero digits dropped,
 //                   kzg.py:113-114), table indices grouped by bucket, buckets ordered by length,
@@ -689,17 +689,33 @@ int srs_export(Ctx* c, const Srs* s, size_t start, size_t count, uint64_t* xy, u
                        : srs_export_t<Bls12_381>(c, s, start, count, xy, inf);
 }
 
-// Commit pipeline: three stages on three internal streams, up to four polynomials in flight.
+// Commit pipeline: three stages on two internal streams, up to four polynomials in flight.
 //   P  prep        digits, two-step partition, bucket order, slices (memory-bound, msm_prep.hip)
 //   A  accumulate  the mixed-addition kernel                        (ALU-bound, persistent)
 //   B  reduce      finalize, row/column sums, bit planes, copy-out  (latency-bound)
 // prep(p+1), accumulate(p) and reduce(p-1) run concurrently ON THE SAME SIMDs: A holds 2 waves x
-// 160 VGPRs of each, P and B workgroups are sized to fit into what is left.  The context's stream only
-// carries ordering: P waits for everything enqueued on it before the call (the scalars), and it
-// waits for P to have consumed the scalars, so later work on the context's stream (the next NTT)
-// can neither race with prep nor queue behind accumulate.  Every buffer belongs to a slot; the
-// host finishes a polynomial (Horner + one inversion) when its slot is recycled or on flush.
+// 160 VGPRs of each, P and B workgroups are sized to fit into what is left.
+// Streams that share a hardware queue run one after another, and a process has few queues (HIP's default is 4 per
+// stream priority, dealt round-robin to every stream of the process), so the pipeline needs only two and keeps the
+// long kernel off everybody else's:
+//   stream_a  accumulate only, created at the highest stream priority: the runtime keeps a pool of hardware queues per
+//             priority (EXPERIMENTS E3: normal-priority streams share queues 1-4, high-priority ones get 5-8), so
+//             neither the caller's stream nor the side stream can land on the queue that holds a 1.8 ms persistent
+//             kernel -- unless the caller itself works on high-priority streams
+//   stream_s  prep AND reduce ("side" work: ~1.1 ms alone, ~1.4 ms beside accumulate, per ~2.1 ms of accumulate).
+//             Reduce(p) waits for accumulate(p), so on a stream in order it has to be queued BEHIND prep(p+1): stage B of
+//             a polynomial is deferred (MsmWork::deferred) until the next polynomial's prep has been queued, or until
+//             somebody is about to wait for it (msm_queue_deferred).  The stream then runs prep(p+1), reduce(p),
+//             prep(p+2), reduce(p+1), ...: prep(p+2) starts when reduce(p) ends, ~0.9 ms into accumulate(p+1), and has
+//             that kernel's remaining ~1.2 ms for its ~0.55 ms.
+// The context's stream only carries ordering: P waits for everything enqueued on it before the call (the scalars), and
+// the scalars are copied into the slot on it, so later work on the context's stream (the next NTT) can neither race
+// with prep nor queue behind accumulate.  Every buffer belongs to a slot; the host finishes a polynomial (Horner + one
+// inversion) when its slot is recycled or on flush.
 constexpr int NSLOT = 4;
+#ifndef KZG_PIPE_PRIO_A      // A/B timing only (tools/build_variant.sh): 0 leaves stream_a at the default priority
+#define KZG_PIPE_PRIO_A 1
+#endif
 
 struct MsmSlot {
   DevBuf prep_ws, vals, bstart, order, slice_off, counter, chunk_rank;              // prep
@@ -719,7 +735,8 @@ struct MsmSlot {
 
 struct MsmWork {
   MsmSlot slot[NSLOT];
-  hipStream_t stream_p = nullptr, stream_a = nullptr, stream_b = nullptr;
+  hipStream_t stream_s = nullptr, stream_a = nullptr;   // side (prep + reduce), accumulate
+  int deferred = -1;           // slot whose stage B is not queued yet (at most one: the newest polynomial), or -1
   int next = 0;
   uint32_t acc_blocks = 0;     // grid of the persistent accumulate kernel
 };
@@ -750,11 +767,14 @@ void msm_free_work(Ctx* c) {
     for (hipEvent_t e : {sl.ev_in, sl.ev_p, sl.ev_a, sl.ev_b})
       if (e) hipEventDestroy(e);
   }
-  for (hipStream_t st : {w->stream_p, w->stream_a, w->stream_b})
+  for (hipStream_t st : {w->stream_s, w->stream_a})   // a deferred stage B is dropped with its slot: nobody can retire it
     if (st) hipStreamDestroy(st);
   delete w;
   c->msm_work = nullptr;
 }
+
+template <class C>
+static int msm_queue_deferred(Ctx* c, MsmWork* w);
 
 template <class C, int WB>
 static int msm_enqueue(Ctx* c, const Srs* s, const uint32_t* d_scalars, uint32_t n, MsmWork* w, int slot_idx) {
@@ -784,9 +804,10 @@ static int msm_enqueue(Ctx* c, const Srs* s, const uint32_t* d_scalars, uint32_t
   for (hipEvent_t* e : {&sl.ev_in, &sl.ev_p, &sl.ev_a, &sl.ev_b})
     if (!*e) KZG_HIP(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
   if (!w->stream_a) {
-    KZG_HIP(c, hipStreamCreateWithFlags(&w->stream_a, hipStreamNonBlocking));
-    KZG_HIP(c, hipStreamCreateWithFlags(&w->stream_p, hipStreamNonBlocking));
-    KZG_HIP(c, hipStreamCreateWithFlags(&w->stream_b, hipStreamNonBlocking));
+    int prio_least = 0, prio_greatest = 0;
+    KZG_HIP(c, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    KZG_HIP(c, hipStreamCreateWithPriority(&w->stream_a, hipStreamNonBlocking, KZG_PIPE_PRIO_A ? prio_greatest : 0));
+    KZG_HIP(c, hipStreamCreateWithFlags(&w->stream_s, hipStreamNonBlocking));
     // accumulate: 2 waves on every SIMD (4 workgroups of 2 waves per CU); KZG_ACC_WGS_PER_CU overrides
     int cus = 0;
     KZG_HIP(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
@@ -800,7 +821,7 @@ static int msm_enqueue(Ctx* c, const Srs* s, const uint32_t* d_scalars, uint32_t
   auto* bstart = static_cast<uint32_t*>(sl.bstart.p);
   auto* order = static_cast<uint32_t*>(sl.order.p);
   auto* slice_off = static_cast<uint32_t*>(sl.slice_off.p);
-  hipStream_t sp = w->stream_p, sa = w->stream_a, sb = w->stream_b;
+  hipStream_t sp = w->stream_s, sa = w->stream_a;
 
   // ---- stage P: prep
   // The scalars are first copied into the slot (n x 32 bytes on the context's stream, ~25 us at 2^20): the caller's
@@ -824,6 +845,8 @@ static int msm_enqueue(Ctx* c, const Srs* s, const uint32_t* d_scalars, uint32_t
     return rc;
   KZG_HIP(c, hipEventRecord(sl.ev_p, sp));
   if (!copy_scalars) KZG_HIP(c, hipStreamWaitEvent(c->stream, sl.ev_p, 0));   // the scalars are free again from here on
+  // the previous polynomial's stage B waits for its accumulate kernel: behind this prep, not in front of it
+  if ((rc = msm_queue_deferred<C>(c, w))) return rc;
 
   // ---- stage A: accumulate
   KZG_HIP(c, hipStreamWaitEvent(sa, sl.ev_p, 0));
@@ -838,7 +861,21 @@ static int msm_enqueue(Ctx* c, const Srs* s, const uint32_t* d_scalars, uint32_t
   KZG_HIP(c, hipGetLastError());
   KZG_HIP(c, hipEventRecord(sl.ev_a, sa));
 
-  // ---- stage B: reduce
+  // ---- stage B (msm_enqueue_reduce) goes on the side stream behind the NEXT polynomial's prep, or when somebody is
+  // about to wait for this slot
+  w->deferred = slot_idx;
+  return KZG_OK;
+}
+
+// ---- stage B: reduce, on the side stream
+template <class C, int WB>
+static int msm_enqueue_reduce(Ctx* c, MsmWork* w, MsmSlot& sl) {
+  using W = Win<WB>;
+  constexpr size_t PT = 4 * C::Fp::N * 4;
+  constexpr uint32_t NB = W::NB;
+  auto* order = static_cast<uint32_t*>(sl.order.p);
+  auto* slice_off = static_cast<uint32_t*>(sl.slice_off.p);
+  hipStream_t sb = w->stream_s;
   KZG_HIP(c, hipStreamWaitEvent(sb, sl.ev_a, 0));
 #ifndef KZG_TIMING_SKIP_REDUCE   // timing experiment only (results are wrong)
   {
@@ -866,6 +903,16 @@ static int msm_enqueue(Ctx* c, const Srs* s, const uint32_t* d_scalars, uint32_t
   KZG_HIP(c, hipMemcpyAsync(sl.h_tb, sl.tb.p, W::NPART * PT, hipMemcpyDeviceToHost, sb));
   KZG_HIP(c, hipEventRecord(sl.ev_b, sb));
   return KZG_OK;
+}
+
+// Queues the one stage B that is still held back.  Called once the next polynomial's prep is on the side stream, and by
+// every path that is about to wait for ev_b: an event that was never recorded would read as complete.
+template <class C>
+static int msm_queue_deferred(Ctx* c, MsmWork* w) {
+  if (w->deferred < 0) return KZG_OK;
+  MsmSlot& sl = w->slot[w->deferred];
+  w->deferred = -1;
+  return sl.win_bits == 20 ? msm_enqueue_reduce<C, 20>(c, w, sl) : msm_enqueue_reduce<C, 16>(c, w, sl);
 }
 
 // host: 2^LO * sum_b 2^b TR_b + sum_b 2^b TC_b + 2^(WB-1) * top; to affine, canonical words
@@ -907,6 +954,11 @@ static void msm_finish_host(const void* h_tb, uint64_t* out_xy, uint8_t* out_inf
 template <class C>
 static int msm_retire(Ctx* c, MsmSlot& sl) {
   if (!sl.pending) { sl.out_eval = nullptr; return KZG_OK; }
+  MsmWork* w = get_work(c);
+  if (w->deferred >= 0 && &w->slot[w->deferred] == &sl) {
+    int rc = msm_queue_deferred<C>(c, w);
+    if (rc) return rc;
+  }
   KZG_HIP(c, hipEventSynchronize(sl.ev_b));
   if (sl.win_bits == 20) msm_finish_host<C, 20>(sl.h_tb, sl.out_xy, sl.out_inf);
   else msm_finish_host<C, 16>(sl.h_tb, sl.out_xy, sl.out_inf);
@@ -921,7 +973,7 @@ static int msm_retire(Ctx* c, MsmSlot& sl) {
 template <class C>
 static int commit_flush_t(Ctx* c) {
   MsmWork* w = get_work(c);
-  int rc = KZG_OK;
+  int rc = msm_queue_deferred<C>(c, w);
   for (int k = 0; k < NSLOT; ++k) {               // drain in issue order
     MsmSlot& sl = w->slot[(w->next + k) % NSLOT];
     int r2 = msm_retire<C>(c, sl);
