@@ -81,7 +81,8 @@ int kzg_ctx_synchronize(kzg_ctx* ctx);
  *   "open_tile_threads"  threads per tile of the opening's scan, 128 | 256 (default: 256 alone, 128 beside one)
  *   "open_direct_tiles"  tile count up to which every tile sums all tile aggregates above it (default 1024)
  *   "open_domain_chunk"  vectors per chunk of kzg_open_domain*, 1..1024 (default: as many as ~2 GiB of scratch holds)
- *   "open_cosets_chunk"  vectors per chunk of kzg_open_cosets*, 1..1024 (default: as many as ~2 GiB of scratch holds) */
+ *   "open_cosets_chunk"  vectors per chunk of kzg_open_cosets*, 1..1024 (default: as many as ~2 GiB of scratch holds)
+ *   "recover_chunk"      vectors per chunk of kzg_recover_cosets*, 1..1024 (default: as many as ~2 GiB of scratch holds) */
 int kzg_ctx_set_tuning(kzg_ctx* ctx, const char* key, int64_t value);
 
 /* ---- NTT: replaces fft_ff (fft_ff.py:3-37) and ifft_ff (fft_ff.py:39-58) -------------
@@ -325,6 +326,32 @@ int kzg_verify_cosets(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uin
                       const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
                       const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy,
                       const uint8_t* proof_inf, size_t K, const uint64_t rho[4], uint64_t* out_xy, uint8_t* out_inf);
+/* ---- coset recovery: b polynomials of degree < n back from their values on any K >= n/l cosets ------------------
+ * The domain {w^t, t < N}, N = 2^log_N, has C = N/l cosets of l = 2^log_l points in kzg_open_cosets' numbering
+ * (coset i = {w^(i + k C), k < l}, the roots of X^l - u^i, u = w^l).  K distinct cosets are given, M are missing:
+ *   V(Y) = prod_(i in M) (Y - u^i), Z(X) = V(X^l): zero exactly on the missing cosets; Z(w^t) = DFT_C(V)[t mod C]
+ *   E = the given values, 0 where missing: E Z = p Z on the whole domain and deg(p Z) < N, so p Z = IDFT_N(E Z)
+ *   on the shifted domain s w^t (s the field's generator, s^N != 1) Z has no zero: p(s w^t) = (p Z)(s w^t) / Z(s w^t)
+ *   p = IDFT_N of that, coefficient t times s^-t; V is a product tree built on the device in O(C log^2 C)
+ *   the values lie on a polynomial of degree < n iff coefficients n .. N-1 vanish (exact; always so for K l = n)
+ * This is recover_cells_and_kzg_proofs of EIP-7594 up to the proofs, which kzg_open_cosets_device gives from d_coeffs.
+ *   coset_idx  [K] host memory in both forms, cell k of every polynomial is coset coset_idx[k], in any order
+ *   values     [b][K][l][4] canonical limbs (reduced by the caller): what kzg_open_cosets' eval_out holds per coset
+ *   out_coeffs [b][n][4];  out_consistent [b], host memory: 1 if the tail is zero, else 0 (the n coefficients of
+ *              the degree < N interpolant are written all the same)
+ * The device form takes device pointers for values and coefficients (32-byte aligned, used on the context's stream)
+ * and synchronises like the host form, because it returns the flags.  One index set serves the whole batch: V, two
+ * size-C transforms and C inversions per call; three size-N transforms and four element-wise passes per polynomial,
+ * in chunks that bound the scratch (tuning key "recover_chunk").
+ * Ranges: 0 <= log_l <= 12, log_l <= log_n <= log_N <= 21, log_l < log_N, b >= 1, K <= C.  KZG_ERR_ARG, before
+ * anything is queued: a range violation, K l < n, an index >= C, a repeated index, a w that is not a primitive N-th
+ * root, a misaligned device pointer. */
+int kzg_recover_cosets(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
+                       const uint32_t* coset_idx, size_t K, const uint64_t* values, size_t b, uint64_t* out_coeffs,
+                       uint8_t* out_consistent);
+int kzg_recover_cosets_device(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
+                              const uint32_t* coset_idx, size_t K, const void* d_values, size_t b, void* d_coeffs,
+                              uint8_t* out_consistent);
 /* ---- KZG.open on ONE polynomial set partitioned by coefficient range across GPUs ----------------
  * Rank g holds coefficients [lo_g, hi_g) of every polynomial (the same ranges for all) and a key
  * shard.  kzg_open_shard_begin combines the slices (sum xi^(i+1) p_i) and returns the slice
@@ -381,13 +408,15 @@ int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size
  * kzg_domain_table_create), "open_domain" (ONE per kzg_open_domain*: every chunk, transform and copy), "coset_table"
  * (one per kzg_coset_table_create), "open_cosets" (ONE per kzg_open_cosets*), "open_coset_poly" (ONE per
  * kzg_open_coset*: combination, division and remainder), "verify_cosets" (ONE per kzg_verify_cosets: the whole call on
- * the context's stream; its MSMs also report under the msm_* names).  kzg_prof_read synchronises the
+ * the context's stream; its MSMs also report under the msm_* names), "recover_cosets" (ONE per kzg_recover_cosets*:
+ * the product tree and every chunk).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.
  * Two names are not spans: "msm_accumulate_shader_mhz" and "ntt_pass_shader_mhz" return (in *total_ms) the shader
  * clock in MHz the accumulate / NTT kernel ran at since the last reset -- s_memtime over s_memrealtime ticks of its
  * first wave -- and *count = 1 when a launch has reported, 0 otherwise; "ntt_tile_log" returns log2 of the LDS
  * tile the last two-pass transform took; "verify_device_bytes" the bytes of device memory the last kzg_verify_cosets
- * asked for (commit-pipeline slots not included). */
+ * asked for (commit-pipeline slots not included); "recover_leaf" the number of linear factors one leaf of
+ * kzg_recover_cosets' product tree multiplies out. */
 int kzg_prof_enable(kzg_ctx* ctx, int on);
 int kzg_prof_reset(kzg_ctx* ctx);
 int kzg_prof_read(kzg_ctx* ctx, const char* name, double* total_ms, uint64_t* count);

@@ -102,6 +102,10 @@ SIGNATURES = {
                                              _vp, _vp, _vp, _vp, _vp, _vp]),
     "kzg_verify_cosets": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_size_t,
                                          _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "kzg_recover_cosets": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
+                                          ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
+    "kzg_recover_cosets_device": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
+                                                 ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
 }
 
 
@@ -245,7 +249,7 @@ class Context:
 
     def set_tuning(self, key, value):
         """Fix a choice the library otherwise makes from what is resident ("ntt_tile_log", "open_tile_threads",
-        "open_direct_tiles"; 0 = the library's choice).  Results never depend on it."""
+        "open_direct_tiles", the "*_chunk" keys; 0 = the library's choice).  Results never depend on it."""
         self._check(lib().kzg_ctx_set_tuning(self._h, key.encode(), int(value)))
 
     # ---- measurement hooks
@@ -456,6 +460,30 @@ class Context:
         # the library retires every pipeline slot before it returns, as kzg_commit_flush does
         self._inflight.clear()
         return out_xy, out_inf
+
+    # ---- coset recovery
+    def recover_cosets(self, log_n, log_N, log_l, w, coset_idx, values, b, d_coeffs=None):
+        """b coefficient vectors of 2^log_n elements from their values on the K cosets coset_idx (uint32[K]) of the
+        domain {w^t, t < 2^log_N}: values uint64[b, K, l, 4] (host) -> (coeffs uint64[b, n, 4], consistent uint8[b]).
+        With d_coeffs (a device pointer to b * n * 32 bytes) `values` is a device pointer as well, the coefficients
+        stay on the device and coeffs is None.  consistent[j] = 0: the values of vector j lie on no polynomial of
+        degree < n."""
+        coset_idx = np.ascontiguousarray(coset_idx, dtype=np.uint32).reshape(-1)
+        K, b = coset_idx.size, int(b)
+        ok = np.zeros(max(b, 1), dtype=np.uint8)
+        w_words = _as_vp(int_to_words(int(w)))
+        if d_coeffs is not None:
+            self._check(lib().kzg_recover_cosets_device(self._h, int(log_n), int(log_N), int(log_l), w_words,
+                                                        _as_vp(coset_idx), K, _as_vp(values), b, _as_vp(d_coeffs),
+                                                        _as_vp(ok)))
+            return None, ok[:b]
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        if values.size != b * K * (4 << int(log_l)):
+            raise ValueError("recover_cosets: values is not [b][K][l][4]")
+        coeffs = np.zeros((max(b, 1), 1 << int(log_n), 4), dtype=np.uint64)
+        self._check(lib().kzg_recover_cosets(self._h, int(log_n), int(log_N), int(log_l), w_words, _as_vp(coset_idx),
+                                             K, _as_vp(values), b, _as_vp(coeffs), _as_vp(ok)))
+        return coeffs[:b], ok[:b]
 
     # ---- commit / open on host buffers
     def commit(self, srs, scalars, lens, stride):

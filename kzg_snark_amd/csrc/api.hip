@@ -166,6 +166,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
   hipFree(c->lagr_tmp.p);
   hipFree(c->dom_tmp.p);
   hipFree(c->ver_tmp.p);
+  hipFree(c->rec_tmp.p);
   for (auto& b : c->poly_tmp) hipFree(b.p);
   for (auto s : c->aux_streams) hipStreamDestroy(s);
   for (auto e : c->aux_events) hipEventDestroy(e);
@@ -224,6 +225,9 @@ int kzg_ctx_set_tuning(kzg_ctx* ctx, const char* key, int64_t value) {
   } else if (k == "open_cosets_chunk") {
     if (value < 0 || value > 1024) return set_err(c, KZG_ERR_ARG, "open_cosets_chunk: 0 .. 1024");
     c->tune_open_cosets_chunk = (int)value;
+  } else if (k == "recover_chunk") {
+    if (value < 0 || value > 1024) return set_err(c, KZG_ERR_ARG, "recover_chunk: 0 .. 1024");
+    c->tune_recover_chunk = (int)value;
   } else {
     return set_err(c, KZG_ERR_ARG, "kzg_ctx_set_tuning: unknown key");
   }
@@ -719,6 +723,28 @@ int kzg_verify_cosets(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uin
                        out_xy, out_inf);
 }
 
+int kzg_recover_cosets(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
+                       const uint32_t* coset_idx, size_t K, const uint64_t* values, size_t b, uint64_t* out_coeffs,
+                       uint8_t* out_consistent) {
+  if (!ctx || !w || !coset_idx || !values || !out_coeffs || !out_consistent) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return recover_cosets(c, log_n, log_N, log_l, reinterpret_cast<const uint32_t*>(w), coset_idx, K,
+                        reinterpret_cast<const uint32_t*>(values), /*host_ptrs=*/true, b,
+                        reinterpret_cast<uint32_t*>(out_coeffs), out_consistent);
+}
+
+int kzg_recover_cosets_device(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
+                              const uint32_t* coset_idx, size_t K, const void* d_values, size_t b, void* d_coeffs,
+                              uint8_t* out_consistent) {
+  if (!ctx || !w || !coset_idx || !d_values || !d_coeffs || !out_consistent) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return recover_cosets(c, log_n, log_N, log_l, reinterpret_cast<const uint32_t*>(w), coset_idx, K,
+                        static_cast<const uint32_t*>(d_values), /*host_ptrs=*/false, b,
+                        static_cast<uint32_t*>(d_coeffs), out_consistent);
+}
+
 #define KZG_VEC_ENTER()                          \
   if (!ctx) return KZG_ERR_ARG;                  \
   Ctx* c = &ctx->c;                              \
@@ -809,6 +835,11 @@ int kzg_prof_read(kzg_ctx* ctx, const char* name, double* total_ms, uint64_t* co
   if (std::string(name) == "verify_device_bytes") {   // not a span: device memory the last kzg_verify_cosets asked for
     *total_ms = (double)c->ver_last_bytes;
     *count = c->ver_last_bytes ? 1 : 0;
+    return KZG_OK;
+  }
+  if (std::string(name) == "recover_leaf") {   // not a span: linear factors per leaf of kzg_recover_cosets' product tree
+    *total_ms = (double)recover_leaf_width();
+    *count = 1;
     return KZG_OK;
   }
   if (std::string(name) == "ntt_tile_log") {   // not a span: log2 of the LDS tile the last transform took

@@ -1,5 +1,5 @@
 // internal.h -- library-private declarations shared by the translation units of
-// libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, poly.hip, verify.hip).
+// libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, poly.hip, verify.hip, recover.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,6 +64,7 @@ struct Ctx {
   DevBuf lagr_tmp;        // lagrange.hip: combined values, denominators, inverses, quotient, partial sums
   DevBuf dom_tmp;         // domain.hip: G1 transform buffers and the Fr vectors of one chunk of kzg_open_domain
   DevBuf ver_tmp;         // verify.hip: staged claims, proof records, weights, power tables, partial sums
+  DevBuf rec_tmp;         // recover.hip: power tables, the product tree, Z and its inverses, one chunk of vectors
   size_t ver_last_bytes = 0;              // what the last kzg_verify_cosets carved out of ver_tmp (kzg_prof_read)
   uint32_t ver_lds_attr_set = 0;          // per ver_cell_kernel instantiation, as ntt_lds_attr_set
   size_t open_shard_n = 0;                // slice length between kzg_open_shard_begin / _finish
@@ -74,6 +75,7 @@ struct Ctx {
   int tune_open_direct_max = 0;           // tiles up to which every tile sums all aggregates above it
   int tune_open_domain_chunk = 0;         // vectors per chunk of kzg_open_domain
   int tune_open_cosets_chunk = 0;         // vectors per chunk of kzg_open_cosets
+  int tune_recover_chunk = 0;             // vectors per chunk of kzg_recover_cosets
   int last_ntt_tile_log = 0;              // what the last transform used (kzg_prof_read "ntt_tile_log")
   void* msm_work = nullptr;               // MsmWork (msm.hip)
   bool prof_on = false;

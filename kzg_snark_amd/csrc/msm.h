@@ -101,6 +101,13 @@ int verify_cosets(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const
                   const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy, const uint8_t* proof_inf,
                   size_t K, const uint32_t* rho_words, uint64_t* out_xy, uint8_t* out_inf);
 
+// recover.hip: b coefficient vectors of n elements from their values on K of the N/l cosets.
+// coset_idx and out_consistent in host memory; values / coeffs in host (host_ptrs) or device memory.  Synchronises.
+int recover_cosets(Ctx* c, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint32_t* w_words,
+                   const uint32_t* coset_idx, size_t K, const uint32_t* values, bool host_ptrs, size_t b,
+                   uint32_t* coeffs, uint8_t* out_consistent);
+uint32_t recover_leaf_width();     // linear factors a leaf of the product tree multiplies out
+
 int open_shard_begin_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                             const uint32_t* z_words, const uint32_t* xi_words, uint64_t* chunk_eval_out);
 int open_shard_finish_device(Ctx* c, const uint32_t* z_words, const uint32_t* carry_words, int first_rank,

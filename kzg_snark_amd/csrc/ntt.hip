@@ -600,7 +600,9 @@ int get_domain(Ctx* c, uint32_t log_n, const uint32_t* w_words, int inverse, Ntt
   for (auto& d : c->domains)
     if (d.log_n == log_n && d.inverse == inverse && memcmp(d.w, w_words, 32) == 0) { dom = &d; break; }
   if (!dom) {
-    if (c->domains.size() >= 8) {   // evict least recently used
+    // 64: a product tree of kzg_recover_cosets visits up to 15 sizes in both directions (a domain's tables hold about
+    // sqrt(n) elements), and a call must not evict what the next one needs
+    if (c->domains.size() >= 64) {   // evict least recently used
       size_t victim = 0;
       for (size_t i = 1; i < c->domains.size(); ++i)
         if (c->domains[i].last_use < c->domains[victim].last_use) victim = i;

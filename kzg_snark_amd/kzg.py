@@ -608,6 +608,95 @@ class KZG:
                   for j in range(len(coeffs))]
         return proofs, values
 
+    # ---- coset recovery: the polynomial back from any n/l of its N/l cosets (recover_cells_and_kzg_proofs of EIP-7594)
+    def _recover_call(self, coset_indices, values, l, n, N, w):
+        """Host-side checks of recover_cosets*, before any device work: -> (uint32 indices, uint64[b, K, l, 4] values,
+        b, log_n, log_N, log_l, w)."""
+        log_l = self._log2_exact(l, "coset size")
+        l = 1 << log_l
+        if log_l > self._COSET_MAX_LOG_L:
+            raise ValueError(f"coset size {l} exceeds 2^{self._COSET_MAX_LOG_L}")
+        log_n = self._log2_exact(n, "degree bound n")
+        n = 1 << log_n
+        N = 2 * n if N is None else int(N)
+        if N < n or N < 2 or N & (N - 1) or N > 2 * self._DOMAIN_MAX:
+            raise ValueError(f"N = {N} is not a power of two in [max(n, 2), 2^21]")
+        if l > n or l >= N:
+            raise ValueError(f"coset size {l} exceeds n = {n} or is not below N = {N}")
+        log_N, w = self._domain(N, w)
+        cosets = N // l
+        idx = [int(i) for i in coset_indices]
+        K = len(idx)
+        if K * l < n:
+            raise ValueError(f"{K} cosets of {l} values cannot determine a polynomial of degree < {n}")
+        if any(i < 0 or i >= cosets for i in idx):
+            raise ValueError(f"a coset index is outside [0, {cosets})")
+        if len(set(idx)) != K:
+            raise ValueError("a coset index is repeated")
+        b = len(values)
+        if b < 1:
+            raise ValueError("recover_cosets needs at least one polynomial")
+        r = self.curve_order
+        flat = []
+        for j, cells in enumerate(values):
+            if len(cells) != K:
+                raise ValueError(f"polynomial {j} has {len(cells)} cells for {K} coset indices")
+            for cell in cells:
+                if len(cell) != l:
+                    raise ValueError(f"a cell of polynomial {j} has {len(cell)} values, not l = {l}")
+                flat.extend(int(v) % r for v in cell)
+        arr = _native.ints_to_limbs(flat).reshape(b, K, l, 4)
+        return np.asarray(idx, dtype=np.uint32), arr, b, log_n, log_N, log_l, w
+
+    @staticmethod
+    def _first_inconsistent(ok, n):
+        bad = [j for j, f in enumerate(ok) if not f]
+        if bad:
+            raise ValueError(f"recover_cosets: the values of polynomial {bad[0]} lie on no polynomial of degree < {n}")
+
+    def recover_cosets(self, coset_indices, values, l, n, N=None, w=None):
+        """The b polynomials of degree < n whose values on the cosets coset_indices[k] of {w^t, t < N} (open_cosets'
+        numbering: coset i is {w^(i + k N/l), k < l}) are values[j][k], any K >= n/l distinct cosets in any order:
+        b coefficient lists of length n.  ValueError names the first polynomial whose values lie on no polynomial of
+        degree < n.  N defaults to 2n, w to Fq.root_of_unity(N)."""
+        idx, arr, b, log_n, log_N, log_l, w = self._recover_call(coset_indices, values, l, n, N, w)
+        coeffs, ok = self._context().recover_cosets(log_n, log_N, log_l, w, idx, arr, b)
+        self._first_inconsistent(ok, 1 << log_n)
+        ints = _native.limbs_to_ints(np.ascontiguousarray(coeffs).reshape(-1, 4))
+        n = 1 << log_n
+        return [ints[j * n:(j + 1) * n] for j in range(b)]
+
+    def recover_cosets_and_open(self, ck_or_table, coset_indices, values, l, n=None, w=None, N=None):
+        """recover_cosets followed by open_cosets_each(..., with_values=True) on the recovered polynomials, whose
+        coefficients never leave the device: (proofs, values) of all N/l cosets of each polynomial.  n defaults to
+        the table's domain size, else to N/2 (N given) or K l."""
+        if isinstance(ck_or_table, LagrangeKey):
+            raise TypeError("recover_cosets_and_open needs a monomial key or a coset table, not a LagrangeKey")
+        if isinstance(ck_or_table, DomainTable):
+            if n is not None and int(n) != ck_or_table.n:
+                raise ValueError(f"n = {n} differs from the table's domain size {ck_or_table.n}")
+            n = ck_or_table.n
+        elif n is None:
+            n = int(N) // 2 if N is not None else len(coset_indices) * int(l)
+        idx, arr, b, log_n, log_N, log_l, w = self._recover_call(coset_indices, values, l, n, N, w)
+        n, l = 1 << log_n, 1 << log_l
+        # what open_cosets asks on top (_fk20_call runs again, on the sizes alone)
+        self._fk20_call("recover_cosets_and_open", ck_or_table, [], n, w, l, 1 << log_N)
+        table = self._coset_table_for(ck_or_table, n, l)
+        ctx = self._context()
+        import torch
+        dev = f"cuda:{ctx.device}"
+        d_vals = torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).to(dev)
+        d_coeffs = torch.empty((b, n, 4), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(ctx.device)
+        _, ok = ctx.recover_cosets(log_n, log_N, log_l, w, idx, d_vals.data_ptr(), b, d_coeffs=d_coeffs.data_ptr())
+        self._first_inconsistent(ok, n)
+        xy, inf, ev = ctx.open_cosets(table.table, d_coeffs.data_ptr(), [n] * b, n, log_N, w, device=True, evals=True)
+        proofs = [self._points(xy[j], inf[j]) for j in range(b)]
+        cosets = (1 << log_N) // l
+        ints = _native.limbs_to_ints(np.ascontiguousarray(ev).reshape(-1, 4))
+        return proofs, [[[ints[(j * cosets + i) * l + k] for k in range(l)] for i in range(cosets)] for j in range(b)]
+
     def _coset_root(self, l, zeta):
         """zeta for cosets of l points: Fq.root_of_unity(l) by default; a given one must be a primitive l-th root."""
         r = self.curve_order
