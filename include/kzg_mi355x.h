@@ -416,7 +416,10 @@ int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size
  * first wave -- and *count = 1 when a launch has reported, 0 otherwise; "ntt_tile_log" returns log2 of the LDS
  * tile the last two-pass transform took; "verify_device_bytes" the bytes of device memory the last kzg_verify_cosets
  * asked for (commit-pipeline slots not included); "recover_leaf" the number of linear factors one leaf of
- * kzg_recover_cosets' product tree multiplies out. */
+ * kzg_recover_cosets' product tree multiplies out; "msm_accumulate_tail_us" and "msm_accumulate_exit_spread_us"
+ * return, in microseconds averaged over the *count accumulate launches since the last reset, how long after the
+ * MEAN exit of its waves the last wave of a launch left (the time its SIMDs stand half empty or idle) and how long
+ * after the FIRST -- for launches of one grid size that do not overlap (those of one context never do). */
 int kzg_prof_enable(kzg_ctx* ctx, int on);
 int kzg_prof_reset(kzg_ctx* ctx);
 int kzg_prof_read(kzg_ctx* ctx, const char* name, double* total_ms, uint64_t* count);

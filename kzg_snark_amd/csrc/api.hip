@@ -804,8 +804,8 @@ int kzg_prof_enable(kzg_ctx* ctx, int on) {
   if (!ctx) return KZG_ERR_ARG;
   Ctx* c = &ctx->c;
   if (on && !c->clk_probe) {
-    KZG_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->clk_probe), 32));
-    KZG_HIP(c, hipMemset(c->clk_probe, 0, 32));
+    KZG_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->clk_probe), CLK_WORDS * 8));
+    KZG_HIP(c, hipMemset(c->clk_probe, 0, CLK_WORDS * 8));
   }
   c->prof_on = on != 0;
   return KZG_OK;
@@ -821,7 +821,7 @@ int kzg_prof_reset(kzg_ctx* ctx) {
     sp.total_ms = 0;
     sp.count = 0;
   }
-  if (c->clk_probe) KZG_HIP(c, hipMemset(c->clk_probe, 0, 32));
+  if (c->clk_probe) KZG_HIP(c, hipMemset(c->clk_probe, 0, CLK_WORDS * 8));
   return KZG_OK;
 }
 
@@ -845,6 +845,20 @@ int kzg_prof_read(kzg_ctx* ctx, const char* name, double* total_ms, uint64_t* co
   if (std::string(name) == "ntt_tile_log") {   // not a span: log2 of the LDS tile the last transform took
     *total_ms = (double)c->last_ntt_tile_log;
     *count = c->last_ntt_tile_log ? 1 : 0;
+    return KZG_OK;
+  }
+  const bool acc_tail = std::string(name) == "msm_accumulate_tail_us", acc_spread = std::string(name) == "msm_accumulate_exit_spread_us";
+  if (acc_tail || acc_spread) {   // not a span: when the waves of msm_accumulate left, microseconds per launch
+    unsigned long long t[CLK_WORDS] = {0};
+    if (c->clk_probe) KZG_HIP(c, hipMemcpy(t, c->clk_probe, sizeof(t), hipMemcpyDeviceToHost));
+    const unsigned long long waves = t[CLK_ACC_WAVES], launches = t[CLK_ACC_LAUNCHES];
+    if (launches && waves) {                                    // launches of one grid size
+      // sums of 100 MHz ticks, formed modulo 2^64: the differences are small and exact
+      const unsigned long long ticks = acc_tail ? (waves * t[CLK_ACC_EXIT_LAST] - t[CLK_ACC_EXIT_SUM]) / waves   // last - mean
+                                                : t[CLK_ACC_EXIT_LAST] - t[CLK_ACC_EXIT_FIRST];                  // last - first
+      *total_ms = (double)ticks / 100.0 / (double)launches;
+      *count = launches;
+    }
     return KZG_OK;
   }
   if (acc_clk || ntt_clk) {   // not a span: the shader clock (MHz) the kernel's probing wave ran at

@@ -30,7 +30,11 @@
 // and 64-bit addition cost three: 21 VALU instructions fewer per mul / sqr, 44 per mul2, 9450 -> 9136 instructions
 // in msm_accumulate_kernel<Bls12_381, 20> (tools/isa_histogram.py, profiles/r05_isa_histograms.txt); measured,
 // 0.892 -> 0.849 G VALU wave-instructions per accumulate launch; +3.8 % commits/s on the box of the A/B
-// (EXPERIMENTS.md E1, round 5).
+// (EXPERIMENTS.md E1, round 5).  The multiply-add's weight 2^(32-L) must stay out of the optimiser's sight: the
+// multiply-add of a cut is one asm statement with the weight as an inline constant (Field::unpeel), where round 5
+// defined the weight in an SGPR by an asm statement per cut: 9136 -> 9179 instructions with the exit probe of
+// msm.hip, s_mov_b32 141 -> 86, VALU count unchanged; +2.9 % commits/s (profiles/r07_isa_histograms.txt,
+// profiles/r07_cut_ab.txt, EXPERIMENTS.md E1, round 7).
 //
 // What the multipliers require of their operands is NOT "limbs < 2^L" but three things:
 //  (1) per column, the product units stay within FIT = 2^(64-2L): a product of two limbs below 2^L is one unit, and
@@ -149,6 +153,16 @@ static KZG_HD uint64_t mad_wide(uint32_t a, uint32_t b, uint64_t c) {
 #endif
   return r;
 }
+
+// -DKZG_CUT_WEIGHT_CONST only (the other form of a cut's weight, Field::unpeel): the constant 1, which the device
+// code must not see as a constant.  It exists in the DEVICE pass only, so the host side neither declares nor
+// registers it: the library has no relocatable device code, every translation unit is a code object of its own with
+// its own copy, initialised when the code object is loaded.  Not `static`: an internal variable is folded to its
+// initialiser.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(KZG_NO_CHAIN_PIN) && defined(KZG_CUT_WEIGHT_CONST)
+#define KZG_CUT_WEIGHT_WORD 1
+__constant__ uint32_t cut_weight_unit = 1u;
+#endif
 
 template <class F>
 struct Fe {
@@ -273,23 +287,31 @@ struct Field {
   }
 
   // A cut (ColumnPlan): the chain goes on from its low word, the high word waits for the outgoing carry, which it
-  // joins by ONE multiply-add, hi * 2^(32-L) + carry.  The weight reaches that multiply-add through an empty asm
-  // statement (an s_mov_b32 per cut): a factor the optimiser can see is turned into
+  // joins by ONE multiply-add, hi * 2^(32-L) + carry.  A weight the optimiser can see is turned into
   // ((acc >> L) & ~(2^(32-L) - 1)) + carry -- a 64-bit shift, two ands and a 64-bit addition per cut, more than
-  // the cut by shift and mask that this replaces.  One definition per cut, not per product: a weight that stays
-  // live costs the 168-VGPR reduce kernels a spilled dword (tools/kernel_resources.py).  The per-cut s_mov_b32 and
-  // s_nop are not free -- the per-product form measured +8 % where this one gives +3.8 % (EXPERIMENTS.md E1).
+  // the cut by shift and mask that this replaces -- so on the device the multiply-add is ONE asm statement with the
+  // weight as an inline constant of the instruction (4 for L = 30): no s_mov_b32 per cut, nothing that stays live in
+  // a register (the 168-VGPR reduce kernels have none to give).  -DKZG_CUT_WEIGHT_CONST builds the other form that
+  // costs no register: no asm at all, the weight is cut_weight_unit << (32 - L) read from constant memory (above),
+  // one s_load_dword and one s_lshl_b32 per KERNEL.  Both beat round 5's asm definition of the weight per cut; the
+  // asm form measured +2.9 %, the constant-memory form +2.2 % (EXPERIMENTS.md E1, round 7).
+  // The host (and KZG_NO_CHAIN_PIN) keeps the plain constant.
   static KZG_HD uint32_t peel(uint64_t& acc) {
     const uint32_t h = (uint32_t)(acc >> 32);
     acc = (uint32_t)acc;
     return h;
   }
   static KZG_HD uint64_t unpeel(uint32_t h, uint64_t carry) {
-    uint32_t weight = 1u << (32 - L);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(KZG_NO_CHAIN_PIN)
-    asm volatile("" : "+s"(weight));
+#if defined(KZG_CUT_WEIGHT_WORD)
+    return mad_wide(h, cut_weight_unit << (32 - L), carry);
+#elif defined(__HIP_DEVICE_COMPILE__) && !defined(KZG_NO_CHAIN_PIN)
+    static_assert((1u << (32 - L)) <= 64, "the weight must be an inline constant of the instruction");
+    uint64_t r, carry_out;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry_out) : "v"(h), "n"(1u << (32 - L)), "v"(carry));
+    return r;
+#else
+    return mad_wide(h, 1u << (32 - L), carry);
 #endif
-    return mad_wide(h, weight, carry);
   }
 
 #ifdef KZG_AUDIT_ON

@@ -48,6 +48,16 @@ struct DevBuf {
   size_t cap = 0;
 };
 
+// words of Ctx::clk_probe
+enum : int {
+  CLK_ACC_LAUNCHES = 4,     // launches of msm_accumulate that reported when their waves left
+  CLK_ACC_EXIT_SUM = 5,     // sum of the exit times of all their waves
+  CLK_ACC_EXIT_FIRST = 6,   // sum over the launches of the first wave's exit time
+  CLK_ACC_EXIT_LAST = 7,    // ... and of the last wave's
+  CLK_ACC_WAVES = 8,        // waves per launch
+  CLK_WORDS = 16
+};
+
 struct Ctx {
   int curve = 0;
   int device = 0;
@@ -80,7 +90,9 @@ struct Ctx {
   void* msm_work = nullptr;               // MsmWork (msm.hip)
   bool prof_on = false;
   std::vector<ProfSpan> prof;
-  unsigned long long* clk_probe = nullptr;   // [4] shader-clock / 100 MHz ticks of one wave of msm_accumulate ([0..1]) and of ntt_pass ([2..3]); profiling only
+  // [CLK_WORDS] profiling only: shader-clock / 100 MHz ticks of one wave of msm_accumulate ([0..1]) and of ntt_pass
+  // ([2..3]); from CLK_ACC_LAUNCHES on, when the waves of msm_accumulate left (100 MHz ticks, sums over every launch)
+  unsigned long long* clk_probe = nullptr;
   std::vector<hipStream_t> aux_streams;   // commit pipeline
   std::vector<hipEvent_t> aux_events;
 };

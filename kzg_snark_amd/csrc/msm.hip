@@ -299,6 +299,21 @@ __global__ __launch_bounds__(128, 3) void msm_accumulate_kernel(const uint32_t* 
         atomicAdd(clk, (unsigned long long)(clock64() - c0));
         atomicAdd(clk + 1, (unsigned long long)(wall_clock64() - w0));
       }
+      // profiling only: when every wave of the launch left, on the 100 MHz clock (the kernel ends with its last wave).
+      // The word behind the chunk counter counts the exits of this launch (stage P zeroes both), which tells the
+      // first and the last wave; the sums wrap, the differences kzg_prof_read forms of them (modulo 2^64) do not.
+      if (clk != nullptr && lane == 0) {
+        const unsigned long long now = (unsigned long long)wall_clock64();
+        const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+        const uint32_t k = atomicAdd(chunk_counter + 1, 1u);
+        atomicAdd(clk + CLK_ACC_EXIT_SUM, now);
+        if (k == 0) {
+          atomicAdd(clk + CLK_ACC_EXIT_FIRST, now);
+          atomicAdd(clk + CLK_ACC_LAUNCHES, 1ull);
+          atomicMax(clk + CLK_ACC_WAVES, (unsigned long long)waves);
+        }
+        if (k == waves - 1) atomicAdd(clk + CLK_ACC_EXIT_LAST, now);
+      }
       break;
     }
     const uint32_t t = chunk * 64 + lane;
@@ -837,7 +852,7 @@ static int msm_enqueue(Ctx* c, const Srs* s, const uint32_t* d_scalars, uint32_t
   KZG_HIP(c, hipStreamWaitEvent(sp, sl.ev_in, 0));
 #ifdef KZG_TIMING_SKIP_PREP   // timing experiment only (results are wrong): reuse the slot's previous prep output
   static int prep_runs = 0;
-  if (prep_runs++ >= 2 * NSLOT) { KZG_HIP(c, hipMemsetAsync(sl.counter.p, 0, 4, sp)); } else
+  if (prep_runs++ >= 2 * NSLOT) { KZG_HIP(c, hipMemsetAsync(sl.counter.p, 0, 8, sp)); } else
 #endif
   if ((rc = msm_prep_enqueue(c, sp, WB, d_scalars, n, (uint32_t)s->n, W::SEG, sl.prep_ws.p, vals, bstart, order,
                              slice_off, static_cast<uint32_t*>(sl.counter.p),

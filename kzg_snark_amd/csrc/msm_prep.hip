@@ -490,7 +490,7 @@ __global__ __launch_bounds__(TPB) void prep_slice_off_kernel(const uint32_t* bst
   const uint32_t v = slices_of_rank<WB>(bstart, order, seg, r);
   const uint32_t incl = block_inclusive_scan(v, sh);
   if (r <= PW<WB>::NB) slice_off[r] = blk_prefix[blockIdx.x] + incl - v;
-  if (r == 0) *chunk_counter = 0;
+  if (r == 0) { chunk_counter[0] = 0; chunk_counter[1] = 0; }     // [1]: the kernel's exit count (profiling only)
 }
 
 // chunk_rank[c] = rank (position in length order) of the bucket that owns slice 64*c, the first slice

@@ -1,10 +1,14 @@
 #!/bin/bash
 # A/B timing of library variants built with KZG_BUILD_DIR=ab/<name> (same box, back to back).
 #   [OUT=dir] tools/ab_bench.sh name1 name2 ...    -> $OUT/ab_<name>.json (OUT defaults to ab)
+# "tree" is the in-tree library.  ab/<name>/env, if there, is sourced for that variant's run (e.g. `export KZG_ACC_WGS_PER_CU=3`);
+# a variant with an env file and no library of its own runs the in-tree library under that environment.
 OUT=${OUT:-ab}
 mkdir -p "$OUT"
 for v in "$@"; do
-  if [ "$v" = tree ]; then unset KZG_MI355X_LIB; else export KZG_MI355X_LIB=$PWD/ab/$v/libkzg_mi355x.so; fi
+  (
+  if [ "$v" = tree ] || { [ -f "ab/$v/env" ] && [ ! -f "ab/$v/libkzg_mi355x.so" ]; }; then unset KZG_MI355X_LIB; else export KZG_MI355X_LIB=$PWD/ab/$v/libkzg_mi355x.so; fi
+  if [ -f "ab/$v/env" ]; then . "ab/$v/env"; fi
   python bench.py --full --mode batch --no-cpu-baseline --steps 30 > "$OUT/ab_$v.json" 2> "$OUT/ab_$v.err" || echo "FAILED $v"
   python - "$v" "$OUT" <<'PY'
 import json, sys
@@ -17,4 +21,5 @@ try:
 except Exception as e:
     print(v, "no result", e)
 PY
+  )
 done
