@@ -316,8 +316,9 @@ int kzg_open_coset_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys,
  * comm_idx = 0.  Cells may repeat, come in any order and cover any subset.  Ranges: 0 <= log_l <= 12,
  * log_l < log_N <= 21, K <= 2^21, K * l <= 2^24; K = 0 is KZG_OK with both points at infinity.  KZG_ERR_ARG, before
  * any MSM is queued: sizes or an index out of range, a w that is not a primitive N-th root, a proof or commitment
- * with a coordinate >= p or off the curve.  Membership in the prime-order subgroup is NOT checked (as in the facade's
- * host verifiers): a caller that takes points from an untrusted party checks it first.
+ * with a coordinate >= p or off the curve.  Membership in the prime-order subgroup is not part of this call: a caller that
+ * takes points from an untrusted party runs them through kzg_g1_check_subgroup first (the facade's verify_cosets /
+ * verify_domain do so with check_subgroup=True), or decompresses them with kzg_g1_decompress(check_subgroup = 1).
  * The proofs are used once, so they are not expanded into a key's window multiples: they become window-0 records
  * only (one record per proof), each scalar is cut into slices of win_bits - 1 bits, and every slice vector runs
  * through the commit pipeline as one polynomial.  Host pointers in, host results out; synchronises.
@@ -375,6 +376,41 @@ int kzg_open_shard_finish(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t z[4],
  * curve.  Replaces the running kzg.add of kzg.py:116 over the ranks' results. */
 int kzg_g1_sum(int curve_id, const uint64_t* xy, const uint8_t* inf, size_t n, uint64_t* out_xy, uint8_t* out_inf);
 
+/* ---- compressed G1 points and subgroup membership ---------------------------------------------------
+ * Byte formats: big-endian x with flags in the top bits of byte 0.
+ *   BLS12-381  48 bytes, ZCash: bit 7 = compressed (must be 1), bit 6 = infinity, bit 5 = y is the larger root
+ *              (y > (p - 1) / 2); infinity = bit 6 set, bit 5 clear, every other bit zero (0xc0, then 47 zero bytes)
+ *   BN254      32 bytes, gnark: top two bits 10 = finite with the smaller y, 11 = finite with the larger y,
+ *              01 = infinity (the other 254 bits zero), 00 = not a compressed point
+ * Status of a point, one byte each, first failure wins:
+ *   0 ok   1 bad encoding (the flags, a malformed infinity, x >= p)   2 x^3 + b is not a square: no such point
+ *   3 on the curve but outside the subgroup of prime order r (BLS12-381 only: BN254's cofactor is 1)
+ * The subgroup test of BLS12-381 is phi(P) = -[u^2] P with phi(x, y) = (beta x, y): exact, 126 doublings and 10
+ * additions per point instead of the ~255 and ~128 of [r] P.  Infinity passes.
+ *   kzg_g1_compress        n affine points (kzg_srs_load_g1's layout) -> n blobs.  A coordinate >= p or a point off
+ *                          the curve is KZG_ERR_ARG (kzg_verify_cosets' rule); nothing is written then.
+ *   kzg_g1_decompress      n blobs -> affine points, infinity flags and statuses.  KZG_OK when it ran: the verdicts are
+ *                          in out_status.  A failed point decompresses to zeros with the flag 0.  check_subgroup = 0
+ *                          never reports 3.
+ *   kzg_g1_decompress_device   the same on device pointers (16-byte aligned; d_xy n * 2*FP_LIMBS limbs, d_inf and
+ *                          d_status n bytes), enqueued on the context's stream without synchronising.
+ *   kzg_g1_check_subgroup  statuses of n affine points: 0, 2 (a coordinate >= p or a point off the curve) or 3.
+ *   kzg_srs_load_g1_compressed   kzg_srs_load_g1 from n blobs: decompressed on the device and expanded there, no
+ *                          round trip of the points through the host.  Any status other than 0 is KZG_ERR_ARG and
+ *                          kzg_last_error names the first such index and its status.  n = 0 is KZG_ERR_ARG, as for
+ *                          kzg_srs_load_g1.
+ *   kzg_srs_export_compressed    points [start, start + count) of a key as blobs (kzg_srs_export's range rule).
+ * n = 0 is KZG_OK with no work; more than 2^24 points per call is KZG_ERR_ARG.  Host pointers in and out and a
+ * synchronised stream, except for the _device form. */
+int kzg_g1_compress(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_bytes);
+int kzg_g1_decompress(kzg_ctx* ctx, const uint8_t* bytes, size_t n, int check_subgroup, uint64_t* out_xy,
+                      uint8_t* out_inf, uint8_t* out_status);
+int kzg_g1_decompress_device(kzg_ctx* ctx, const void* d_bytes, size_t n, int check_subgroup, void* d_xy, void* d_inf,
+                             void* d_status);
+int kzg_g1_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status);
+int kzg_srs_load_g1_compressed(kzg_ctx* ctx, const uint8_t* bytes, size_t n, int check_subgroup, kzg_srs** out);
+int kzg_srs_export_compressed(kzg_ctx* ctx, const kzg_srs* srs, size_t start, size_t count, uint8_t* out_bytes);
+
 /* ---- device vector / polynomial primitives over Fr ------------------------------------------------
  * What the reference's callers do with Sage's dense polynomials between the transforms and the
  * commitments (plonk/prover.py:243-316: accumulator ratios, products, division by Z_H on a coset),
@@ -409,7 +445,9 @@ int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size
  * (one per kzg_coset_table_create), "open_cosets" (ONE per kzg_open_cosets*), "open_coset_poly" (ONE per
  * kzg_open_coset*: combination, division and remainder), "verify_cosets" (ONE per kzg_verify_cosets: the whole call on
  * the context's stream; its MSMs also report under the msm_* names), "recover_cosets" (ONE per kzg_recover_cosets*:
- * the product tree and every chunk).  kzg_prof_read synchronises the
+ * the product tree and every chunk), "g1_decompress" (ONE per kzg_g1_decompress*, and one per
+ * kzg_srs_load_g1_compressed: the decoding, with the subgroup test when asked for), "g1_subgroup" (ONE per
+ * kzg_g1_check_subgroup).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.
  * Two names are not spans: "msm_accumulate_shader_mhz" and "ntt_pass_shader_mhz" return (in *total_ms) the shader
  * clock in MHz the accumulate / NTT kernel ran at since the last reset -- s_memtime over s_memrealtime ticks of its

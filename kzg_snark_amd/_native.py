@@ -104,6 +104,12 @@ SIGNATURES = {
                                          _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "kzg_recover_cosets": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
                                           ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
+    "kzg_g1_compress": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "kzg_g1_decompress": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp]),
+    "kzg_g1_decompress_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp]),
+    "kzg_g1_check_subgroup": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "kzg_srs_load_g1_compressed": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "kzg_srs_export_compressed": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "kzg_recover_cosets_device": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
                                                  ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
 }
@@ -310,6 +316,64 @@ class Context:
         h = ctypes.c_void_p()
         self._check(lib().kzg_srs_load_g1(self._h, _as_vp(xy), _as_vp(inf), n, ctypes.byref(h)))
         return Srs(self, h, n)
+
+    def srs_load_g1_compressed(self, blobs, check_subgroup=True):
+        """blobs: uint8[n, g1_bytes] compressed points (include/kzg_mi355x.h: the byte formats); decompressed and
+        expanded on the device.  A point that does not decompress (or, with check_subgroup, lies outside the
+        subgroup) raises NativeError naming the first such index."""
+        blobs = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(-1, self.g1_bytes)
+        h = ctypes.c_void_p()
+        self._check(lib().kzg_srs_load_g1_compressed(self._h, _as_vp(blobs), blobs.shape[0], int(bool(check_subgroup)),
+                                                     ctypes.byref(h)))
+        return Srs(self, h, blobs.shape[0])
+
+    # ---- compressed points and subgroup membership
+    @property
+    def g1_bytes(self):
+        """bytes of a compressed G1 point: 48 (bls12_381) or 32 (bn254)"""
+        return 8 * self.fp_limbs
+
+    def g1_compress(self, xy, inf=None):
+        """affine points (uint64[n, 2*fp_limbs], uint8[n] flags or None) -> uint8[n, g1_bytes]"""
+        xy = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, 2 * self.fp_limbs)
+        n = xy.shape[0]
+        if inf is not None:
+            inf = np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1)
+            if inf.size != n:
+                raise ValueError("g1_compress: inf and xy differ in length")
+        out = np.zeros((n, self.g1_bytes), dtype=np.uint8)
+        self._check(lib().kzg_g1_compress(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(out)))
+        return out
+
+    def g1_decompress(self, blobs, check_subgroup=True):
+        """uint8[n, g1_bytes] -> (xy uint64[n, 2*fp_limbs], inf uint8[n], status uint8[n]); status 0 ok, 1 bad
+        encoding, 2 no such point, 3 outside the subgroup.  A failed point is all zeros."""
+        blobs = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(-1, self.g1_bytes)
+        n = blobs.shape[0]
+        xy = np.zeros((n, 2 * self.fp_limbs), dtype=np.uint64)
+        inf = np.zeros(n, dtype=np.uint8)
+        status = np.zeros(n, dtype=np.uint8)
+        self._check(lib().kzg_g1_decompress(self._h, _as_vp(blobs), n, int(bool(check_subgroup)), _as_vp(xy),
+                                            _as_vp(inf), _as_vp(status)))
+        return xy, inf, status
+
+    def g1_decompress_device(self, d_bytes, n, check_subgroup, d_xy, d_inf, d_status):
+        """The same on device pointers, enqueued on the context's stream (no synchronisation)."""
+        self._check(lib().kzg_g1_decompress_device(self._h, _as_vp(d_bytes), int(n), int(bool(check_subgroup)),
+                                                   _as_vp(d_xy), _as_vp(d_inf), _as_vp(d_status)))
+
+    def g1_check_subgroup(self, xy, inf=None):
+        """status uint8[n] of affine points: 0 in the subgroup (infinity included), 2 a coordinate >= p or off the
+        curve, 3 on the curve but outside the subgroup"""
+        xy = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, 2 * self.fp_limbs)
+        n = xy.shape[0]
+        if inf is not None:
+            inf = np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1)
+            if inf.size != n:
+                raise ValueError("g1_check_subgroup: inf and xy differ in length")
+        status = np.zeros(n, dtype=np.uint8)
+        self._check(lib().kzg_g1_check_subgroup(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(status)))
+        return status
 
     def srs_generate(self, tau_words, n, start=0):
         h = ctypes.c_void_p()
@@ -610,6 +674,13 @@ class Srs:
         inf = np.zeros(count, dtype=np.uint8)
         self.ctx._check(lib().kzg_srs_export(self.ctx._h, self._h, start, count, _as_vp(xy), _as_vp(inf)))
         return xy, inf
+
+    def export_compressed(self, start=0, count=None):
+        """points [start, start + count) as compressed blobs, uint8[count, g1_bytes]"""
+        count = self.n - start if count is None else count
+        out = np.zeros((count, self.ctx.g1_bytes), dtype=np.uint8)
+        self.ctx._check(lib().kzg_srs_export_compressed(self.ctx._h, self._h, start, count, _as_vp(out)))
+        return out
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):

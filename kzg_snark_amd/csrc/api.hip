@@ -389,6 +389,56 @@ int kzg_srs_export(kzg_ctx* ctx, const kzg_srs* srs, size_t start, size_t count,
   return srs_export(c, srs->s, start, count, xy, inf);
 }
 
+int kzg_srs_load_g1_compressed(kzg_ctx* ctx, const uint8_t* bytes, size_t n, int check_subgroup, kzg_srs** out) {
+  if (!ctx || !bytes || !out) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  *out = nullptr;
+  KZG_HIP(c, hipSetDevice(c->device));
+  Srs* s = nullptr;
+  int rc = srs_load_g1_compressed(c, bytes, n, check_subgroup, &s);
+  if (rc) return rc;
+  *out = new kzg_srs{s};
+  return KZG_OK;
+}
+
+int kzg_srs_export_compressed(kzg_ctx* ctx, const kzg_srs* srs, size_t start, size_t count, uint8_t* out_bytes) {
+  if (!ctx || !srs || (count && !out_bytes)) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  if (srs->s->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
+  return srs_export_compressed(c, srs->s, start, count, out_bytes);
+}
+
+int kzg_g1_compress(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_bytes) {
+  if (!ctx || (n && (!xy || !out_bytes))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return g1_compress(c, xy, inf, n, out_bytes);
+}
+
+int kzg_g1_decompress(kzg_ctx* ctx, const uint8_t* bytes, size_t n, int check_subgroup, uint64_t* out_xy,
+                      uint8_t* out_inf, uint8_t* out_status) {
+  if (!ctx || (n && (!bytes || !out_xy || !out_inf || !out_status))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return g1_decompress(c, bytes, n, check_subgroup, out_xy, out_inf, out_status);
+}
+
+int kzg_g1_decompress_device(kzg_ctx* ctx, const void* d_bytes, size_t n, int check_subgroup, void* d_xy, void* d_inf,
+                             void* d_status) {
+  if (!ctx || (n && (!d_bytes || !d_xy || !d_inf || !d_status))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return g1_decompress_device(c, d_bytes, n, check_subgroup, d_xy, d_inf, d_status);
+}
+
+int kzg_g1_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status) {
+  if (!ctx || (n && (!xy || !out_status))) return KZG_ERR_ARG;
+  Ctx* c = &ctx->c;
+  KZG_HIP(c, hipSetDevice(c->device));
+  return g1_check_subgroup(c, xy, inf, n, out_status);
+}
+
 size_t kzg_srs_size(const kzg_srs* srs) { return srs ? srs->s->n : 0; }
 
 void kzg_srs_free(kzg_srs* srs) {

@@ -1,5 +1,5 @@
 // internal.h -- library-private declarations shared by the translation units of
-// libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, poly.hip, verify.hip, recover.hip).
+// libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, poly.hip, verify.hip, recover.hip, g1_bytes.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -23,6 +23,8 @@ constexpr int SRS_MONOMIAL = 0;
 constexpr int SRS_LAGRANGE = 1;
 
 int srs_load(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, Srs** out);
+// the same from points already on the device: canonical words x | y per point, flags or null (g1_bytes.hip)
+int srs_load_device(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n, Srs** out);
 // run_len = 0: the contiguous range tau^(start + i); otherwise record i = tau^(start + (i / run_len) * outer_stride +
 // (i % run_len) * inner_stride)
 int srs_generate(Ctx* c, const uint64_t* tau, size_t start, size_t n, Srs** out, size_t run_len = 0,
@@ -107,6 +109,17 @@ int recover_cosets(Ctx* c, uint32_t log_n, uint32_t log_N, uint32_t log_l, const
                    const uint32_t* coset_idx, size_t K, const uint32_t* values, bool host_ptrs, size_t b,
                    uint32_t* coeffs, uint8_t* out_consistent);
 uint32_t recover_leaf_width();     // linear factors a leaf of the product tree multiplies out
+
+// g1_bytes.hip: compressed points and subgroup checks; the contracts are those of the kzg_* entry
+// points of the same names.  n = 0 does nothing; more than 2^24 points is KZG_ERR_ARG.
+int g1_compress(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_bytes);
+int g1_decompress(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, uint64_t* out_xy, uint8_t* out_inf,
+                  uint8_t* out_status);
+int g1_decompress_device(Ctx* c, const void* d_bytes, size_t n, int check_subgroup, void* d_xy, void* d_inf,
+                         void* d_status);
+int g1_check_subgroup(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status);
+int srs_load_g1_compressed(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, Srs** out);
+int srs_export_compressed(Ctx* c, const Srs* s, size_t start, size_t count, uint8_t* out_bytes);
 
 int open_shard_begin_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                             const uint32_t* z_words, const uint32_t* xi_words, uint64_t* chunk_eval_out);

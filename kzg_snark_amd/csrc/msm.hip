@@ -563,23 +563,18 @@ static Srs* srs_alloc(Ctx* c, size_t n) {
   return s;
 }
 
+// the key from n affine points ALREADY ON THE DEVICE (canonical words x | y, flags or null; the caller keeps them
+// alive until this returns): import with the on-curve check, then the window multiples.  Synchronises.
 template <class C>
-static int srs_load_t(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, Srs** out) {
-  using F = typename C::Fp;
+static int srs_load_device_t(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n, Srs** out) {
   if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, "kzg_srs_load_g1: bad size");
   Srs* s = srs_alloc(c, n);
   const size_t table_bytes = (size_t)s->nwin * n * rec_bytes<C>();
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->recs), table_bytes);
   if (e != hipSuccess) { delete s; return set_err(c, KZG_ERR_ALLOC, "hipMalloc(SRS table)", e); }
-  uint32_t* d_xy = nullptr; uint8_t* d_inf = nullptr; uint32_t* d_bad = nullptr;
-  const size_t xy_bytes = n * 2 * F::NW * 4;
-  auto cleanup = [&]() { hipFree(d_xy); hipFree(d_inf); hipFree(d_bad); };
-  auto fail = [&](int rc) { cleanup(); hipFree(s->recs); delete s; return rc; };
-  if (hipMalloc(reinterpret_cast<void**>(&d_xy), xy_bytes) != hipSuccess) return fail(set_err(c, KZG_ERR_ALLOC, "hipMalloc"));
+  uint32_t* d_bad = nullptr;
+  auto fail = [&](int rc) { hipFree(d_bad); hipFree(s->recs); delete s; return rc; };
   if (hipMalloc(reinterpret_cast<void**>(&d_bad), 4) != hipSuccess) return fail(set_err(c, KZG_ERR_ALLOC, "hipMalloc"));
-  if (inf && hipMalloc(reinterpret_cast<void**>(&d_inf), n) != hipSuccess) return fail(set_err(c, KZG_ERR_ALLOC, "hipMalloc"));
-  hipMemcpyAsync(d_xy, xy, xy_bytes, hipMemcpyHostToDevice, c->stream);
-  if (inf) hipMemcpyAsync(d_inf, inf, n, hipMemcpyHostToDevice, c->stream);
   hipMemsetAsync(d_bad, 0, 4, c->stream);
   hipLaunchKernelGGL(srs_import_kernel<C>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, d_xy, d_inf,
                      s->recs, n, d_bad);
@@ -588,11 +583,27 @@ static int srs_load_t(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, 
   e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, "srs import", e));
   if (bad) return fail(set_err(c, KZG_ERR_ARG, "kzg_srs_load_g1: point not on the curve"));
-  cleanup();
+  hipFree(d_bad);
   int rc = srs_build_windows<C>(c, s);
   if (rc) { hipFree(s->recs); delete s; return rc; }
   *out = s;
   return KZG_OK;
+}
+
+template <class C>
+static int srs_load_t(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, Srs** out) {
+  using F = typename C::Fp;
+  if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, "kzg_srs_load_g1: bad size");
+  uint32_t* d_xy = nullptr; uint8_t* d_inf = nullptr;
+  const size_t xy_bytes = n * 2 * F::NW * 4;
+  auto cleanup = [&]() { hipFree(d_xy); hipFree(d_inf); };
+  if (hipMalloc(reinterpret_cast<void**>(&d_xy), xy_bytes) != hipSuccess) return set_err(c, KZG_ERR_ALLOC, "hipMalloc");
+  if (inf && hipMalloc(reinterpret_cast<void**>(&d_inf), n) != hipSuccess) { cleanup(); return set_err(c, KZG_ERR_ALLOC, "hipMalloc"); }
+  hipMemcpyAsync(d_xy, xy, xy_bytes, hipMemcpyHostToDevice, c->stream);
+  if (inf) hipMemcpyAsync(d_inf, inf, n, hipMemcpyHostToDevice, c->stream);
+  const int rc = srs_load_device_t<C>(c, d_xy, d_inf, n, out);     // synchronises: the uploads are done with
+  cleanup();
+  return rc;
 }
 
 template <class C>
@@ -641,6 +652,9 @@ static const uint64_t GEN_BLS[12] = {
 
 int srs_load(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, Srs** out) {
   return c->curve == 0 ? srs_load_t<Bn254>(c, xy, inf, n, out) : srs_load_t<Bls12_381>(c, xy, inf, n, out);
+}
+int srs_load_device(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n, Srs** out) {
+  return c->curve == 0 ? srs_load_device_t<Bn254>(c, d_xy, d_inf, n, out) : srs_load_device_t<Bls12_381>(c, d_xy, d_inf, n, out);
 }
 int srs_generate(Ctx* c, const uint64_t* tau, size_t start, size_t n, Srs** out, size_t run_len, size_t inner_stride,
                  size_t outer_stride) {

@@ -224,3 +224,86 @@ def on_curve_g2(pt, cv):
         return True
     x, y = pt[0], pt[1]
     return K.sub(K.mul(y, y), K.add(K.mul(K.mul(x, x), x), cv.b2)) == (0, 0)
+
+
+# ---- compressed G1 points and subgroup membership (single-point host helpers; the data-parallel forms are the
+# ---- kernels of csrc/g1_bytes.hip, which the tests compare against these) ----------------------------------------
+#   bls12_381  48 bytes, ZCash format: big-endian x; bit 7 of byte 0 = compressed (always 1), bit 6 = infinity,
+#              bit 5 = y is the larger of the two roots (y > (p - 1) / 2); infinity is 0xc0 and 47 zero bytes
+#   bn254      32 bytes, gnark's format: big-endian x; top two bits of byte 0: 10 = finite with the smaller y,
+#              11 = finite with the larger y, 01 = infinity (the other 254 bits zero), 00 = not a compressed point
+# Status of a blob, first failure wins (the per-point codes of kzg_g1_decompress):
+G1_OK, G1_BAD_ENCODING, G1_NOT_ON_CURVE, G1_NOT_IN_SUBGROUP = 0, 1, 2, 3
+G1_STATUS_TEXT = {G1_OK: "ok", G1_BAD_ENCODING: "bad encoding", G1_NOT_ON_CURVE: "x^3 + b is not a square: no such point",
+                  G1_NOT_IN_SUBGROUP: "on the curve but outside the prime-order subgroup"}
+
+
+def g1_compressed_size(cv):
+    return 48 if cv.name == "bls12_381" else 32
+
+
+def sqrt_fp(a, p):
+    """A square root of a modulo p = 3 (mod 4), or None when a is not a square."""
+    assert p % 4 == 3
+    s = pow(a, (p + 1) // 4, p)
+    return s if s * s % p == a % p else None
+
+
+def compress_g1(pt, cv):
+    size = g1_compressed_size(cv)
+    bls = cv.name == "bls12_381"
+    if pt[2] == 0:
+        return bytes([0xc0 if bls else 0x40]) + bytes(size - 1)
+    x, y = int(pt[0]) % cv.p, int(pt[1]) % cv.p
+    larger = y > (cv.p - 1) // 2
+    raw = bytearray(x.to_bytes(size, "big"))
+    raw[0] |= (0x80 | (0x20 if larger else 0)) if bls else (0xc0 if larger else 0x80)
+    return bytes(raw)
+
+
+def in_subgroup_g1(pt, cv):
+    """[r] P = O, for a point on the curve (infinity included)."""
+    if pt[2] == 0:
+        return True
+    return g1_group(cv).multiply((int(pt[0]), int(pt[1]), 1), cv.r)[2] == 0
+
+
+def decompress_g1_status(blob, cv, check_subgroup=True):
+    """(point or None, status) of one compressed point."""
+    size = g1_compressed_size(cv)
+    blob = bytes(blob)
+    if len(blob) != size:
+        return None, G1_BAD_ENCODING
+    rest = int.from_bytes(blob, "big")
+    if cv.name == "bls12_381":
+        flags, x = blob[0] >> 5, rest & ((1 << 381) - 1)
+        if not flags & 4:
+            return None, G1_BAD_ENCODING
+        if flags & 2:
+            return ((1, 1, 0), G1_OK) if flags == 6 and x == 0 else (None, G1_BAD_ENCODING)
+        larger = bool(flags & 1)
+    else:
+        flags, x = blob[0] >> 6, rest & ((1 << 254) - 1)
+        if flags == 0:
+            return None, G1_BAD_ENCODING
+        if flags == 1:
+            return ((1, 1, 0), G1_OK) if x == 0 else (None, G1_BAD_ENCODING)
+        larger = flags == 3
+    if x >= cv.p:
+        return None, G1_BAD_ENCODING
+    y = sqrt_fp((x * x * x + cv.b) % cv.p, cv.p)
+    if y is None:
+        return None, G1_NOT_ON_CURVE
+    if (y > (cv.p - 1) // 2) != larger:
+        y = cv.p - y
+    pt = (x, y, 1)
+    if check_subgroup and not in_subgroup_g1(pt, cv):
+        return None, G1_NOT_IN_SUBGROUP
+    return pt, G1_OK
+
+
+def decompress_g1(blob, cv, check_subgroup=True):
+    pt, status = decompress_g1_status(blob, cv, check_subgroup)
+    if status != G1_OK:
+        raise ValueError(f"compressed G1 point: {G1_STATUS_TEXT[status]}")
+    return pt

@@ -10,6 +10,7 @@ commit and open -- executed by the gfx950 engine through the C ABI.
     check(rk, commitments, z, evaluations, proof, xi) -> bool            kzg.py:161
     batch_check(rk, commitments_list, z_list, evaluations_list, proof_list, xi_list, r=None)   kzg.py:213
     verify_cosets / verify_domain: any number of coset (or single-point) claims folded on the device, two pairings
+    compress_g1 / decompress_g1 / in_subgroup: 48- / 32-byte points and subgroup membership, on the device
 
 Points are py_ecc-shaped 3-tuples, always normalised: (x, y, 1), infinity (1, 1, 0).
 The reference returns un-normalised projective triples whose representative
@@ -230,15 +231,23 @@ class KZG:
     #   bytes 0..7   magic b"KZGSRS1\0"      bytes 8..11  curve id (u32 LE: 0 bn254, 1 bls12_381)
     #   bytes 12..15 uint64 limbs per coordinate (u32 LE)   bytes 16..23 number of points n (u64 LE)
     #   then n * 2 * limbs little-endian uint64 (affine x | y, canonical), then n infinity-flag bytes
+    #   version 2 (save_key(compressed=True)): magic b"KZGSRS2\0", the same 16 header bytes, then n compressed points
+    #   of 8 * limbs bytes each (include/kzg_mi355x.h: ZCash's 48 bytes for bls12_381, gnark's 32 for bn254); the
+    #   points are decompressed -- and checked for subgroup membership -- on the device when the file is loaded
     _MAGIC = b"KZGSRS1\0"
+    _MAGIC_COMPRESSED = b"KZGSRS2\0"
 
-    def save_key(self, ck, path, chunk=1 << 16):
+    def save_key(self, ck, path, chunk=1 << 16, compressed=False):
         key = self._key(ck)
         ctx = self._context()
         n, L = len(key), ctx.fp_limbs
         with open(path, "wb") as f:
-            f.write(self._MAGIC)
+            f.write(self._MAGIC_COMPRESSED if compressed else self._MAGIC)
             f.write(int(ctx.curve_id).to_bytes(4, "little") + int(L).to_bytes(4, "little") + int(n).to_bytes(8, "little"))
+            if compressed:
+                for start in range(0, n, chunk):
+                    f.write(key.srs.export_compressed(start, min(chunk, n - start)).tobytes())
+                return
             flags = []
             for start in range(0, n, chunk):
                 xy, inf = key.srs.export(start, min(chunk, n - start))
@@ -246,19 +255,76 @@ class KZG:
                 flags.append(inf)
             f.write(np.concatenate(flags).astype(np.uint8).tobytes())
 
-    def load_key(self, path):
+    def load_key(self, path, check_subgroup=True):
+        """check_subgroup applies to version-2 (compressed) files: every point must lie in the prime-order subgroup.
+        A point that does not decompress, or fails that check, raises ValueError naming its index."""
         ctx = self._context()
         with open(path, "rb") as f:
             head = f.read(24)
-            if head[:8] != self._MAGIC:
+            if head[:8] not in (self._MAGIC, self._MAGIC_COMPRESSED):
                 raise ValueError("not a KZG SRS file")
             cid, L, n = (int.from_bytes(head[8:12], "little"), int.from_bytes(head[12:16], "little"),
                          int.from_bytes(head[16:24], "little"))
             if cid != ctx.curve_id or L != ctx.fp_limbs:
                 raise ValueError("SRS file belongs to another curve")
+            if head[:8] == self._MAGIC_COMPRESSED:
+                blobs = np.frombuffer(f.read(n * ctx.g1_bytes), dtype=np.uint8)
+                if blobs.size != n * ctx.g1_bytes:
+                    raise ValueError("SRS file is shorter than its header says")
+                try:
+                    return CommitmentKey(ctx, ctx.srs_load_g1_compressed(blobs.reshape(n, ctx.g1_bytes), check_subgroup))
+                except _native.NativeError as e:
+                    if e.code == -1:
+                        raise ValueError(str(e)) from e
+                    raise
             xy = np.frombuffer(f.read(n * 2 * L * 8), dtype="<u8").reshape(n, 2 * L).astype(np.uint64)
             inf = np.frombuffer(f.read(n), dtype=np.uint8).copy()
         return CommitmentKey(ctx, ctx.srs_load_g1(np.ascontiguousarray(xy), inf))
+
+    # ---- compressed points and subgroup membership, any number of points per call on the device -------------------
+    def compress_g1(self, points):
+        """points: a list of point tuples, or (xy, inf) arrays in the C layout -> list of bytes objects (48 bytes each
+        on bls12_381, ZCash's format; 32 on bn254, gnark's).  A point off the curve raises ValueError."""
+        xy, inf = self._g1_arrays(points, "points")
+        try:
+            out = self._context().g1_compress(xy, inf)
+        except _native.NativeError as e:
+            if e.code == -1:
+                raise ValueError(str(e)) from e
+            raise
+        return [row.tobytes() for row in out]
+
+    def decompress_g1(self, blobs, check_subgroup=True, strict=True):
+        """blobs: a list of bytes objects or a uint8[n, size] array -> list of points.  strict: the first blob that is
+        malformed, names no point of the curve or (check_subgroup) a point outside the prime-order subgroup raises
+        ValueError with its index and the reason; strict=False returns (points, status) instead, status a uint8 array
+        (curve.G1_STATUS_TEXT) and None in place of a failed point."""
+        ctx = self._context()
+        if isinstance(blobs, np.ndarray):
+            arr = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(-1, ctx.g1_bytes)
+        else:
+            blobs = [bytes(b) for b in blobs]
+            for i, b in enumerate(blobs):
+                if len(b) != ctx.g1_bytes:
+                    raise ValueError(f"compressed point {i}: {len(b)} bytes, expected {ctx.g1_bytes}")
+            arr = np.frombuffer(b"".join(blobs), dtype=np.uint8).reshape(len(blobs), ctx.g1_bytes)
+        xy, inf, status = ctx.g1_decompress(arr, check_subgroup)
+        bad = np.flatnonzero(status)
+        if strict and bad.size:
+            i = int(bad[0])
+            raise ValueError(f"compressed point {i}: {_curve.G1_STATUS_TEXT[int(status[i])]}")
+        points = self._points(xy, inf)
+        if strict:
+            return points
+        for i in bad:
+            points[int(i)] = None
+        return points, status
+
+    def in_subgroup(self, points):
+        """bool array: point i is on the curve AND in the subgroup of prime order (infinity: True).  BLS12-381's G1
+        has cofactor 0x396c8c005555e1568c00aaab0000aaab; on bn254 every point of the curve is in the subgroup."""
+        xy, inf = self._g1_arrays(points, "points")
+        return self._context().g1_check_subgroup(xy, inf) == 0
 
     def commit(self, ck, polynomials):
         """kzg.py:80-120."""
@@ -853,14 +919,17 @@ class KZG:
         return np.ascontiguousarray(xy), inf
 
     def verify_cosets(self, ck, rk_l, commitments, commitment_indices, coset_indices, values, proofs, l, N, w=None,
-                      r=None):
+                      r=None, check_subgroup=False):
         """Cell k claims: the polynomial of commitments[commitment_indices[k]] takes the l values values[k][t] at
         w^(coset_indices[k] + t N/l), t < l, with proof proofs[k] -- open_cosets' numbering; l = 1: single points.
         All claims are combined with weights r^(k+1) (r sampled when not given, as in batch_check) into two G1 points
         on the device, then pairing(G2, L) == pairing(rk_l, R) with rk_l = [tau^l] G2 (coset_verification_key).
         proofs / commitments: lists of point tuples or (xy, inf) arrays in the C layout (what Context.open_cosets
         returns); values: nested lists or a uint64[K, l, 4] array.  A point off the curve: False.  No claims: True.
-        Membership in the prime-order subgroup is not checked (as in check / batch_check)."""
+        check_subgroup=True first runs commitments and proofs through kzg_g1_check_subgroup on the device and returns
+        False when one lies outside the prime-order subgroup: for a point T of the cofactor torsion pi + T satisfies
+        the pairing equation whenever pi does, so a verifier of untrusted proofs wants it.  The default skips the
+        test (as check / batch_check do)."""
         if isinstance(ck, (LagrangeKey, DomainTable)):
             raise TypeError("verify_cosets needs a monomial key (setup / load_key / a list of points)")
         l = 1 << self._log2_exact(l, "coset size")
@@ -903,6 +972,10 @@ class KZG:
         if K == 0:
             return True
         key = self._key(ck)
+        if check_subgroup:
+            ctx = self._context()
+            if ctx.g1_check_subgroup(cxy, cinf).any() or ctx.g1_check_subgroup(pxy, pinf).any():
+                return False
         try:
             xy, inf = self._context().verify_cosets(key.srs, log_N, l.bit_length() - 1, w, cxy, cinf,
                                                     comm_idx.astype(np.uint32), coset_idx.astype(np.uint32),
@@ -914,9 +987,9 @@ class KZG:
         L_pt, R_pt = self._points(xy, inf)
         return self.pairing(self.G2, L_pt) == self.pairing(rk_l, R_pt)
 
-    def verify_domain(self, ck, rk, commitment, values, proofs, N=None, w=None, r=None):
+    def verify_domain(self, ck, rk, commitment, values, proofs, N=None, w=None, r=None, check_subgroup=False):
         """The whole output of open_domain at once: proofs[i] opens `commitment` to values[i] at w^i, i < N (N defaults
-        to the number of proofs); rk is setup's tau G2.  verify_cosets with l = 1."""
+        to the number of proofs); rk is setup's tau G2.  verify_cosets with l = 1 (check_subgroup: as there)."""
         if isinstance(values, np.ndarray) and values.dtype == np.uint64:
             count = values.size // 4
         else:
@@ -924,4 +997,5 @@ class KZG:
             count = len(values)
         N = count if N is None else int(N)
         return self.verify_cosets(ck, rk, [commitment], np.zeros(count, dtype=np.int64),
-                                  np.arange(count, dtype=np.int64), values, proofs, 1, N, w=w, r=r)
+                                  np.arange(count, dtype=np.int64), values, proofs, 1, N, w=w, r=r,
+                                  check_subgroup=check_subgroup)
