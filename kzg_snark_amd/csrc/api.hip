@@ -1,6 +1,6 @@
 // api.hip -- the extern "C" surface of libkzg_mi355x.so (include/kzg_mi355x.h).
 #include "internal.h"
-#include "ec.h"
+#include "g1_words.h"
 #include "msm.h"
 #include "../../include/kzg_mi355x.h"
 #include <cstdio>
@@ -78,41 +78,42 @@ namespace kzg {
 template <class C>
 static int g1_sum_t(const uint64_t* xy, const uint8_t* inf, size_t n, uint64_t* out_xy, uint8_t* out_inf) {
   using F = typename C::Fp;
-  using Fd = Field<F>;
   const uint32_t* w = reinterpret_cast<const uint32_t*>(xy);
   XYZZ<C> acc = Ec<C>::infinity();
   for (size_t i = 0; i < n; ++i) {
     if (inf && inf[i]) continue;
-    const Fe<F> x = Fd::from_words(w + i * 2 * F::NW), y = Fd::from_words(w + i * 2 * F::NW + F::NW);
-    // coordinates must be canonical field elements of a point on the curve
-    for (int half = 0; half < 2; ++half) {
-      const uint32_t* q = w + i * 2 * F::NW + half * F::NW;
-      bool below = false;
-      for (int k = F::NW - 1; k >= 0 && !below; --k) {
-        if (q[k] < F::PW[k]) below = true;
-        else if (q[k] > F::PW[k]) return KZG_ERR_ARG;
-      }
-      if (!below) return KZG_ERR_ARG;
-    }
-    const Fe<F> xm = Fd::reduce(Fd::to_mont(x)), ym = Fd::reduce(Fd::to_mont(y));
-    if (!Ec<C>::on_curve(xm, ym)) return KZG_ERR_ARG;
-    acc = Ec<C>::madd(acc, xm, ym);
+    Fe<F> x, y;   // coordinates must be canonical field elements of a point on the curve
+    if (!import_affine<C>(w + i * 2 * F::NW, w + i * 2 * F::NW + F::NW, x, y)) return KZG_ERR_ARG;
+    acc = Ec<C>::madd(acc, x, y);
   }
-  const Affine<C> a = Ec<C>::to_affine(acc);
-  uint32_t* o = reinterpret_cast<uint32_t*>(out_xy);
-  if (a.inf) {
-    memset(o, 0, 2 * F::NW * 4);
-    *out_inf = 1;
-    return KZG_OK;
-  }
-  Fd::to_words(Fd::from_mont(a.x), o);
-  Fd::to_words(Fd::from_mont(a.y), o + F::NW);
-  *out_inf = 0;
+  *out_inf = affine_to_words<C>(Ec<C>::to_affine(acc), reinterpret_cast<uint32_t*>(out_xy));
   return KZG_OK;
 }
 }  // namespace kzg
 
 using namespace kzg;
+
+// The prologue of every entry point that takes a context: `bad` (the null checks of its arguments) is KZG_ERR_ARG,
+// then `c` is the context and its device the current one.
+#define KZG_ENTER(bad)                           \
+  if (!ctx || (bad)) return KZG_ERR_ARG;         \
+  Ctx* c = &ctx->c;                              \
+  KZG_HIP(c, hipSetDevice(c->device))
+
+// the epilogue of the key constructors: a key that was built becomes the caller's handle
+static int adopt_srs(int rc, Srs* s, kzg_srs** out) {
+  if (rc == KZG_OK) *out = new kzg_srs{s};
+  return rc;
+}
+
+// the host-pointer entry points: `bytes` of host memory into the context's staging buffer, in stream order
+static int stage_host(Ctx* c, const void* src, size_t bytes, void** d) {
+  int rc = ensure_buf(c, c->io, bytes ? bytes : 32);
+  if (rc) return rc;
+  if (bytes) KZG_HIP(c, hipMemcpyAsync(c->io.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+  *d = c->io.p;
+  return KZG_OK;
+}
 
 extern "C" {
 
@@ -159,15 +160,10 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
   hipDeviceSynchronize();
   ntt_free_domains(c);
   msm_free_work(c);
-  hipFree(c->ntt_scratch.p);
-  hipFree(c->io.p);
+  for (DevBuf* b : {&c->ntt_scratch, &c->io, &c->scan_tmp, &c->lagr_tmp, &c->dom_tmp, &c->ver_tmp, &c->rec_tmp,
+                    &c->poly_tmp[0], &c->poly_tmp[1], &c->poly_tmp[2], &c->poly_tmp[3]})
+    hipFree(b->p);
   hipFree(c->clk_probe);
-  hipFree(c->scan_tmp.p);
-  hipFree(c->lagr_tmp.p);
-  hipFree(c->dom_tmp.p);
-  hipFree(c->ver_tmp.p);
-  hipFree(c->rec_tmp.p);
-  for (auto& b : c->poly_tmp) hipFree(b.p);
   for (auto s : c->aux_streams) hipStreamDestroy(s);
   for (auto e : c->aux_events) hipEventDestroy(e);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -177,9 +173,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
 const char* kzg_last_error(const kzg_ctx* ctx) { return ctx ? ctx->c.err.c_str() : "null context"; }
 
 int kzg_ctx_set_stream(kzg_ctx* ctx, void* hip_stream) {
-  if (!ctx) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(false);
   if (hip_stream) {
     // HIP offers no validation of a stream handle: every entry point, hipStreamQuery included, dereferences it (a
     // readable buffer that is no stream crashed the process on ROCm 7.2, profiles/r03_stream_query_crash.log, and a
@@ -243,79 +237,62 @@ int kzg_ctx_synchronize(kzg_ctx* ctx) {
 
 int kzg_ntt_device(kzg_ctx* ctx, void* d_data, uint32_t log_n, const uint64_t w[4], int inverse,
                    uint32_t batch) {
-  if (!ctx || !d_data || !w) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!d_data || !w);
   return ntt_run_device(c, static_cast<uint32_t*>(d_data), log_n, reinterpret_cast<const uint32_t*>(w),
                         inverse ? 1 : 0, batch);
 }
 
 int kzg_ntt_columns_device(kzg_ctx* ctx, void* d_data, uint32_t log_n, const uint64_t w[4], int inverse,
                            uint64_t n_cols, uint64_t col_base) {
-  if (!ctx || !d_data || !w) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!d_data || !w);
   return ntt_partial_device(c, static_cast<uint32_t*>(d_data), log_n, reinterpret_cast<const uint32_t*>(w),
                             inverse ? 1 : 0, 0, n_cols, col_base);
 }
 
 int kzg_ntt_rows_device(kzg_ctx* ctx, void* d_data, uint32_t log_n, const uint64_t w[4], int inverse,
                         uint64_t n_rows) {
-  if (!ctx || !d_data || !w) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!d_data || !w);
   return ntt_partial_device(c, static_cast<uint32_t*>(d_data), log_n, reinterpret_cast<const uint32_t*>(w),
                             inverse ? 1 : 0, 1, n_rows, 0);
 }
 
 int kzg_ntt_rows_twist_device(kzg_ctx* ctx, void* d_data, uint32_t log_n, const uint64_t w[4], int inverse,
                               uint64_t n_rows, uint64_t row_base) {
-  if (!ctx || !d_data || !w) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!d_data || !w);
   return ntt_partial_device(c, static_cast<uint32_t*>(d_data), log_n, reinterpret_cast<const uint32_t*>(w),
                             inverse ? 1 : 0, 2, n_rows, row_base);
 }
 
 int kzg_ntt_columns_plain_device(kzg_ctx* ctx, void* d_data, uint32_t log_n, const uint64_t w[4], int inverse,
                                  uint64_t n_cols) {
-  if (!ctx || !d_data || !w) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!d_data || !w);
   return ntt_partial_device(c, static_cast<uint32_t*>(d_data), log_n, reinterpret_cast<const uint32_t*>(w),
                             inverse ? 1 : 0, 3, n_cols, 0);
 }
 
 int kzg_ntt_rows_exchange_device(kzg_ctx* ctx, const void* d_src, void* d_dst, uint32_t log_n, const uint64_t w[4],
                                  int inverse, uint64_t n_rows, uint32_t world, int blocked_out) {
-  if (!ctx || !d_src || !d_dst || !w) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!d_src || !d_dst || !w);
   return ntt_rows_exchange_device(c, static_cast<const uint32_t*>(d_src), static_cast<uint32_t*>(d_dst), log_n,
                                   reinterpret_cast<const uint32_t*>(w), inverse ? 1 : 0, n_rows, world, blocked_out);
 }
 
 int kzg_ntt(kzg_ctx* ctx, uint64_t* data, uint32_t log_n, const uint64_t w[4], int inverse) {
-  if (!ctx || !data || !w) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
+  KZG_ENTER(!data || !w);
   if (log_n > 24) return set_err(c, KZG_ERR_ARG, "kzg_ntt: log_n > 24 not supported");
-  KZG_HIP(c, hipSetDevice(c->device));
   const size_t bytes = (size_t)32 << log_n;
-  int rc = ensure_buf(c, c->io, bytes);
+  void* d = nullptr;
+  int rc = stage_host(c, data, bytes, &d);
   if (rc) return rc;
-  KZG_HIP(c, hipMemcpyAsync(c->io.p, data, bytes, hipMemcpyHostToDevice, c->stream));
-  rc = ntt_run_device(c, static_cast<uint32_t*>(c->io.p), log_n, reinterpret_cast<const uint32_t*>(w),
-                      inverse ? 1 : 0, 1);
+  rc = ntt_run_device(c, static_cast<uint32_t*>(d), log_n, reinterpret_cast<const uint32_t*>(w), inverse ? 1 : 0, 1);
   if (rc) return rc;
-  KZG_HIP(c, hipMemcpyAsync(data, c->io.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  KZG_HIP(c, hipMemcpyAsync(data, d, bytes, hipMemcpyDeviceToHost, c->stream));
   KZG_HIP(c, hipStreamSynchronize(c->stream));
   return KZG_OK;
 }
 
 int kzg_fft_ff_any_device(kzg_ctx* ctx, void* d_data, size_t n, const uint64_t w[4], int inverse) {
-  if (!ctx || !d_data || !w) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!d_data || !w);
   if (n && !(n & (n - 1))) {   // power of two: the tiled kernels compute the same recursion
     uint32_t log_n = 0;
     while ((1ull << log_n) < n) ++log_n;
@@ -326,56 +303,42 @@ int kzg_fft_ff_any_device(kzg_ctx* ctx, void* d_data, size_t n, const uint64_t w
 }
 
 int kzg_fft_ff_any(kzg_ctx* ctx, uint64_t* data, size_t n, const uint64_t w[4], int inverse) {
-  if (!ctx || !data || !w) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
+  KZG_ENTER(!data || !w);
   if (n == 0 || n > ((size_t)1 << 24)) return set_err(c, KZG_ERR_ARG, "kzg_fft_ff_any: length must be in [1, 2^24]");
-  KZG_HIP(c, hipSetDevice(c->device));
   const size_t bytes = n * 32;
-  int rc = ensure_buf(c, c->io, bytes);
+  void* d = nullptr;
+  int rc = stage_host(c, data, bytes, &d);
   if (rc) return rc;
-  KZG_HIP(c, hipMemcpyAsync(c->io.p, data, bytes, hipMemcpyHostToDevice, c->stream));
-  rc = kzg_fft_ff_any_device(ctx, c->io.p, n, w, inverse);
+  rc = kzg_fft_ff_any_device(ctx, d, n, w, inverse);
   if (rc) return rc;
-  KZG_HIP(c, hipMemcpyAsync(data, c->io.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  KZG_HIP(c, hipMemcpyAsync(data, d, bytes, hipMemcpyDeviceToHost, c->stream));
   KZG_HIP(c, hipStreamSynchronize(c->stream));
   return KZG_OK;
 }
 
 int kzg_srs_load_g1(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, kzg_srs** out) {
-  if (!ctx || !xy || !out) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
+  KZG_ENTER(!xy || !out);
   *out = nullptr;
-  KZG_HIP(c, hipSetDevice(c->device));
   Srs* s = nullptr;
-  int rc = srs_load(c, xy, inf, n, &s);
-  if (rc) return rc;
-  *out = new kzg_srs{s};
-  return KZG_OK;
+  const int rc = srs_load(c, xy, inf, n, &s);
+  return adopt_srs(rc, s, out);
 }
 
 int kzg_srs_generate_range(kzg_ctx* ctx, const uint64_t tau[4], size_t start, size_t n, kzg_srs** out) {
-  if (!ctx || !tau || !out) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
+  KZG_ENTER(!tau || !out);
   *out = nullptr;
-  KZG_HIP(c, hipSetDevice(c->device));
   Srs* s = nullptr;
-  int rc = srs_generate(c, tau, start, n, &s);
-  if (rc) return rc;
-  *out = new kzg_srs{s};
-  return KZG_OK;
+  const int rc = srs_generate(c, tau, start, n, &s);
+  return adopt_srs(rc, s, out);
 }
 
 int kzg_srs_generate_strided(kzg_ctx* ctx, const uint64_t tau[4], size_t start, size_t n, size_t run_len,
                              size_t inner_stride, size_t outer_stride, kzg_srs** out) {
-  if (!ctx || !tau || !out || run_len == 0) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
+  KZG_ENTER(!tau || !out || run_len == 0);
   *out = nullptr;
-  KZG_HIP(c, hipSetDevice(c->device));
   Srs* s = nullptr;
-  int rc = srs_generate(c, tau, start, n, &s, run_len, inner_stride, outer_stride);
-  if (rc) return rc;
-  *out = new kzg_srs{s};
-  return KZG_OK;
+  const int rc = srs_generate(c, tau, start, n, &s, run_len, inner_stride, outer_stride);
+  return adopt_srs(rc, s, out);
 }
 
 int kzg_srs_generate(kzg_ctx* ctx, const uint64_t tau[4], size_t n, kzg_srs** out) {
@@ -383,59 +346,43 @@ int kzg_srs_generate(kzg_ctx* ctx, const uint64_t tau[4], size_t n, kzg_srs** ou
 }
 
 int kzg_srs_export(kzg_ctx* ctx, const kzg_srs* srs, size_t start, size_t count, uint64_t* xy, uint8_t* inf) {
-  if (!ctx || !srs || !xy || !inf) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !xy || !inf);
   return srs_export(c, srs->s, start, count, xy, inf);
 }
 
 int kzg_srs_load_g1_compressed(kzg_ctx* ctx, const uint8_t* bytes, size_t n, int check_subgroup, kzg_srs** out) {
-  if (!ctx || !bytes || !out) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
+  KZG_ENTER(!bytes || !out);
   *out = nullptr;
-  KZG_HIP(c, hipSetDevice(c->device));
   Srs* s = nullptr;
-  int rc = srs_load_g1_compressed(c, bytes, n, check_subgroup, &s);
-  if (rc) return rc;
-  *out = new kzg_srs{s};
-  return KZG_OK;
+  const int rc = srs_load_g1_compressed(c, bytes, n, check_subgroup, &s);
+  return adopt_srs(rc, s, out);
 }
 
 int kzg_srs_export_compressed(kzg_ctx* ctx, const kzg_srs* srs, size_t start, size_t count, uint8_t* out_bytes) {
-  if (!ctx || !srs || (count && !out_bytes)) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || (count && !out_bytes));
   if (srs->s->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
   return srs_export_compressed(c, srs->s, start, count, out_bytes);
 }
 
 int kzg_g1_compress(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_bytes) {
-  if (!ctx || (n && (!xy || !out_bytes))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(n && (!xy || !out_bytes));
   return g1_compress(c, xy, inf, n, out_bytes);
 }
 
 int kzg_g1_decompress(kzg_ctx* ctx, const uint8_t* bytes, size_t n, int check_subgroup, uint64_t* out_xy,
                       uint8_t* out_inf, uint8_t* out_status) {
-  if (!ctx || (n && (!bytes || !out_xy || !out_inf || !out_status))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(n && (!bytes || !out_xy || !out_inf || !out_status));
   return g1_decompress(c, bytes, n, check_subgroup, out_xy, out_inf, out_status);
 }
 
 int kzg_g1_decompress_device(kzg_ctx* ctx, const void* d_bytes, size_t n, int check_subgroup, void* d_xy, void* d_inf,
                              void* d_status) {
-  if (!ctx || (n && (!d_bytes || !d_xy || !d_inf || !d_status))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(n && (!d_bytes || !d_xy || !d_inf || !d_status));
   return g1_decompress_device(c, d_bytes, n, check_subgroup, d_xy, d_inf, d_status);
 }
 
 int kzg_g1_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status) {
-  if (!ctx || (n && (!xy || !out_status))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(n && (!xy || !out_status));
   return g1_check_subgroup(c, xy, inf, n, out_status);
 }
 
@@ -449,33 +396,25 @@ void kzg_srs_free(kzg_srs* srs) {
 
 int kzg_commit_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_scalars, const size_t* lens, size_t n_polys,
                       size_t stride, uint64_t* out_xy, uint8_t* out_inf) {
-  if (!ctx || !srs || !lens || !out_xy || !out_inf || (n_polys && !d_scalars)) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !lens || !out_xy || !out_inf || (n_polys && !d_scalars));
   return commit_device(c, srs->s, static_cast<const uint32_t*>(d_scalars), lens, n_polys, stride, out_xy, out_inf);
 }
 
 int kzg_commit_device_async(kzg_ctx* ctx, const kzg_srs* srs, const void* d_scalars, const size_t* lens,
                             size_t n_polys, size_t stride, uint64_t* out_xy, uint8_t* out_inf) {
-  if (!ctx || !srs || !lens || !out_xy || !out_inf || (n_polys && !d_scalars)) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !lens || !out_xy || !out_inf || (n_polys && !d_scalars));
   return commit_device(c, srs->s, static_cast<const uint32_t*>(d_scalars), lens, n_polys, stride, out_xy, out_inf,
                        false);
 }
 
 int kzg_commit_flush(kzg_ctx* ctx) {
-  if (!ctx) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(false);
   return commit_flush(c);
 }
 
 int kzg_commit(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* scalars, const size_t* lens, size_t n_polys,
                size_t stride, uint64_t* out_xy, uint8_t* out_inf) {
-  if (!ctx || !srs || !lens || !out_xy || !out_inf || (n_polys && stride && !scalars)) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !lens || !out_xy || !out_inf || (n_polys && stride && !scalars));
   const size_t bytes = n_polys * stride * 32;
   int rc = ensure_buf(c, c->io, bytes ? bytes : 32);
   if (rc) return rc;
@@ -500,9 +439,7 @@ int kzg_commit(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* scalars, const 
 int kzg_open_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,
                     size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf,
                     uint64_t* eval_out) {
-  if (!ctx || !srs || !z || !xi || !out_xy || !out_inf || (k && (!lens || !d_polys))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !z || !xi || !out_xy || !out_inf || (k && (!lens || !d_polys)));
   uint32_t* d_quot = nullptr;
   size_t qlen = 0;
   uint64_t ev[4];
@@ -527,9 +464,7 @@ int kzg_open_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const
 int kzg_open_device_async(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,
                           size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf,
                           uint64_t* eval_out) {
-  if (!ctx || !srs || !z || !xi || !out_xy || !out_inf || !eval_out || (k && (!lens || !d_polys))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !z || !xi || !out_xy || !out_inf || !eval_out || (k && (!lens || !d_polys)));
   uint32_t* d_quot = nullptr;
   size_t qlen = 0;
   int rc = open_quotient_device(c, static_cast<const uint32_t*>(d_polys), lens, k, stride,
@@ -557,21 +492,15 @@ int kzg_open_device_async(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys,
 
 int kzg_open(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* polys, const size_t* lens, size_t k, size_t stride,
              const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
-  if (!ctx || !srs || !z || !xi || !out_xy || !out_inf || (k && (!lens || !polys))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
-  const size_t bytes = k * stride * 32;
-  int rc = ensure_buf(c, c->io, bytes ? bytes : 32);
-  if (rc) return rc;
-  if (bytes) KZG_HIP(c, hipMemcpyAsync(c->io.p, polys, bytes, hipMemcpyHostToDevice, c->stream));
-  return kzg_open_device(ctx, srs, c->io.p, lens, k, stride, z, xi, out_xy, out_inf, eval_out);
+  KZG_ENTER(!srs || !z || !xi || !out_xy || !out_inf || (k && (!lens || !polys)));
+  void* d = nullptr;
+  if (int rc = stage_host(c, polys, k * stride * 32, &d)) return rc;
+  return kzg_open_device(ctx, srs, d, lens, k, stride, z, xi, out_xy, out_inf, eval_out);
 }
 
 int kzg_open_shard_begin(kzg_ctx* ctx, const void* d_polys, const size_t* lens, size_t k, size_t stride,
                          const uint64_t z[4], const uint64_t xi[4], uint64_t* chunk_eval_out) {
-  if (!ctx || !z || !xi || !chunk_eval_out || (k && (!lens || !d_polys))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!z || !xi || !chunk_eval_out || (k && (!lens || !d_polys)));
   return open_shard_begin_device(c, static_cast<const uint32_t*>(d_polys), lens, k, stride,
                                  reinterpret_cast<const uint32_t*>(z), reinterpret_cast<const uint32_t*>(xi),
                                  chunk_eval_out);
@@ -579,9 +508,7 @@ int kzg_open_shard_begin(kzg_ctx* ctx, const void* d_polys, const size_t* lens, 
 
 int kzg_open_shard_finish(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t z[4], const uint64_t carry[4],
                           int first_rank, uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
-  if (!ctx || !srs || !z || !carry || !out_xy || !out_inf) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !z || !carry || !out_xy || !out_inf);
   uint32_t* d_vec = nullptr;
   size_t len = 0;
   uint64_t ev[4];
@@ -595,36 +522,26 @@ int kzg_open_shard_finish(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t z[4],
 
 int kzg_srs_generate_lagrange(kzg_ctx* ctx, const uint64_t tau[4], uint32_t log_n, const uint64_t w[4],
                               kzg_srs** out) {
-  if (!ctx || !tau || !w || !out) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
+  KZG_ENTER(!tau || !w || !out);
   *out = nullptr;
-  KZG_HIP(c, hipSetDevice(c->device));
   Srs* s = nullptr;
-  int rc = srs_generate_lagrange(c, reinterpret_cast<const uint32_t*>(tau), log_n, reinterpret_cast<const uint32_t*>(w),
+  const int rc = srs_generate_lagrange(c, reinterpret_cast<const uint32_t*>(tau), log_n, reinterpret_cast<const uint32_t*>(w),
                                  &s);
-  if (rc) return rc;
-  *out = new kzg_srs{s};
-  return KZG_OK;
+  return adopt_srs(rc, s, out);
 }
 
 int kzg_srs_lagrange(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_n, const uint64_t w[4], kzg_srs** out) {
-  if (!ctx || !monomial || !w || !out) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
+  KZG_ENTER(!monomial || !w || !out);
   *out = nullptr;
-  KZG_HIP(c, hipSetDevice(c->device));
   Srs* s = nullptr;
-  int rc = srs_lagrange(c, monomial->s, log_n, reinterpret_cast<const uint32_t*>(w), &s);
-  if (rc) return rc;
-  *out = new kzg_srs{s};
-  return KZG_OK;
+  const int rc = srs_lagrange(c, monomial->s, log_n, reinterpret_cast<const uint32_t*>(w), &s);
+  return adopt_srs(rc, s, out);
 }
 
 int kzg_open_evals_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_vals, const size_t* lens, size_t k,
                           size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf,
                           uint64_t* eval_out) {
-  if (!ctx || !srs || !z || !xi || !out_xy || !out_inf || (k && (!lens || !d_vals))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !z || !xi || !out_xy || !out_inf || (k && (!lens || !d_vals)));
   return open_evals_device(c, srs->s, static_cast<const uint32_t*>(d_vals), lens, k, stride,
                            reinterpret_cast<const uint32_t*>(z), reinterpret_cast<const uint32_t*>(xi), out_xy, out_inf,
                            eval_out, /*sync=*/true);
@@ -633,9 +550,7 @@ int kzg_open_evals_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_vals, 
 int kzg_open_evals_device_async(kzg_ctx* ctx, const kzg_srs* srs, const void* d_vals, const size_t* lens, size_t k,
                                 size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy,
                                 uint8_t* out_inf, uint64_t* eval_out) {
-  if (!ctx || !srs || !z || !xi || !out_xy || !out_inf || !eval_out || (k && (!lens || !d_vals))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !z || !xi || !out_xy || !out_inf || !eval_out || (k && (!lens || !d_vals)));
   return open_evals_device(c, srs->s, static_cast<const uint32_t*>(d_vals), lens, k, stride,
                            reinterpret_cast<const uint32_t*>(z), reinterpret_cast<const uint32_t*>(xi), out_xy, out_inf,
                            eval_out, /*sync=*/false);
@@ -643,21 +558,15 @@ int kzg_open_evals_device_async(kzg_ctx* ctx, const kzg_srs* srs, const void* d_
 
 int kzg_open_evals(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* vals, const size_t* lens, size_t k, size_t stride,
                    const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
-  if (!ctx || !srs || !z || !xi || !out_xy || !out_inf || (k && (!lens || !vals))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
-  const size_t bytes = k * stride * 32;
-  int rc = ensure_buf(c, c->io, bytes ? bytes : 32);
-  if (rc) return rc;
-  if (bytes) KZG_HIP(c, hipMemcpyAsync(c->io.p, vals, bytes, hipMemcpyHostToDevice, c->stream));
-  return kzg_open_evals_device(ctx, srs, c->io.p, lens, k, stride, z, xi, out_xy, out_inf, eval_out);
+  KZG_ENTER(!srs || !z || !xi || !out_xy || !out_inf || (k && (!lens || !vals)));
+  void* d = nullptr;
+  if (int rc = stage_host(c, vals, k * stride * 32, &d)) return rc;
+  return kzg_open_evals_device(ctx, srs, d, lens, k, stride, z, xi, out_xy, out_inf, eval_out);
 }
 
 int kzg_domain_table_create(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_n, kzg_domain_table** out) {
-  if (!ctx || !monomial || !out) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
+  KZG_ENTER(!monomial || !out);
   *out = nullptr;
-  KZG_HIP(c, hipSetDevice(c->device));
   DomainTable* t = nullptr;
   int rc = domain_table_create(c, monomial->s, log_n, &t);
   if (rc) return rc;
@@ -676,28 +585,22 @@ void kzg_domain_table_free(kzg_domain_table* t) {
 int kzg_open_domain_device(kzg_ctx* ctx, const kzg_domain_table* t, const void* d_polys, const size_t* lens, size_t b,
                            size_t stride, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf,
                            uint64_t* eval_out) {
-  if (!ctx || !t || !w || (b && (!lens || !d_polys || !out_xy || !out_inf))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!t || !w || (b && (!lens || !d_polys || !out_xy || !out_inf)));
   return open_domain(c, t->t, static_cast<const uint32_t*>(d_polys), /*host_polys=*/false, lens, b, stride,
                      reinterpret_cast<const uint32_t*>(w), out_xy, out_inf, eval_out);
 }
 
 int kzg_open_domain(kzg_ctx* ctx, const kzg_domain_table* t, const uint64_t* polys, const size_t* lens, size_t b,
                     size_t stride, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
-  if (!ctx || !t || !w || (b && (!lens || !polys || !out_xy || !out_inf))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!t || !w || (b && (!lens || !polys || !out_xy || !out_inf)));
   return open_domain(c, t->t, reinterpret_cast<const uint32_t*>(polys), /*host_polys=*/true, lens, b, stride,
                      reinterpret_cast<const uint32_t*>(w), out_xy, out_inf, eval_out);
 }
 
 int kzg_coset_table_create(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_n, uint32_t log_l,
                            kzg_domain_table** out) {
-  if (!ctx || !monomial || !out) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
+  KZG_ENTER(!monomial || !out);
   *out = nullptr;
-  KZG_HIP(c, hipSetDevice(c->device));
   DomainTable* t = nullptr;
   int rc = coset_table_create(c, monomial->s, log_n, log_l, &t);
   if (rc) return rc;
@@ -708,9 +611,7 @@ int kzg_coset_table_create(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_n
 int kzg_open_cosets_device(kzg_ctx* ctx, const kzg_domain_table* t, const void* d_polys, const size_t* lens, size_t b,
                            size_t stride, uint32_t log_N, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf,
                            uint64_t* eval_out) {
-  if (!ctx || !t || !w || (b && (!lens || !d_polys || !out_xy || !out_inf))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!t || !w || (b && (!lens || !d_polys || !out_xy || !out_inf)));
   return open_cosets(c, t->t, static_cast<const uint32_t*>(d_polys), /*host_polys=*/false, lens, b, stride, log_N,
                      reinterpret_cast<const uint32_t*>(w), out_xy, out_inf, eval_out);
 }
@@ -718,9 +619,7 @@ int kzg_open_cosets_device(kzg_ctx* ctx, const kzg_domain_table* t, const void* 
 int kzg_open_cosets(kzg_ctx* ctx, const kzg_domain_table* t, const uint64_t* polys, const size_t* lens, size_t b,
                     size_t stride, uint32_t log_N, const uint64_t w[4], uint64_t* out_xy, uint8_t* out_inf,
                     uint64_t* eval_out) {
-  if (!ctx || !t || !w || (b && (!lens || !polys || !out_xy || !out_inf))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!t || !w || (b && (!lens || !polys || !out_xy || !out_inf)));
   return open_cosets(c, t->t, reinterpret_cast<const uint32_t*>(polys), /*host_polys=*/true, lens, b, stride, log_N,
                      reinterpret_cast<const uint32_t*>(w), out_xy, out_inf, eval_out);
 }
@@ -728,9 +627,7 @@ int kzg_open_cosets(kzg_ctx* ctx, const kzg_domain_table* t, const uint64_t* pol
 int kzg_open_coset_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,
                           size_t stride, uint32_t log_l, const uint64_t h[4], const uint64_t zeta[4],
                           const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
-  if (!ctx || !srs || !h || !zeta || !xi || !out_xy || !out_inf || (k && (!lens || !d_polys))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !h || !zeta || !xi || !out_xy || !out_inf || (k && (!lens || !d_polys)));
   if (srs->s->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
   if (srs->s->basis != SRS_MONOMIAL) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: the key must be monomial");
   uint32_t* d_quot = nullptr;
@@ -745,29 +642,23 @@ int kzg_open_coset_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys,
 int kzg_open_coset(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* polys, const size_t* lens, size_t k,
                    size_t stride, uint32_t log_l, const uint64_t h[4], const uint64_t zeta[4], const uint64_t xi[4],
                    uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
-  if (!ctx || !srs || !h || !zeta || !xi || !out_xy || !out_inf || (k && (!lens || !polys))) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!srs || !h || !zeta || !xi || !out_xy || !out_inf || (k && (!lens || !polys)));
   if (srs->s->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
   if (srs->s->basis != SRS_MONOMIAL) return set_err(c, KZG_ERR_ARG, "kzg_open_coset: the key must be monomial");
   int rc = open_coset_check(c, lens, k, stride, log_l, reinterpret_cast<const uint32_t*>(h),
                             reinterpret_cast<const uint32_t*>(zeta), srs->s->n);     // before anything is queued
   if (rc) return rc;
-  const size_t bytes = k * stride * 32;
-  if ((rc = ensure_buf(c, c->io, bytes ? bytes : 32))) return rc;
-  if (bytes) KZG_HIP(c, hipMemcpyAsync(c->io.p, polys, bytes, hipMemcpyHostToDevice, c->stream));
-  return kzg_open_coset_device(ctx, srs, c->io.p, lens, k, stride, log_l, h, zeta, xi, out_xy, out_inf, eval_out);
+  void* d = nullptr;
+  if ((rc = stage_host(c, polys, k * stride * 32, &d))) return rc;
+  return kzg_open_coset_device(ctx, srs, d, lens, k, stride, log_l, h, zeta, xi, out_xy, out_inf, eval_out);
 }
 
 int kzg_verify_cosets(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
                       const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
                       const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy,
                       const uint8_t* proof_inf, size_t K, const uint64_t rho[4], uint64_t* out_xy, uint8_t* out_inf) {
-  if (!ctx || !monomial || !w || !rho || !out_xy || !out_inf || !comm_xy ||
-      (K && (!comm_idx || !coset_idx || !values || !proof_xy)))
-    return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!monomial || !w || !rho || !out_xy || !out_inf || !comm_xy || (K && (!comm_idx || !coset_idx ||
+            !values || !proof_xy)));
   return verify_cosets(c, monomial->s, log_N, log_l, reinterpret_cast<const uint32_t*>(w), comm_xy, comm_inf, n_comm,
                        comm_idx, coset_idx, values, proof_xy, proof_inf, K, reinterpret_cast<const uint32_t*>(rho),
                        out_xy, out_inf);
@@ -776,9 +667,7 @@ int kzg_verify_cosets(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uin
 int kzg_recover_cosets(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
                        const uint32_t* coset_idx, size_t K, const uint64_t* values, size_t b, uint64_t* out_coeffs,
                        uint8_t* out_consistent) {
-  if (!ctx || !w || !coset_idx || !values || !out_coeffs || !out_consistent) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!w || !coset_idx || !values || !out_coeffs || !out_consistent);
   return recover_cosets(c, log_n, log_N, log_l, reinterpret_cast<const uint32_t*>(w), coset_idx, K,
                         reinterpret_cast<const uint32_t*>(values), /*host_ptrs=*/true, b,
                         reinterpret_cast<uint32_t*>(out_coeffs), out_consistent);
@@ -787,21 +676,15 @@ int kzg_recover_cosets(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint32_t lo
 int kzg_recover_cosets_device(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
                               const uint32_t* coset_idx, size_t K, const void* d_values, size_t b, void* d_coeffs,
                               uint8_t* out_consistent) {
-  if (!ctx || !w || !coset_idx || !d_values || !d_coeffs || !out_consistent) return KZG_ERR_ARG;
-  Ctx* c = &ctx->c;
-  KZG_HIP(c, hipSetDevice(c->device));
+  KZG_ENTER(!w || !coset_idx || !d_values || !d_coeffs || !out_consistent);
   return recover_cosets(c, log_n, log_N, log_l, reinterpret_cast<const uint32_t*>(w), coset_idx, K,
                         static_cast<const uint32_t*>(d_values), /*host_ptrs=*/false, b,
                         static_cast<uint32_t*>(d_coeffs), out_consistent);
 }
 
-#define KZG_VEC_ENTER()                          \
-  if (!ctx) return KZG_ERR_ARG;                  \
-  Ctx* c = &ctx->c;                              \
-  KZG_HIP(c, hipSetDevice(c->device));
-
+// The vector primitives select the device first and check their arguments then.
 int kzg_fr_vec_op(kzg_ctx* ctx, int op, size_t n, const void* d_a, const void* d_b, void* d_out) {
-  KZG_VEC_ENTER();
+  KZG_ENTER(false);
   if (op < 0 || op > 2 || (n && (!d_a || !d_b || !d_out))) return KZG_ERR_ARG;
   return fr_vec_binary(c, op, n, static_cast<const uint32_t*>(d_a), static_cast<const uint32_t*>(d_b),
                        static_cast<uint32_t*>(d_out));
@@ -809,7 +692,7 @@ int kzg_fr_vec_op(kzg_ctx* ctx, int op, size_t n, const void* d_a, const void* d
 
 int kzg_fr_vec_lincomb(kzg_ctx* ctx, size_t n, size_t k, const void* const* d_ptrs, const size_t* lens,
                        const uint64_t* scalars, void* d_out) {
-  KZG_VEC_ENTER();
+  KZG_ENTER(false);
   if (k && (!d_ptrs || !lens || !scalars)) return KZG_ERR_ARG;
   if (n && !d_out) return KZG_ERR_ARG;
   return fr_vec_lincomb(c, n, k, reinterpret_cast<const uint32_t* const*>(d_ptrs), lens,
@@ -818,33 +701,33 @@ int kzg_fr_vec_lincomb(kzg_ctx* ctx, size_t n, size_t k, const void* const* d_pt
 
 int kzg_fr_vec_mul_powers(kzg_ctx* ctx, size_t n, const void* d_a, const uint64_t s[4], const uint64_t c0[4],
                           void* d_out) {
-  KZG_VEC_ENTER();
+  KZG_ENTER(false);
   if (!s || !c0 || (n && (!d_a || !d_out))) return KZG_ERR_ARG;
   return fr_vec_mul_powers(c, n, static_cast<const uint32_t*>(d_a), reinterpret_cast<const uint32_t*>(s),
                            reinterpret_cast<const uint32_t*>(c0), static_cast<uint32_t*>(d_out));
 }
 
 int kzg_fr_vec_inverse(kzg_ctx* ctx, size_t n, const void* d_a, void* d_out) {
-  KZG_VEC_ENTER();
+  KZG_ENTER(false);
   if (n && (!d_a || !d_out)) return KZG_ERR_ARG;
   return fr_vec_inverse(c, n, static_cast<const uint32_t*>(d_a), static_cast<uint32_t*>(d_out));
 }
 
 int kzg_fr_vec_prefix_product(kzg_ctx* ctx, size_t n, const void* d_a, void* d_out) {
-  KZG_VEC_ENTER();
+  KZG_ENTER(false);
   if (n && (!d_a || !d_out)) return KZG_ERR_ARG;
   return fr_vec_prefix_product(c, n, static_cast<const uint32_t*>(d_a), static_cast<uint32_t*>(d_out));
 }
 
 int kzg_fr_poly_eval(kzg_ctx* ctx, size_t n, const void* d_a, const uint64_t z[4], uint64_t out[4]) {
-  KZG_VEC_ENTER();
+  KZG_ENTER(false);
   if (!z || !out || (n && !d_a)) return KZG_ERR_ARG;
   return fr_poly_eval(c, n, static_cast<const uint32_t*>(d_a), reinterpret_cast<const uint32_t*>(z), out);
 }
 
 int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size_t len, const void* d_vals,
                          const uint64_t z[4], uint64_t out[4]) {
-  KZG_VEC_ENTER();
+  KZG_ENTER(false);
   if (!w || !z || !out || (len && !d_vals)) return KZG_ERR_ARG;
   return fr_eval_lagrange(c, log_n, reinterpret_cast<const uint32_t*>(w), len, static_cast<const uint32_t*>(d_vals),
                           reinterpret_cast<const uint32_t*>(z), out);

@@ -24,6 +24,7 @@
 #include "g1_util.h"
 #include "msm.h"
 #include "srs_rec.h"
+#include "g1_words.h"
 
 namespace kzg {
 
@@ -34,7 +35,6 @@ template <class C>
 struct Tbl {
   static constexpr int NW = C::Fp::NW;
   static constexpr int WORDS = 2 * NW + 4;       // 20 (BN254) / 28 (BLS12-381) words
-  static constexpr int Q = WORDS / 4;
 };
 
 // the table point as XYZZ (Montgomery)
@@ -42,13 +42,8 @@ template <class C>
 __device__ __forceinline__ XYZZ<C> ld_tbl(const uint32_t* tbl, size_t idx) {
   using Fd = Field<typename C::Fp>;
   constexpr int NW = C::Fp::NW;
-  const uint4* p = reinterpret_cast<const uint4*>(tbl + idx * Tbl<C>::WORDS);
   uint32_t w[Tbl<C>::WORDS];
-#pragma unroll
-  for (int q = 0; q < Tbl<C>::Q; ++q) {
-    const uint4 v = p[q];
-    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-  }
+  ld_words<Tbl<C>::WORDS>(tbl + idx * Tbl<C>::WORDS, w);
   Affine<C> a;
   a.inf = (w[2 * NW] & 1u) != 0;
   a.x = Fd::to_mont(Fd::from_words(w));
@@ -58,22 +53,12 @@ __device__ __forceinline__ XYZZ<C> ld_tbl(const uint32_t* tbl, size_t idx) {
 
 template <class C>
 __device__ __forceinline__ void st_tbl(uint32_t* tbl, size_t idx, const Affine<C>& a) {
-  using Fd = Field<typename C::Fp>;
   constexpr int NW = C::Fp::NW;
   uint32_t w[Tbl<C>::WORDS];
-  if (a.inf) {
-#pragma unroll
-    for (int q = 0; q < 2 * NW; ++q) w[q] = 0;
-  } else {
-    Fd::to_words(Fd::from_mont(a.x), w);
-    Fd::to_words(Fd::from_mont(a.y), w + NW);
-  }
-  w[2 * NW] = a.inf ? 1u : 0u;
+  w[2 * NW] = affine_to_words<C>(a, w) ? 1u : 0u;
 #pragma unroll
   for (int q = 2 * NW + 1; q < Tbl<C>::WORDS; ++q) w[q] = 0;
-  uint4* p = reinterpret_cast<uint4*>(tbl + idx * Tbl<C>::WORDS);
-#pragma unroll
-  for (int q = 0; q < Tbl<C>::Q; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  st_words<Tbl<C>::WORDS>(tbl + idx * Tbl<C>::WORDS, w);
 }
 
 // ---- kernels -----------------------------------------------------------------------------------------------------
@@ -266,23 +251,12 @@ __global__ __launch_bounds__(64) void dom_finish_table_kernel(const uint32_t* bu
 template <class C>
 __global__ __launch_bounds__(64) void dom_finish_proofs_kernel(const uint32_t* buf, uint32_t count, uint32_t* out_xy,
                                                                uint8_t* out_inf) {
-  using F = typename C::Fp;
-  using Fd = Field<F>;
+  constexpr int NW = C::Fp::NW;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  const Affine<C> a = Ec<C>::to_affine(ld_point<C>(buf, i));
-  uint32_t w[2 * F::NW];
-  if (a.inf) {
-#pragma unroll
-    for (int q = 0; q < 2 * F::NW; ++q) w[q] = 0;
-  } else {
-    Fd::to_words(Fd::from_mont(a.x), w);
-    Fd::to_words(Fd::from_mont(a.y), w + F::NW);
-  }
-  uint4* p = reinterpret_cast<uint4*>(out_xy + (size_t)i * 2 * F::NW);
-#pragma unroll
-  for (int q = 0; q < 2 * F::NW / 4; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-  out_inf[i] = a.inf ? 1 : 0;
+  uint32_t w[2 * NW];
+  out_inf[i] = affine_to_words<C>(Ec<C>::to_affine(ld_point<C>(buf, i)), w) ? 1 : 0;
+  st_words<2 * NW>(out_xy + (size_t)i * 2 * NW, w);
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------
@@ -292,13 +266,6 @@ constexpr uint32_t DOM_MAX_LOG = 20;
 // the chunk instead)
 constexpr size_t DOM_SCRATCH_BYTES = (size_t)2 << 30;
 constexpr uint32_t DOM_MAX_CHUNK = 1024;       // keeps every launch below 2^31 threads (N <= 2^21)
-
-// small integer -> Montgomery element
-template <class F>
-Fe<F> fr_small(uint32_t v) {
-  uint32_t w[8] = {v, 0, 0, 0, 0, 0, 0, 0};
-  return mont_from_words<F>(w);
-}
 
 template <class F>
 Fe<F> fr_pow_words(const Fe<F>& base, const uint32_t* e) {
@@ -312,7 +279,7 @@ Fe<F> fr_pow_words(const Fe<F>& base, const uint32_t* e) {
   return acc;
 }
 
-// the library's primitive 2^log_len-th root: g^((r-1) / 2^log_len), g = 5 (BN254) / 7 (BLS12-381), Montgomery
+// the library's primitive 2^log_len-th root: g^((r-1) / 2^log_len), g = fr_generator (fr_util.h), Montgomery
 template <class C>
 Fe<typename C::Fr> dom_omega(uint32_t log_len) {
   using F = typename C::Fr;
@@ -323,7 +290,7 @@ Fe<typename C::Fr> dom_omega(uint32_t log_len) {
     const uint32_t hi = k + 1 < 8 ? e[k + 1] : 0u;
     e[k] = (e[k] >> log_len) | (log_len ? hi << (32 - log_len) : 0u);
   }
-  return fr_pow_words<F>(fr_small<F>(C::ID == 0 ? 5u : 7u), e);
+  return fr_pow_words<F>(fr_generator<C>(), e);
 }
 
 template <class C>
@@ -453,7 +420,7 @@ int open_domain_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
   const Fe<F> omega = dom_omega<C>(log_nn);
   const Fe<F> omega_inv = Fd::inv(omega);
   uint32_t omega_words[8];
-  Fd::to_words(Fd::from_mont(omega), omega_words);
+  words_from_mont<F>(omega, omega_words);
   const Fe<F> ninv = Fd::reduce(inv_pow2<F>(log_nn));
   const Fe<F> w = mont_from_words<F>(w_words);
   const hipMemcpyKind kind = host_polys ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -543,7 +510,7 @@ int open_cosets_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
   const Fe<F> omega = dom_omega<C>(log_mm);
   const Fe<F> omega_inv = Fd::inv(omega);
   uint32_t omega_words[8];
-  Fd::to_words(Fd::from_mont(omega), omega_words);
+  words_from_mont<F>(omega, omega_words);
   const Fe<F> mminv = Fd::reduce(inv_pow2<F>(log_mm));
   Fe<F> wl = mont_from_words<F>(w_words);                                         // w^l: the final transform's root
   for (uint32_t q = 0; q < log_l; ++q) wl = Fd::sqr(wl);
@@ -606,12 +573,10 @@ int launch_levels(Ctx* c, uint32_t* buf, uint32_t nvec, uint32_t log_len, const 
   return KZG_OK;
 }
 int domain_table_create(Ctx* c, const Srs* mono, uint32_t log_n, DomainTable** out) {
-  return c->curve == 0 ? domain_table_t<Bn254>(c, mono, log_n, 0, "kzg_domain_table_create", "domain_table", out)
-                       : domain_table_t<Bls12_381>(c, mono, log_n, 0, "kzg_domain_table_create", "domain_table", out);
+  return KZG_BY_CURVE(c, domain_table_t, c, mono, log_n, 0, "kzg_domain_table_create", "domain_table", out);
 }
 int coset_table_create(Ctx* c, const Srs* mono, uint32_t log_n, uint32_t log_l, DomainTable** out) {
-  return c->curve == 0 ? domain_table_t<Bn254>(c, mono, log_n, log_l, "kzg_coset_table_create", "coset_table", out)
-                       : domain_table_t<Bls12_381>(c, mono, log_n, log_l, "kzg_coset_table_create", "coset_table", out);
+  return KZG_BY_CURVE(c, domain_table_t, c, mono, log_n, log_l, "kzg_coset_table_create", "coset_table", out);
 }
 void domain_table_free(DomainTable* t) {
   if (!t) return;
@@ -621,17 +586,13 @@ void domain_table_free(DomainTable* t) {
 size_t domain_table_size(const DomainTable* t) { return t ? t->n : 0; }
 int open_domain(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_polys, const size_t* lens, size_t b,
                 size_t stride, const uint32_t* w_words, uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out) {
-  return c->curve == 0
-             ? open_domain_t<Bn254>(c, t, polys, host_polys, lens, b, stride, w_words, out_xy, out_inf, eval_out)
-             : open_domain_t<Bls12_381>(c, t, polys, host_polys, lens, b, stride, w_words, out_xy, out_inf, eval_out);
+  return KZG_BY_CURVE(c, open_domain_t, c, t, polys, host_polys, lens, b, stride, w_words, out_xy, out_inf, eval_out);
 }
 int open_cosets(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_polys, const size_t* lens, size_t b,
                 size_t stride, uint32_t log_N, const uint32_t* w_words, uint64_t* out_xy, uint8_t* out_inf,
                 uint64_t* eval_out) {
-  return c->curve == 0 ? open_cosets_t<Bn254>(c, t, polys, host_polys, lens, b, stride, log_N, w_words, out_xy, out_inf,
-                                              eval_out)
-                       : open_cosets_t<Bls12_381>(c, t, polys, host_polys, lens, b, stride, log_N, w_words, out_xy,
-                                                  out_inf, eval_out);
+  return KZG_BY_CURVE(c, open_cosets_t, c, t, polys, host_polys, lens, b, stride, log_N, w_words, out_xy, out_inf,
+                      eval_out);
 }
 
 }  // namespace kzg

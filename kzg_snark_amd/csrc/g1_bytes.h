@@ -17,6 +17,7 @@
 // (what a vector load leaves in registers), so canonical word k of x is the byte-swapped raw[NW - 1 - k].
 #pragma once
 #include "ec.h"
+#include "g1_words.h"
 
 namespace kzg {
 
@@ -97,16 +98,6 @@ struct FpRoot {
       if (!lt && !gt) { lt = w[k] < h; gt = w[k] > h; }
     }
     return gt;
-  }
-  // canonical words < p
-  static KZG_HD bool words_below_p(const uint32_t* w) {
-    bool lt = false, gt = false;
-#pragma unroll
-    for (int k = F::NW - 1; k >= 0; --k) {
-      const uint32_t pw = F::PW[k];
-      if (!lt && !gt) { lt = w[k] < pw; gt = w[k] > pw; }
-    }
-    return lt;
   }
 };
 
@@ -200,7 +191,7 @@ struct G1Bytes {
       }
       larger = flags == 3u;
     }
-    if (!Root::words_below_p(w)) return G1_BAD_ENCODING;
+    if (!words_below_p<F>(w)) return G1_BAD_ENCODING;
     const E x = Fd::to_mont(Fd::from_words(w));
     E y;
     if (!fp_sqrt<F>(Fd::add(Fd::mul(Fd::sqr(x), x), curve_b()), y)) return G1_NOT_ON_CURVE;
@@ -228,20 +219,11 @@ struct G1Bytes {
     for (int k = 0; k < NW; ++k) raw[NW - 1 - k] = bswap32(w[k]);
   }
 
-  // canonical affine words: both coordinates below p and the point on the curve (ver_import_kernel's rule);
-  // x, y: the point in Montgomery form
-  static KZG_HD bool import_affine(const uint32_t* wx, const uint32_t* wy, E& x, E& y) {
-    const bool below = Root::words_below_p(wx) && Root::words_below_p(wy);
-    x = Fd::reduce(Fd::to_mont(Fd::from_words(wx)));
-    y = Fd::reduce(Fd::to_mont(Fd::from_words(wy)));
-    return below && Ec<C>::on_curve(x, y);
-  }
-
-  // status of an affine point: 0, 2 (a coordinate >= p or off the curve) or 3
+  // status of an affine point: 0, 2 (a coordinate >= p or off the curve: g1_words.h's import_affine) or 3
   static KZG_HD int check_affine(const uint32_t* wx, const uint32_t* wy, bool inf) {
     if (inf) return G1_OK;
     E x, y;
-    if (!import_affine(wx, wy, x, y)) return G1_NOT_ON_CURVE;
+    if (!import_affine<C>(wx, wy, x, y)) return G1_NOT_ON_CURVE;
     return in_subgroup(x, y) ? G1_OK : G1_NOT_IN_SUBGROUP;
   }
 };

@@ -7,6 +7,7 @@
 // vector accesses (a blob is 3 or 2 of them, an affine point 6 or 4), statuses and flags as per-lane byte stores.
 #include "internal.h"
 #include "msm.h"
+#include "g1_util.h"
 #include "srs_rec.h"
 #include "g1_bytes.h"
 #include <string>
@@ -17,24 +18,6 @@ namespace kzg {
 namespace {
 
 constexpr size_t G1_MAX_POINTS = (size_t)1 << 24;
-
-template <int W>
-__device__ __forceinline__ void ld_words(const uint32_t* p, uint32_t* w) {
-  static_assert(W % 4 == 0, "whole 16-byte accesses");
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-#pragma unroll
-  for (int i = 0; i < W / 4; ++i) {
-    const uint4 v = q[i];
-    w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-  }
-}
-template <int W>
-__device__ __forceinline__ void st_words(uint32_t* p, const uint32_t* w) {
-  static_assert(W % 4 == 0, "whole 16-byte accesses");
-  uint4* q = reinterpret_cast<uint4*>(p);
-#pragma unroll
-  for (int i = 0; i < W / 4; ++i) q[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-}
 
 // blobs -> canonical affine words, infinity flags, statuses 0 / 1 / 2 (the subgroup is g1_subgroup_kernel's)
 template <class C>
@@ -80,32 +63,26 @@ __global__ __launch_bounds__(256) void g1_subgroup_kernel(uint32_t* xy, const ui
   }
 }
 
-// affine points -> blobs.  recs == nullptr: canonical words (xy, inf), validated by ver_import_kernel's rule (a
+// affine points -> blobs.  recs == nullptr: canonical words (xy, inf), validated by g1_words.h's import_affine (a
 // coordinate >= p or a point off the curve is counted in *bad).  Otherwise the window-0 records start .. start + n - 1
 // of a key (Montgomery form, canonical; nothing to validate).
 template <class C>
 __global__ __launch_bounds__(256) void g1_compress_kernel(const uint32_t* xy, const uint8_t* inf, const uint32_t* recs,
                                                           size_t start, size_t n, uint32_t* bytes, uint32_t* bad) {
-  using F = typename C::Fp;
-  using Fd = Field<F>;
   using G = G1Bytes<C>;
   constexpr int NW = G::NW;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t w[2 * NW], raw[NW];
   bool is_inf;
+  Affine<C> a;
   if (recs) {
-    Fe<F> x, y;
-    is_inf = load_rec<C>(recs, start + i, x, y) & 1u;
-    Fd::to_words(Fd::from_mont(x), w);
-    Fd::to_words(Fd::from_mont(y), w + NW);
+    a.inf = load_rec<C>(recs, start + i, a.x, a.y) & 1u;
+    is_inf = affine_to_words<C>(a, w);
   } else {
     is_inf = inf && inf[i];
     ld_words<2 * NW>(xy + i * 2 * NW, w);
-    if (!is_inf) {
-      Fe<F> x, y;
-      if (!G::import_affine(w, w + NW, x, y)) atomicAdd(bad, 1u);
-    }
+    if (!is_inf && !import_affine<C>(w, w + NW, a.x, a.y)) atomicAdd(bad, 1u);
   }
   G::encode(w, w + NW, is_inf, raw);
   st_words<NW>(bytes + i * NW, raw);
@@ -252,8 +229,6 @@ int export_compressed_t(Ctx* c, const Srs* s, size_t start, size_t count, uint8_
 
 }  // namespace
 
-#define G1_BY_CURVE(fn, ...) (c->curve == 0 ? fn<Bn254>(__VA_ARGS__) : fn<Bls12_381>(__VA_ARGS__))
-
 static int size_check(Ctx* c, size_t n, const char* who) {
   if (n > G1_MAX_POINTS) {
     const std::string msg = std::string(who) + ": more than 2^24 points";
@@ -265,13 +240,13 @@ static int size_check(Ctx* c, size_t n, const char* who) {
 int g1_compress(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_bytes) {
   if (n == 0) return KZG_OK;
   if (int rc = size_check(c, n, "kzg_g1_compress")) return rc;
-  return G1_BY_CURVE(compress_t, c, xy, inf, n, out_bytes);
+  return KZG_BY_CURVE(c, compress_t, c, xy, inf, n, out_bytes);
 }
 int g1_decompress(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, uint64_t* out_xy, uint8_t* out_inf,
                   uint8_t* out_status) {
   if (n == 0) return KZG_OK;
   if (int rc = size_check(c, n, "kzg_g1_decompress")) return rc;
-  return G1_BY_CURVE(decompress_t, c, bytes, n, check_subgroup, out_xy, out_inf, out_status);
+  return KZG_BY_CURVE(c, decompress_t, c, bytes, n, check_subgroup, out_xy, out_inf, out_status);
 }
 int g1_decompress_device(Ctx* c, const void* d_bytes, size_t n, int check_subgroup, void* d_xy, void* d_inf,
                          void* d_status) {
@@ -280,24 +255,24 @@ int g1_decompress_device(Ctx* c, const void* d_bytes, size_t n, int check_subgro
   if (!aligned16(d_bytes) || !aligned16(d_xy))
     return set_err(c, KZG_ERR_ARG, "kzg_g1_decompress_device: misaligned device pointer");
   ProfScope span(c, "g1_decompress");
-  return G1_BY_CURVE(decompress_launch, c, static_cast<const uint32_t*>(d_bytes), n, check_subgroup,
+  return KZG_BY_CURVE(c, decompress_launch, c, static_cast<const uint32_t*>(d_bytes), n, check_subgroup,
                      static_cast<uint32_t*>(d_xy), static_cast<uint8_t*>(d_inf), static_cast<uint8_t*>(d_status));
 }
 int g1_check_subgroup(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status) {
   if (n == 0) return KZG_OK;
   if (int rc = size_check(c, n, "kzg_g1_check_subgroup")) return rc;
-  return G1_BY_CURVE(check_subgroup_t, c, xy, inf, n, out_status);
+  return KZG_BY_CURVE(c, check_subgroup_t, c, xy, inf, n, out_status);
 }
 int srs_load_g1_compressed(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, Srs** out) {
   if (n == 0) return set_err(c, KZG_ERR_ARG, "kzg_srs_load_g1_compressed: bad size");
   if (int rc = size_check(c, n, "kzg_srs_load_g1_compressed")) return rc;
-  return G1_BY_CURVE(load_compressed_t, c, bytes, n, check_subgroup, out);
+  return KZG_BY_CURVE(c, load_compressed_t, c, bytes, n, check_subgroup, out);
 }
 int srs_export_compressed(Ctx* c, const Srs* s, size_t start, size_t count, uint8_t* out_bytes) {
   if (start > s->n || count > s->n - start) return set_err(c, KZG_ERR_ARG, "kzg_srs_export_compressed: range");
   if (count == 0) return KZG_OK;
   if (int rc = size_check(c, count, "kzg_srs_export_compressed")) return rc;
-  return G1_BY_CURVE(export_compressed_t, c, s, start, count, out_bytes);
+  return KZG_BY_CURVE(c, export_compressed_t, c, s, start, count, out_bytes);
 }
 
 }  // namespace kzg

@@ -1,5 +1,9 @@
 // internal.h -- library-private declarations shared by the translation units of
-// libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, poly.hip, verify.hip, recover.hip, g1_bytes.hip).
+// libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, msm_prep.hip, poly.hip, lagrange.hip, domain.hip, verify.hip,
+// recover.hip, g1_bytes.hip): the context, error and profiling plumbing, the dispatch by curve (KZG_BY_CURVE,
+// KZG_BY_FR) and the entry points of ntt.hip and poly.hip.  Shared device helpers live in fr_util.h (one Fr element,
+// the power-table lookup), g1_util.h (word arrays, XYZZ points), g1_words.h (point <-> canonical words) and
+// srs_rec.h (key records).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -115,6 +119,11 @@ int ensure_buf(Ctx* c, DevBuf& b, size_t bytes);
     if (e__ != hipSuccess) return set_err((c), KZG_ERR_HIP, #call, e__); \
   } while (0)
 
+// Call-through by the context's curve: fn<Bn254 | Bls12_381>(args) for code over the curve, fn<BnFr | BlsFr>(args) for
+// code over the scalar field alone.
+#define KZG_BY_CURVE(c, fn, ...) ((c)->curve == 0 ? fn<Bn254>(__VA_ARGS__) : fn<Bls12_381>(__VA_ARGS__))
+#define KZG_BY_FR(c, fn, ...) ((c)->curve == 0 ? fn<BnFr>(__VA_ARGS__) : fn<BlsFr>(__VA_ARGS__))
+
 // msm.hip: is an accumulate kernel of the commit pipeline queued or running?
 bool msm_accumulate_in_flight(Ctx* c);
 
@@ -136,5 +145,12 @@ int fr_vec_mul_powers(Ctx* c, size_t n, const uint32_t* a, const uint32_t* s, co
 int fr_vec_inverse(Ctx* c, size_t n, const uint32_t* a, uint32_t* out);
 int fr_vec_prefix_product(Ctx* c, size_t n, const uint32_t* a, uint32_t* out);
 int fr_poly_eval(Ctx* c, size_t n, const uint32_t* a, const uint32_t* z, uint64_t* out);
+
+// lagrange.hip (beside its table of w^i; not poly.hip, whose multiplier is built without field.h's chain pin):
+// d_tab <- the two-level power table of `base` (Montgomery form), POW_TAB entries of 32 bytes, read by fr_pow_lookup
+// (fr_util.h).  Enqueues one launch of fr_pow_table_kernel.
+struct FrArg;   // fr_util.h
+__attribute__((visibility("hidden")))   // library-private: not in the exported symbol list
+int fr_pow_table(Ctx* c, const FrArg& base, uint32_t* d_tab);
 
 }  // namespace kzg

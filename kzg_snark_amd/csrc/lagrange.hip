@@ -37,14 +37,6 @@ constexpr uint32_t SUM_TB = 128;  // threads per workgroup of the reduction pass
 // 32 elements per thread at 2^20: 115 us; 2048: 4 per thread)
 constexpr uint32_t SUM_MAXG = 2048;
 
-template <class F>
-__device__ __forceinline__ Fe<F> shfl_xor_fe(const Fe<F>& v, int mask) {
-  Fe<F> r;
-#pragma unroll
-  for (int j = 0; j < F::N; ++j) r.l[j] = __shfl_xor(v.l[j], mask);
-  return r;
-}
-
 // ---- Fr passes ------------------------------------------------------------------------------------
 
 // out[i] = w^i (canonical words); w in Montgomery form
@@ -59,6 +51,31 @@ __global__ __launch_bounds__(256) void lagr_wpow_kernel(uint32_t n, FrArg w, uin
     b = Fd::sqr(b);
   }
   store_words<F>(out + (size_t)i * 8, Fd::from_mont(acc));
+}
+
+// tab <- the two-level power table of `base` (fr_util.h: POW_TAB entries, Montgomery words); base_hi = base^POW_TLO
+template <class F>
+__global__ __launch_bounds__(256) void fr_pow_table_kernel(FrArg base, FrArg base_hi, uint32_t* tab) {
+  using Fd = Field<F>;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= POW_TAB) return;
+  Fe<F> b = arg_fe<F>(i < POW_TLO ? base : base_hi), acc = Fd::one();
+  for (uint32_t bits = i < POW_TLO ? i : i - POW_TLO; bits; bits >>= 1) {
+    if (bits & 1u) acc = Fd::mul(acc, b);
+    b = Fd::sqr(b);
+  }
+  store_words<F>(tab + (size_t)i * 8, acc);
+}
+
+template <class F>
+int pow_table_t(Ctx* c, const FrArg& base, uint32_t* d_tab) {
+  Fe<F> hi;
+  memcpy(hi.l, base.l, sizeof(hi.l));
+  for (uint32_t q = 0; q < POW_TLOG; ++q) hi = Field<F>::sqr(hi);
+  hipLaunchKernelGGL(fr_pow_table_kernel<F>, dim3((POW_TAB + 255) / 256), dim3(256), 0, c->stream, base, fr_arg<F>(hi),
+                     d_tab);
+  KZG_HIP(c, hipGetLastError());
+  return KZG_OK;
 }
 
 // d[i] = z - w^i (z in standard form: the difference of two standard values is one)
@@ -201,11 +218,6 @@ __global__ __launch_bounds__(64) void g1_intt_finish_kernel(const uint32_t* buf,
 
 // ---- host side --------------------------------------------------------------------------------------
 
-template <class F>
-void lg_words(const Fe<F>& mont, uint32_t* w) {
-  Field<F>::to_words(Field<F>::from_mont(mont), w);
-}
-
 // (z^n - 1)/n (Montgomery) and whether z^n = 1 (z in H)
 template <class F>
 Fe<F> vanishing_over_n(const Fe<F>& z_mont, uint32_t log_n, bool* in_domain) {
@@ -323,7 +335,7 @@ int srs_lagrange_t(Ctx* c, const Srs* mono, uint32_t log_n, const uint32_t* w_wo
     if ((rc = launch_wpow<F>(c, n, w_words, s->d_wpow))) return fail(rc);
     const Fe<F> winv = Fd::inv(mont_from_words<F>(w_words));
     LgWords ninv;
-    lg_words<F>(inv_pow2<F>(log_n), ninv.w);
+    words_from_mont<F>(inv_pow2<F>(log_n), ninv.w);
     hipLaunchKernelGGL(g1_intt_load_kernel<C>, dim3((n + 127) / 128), dim3(128), 0, c->stream, mono->recs, n, log_n,
                        d_buf);
     if ((rc = launch_levels(c, d_buf, 1, log_n, fr_arg<F>(winv)))) return fail(rc);
@@ -375,7 +387,7 @@ int open_evals_t(Ctx* c, const Srs* s, const uint32_t* d_vals, const size_t* len
     for (size_t j = 0; j < k; ++j) {
       ptrs[j] = d_vals + j * stride * 8;
       xp = Fd::mul(xp, xi);                                // xi^(j+1): kzg.py:148-150
-      lg_words<F>(xp, &xw[j * 8]);
+      words_from_mont<F>(xp, &xw[j * 8]);
     }
     if ((rc = fr_vec_lincomb(c, n, k, ptrs.data(), lens, xw.data(), d_P))) return rc;
     if ((rc = value_pass<F>(c, s->log_n, (uint32_t)n, d_P, s->d_wpow, z_words, d_den, d_inv, d_part, d_val, d_den)))
@@ -418,25 +430,21 @@ int fr_eval_lagrange_t(Ctx* c, uint32_t log_n, const uint32_t* w_words, size_t l
 
 }  // namespace
 
+int fr_pow_table(Ctx* c, const FrArg& base, uint32_t* d_tab) { return KZG_BY_FR(c, pow_table_t, c, base, d_tab); }
 int srs_generate_lagrange(Ctx* c, const uint32_t* tau_words, uint32_t log_n, const uint32_t* w_words, Srs** out) {
-  return c->curve == 0 ? srs_generate_lagrange_t<Bn254>(c, tau_words, log_n, w_words, out)
-                       : srs_generate_lagrange_t<Bls12_381>(c, tau_words, log_n, w_words, out);
+  return KZG_BY_CURVE(c, srs_generate_lagrange_t, c, tau_words, log_n, w_words, out);
 }
 int srs_lagrange(Ctx* c, const Srs* mono, uint32_t log_n, const uint32_t* w_words, Srs** out) {
-  return c->curve == 0 ? srs_lagrange_t<Bn254>(c, mono, log_n, w_words, out)
-                       : srs_lagrange_t<Bls12_381>(c, mono, log_n, w_words, out);
+  return KZG_BY_CURVE(c, srs_lagrange_t, c, mono, log_n, w_words, out);
 }
 int open_evals_device(Ctx* c, const Srs* s, const uint32_t* d_vals, const size_t* lens, size_t k, size_t stride,
                       const uint32_t* z_words, const uint32_t* xi_words, uint64_t* out_xy, uint8_t* out_inf,
                       uint64_t* eval_out, bool sync) {
-  return c->curve == 0
-             ? open_evals_t<BnFr>(c, s, d_vals, lens, k, stride, z_words, xi_words, out_xy, out_inf, eval_out, sync)
-             : open_evals_t<BlsFr>(c, s, d_vals, lens, k, stride, z_words, xi_words, out_xy, out_inf, eval_out, sync);
+  return KZG_BY_FR(c, open_evals_t, c, s, d_vals, lens, k, stride, z_words, xi_words, out_xy, out_inf, eval_out, sync);
 }
 int fr_eval_lagrange(Ctx* c, uint32_t log_n, const uint32_t* w_words, size_t len, const uint32_t* d_vals,
                      const uint32_t* z_words, uint64_t* out) {
-  return c->curve == 0 ? fr_eval_lagrange_t<BnFr>(c, log_n, w_words, len, d_vals, z_words, out)
-                       : fr_eval_lagrange_t<BlsFr>(c, log_n, w_words, len, d_vals, z_words, out);
+  return KZG_BY_FR(c, fr_eval_lagrange_t, c, log_n, w_words, len, d_vals, z_words, out);
 }
 
 }  // namespace kzg

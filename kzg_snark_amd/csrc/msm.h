@@ -29,6 +29,12 @@ int srs_load_device(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n
 // (i % run_len) * inner_stride)
 int srs_generate(Ctx* c, const uint64_t* tau, size_t start, size_t n, Srs** out, size_t run_len = 0,
                  size_t inner_stride = 1, size_t outer_stride = 0);
+// canonical affine words (x | y per point, flags or null) -> window-0 records at d_recs; *d_bad counts the points that
+// fail.  range = true: both coordinates below p and the curve equation (g1_words.h's import_affine: verification,
+// compression).  range = false: the curve equation alone, coordinates taken modulo p (key loading).  Enqueue only.
+__attribute__((visibility("hidden")))   // library-private: not in the exported symbol list
+int g1_import(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n, bool range, uint32_t* d_recs,
+              uint32_t* d_bad);
 int srs_export(Ctx* c, const Srs* s, size_t start, size_t count, uint64_t* xy, uint8_t* inf);
 void srs_free(Srs* s);
 // record i = scalars[i] * G1 (device vector of n canonical scalars), windows built; synchronises

@@ -36,6 +36,7 @@
 #include "msm.h"
 #include "msm_prep.h"
 #include "srs_rec.h"
+#include "g1_words.h"
 
 namespace kzg {
 
@@ -98,25 +99,31 @@ __device__ __forceinline__ XYZZ<C> shfl_xor_xyzz(const XYZZ<C>& v, int mask) {
 
 // ---- SRS table construction ------------------------------------------------------
 
-// canonical affine words (x | y, NW 32-bit words each) -> window-0 records
-template <class C>
-__global__ void srs_import_kernel(const uint32_t* xy, const uint8_t* inf, uint32_t* recs, size_t n,
-                                  uint32_t* bad_count) {
+// canonical affine words (x | y, NW 32-bit words each) -> window-0 records; a point that fails the rule is counted in
+// *bad.  RANGE: g1_words.h's import_affine (both coordinates below p, on the curve).  Otherwise the curve equation
+// alone, on the coordinates taken modulo p: what kzg_srs_load_g1 has always accepted.
+template <class C, bool RANGE>
+__global__ __launch_bounds__(256) void g1_import_kernel(const uint32_t* xy, const uint8_t* inf, uint32_t* recs, size_t n,
+                                                        uint32_t* bad) {
   using F = typename C::Fp;
-  using Fd = Field<F>;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const bool is_inf = inf && inf[i];
-  Fe<F> x = Fd::zero(), y = Fd::zero();
-  if (!is_inf) {
-    uint32_t wx[F::NW], wy[F::NW];
+  Affine<C> a = affine_from_words<C>(nullptr, true);   // zeros
+  a.inf = inf && inf[i];
+  if (!a.inf) {
+    uint32_t w[2 * F::NW];
 #pragma unroll
-    for (int k = 0; k < F::NW; ++k) { wx[k] = xy[i * 2 * F::NW + k]; wy[k] = xy[i * 2 * F::NW + F::NW + k]; }
-    x = Fd::reduce(Fd::to_mont(Fd::from_words(wx)));
-    y = Fd::reduce(Fd::to_mont(Fd::from_words(wy)));
-    if (!Ec<C>::on_curve(x, y)) atomicAdd(bad_count, 1u);
+    for (int k = 0; k < 2 * F::NW; ++k) w[k] = xy[i * 2 * F::NW + k];
+    bool ok;
+    if constexpr (RANGE) {
+      ok = import_affine<C>(w, w + F::NW, a.x, a.y);
+    } else {
+      a = affine_from_words<C>(w, false);
+      ok = Ec<C>::on_curve(a.x, a.y);
+    }
+    if (!ok) atomicAdd(bad, 1u);
   }
-  store_rec<C>(recs, i, x, y, is_inf);
+  store_rec<C>(recs, i, a.x, a.y, a.inf);
 }
 
 // records of window j -> window j+1: multiply every point by 2^win_bits
@@ -139,21 +146,15 @@ __global__ __launch_bounds__(128) void srs_window_kernel(const uint32_t* src, ui
 template <class C>
 __global__ void srs_export_kernel(const uint32_t* recs, size_t start, size_t count, uint32_t* xy, uint8_t* inf) {
   using F = typename C::Fp;
-  using Fd = Field<F>;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  Fe<F> x, y;
-  load_rec<C>(recs, start + i, x, y);
-  const bool is_inf = recs[(start + i) * Rec<C>::WORDS + Rec<C>::FLAG] & 1u;
-  uint32_t wx[F::NW], wy[F::NW];
-  Fd::to_words(Fd::from_mont(x), wx);
-  Fd::to_words(Fd::from_mont(y), wy);
+  Affine<C> a;
+  load_rec<C>(recs, start + i, a.x, a.y);
+  a.inf = recs[(start + i) * Rec<C>::WORDS + Rec<C>::FLAG] & 1u;
+  uint32_t w[2 * F::NW];
+  inf[i] = affine_to_words<C>(a, w) ? 1 : 0;
 #pragma unroll
-  for (int k = 0; k < F::NW; ++k) {
-    xy[i * 2 * F::NW + k] = is_inf ? 0u : wx[k];
-    xy[i * 2 * F::NW + F::NW + k] = is_inf ? 0u : wy[k];
-  }
-  inf[i] = is_inf ? 1 : 0;
+  for (int k = 0; k < 2 * F::NW; ++k) xy[i * 2 * F::NW + k] = w[k];
 }
 
 // fixed-base table for kzg_srs_generate: tab[j][d-1] = d * 2^(8j) * G, d = 1..255, j = 0..31.
@@ -541,6 +542,22 @@ int nwin_of(int wb) { return (256 + wb - 1) / wb; }
 // ---- host-side drivers ----------------------------------------------------------------
 
 template <class C>
+static int g1_import_t(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n, bool range, uint32_t* d_recs,
+                       uint32_t* d_bad) {
+  const dim3 grid((uint32_t)((n + 255) / 256));
+  if (range)
+    hipLaunchKernelGGL((g1_import_kernel<C, true>), grid, dim3(256), 0, c->stream, d_xy, d_inf, d_recs, n, d_bad);
+  else
+    hipLaunchKernelGGL((g1_import_kernel<C, false>), grid, dim3(256), 0, c->stream, d_xy, d_inf, d_recs, n, d_bad);
+  KZG_HIP(c, hipGetLastError());
+  return KZG_OK;
+}
+int g1_import(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n, bool range, uint32_t* d_recs,
+              uint32_t* d_bad) {
+  return KZG_BY_CURVE(c, g1_import_t, c, d_xy, d_inf, n, range, d_recs, d_bad);
+}
+
+template <class C>
 static int srs_build_windows(Ctx* c, Srs* s) {
   const size_t n = s->n;
   const uint32_t blocks = (uint32_t)((n + 127) / 128);
@@ -576,8 +593,7 @@ static int srs_load_device_t(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf,
   auto fail = [&](int rc) { hipFree(d_bad); hipFree(s->recs); delete s; return rc; };
   if (hipMalloc(reinterpret_cast<void**>(&d_bad), 4) != hipSuccess) return fail(set_err(c, KZG_ERR_ALLOC, "hipMalloc"));
   hipMemsetAsync(d_bad, 0, 4, c->stream);
-  hipLaunchKernelGGL(srs_import_kernel<C>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, d_xy, d_inf,
-                     s->recs, n, d_bad);
+  if (int rc = g1_import(c, d_xy, d_inf, n, /*range=*/false, s->recs, d_bad)) return fail(rc);
   uint32_t bad = 0;
   hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream);
   e = hipStreamSynchronize(c->stream);
@@ -606,12 +622,20 @@ static int srs_load_t(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, 
   return rc;
 }
 
+// the generators, canonical affine words x | y
+static const uint64_t GEN_BN254[8] = {1, 0, 0, 0, 2, 0, 0, 0};
+static const uint64_t GEN_BLS[12] = {
+    0xfb3af00adb22c6bbull, 0x6c55e83ff97a1aefull, 0xa14e3a3f171bac58ull, 0xc3688c4f9774b905ull,
+    0x2695638c4fa9ac0full, 0x17f1d3a73197d794ull,
+    0x0caa232946c5e7e1ull, 0xd03cc744a2888ae4ull, 0x00db18cb2c04b3edull, 0xfcf5e095d5d00af6ull,
+    0xa09e30ed741d8ae4ull, 0x08b3f481e3aaa0f1ull};
+
 template <class C>
-static int srs_generate_t(Ctx* c, const uint32_t* tau_words, size_t start, size_t n, const uint64_t* gen_xy,
-                          Srs** out, size_t run_len, size_t inner_stride, size_t outer_stride,
-                          const uint32_t* d_scalars = nullptr) {
+static int srs_generate_t(Ctx* c, const uint32_t* tau_words, size_t start, size_t n, Srs** out, size_t run_len,
+                          size_t inner_stride, size_t outer_stride, const uint32_t* d_scalars = nullptr) {
   using F = typename C::Fp;
   using Fr = typename C::Fr;
+  const uint64_t* gen_xy = C::ID == 0 ? GEN_BN254 : GEN_BLS;
   if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, "kzg_srs_generate: bad size");
   Srs* s = srs_alloc(c, n);
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->recs), (size_t)s->nwin * n * rec_bytes<C>());
@@ -629,7 +653,7 @@ static int srs_generate_t(Ctx* c, const uint32_t* tau_words, size_t start, size_
   hipMemcpy(d_tau, tau.l, Fr::N * 4, hipMemcpyHostToDevice);
   hipMemcpy(d_xy, gen_xy, 2 * F::NW * 4, hipMemcpyHostToDevice);
   hipMemsetAsync(d_bad, 0, 4, c->stream);
-  hipLaunchKernelGGL(srs_import_kernel<C>, dim3(1), dim3(64), 0, c->stream, d_xy, (const uint8_t*)nullptr, d_g,
+  hipLaunchKernelGGL((g1_import_kernel<C, false>), dim3(1), dim3(64), 0, c->stream, d_xy, (const uint8_t*)nullptr, d_g,
                      (size_t)1, d_bad);
   hipLaunchKernelGGL(gen_table_kernel<C>, dim3(32), dim3(256), 0, c->stream, d_g, d_tab);
   hipLaunchKernelGGL(srs_generate_kernel<C>, dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, c->stream, d_tab, d_tau,
@@ -643,33 +667,24 @@ static int srs_generate_t(Ctx* c, const uint32_t* tau_words, size_t start, size_
   return KZG_OK;
 }
 
-static const uint64_t GEN_BN254[8] = {1, 0, 0, 0, 2, 0, 0, 0};
-static const uint64_t GEN_BLS[12] = {
-    0xfb3af00adb22c6bbull, 0x6c55e83ff97a1aefull, 0xa14e3a3f171bac58ull, 0xc3688c4f9774b905ull,
-    0x2695638c4fa9ac0full, 0x17f1d3a73197d794ull,
-    0x0caa232946c5e7e1ull, 0xd03cc744a2888ae4ull, 0x00db18cb2c04b3edull, 0xfcf5e095d5d00af6ull,
-    0xa09e30ed741d8ae4ull, 0x08b3f481e3aaa0f1ull};
-
 int srs_load(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, Srs** out) {
-  return c->curve == 0 ? srs_load_t<Bn254>(c, xy, inf, n, out) : srs_load_t<Bls12_381>(c, xy, inf, n, out);
+  return KZG_BY_CURVE(c, srs_load_t, c, xy, inf, n, out);
 }
 int srs_load_device(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n, Srs** out) {
-  return c->curve == 0 ? srs_load_device_t<Bn254>(c, d_xy, d_inf, n, out) : srs_load_device_t<Bls12_381>(c, d_xy, d_inf, n, out);
+  return KZG_BY_CURVE(c, srs_load_device_t, c, d_xy, d_inf, n, out);
 }
 int srs_generate(Ctx* c, const uint64_t* tau, size_t start, size_t n, Srs** out, size_t run_len, size_t inner_stride,
                  size_t outer_stride) {
   const uint32_t* t = reinterpret_cast<const uint32_t*>(tau);
   if (run_len == 0) { run_len = n ? n : 1; inner_stride = 1; outer_stride = 0; }
-  return c->curve == 0 ? srs_generate_t<Bn254>(c, t, start, n, GEN_BN254, out, run_len, inner_stride, outer_stride)
-                       : srs_generate_t<Bls12_381>(c, t, start, n, GEN_BLS, out, run_len, inner_stride, outer_stride);
+  return KZG_BY_CURVE(c, srs_generate_t, c, t, start, n, out, run_len, inner_stride, outer_stride);
 }
 int srs_generate_scalars(Ctx* c, const uint32_t* d_scalars, size_t n, Srs** out) {
   static const uint32_t zero[8] = {0};
-  return c->curve == 0 ? srs_generate_t<Bn254>(c, zero, 0, n, GEN_BN254, out, n ? n : 1, 1, 0, d_scalars)
-                       : srs_generate_t<Bls12_381>(c, zero, 0, n, GEN_BLS, out, n ? n : 1, 1, 0, d_scalars);
+  return KZG_BY_CURVE(c, srs_generate_t, c, zero, 0, n, out, n ? n : 1, 1, 0, d_scalars);
 }
 int srs_create(Ctx* c, size_t n, Srs** out) {
-  const size_t rb = c->curve == 0 ? rec_bytes<Bn254>() : rec_bytes<Bls12_381>();
+  const size_t rb = srs_rec_bytes(c->curve);
   if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, "SRS: bad size");
   Srs* s = srs_alloc(c, n);
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->recs), (size_t)s->nwin * n * rb);
@@ -678,7 +693,7 @@ int srs_create(Ctx* c, size_t n, Srs** out) {
   return KZG_OK;
 }
 int srs_finish_windows(Ctx* c, Srs* s) {
-  return c->curve == 0 ? srs_build_windows<Bn254>(c, s) : srs_build_windows<Bls12_381>(c, s);
+  return KZG_BY_CURVE(c, srs_build_windows, c, s);
 }
 void srs_window0_view(const Ctx* c, uint32_t* recs, size_t n, Srs* out) {
   *out = Srs();
@@ -714,8 +729,7 @@ static int srs_export_t(Ctx* c, const Srs* s, size_t start, size_t count, uint64
   return KZG_OK;
 }
 int srs_export(Ctx* c, const Srs* s, size_t start, size_t count, uint64_t* xy, uint8_t* inf) {
-  return c->curve == 0 ? srs_export_t<Bn254>(c, s, start, count, xy, inf)
-                       : srs_export_t<Bls12_381>(c, s, start, count, xy, inf);
+  return KZG_BY_CURVE(c, srs_export_t, c, s, start, count, xy, inf);
 }
 
 // Commit pipeline: three stages on two internal streams, up to four polynomials in flight.
@@ -947,10 +961,8 @@ static int msm_queue_deferred(Ctx* c, MsmWork* w) {
 // host: 2^LO * sum_b 2^b TR_b + sum_b 2^b TC_b + 2^(WB-1) * top; to affine, canonical words
 template <class C, int WB>
 static void msm_finish_host(const void* h_tb, uint64_t* out_xy, uint8_t* out_inf) {
-  using F = typename C::Fp;
-  using Fd = Field<F>;
   using W = Win<WB>;
-  constexpr int N = F::N;
+  constexpr int N = C::Fp::N;
   const uint32_t* p = static_cast<const uint32_t*>(h_tb);
   auto pt = [&](int idx) {
     XYZZ<C> t;
@@ -968,16 +980,7 @@ static void msm_finish_host(const void* h_tb, uint64_t* out_xy, uint8_t* out_inf
     if (e >= W::LO) acc = Ec<C>::add(acc, pt(e - W::LO));          // TR_{e-LO}
     if (e < W::LO) acc = Ec<C>::add(acc, pt(W::HI + e));           // TC_e
   }
-  const Affine<C> a = Ec<C>::to_affine(acc);
-  uint32_t* o = reinterpret_cast<uint32_t*>(out_xy);
-  if (a.inf) {
-    memset(o, 0, 2 * F::NW * 4);
-    *out_inf = 1;
-    return;
-  }
-  Fd::to_words(Fd::from_mont(a.x), o);
-  Fd::to_words(Fd::from_mont(a.y), o + F::NW);
-  *out_inf = 0;
+  *out_inf = affine_to_words<C>(Ec<C>::to_affine(acc), reinterpret_cast<uint32_t*>(out_xy));
 }
 
 template <class C>
@@ -1063,16 +1066,14 @@ static int commit_t(Ctx* c, const Srs* s, const uint32_t* d_scalars, const size_
   return rc;
 }
 
-int commit_flush(Ctx* c) { return c->curve == 0 ? commit_flush_t<Bn254>(c) : commit_flush_t<Bls12_381>(c); }
+int commit_flush(Ctx* c) { return KZG_BY_CURVE(c, commit_flush_t, c); }
 
 int commit_device(Ctx* c, const Srs* s, const uint32_t* d_scalars, const size_t* lens, size_t n_polys,
                   size_t stride, uint64_t* out_xy, uint8_t* out_inf, bool drain, const uint32_t* d_eval,
                   uint64_t* out_eval) {
   if (s->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
   if (d_eval && n_polys != 1) return set_err(c, KZG_ERR_ARG, "an evaluation rides with exactly one polynomial");
-  return c->curve == 0
-             ? commit_t<Bn254>(c, s, d_scalars, lens, n_polys, stride, out_xy, out_inf, drain, d_eval, out_eval)
-             : commit_t<Bls12_381>(c, s, d_scalars, lens, n_polys, stride, out_xy, out_inf, drain, d_eval, out_eval);
+  return KZG_BY_CURVE(c, commit_t, c, s, d_scalars, lens, n_polys, stride, out_xy, out_inf, drain, d_eval, out_eval);
 }
 
 }  // namespace kzg

@@ -724,30 +724,25 @@ int fft_ragged_device(Ctx* c, uint32_t* d_data, uint64_t n, const uint32_t* w_wo
   if (n == 0) return set_err(c, KZG_ERR_ARG, "fft_ff of an empty list: the reference recursion never terminates");
   if (n > (1ull << 24)) return set_err(c, KZG_ERR_ARG, "kzg_fft_ff_any: n > 2^24 not supported");
   if (n == 1) return KZG_OK;                       // fft_ff.py:16-17; F(1)^-1 = 1
-  return c->curve == 0 ? fft_ragged_t<BnFr>(c, d_data, n, w_words, inverse)
-                       : fft_ragged_t<BlsFr>(c, d_data, n, w_words, inverse);
+  return KZG_BY_FR(c, fft_ragged_t, c, d_data, n, w_words, inverse);
 }
 
 int ntt_run_device(Ctx* c, uint32_t* d_data, uint32_t log_n, const uint32_t* w_words, int inverse, uint32_t batch) {
   if (log_n > 24) return set_err(c, KZG_ERR_ARG, "kzg_ntt: log_n > 24 not supported");
-  if (c->curve == 0) return ntt_run_t<BnFr>(c, d_data, log_n, w_words, inverse, batch);
-  return ntt_run_t<BlsFr>(c, d_data, log_n, w_words, inverse, batch);
+  return KZG_BY_FR(c, ntt_run_t, c, d_data, log_n, w_words, inverse, batch);
 }
 
 int ntt_partial_device(Ctx* c, uint32_t* d_data, uint32_t log_n, const uint32_t* w_words, int inverse, int rows_pass,
                        uint64_t count, uint64_t col_base) {
   if (log_n > 24) return set_err(c, KZG_ERR_ARG, "kzg_ntt: log_n > 24 not supported");
-  return c->curve == 0 ? ntt_partial_t<BnFr>(c, d_data, log_n, w_words, inverse, rows_pass, count, col_base)
-                       : ntt_partial_t<BlsFr>(c, d_data, log_n, w_words, inverse, rows_pass, count, col_base);
+  return KZG_BY_FR(c, ntt_partial_t, c, d_data, log_n, w_words, inverse, rows_pass, count, col_base);
 }
 
 int ntt_rows_exchange_device(Ctx* c, const uint32_t* d_src, uint32_t* d_dst, uint32_t log_n, const uint32_t* w_words,
                              int inverse, uint64_t n_rows, uint32_t world, int blocked_out) {
   if (log_n > 24) return set_err(c, KZG_ERR_ARG, "kzg_ntt: log_n > 24 not supported");
   uint32_t* src = const_cast<uint32_t*>(d_src);
-  return c->curve == 0
-             ? ntt_partial_t<BnFr>(c, src, log_n, w_words, inverse, 1, n_rows, 0, d_dst, world, blocked_out)
-             : ntt_partial_t<BlsFr>(c, src, log_n, w_words, inverse, 1, n_rows, 0, d_dst, world, blocked_out);
+  return KZG_BY_FR(c, ntt_partial_t, c, src, log_n, w_words, inverse, 1, n_rows, 0, d_dst, world, blocked_out);
 }
 
 void ntt_free_domains(Ctx* c) {

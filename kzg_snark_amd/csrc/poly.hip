@@ -823,7 +823,7 @@ int open_coset_quotient_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, s
         }
       }
     }
-    for (size_t q = 0; q < l; ++q) Fd::to_words(Fd::from_mont(v[q]), reinterpret_cast<uint32_t*>(eval_out + q * 4));
+    for (size_t q = 0; q < l; ++q) words_from_mont<F>(v[q], reinterpret_cast<uint32_t*>(eval_out + q * 4));
   }
   if (n > l) {
     *d_quot_out = d_S + l * 8;
@@ -837,37 +837,30 @@ int open_coset_quotient_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, s
 int open_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                          const uint32_t* z_words, const uint32_t* xi_words, uint32_t** d_quot_out, size_t* quot_len,
                          uint64_t* eval_out, bool sync) {
-  return c->curve == 0 ? open_quotient_t<BnFr>(c, d_polys, lens, k, stride, z_words, xi_words, d_quot_out, quot_len,
-                                               eval_out, sync)
-                       : open_quotient_t<BlsFr>(c, d_polys, lens, k, stride, z_words, xi_words, d_quot_out, quot_len,
-                                                eval_out, sync);
+  return KZG_BY_FR(c, open_quotient_t, c, d_polys, lens, k, stride, z_words, xi_words, d_quot_out, quot_len, eval_out,
+                   sync);
 }
 
 int open_shard_begin_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                             const uint32_t* z_words, const uint32_t* xi_words, uint64_t* chunk_eval_out) {
-  return c->curve == 0 ? open_shard_begin_t<BnFr>(c, d_polys, lens, k, stride, z_words, xi_words, chunk_eval_out)
-                       : open_shard_begin_t<BlsFr>(c, d_polys, lens, k, stride, z_words, xi_words, chunk_eval_out);
+  return KZG_BY_FR(c, open_shard_begin_t, c, d_polys, lens, k, stride, z_words, xi_words, chunk_eval_out);
 }
 int open_shard_finish_device(Ctx* c, const uint32_t* z_words, const uint32_t* carry_words, int first_rank,
                              uint32_t** d_vec_out, size_t* vec_len, uint64_t* eval_out) {
-  return c->curve == 0 ? open_shard_finish_t<BnFr>(c, z_words, carry_words, first_rank, d_vec_out, vec_len, eval_out)
-                       : open_shard_finish_t<BlsFr>(c, z_words, carry_words, first_rank, d_vec_out, vec_len, eval_out);
+  return KZG_BY_FR(c, open_shard_finish_t, c, z_words, carry_words, first_rank, d_vec_out, vec_len, eval_out);
 }
 
 int open_coset_check(Ctx* c, const size_t* lens, size_t k, size_t stride, uint32_t log_l, const uint32_t* h_words,
                      const uint32_t* zeta_words, size_t key_n) {
   size_t n = 0;
-  return c->curve == 0 ? open_coset_check_t<BnFr>(c, lens, k, stride, log_l, h_words, zeta_words, key_n, &n)
-                       : open_coset_check_t<BlsFr>(c, lens, k, stride, log_l, h_words, zeta_words, key_n, &n);
+  return KZG_BY_FR(c, open_coset_check_t, c, lens, k, stride, log_l, h_words, zeta_words, key_n, &n);
 }
 int open_coset_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                                uint32_t log_l, const uint32_t* h_words, const uint32_t* zeta_words,
                                const uint32_t* xi_words, size_t key_n, uint32_t** d_quot_out, size_t* quot_len,
                                uint64_t* eval_out) {
-  return c->curve == 0 ? open_coset_quotient_t<BnFr>(c, d_polys, lens, k, stride, log_l, h_words, zeta_words, xi_words,
-                                                      key_n, d_quot_out, quot_len, eval_out)
-                       : open_coset_quotient_t<BlsFr>(c, d_polys, lens, k, stride, log_l, h_words, zeta_words,
-                                                       xi_words, key_n, d_quot_out, quot_len, eval_out);
+  return KZG_BY_FR(c, open_coset_quotient_t, c, d_polys, lens, k, stride, log_l, h_words, zeta_words, xi_words, key_n,
+                   d_quot_out, quot_len, eval_out);
 }
 
 // true iff any of the elements [from, to) of a canonical-word array is non-zero
@@ -1204,23 +1197,22 @@ int poly_eval_t(Ctx* c, size_t n, const uint32_t* a, const uint32_t* z_words, ui
 
 }  // namespace
 
-#define KZG_FR_DISPATCH(fn, ...) (c->curve == 0 ? fn<BnFr>(__VA_ARGS__) : fn<BlsFr>(__VA_ARGS__))
 int fr_vec_binary(Ctx* c, int op, size_t n, const uint32_t* a, const uint32_t* b, uint32_t* out) {
-  return KZG_FR_DISPATCH(vec_binary_t, c, op, n, a, b, out);
+  return KZG_BY_FR(c, vec_binary_t, c, op, n, a, b, out);
 }
 int fr_vec_lincomb(Ctx* c, size_t n, size_t k, const uint32_t* const* ptrs, const size_t* lens, const uint32_t* scalars,
                    uint32_t* out) {
-  return KZG_FR_DISPATCH(vec_lincomb_t, c, n, k, ptrs, lens, scalars, out);
+  return KZG_BY_FR(c, vec_lincomb_t, c, n, k, ptrs, lens, scalars, out);
 }
 int fr_vec_mul_powers(Ctx* c, size_t n, const uint32_t* a, const uint32_t* s, const uint32_t* cc, uint32_t* out) {
-  return KZG_FR_DISPATCH(vec_mul_powers_t, c, n, a, s, cc, out);
+  return KZG_BY_FR(c, vec_mul_powers_t, c, n, a, s, cc, out);
 }
-int fr_vec_inverse(Ctx* c, size_t n, const uint32_t* a, uint32_t* out) { return KZG_FR_DISPATCH(vec_inverse_t, c, n, a, out); }
+int fr_vec_inverse(Ctx* c, size_t n, const uint32_t* a, uint32_t* out) { return KZG_BY_FR(c, vec_inverse_t, c, n, a, out); }
 int fr_vec_prefix_product(Ctx* c, size_t n, const uint32_t* a, uint32_t* out) {
-  return KZG_FR_DISPATCH(vec_prefix_product_t, c, n, a, out);
+  return KZG_BY_FR(c, vec_prefix_product_t, c, n, a, out);
 }
 int fr_poly_eval(Ctx* c, size_t n, const uint32_t* a, const uint32_t* z, uint64_t* out) {
-  return KZG_FR_DISPATCH(poly_eval_t, c, n, a, z, out);
+  return KZG_BY_FR(c, poly_eval_t, c, n, a, z, out);
 }
 
 }  // namespace kzg

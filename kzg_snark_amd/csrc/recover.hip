@@ -10,7 +10,7 @@
 //
 // V is a product tree (once per call, shared by the batch).  The host knows M, hence every node's degree:
 //   leaves   rec_leaf_kernel: one workgroup multiplies out up to REC_LEAF = 64 linear factors in LDS (schoolbook,
-//            Montgomery form), the roots from a two-level power table of w; a leaf without roots is the constant 1
+//            Montgomery form), the roots from a two-level power table of w (fr_pow_table); a leaf without roots is the constant 1
 //   level    nodes of capacity d are multiplied in pairs at transform size T = 2d: forward transform of both
 //            (ntt_run_device, batch = nodes), rec_pair_mul_kernel, inverse transform.  Only two FULL monic nodes
 //            reach degree T: their leading 1 wraps onto position 0, and rec_expand_kernel -- which lays the products
@@ -32,33 +32,9 @@ namespace {
 
 constexpr uint32_t REC_LEAF_LOG = 6;
 constexpr uint32_t REC_LEAF = 1u << REC_LEAF_LOG;               // linear factors per leaf
-constexpr uint32_t REC_TLOG = 11;                               // x^e = lo[e & 2047] * hi[e >> 11], e <= 2^21
-constexpr uint32_t REC_TLO = 1u << REC_TLOG;
-constexpr uint32_t REC_THI = (1u << (21 - REC_TLOG)) + 1;
-constexpr uint32_t REC_TAB = REC_TLO + REC_THI;
 constexpr uint32_t REC_MISSING = 0xffffffffu;                   // pos[] entry of a coset that was not given
 constexpr size_t REC_SCRATCH_BYTES = (size_t)2 << 30;           // chunks of polynomials stay below this
 constexpr uint32_t REC_MAX_CHUNK = 1024;
-
-template <class F>
-__device__ __forceinline__ Fe<F> rec_pow(const uint32_t* tab, uint32_t e) {
-  return Field<F>::mul(load_words<F>(tab + (size_t)(e & (REC_TLO - 1)) * 8),
-                       load_words<F>(tab + (size_t)(REC_TLO + (e >> REC_TLOG)) * 8));
-}
-
-// tab[i] = base^i (i < REC_TLO), tab[REC_TLO + i] = base_hi^i (i < REC_THI), base_hi = base^REC_TLO; Montgomery words
-template <class F>
-__global__ __launch_bounds__(256) void rec_pow_table_kernel(FrArg base, FrArg base_hi, uint32_t* tab) {
-  using Fd = Field<F>;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= REC_TAB) return;
-  Fe<F> b = arg_fe<F>(i < REC_TLO ? base : base_hi), acc = Fd::one();
-  for (uint32_t bits = i < REC_TLO ? i : i - REC_TLO; bits; bits >>= 1) {
-    if (bits & 1u) acc = Fd::mul(acc, b);
-    b = Fd::sqr(b);
-  }
-  store_words<F>(tab + (size_t)i * 8, acc);
-}
 
 // Leaf q = blockIdx.x: prod (Y - u^i) over the missing cosets miss[q REC_LEAF .. ), at most REC_LEAF of them, written
 // as standard-form coefficients into out[q][0 .. slot) (zero above the degree).  slot > the degree: the host passes
@@ -72,7 +48,7 @@ __global__ __launch_bounds__(128) void rec_leaf_kernel(uint32_t m, const uint32_
   const uint32_t q = blockIdx.x, tid = threadIdx.x;
   const uint32_t first = q << REC_LEAF_LOG;
   const uint32_t deg = first >= m ? 0u : min(m - first, REC_LEAF);
-  if (tid < deg) store_limbs<F>(root + tid * F::N, rec_pow<F>(wtab, miss[first + tid] << log_l));   // u^i = w^(i l)
+  if (tid < deg) store_limbs<F>(root + tid * F::N, fr_pow_lookup<F>(wtab, miss[first + tid] << log_l));   // u^i = w^(i l)
   if (tid <= REC_LEAF) store_limbs<F>(coef + tid * F::N, tid == 0 ? Fd::one() : Fd::zero());
   __syncthreads();
   for (uint32_t j = 0; j < deg; ++j) {                  // times (Y - r): c_i <- c_(i-1) - r c_i, i <= j + 1
@@ -166,7 +142,7 @@ __global__ __launch_bounds__(256) void rec_shift_kernel(uint32_t* x, uint32_t nv
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= ((size_t)nvec << log_N)) return;
   const uint32_t t = (uint32_t)(g & (((size_t)1 << log_N) - 1));
-  store_words<F>(x + g * 8, Fd::mul(load_words<F>(x + g * 8), rec_pow<F>(tab, t)));
+  store_words<F>(x + g * 8, Fd::mul(load_words<F>(x + g * 8), fr_pow_lookup<F>(tab, t)));
 }
 
 // x[j][t] <- x[j][t] zinv[t mod C] (zinv: Montgomery words)
@@ -192,7 +168,7 @@ __global__ __launch_bounds__(256) void rec_finish_kernel(const uint32_t* x, uint
   const size_t j = g >> log_N;
   const uint32_t t = (uint32_t)(g & (((size_t)1 << log_N) - 1));
   if (t < (1u << log_n)) {
-    store_words<F>(coeffs + ((j << log_n) + t) * 8, Fd::mul(load_words<F>(x + g * 8), rec_pow<F>(sitab, t)));
+    store_words<F>(coeffs + ((j << log_n) + t) * 8, Fd::mul(load_words<F>(x + g * 8), fr_pow_lookup<F>(sitab, t)));
   } else {
     const uint4* p = reinterpret_cast<const uint4*>(x + g * 8);
     const uint4 lo = p[0], hi = p[1];
@@ -207,17 +183,13 @@ struct RecLevel {
   uint32_t nn;         // pairs
 };
 
-template <class F>
-void words_of(const Fe<F>& mont, uint32_t* w) {
-  Field<F>::to_words(Field<F>::from_mont(mont), w);
-}
-
 inline dim3 rec_grid(size_t threads) { return dim3((uint32_t)((threads + 255) / 256)); }
 
-template <class F>
+template <class Cv>
 int recover_t(Ctx* c, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint32_t* w_words,
               const uint32_t* coset_idx, size_t K, const uint32_t* values, bool host, size_t b, uint32_t* coeffs,
               uint8_t* out_consistent) {
+  using F = typename Cv::Fr;
   using Fd = Field<F>;
   if (log_l > 12 || log_l > log_n || log_n > log_N || log_N > 21 || log_l >= log_N)
     return set_err(c, KZG_ERR_ARG, "kzg_recover_cosets: need 0 <= log_l <= 12, log_l <= log_n <= log_N <= 21 and log_l < log_N");
@@ -264,8 +236,8 @@ int recover_t(Ctx* c, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint
   chunk = std::min<size_t>({chunk, b, REC_MAX_CHUNK});
   size_t total = 0;
   auto reserve = [&](size_t bytes) { const size_t o = total; total += (bytes + 255) / 256 * 256; return o; };
-  const size_t o_wtab = reserve((size_t)REC_TAB * 32), o_stab = reserve((size_t)REC_TAB * 32),
-               o_sitab = reserve((size_t)REC_TAB * 32), o_miss = reserve((size_t)m * 4), o_pos = reserve(C * 4),
+  const size_t o_wtab = reserve((size_t)POW_TAB * 32), o_stab = reserve((size_t)POW_TAB * 32),
+               o_sitab = reserve((size_t)POW_TAB * 32), o_miss = reserve((size_t)m * 4), o_pos = reserve(C * 4),
                o_a = reserve(cap_a * 32), o_b = reserve(cap_b * 32), o_v = reserve(C * 32), o_z = reserve(2 * C * 32),
                o_zinv = reserve(C * 32), o_flag = reserve(b * 4), o_x = reserve(chunk * N * 32),
                o_vals = reserve(host ? chunk * cells * 32 : 0), o_out = reserve(host ? chunk * n * 32 : 0);
@@ -278,27 +250,24 @@ int recover_t(Ctx* c, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint
            *d_zs = u32(o_z) + C * 8, *d_zinv = u32(o_zinv), *d_flag = u32(o_flag), *d_x = u32(o_x),
            *d_vals = u32(o_vals), *d_out = u32(o_out);
 
-  uint32_t gw[8] = {c->curve == 0 ? 5u : 7u, 0, 0, 0, 0, 0, 0, 0};           // the multiplicative generator: s^N != 1
-  const Fe<F> s = mont_from_words<F>(gw), s_inv = Fd::inv(s);
-  Fe<F> w_hi = w, s_hi = s, si_hi = s_inv, s_l = s;
-  for (uint32_t q = 0; q < REC_TLOG; ++q) { w_hi = Fd::sqr(w_hi); s_hi = Fd::sqr(s_hi); si_hi = Fd::sqr(si_hi); }
+  const Fe<F> s = fr_generator<Cv>(), s_inv = Fd::inv(s);                      // the multiplicative generator: s^N != 1
+  Fe<F> s_l = s;
   for (uint32_t q = 0; q < log_l; ++q) s_l = Fd::sqr(s_l);
   uint32_t sl_words[8], one_words[8] = {1, 0, 0, 0, 0, 0, 0, 0}, u_words[8];
-  words_of<F>(s_l, sl_words);
+  words_from_mont<F>(s_l, sl_words);
   std::vector<Fe<F>> w_pow(log_N + 1);                   // w_pow[k] = w^(N / 2^k): the root of a size-2^k transform
   w_pow[log_N] = w;
   for (uint32_t k = log_N; k-- > 0;) w_pow[k] = Fd::sqr(w_pow[k + 1]);
-  words_of<F>(w_pow[log_c], u_words);
+  words_from_mont<F>(w_pow[log_c], u_words);
 
   ProfScope ps(c, "recover_cosets");
   hipStream_t st = c->stream;
   if (m) KZG_HIP(c, hipMemcpyAsync(d_miss, miss.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
   KZG_HIP(c, hipMemcpyAsync(d_pos, pos.data(), C * 4, hipMemcpyHostToDevice, st));
   KZG_HIP(c, hipMemsetAsync(d_flag, 0, b * 4, st));
-  const dim3 tab_grid((REC_TAB + 255) / 256);
-  hipLaunchKernelGGL(rec_pow_table_kernel<F>, tab_grid, dim3(256), 0, st, fr_arg<F>(w), fr_arg<F>(w_hi), d_wtab);
-  hipLaunchKernelGGL(rec_pow_table_kernel<F>, tab_grid, dim3(256), 0, st, fr_arg<F>(s), fr_arg<F>(s_hi), d_stab);
-  hipLaunchKernelGGL(rec_pow_table_kernel<F>, tab_grid, dim3(256), 0, st, fr_arg<F>(s_inv), fr_arg<F>(si_hi), d_sitab);
+  if ((rc = fr_pow_table(c, fr_arg<F>(w), d_wtab))) return rc;
+  if ((rc = fr_pow_table(c, fr_arg<F>(s), d_stab))) return rc;
+  if ((rc = fr_pow_table(c, fr_arg<F>(s_inv), d_sitab))) return rc;
 
   // ---- V: leaves, then one level per doubling
   if (levels.empty()) {
@@ -311,7 +280,7 @@ int recover_t(Ctx* c, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint
   for (size_t lv = 0; lv < levels.size(); ++lv) {
     const uint32_t log_t = levels[lv].log_t, nn = levels[lv].nn;
     uint32_t root_words[8];
-    words_of<F>(w_pow[log_t], root_words);               // log_t <= log_c: T <= C whenever a level exists
+    words_from_mont<F>(w_pow[log_t], root_words);               // log_t <= log_c: T <= C whenever a level exists
     if ((rc = ntt_run_device(c, d_a, log_t, root_words, 0, 2 * nn))) return rc;
     hipLaunchKernelGGL(rec_pair_mul_kernel<F>, rec_grid((size_t)nn << log_t), dim3(256), 0, st, d_a, nn, log_t, d_b);
     KZG_HIP(c, hipGetLastError());
@@ -374,10 +343,8 @@ uint32_t recover_leaf_width() { return REC_LEAF; }
 int recover_cosets(Ctx* c, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint32_t* w_words,
                    const uint32_t* coset_idx, size_t K, const uint32_t* values, bool host_ptrs, size_t b,
                    uint32_t* coeffs, uint8_t* out_consistent) {
-  return c->curve == 0 ? recover_t<BnFr>(c, log_n, log_N, log_l, w_words, coset_idx, K, values, host_ptrs, b, coeffs,
-                                         out_consistent)
-                       : recover_t<BlsFr>(c, log_n, log_N, log_l, w_words, coset_idx, K, values, host_ptrs, b, coeffs,
-                                          out_consistent);
+  return KZG_BY_CURVE(c, recover_t, c, log_n, log_N, log_l, w_words, coset_idx, K, values, host_ptrs, b, coeffs,
+                      out_consistent);
 }
 
 }  // namespace kzg

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ec.h"
+#include "g1_util.h"
 
 namespace kzg {
 
@@ -22,12 +23,7 @@ __device__ __forceinline__ uint32_t load_rec(const uint32_t* recs, size_t idx, F
   constexpr int Q = (2 * N + 3) / 4;                 // 16-byte loads covering x and y
   uint32_t w[4 * Q];
   if constexpr (4 * Q <= Rec<C>::WORDS && (Rec<C>::WORDS % 4) == 0) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-#pragma unroll
-    for (int i = 0; i < Q; ++i) {
-      const uint4 v = q[i];
-      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
+    ld_words<4 * Q>(p, w);
     if constexpr (Rec<C>::FLAG < 4 * Q) flag = w[Rec<C>::FLAG]; else flag = p[Rec<C>::FLAG];
   } else {
     const uint2* q = reinterpret_cast<const uint2*>(p);

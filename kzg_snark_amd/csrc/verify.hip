@@ -7,13 +7,13 @@
 //     R = sum_k r_k pi_k                           accept iff e(L, G2) = e(R, [tau^l] G2)       
 //
 //   powers    w^e (e < N <= 2^21) and rho^e (e <= K <= 2^21) come from two-level tables x^e = lo[e & 2047] hi[e >> 11]
-//             (ver_pow_table_kernel, 3073 entries each): one product per power, no per-cell exponentiation
+//             (fr_pow_table, 3073 entries each): one product per power, no per-cell exponentiation
 //   weights   r_k and s_k = r_k a_k as canonical scalars (ver_weights_kernel); the per-commitment sums of r_k over the
 //             cells grouped by commitment (a counting sort of the small indices on the host, ver_commsum_kernel)
 //   values    ver_cell_kernel: tiles of max(l, 256) elements in LDS, a decimation-in-frequency inverse transform per
 //             cell (twiddles from the w table), then r_k l^-1 h_k^-j applied on the way back to memory;
 //             ver_colsum_kernel / ver_colsum_final_kernel add the cells up: T
-//   proofs    imported as window-0 records (ver_import_kernel: coordinates < p, on the curve) of a key that holds NO
+//   proofs    imported as window-0 records (g1_import: coordinates < p, on the curve) of a key that holds NO
 //             other window; every scalar is cut into slices of win_bits - 1 bits (ver_slice_kernel) and each slice
 //             vector goes through the commit pipeline as one polynomial: a slice yields one digit, in window 0, without
 //             a carry.  sum_s 2^(s (win_bits - 1)) P_s is finished on the host.
@@ -28,48 +28,15 @@
 #include "fr_util.h"
 #include "g1_util.h"
 #include "msm.h"
-#include "srs_rec.h"
+#include "g1_words.h"
 
 namespace kzg {
 
 namespace {
 
-constexpr uint32_t VER_TLOG = 11;                               // x^e = lo[e & 2047] * hi[e >> 11]
-constexpr uint32_t VER_TLO = 1u << VER_TLOG;
-constexpr uint32_t VER_THI = (1u << (21 - VER_TLOG)) + 1;       // exponents up to 2^21 inclusive
-constexpr uint32_t VER_TAB = VER_TLO + VER_THI;
 constexpr uint32_t VER_MIN_TILE_LOG = 8;                        // ver_cell_kernel: tile of max(l, 256) elements
 constexpr uint32_t VER_SUM_THREADS = 1u << 15;                  // ver_colsum_kernel: threads (a multiple of every l)
 constexpr uint32_t VER_COMM_SPLIT = 64;                         // ver_commsum_kernel: workgroups per commitment when few
-
-template <class F>
-__device__ __forceinline__ Fe<F> ver_shfl_xor(const Fe<F>& v, int mask) {
-  Fe<F> r;
-#pragma unroll
-  for (int j = 0; j < F::N; ++j) r.l[j] = __shfl_xor(v.l[j], mask);
-  return r;
-}
-
-// x^e from a two-level table (Montgomery form)
-template <class F>
-__device__ __forceinline__ Fe<F> ver_pow(const uint32_t* tab, uint32_t e) {
-  return Field<F>::mul(load_words<F>(tab + (size_t)(e & (VER_TLO - 1)) * 8),
-                       load_words<F>(tab + (size_t)(VER_TLO + (e >> VER_TLOG)) * 8));
-}
-
-// tab[i] = base^i (i < VER_TLO), tab[VER_TLO + i] = base_hi^i (i < VER_THI), base_hi = base^VER_TLO; Montgomery words
-template <class F>
-__global__ __launch_bounds__(256) void ver_pow_table_kernel(FrArg base, FrArg base_hi, uint32_t* tab) {
-  using Fd = Field<F>;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= VER_TAB) return;
-  Fe<F> b = arg_fe<F>(i < VER_TLO ? base : base_hi), acc = Fd::one();
-  for (uint32_t bits = i < VER_TLO ? i : i - VER_TLO; bits; bits >>= 1) {
-    if (bits & 1u) acc = Fd::mul(acc, b);
-    b = Fd::sqr(b);
-  }
-  store_words<F>(tab + (size_t)i * 8, acc);
-}
 
 // r_k = rho^(k+1) and s_k = r_k w^(i_k l), canonical words
 template <class F>
@@ -79,8 +46,8 @@ __global__ __launch_bounds__(256) void ver_weights_kernel(uint32_t K, uint32_t l
   using Fd = Field<F>;
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
-  const Fe<F> r = ver_pow<F>(rtab, k + 1);
-  const Fe<F> s = Fd::mul(r, ver_pow<F>(wtab, coset_idx[k] << log_l));     // i_k < N/l: the exponent is below N
+  const Fe<F> r = fr_pow_lookup<F>(rtab, k + 1);
+  const Fe<F> s = Fd::mul(r, fr_pow_lookup<F>(wtab, coset_idx[k] << log_l));     // i_k < N/l: the exponent is below N
   store_words<F>(r_out + (size_t)k * 8, Fd::from_mont(r));
   store_words<F>(s_out + (size_t)k * 8, Fd::from_mont(s));
 }
@@ -124,7 +91,7 @@ __global__ __launch_bounds__(256) void ver_cell_kernel(uint32_t K, uint32_t log_
         const Fe<F> u = ver_lds_load<F>(ver_tile, pos), v = ver_lds_load<F>(ver_tile, pos + half);
         const uint32_t ex = (N - (N >> ll) * i) & (N - 1);             // (zeta^-1)^(i l / 2^ll) = w^(-i N / 2^ll)
         store_words<F>(ver_tile + (size_t)pos * 8, Fd::add(u, v));
-        store_words<F>(ver_tile + (size_t)(pos + half) * 8, Fd::mul(Fd::sub(u, v), ver_pow<F>(wtab, ex)));
+        store_words<F>(ver_tile + (size_t)(pos + half) * 8, Fd::mul(Fd::sub(u, v), fr_pow_lookup<F>(wtab, ex)));
       }
       __syncthreads();
     }
@@ -133,7 +100,7 @@ __global__ __launch_bounds__(256) void ver_cell_kernel(uint32_t K, uint32_t log_
       const uint32_t k = (uint32_t)((base + p) >> log_l), j = p & (l - 1);
       const Fe<F> x = ver_lds_load<F>(ver_tile, (p & ~(l - 1)) + bitrev(j, log_l));
       const uint32_t ex = (N - (uint32_t)(((uint64_t)coset_idx[k] * j) & (N - 1))) & (N - 1);   // h_k^-j
-      const Fe<F> f = Fd::mul(Fd::mul(ver_pow<F>(rtab, k + 1), arg_fe<F>(linv)), ver_pow<F>(wtab, ex));
+      const Fe<F> f = Fd::mul(Fd::mul(fr_pow_lookup<F>(rtab, k + 1), arg_fe<F>(linv)), fr_pow_lookup<F>(wtab, ex));
       store_words<F>(vals + (base + p) * 8, Fd::mul(x, f));
     }
     __syncthreads();
@@ -160,7 +127,7 @@ __global__ __launch_bounds__(64) void ver_colsum_final_kernel(uint32_t cols, uin
   Fe<F> acc = Fd::zero();
   for (uint32_t q = threadIdx.x; q < cnt; q += 64) acc = Fd::add(acc, load_words<F>(part + ((size_t)q * cols + j) * 8));
 #pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) acc = Fd::add(acc, ver_shfl_xor<F>(acc, m));
+  for (int m = 32; m >= 1; m >>= 1) acc = Fd::add(acc, shfl_xor_fe<F>(acc, m));
   if (threadIdx.x == 0) store_words<F>(out + (size_t)j * 8, acc);
 }
 
@@ -177,7 +144,7 @@ __global__ __launch_bounds__(256) void ver_commsum_kernel(const uint32_t* r, con
   Fe<F> acc = Fd::zero();
   for (uint32_t q = a + threadIdx.x; q < b; q += 256) acc = Fd::add(acc, load_words<F>(r + (size_t)perm[q] * 8));
 #pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) acc = Fd::add(acc, ver_shfl_xor<F>(acc, m));
+  for (int m = 32; m >= 1; m >>= 1) acc = Fd::add(acc, shfl_xor_fe<F>(acc, m));
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   if (lane == 0) store_limbs<F>(red[wave], acc);
   __syncthreads();
@@ -200,64 +167,11 @@ __global__ __launch_bounds__(256) void ver_slice_kernel(uint32_t K, const uint32
   o[1] = make_uint4(0, 0, 0, 0);
 }
 
-// canonical affine words -> window-0 records, as srs_import_kernel (msm.hip); a coordinate >= p or a point off the
-// curve is counted in *bad
-template <class C>
-__global__ __launch_bounds__(256) void ver_import_kernel(const uint32_t* xy, const uint8_t* inf, uint32_t* recs,
-                                                         size_t n, uint32_t* bad) {
-  using F = typename C::Fp;
-  using Fd = Field<F>;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const bool is_inf = inf && inf[i];
-  Fe<F> x = Fd::zero(), y = Fd::zero();
-  if (!is_inf) {
-    uint32_t wx[F::NW], wy[F::NW];
-#pragma unroll
-    for (int k = 0; k < F::NW; ++k) { wx[k] = xy[i * 2 * F::NW + k]; wy[k] = xy[i * 2 * F::NW + F::NW + k]; }
-    bool x_lt = false, x_gt = false, y_lt = false, y_gt = false;       // compared with p from the top word down
-#pragma unroll
-    for (int k = F::NW - 1; k >= 0; --k) {
-      const uint32_t pw = F::PW[k];
-      if (!x_lt && !x_gt) { x_lt = wx[k] < pw; x_gt = wx[k] > pw; }
-      if (!y_lt && !y_gt) { y_lt = wy[k] < pw; y_gt = wy[k] > pw; }
-    }
-    x = Fd::reduce(Fd::to_mont(Fd::from_words(wx)));
-    y = Fd::reduce(Fd::to_mont(Fd::from_words(wy)));
-    if (!x_lt || !y_lt || !Ec<C>::on_curve(x, y)) atomicAdd(bad, 1u);
-  }
-  store_rec<C>(recs, i, x, y, is_inf);
-}
-
 // ---- host side --------------------------------------------------------------------------------------
 
 template <class C>
-XYZZ<C> point_from_words(const uint64_t* xy, uint8_t inf) {
-  using Fd = Field<typename C::Fp>;
-  constexpr int NW = C::Fp::NW;
-  if (inf) return Ec<C>::infinity();
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(xy);
-  Affine<C> a;
-  a.x = Fd::reduce(Fd::to_mont(Fd::from_words(w)));
-  a.y = Fd::reduce(Fd::to_mont(Fd::from_words(w + NW)));
-  a.inf = false;
-  return Ec<C>::from_affine(a);
-}
-
-template <class C>
-void point_to_words(const XYZZ<C>& p, uint64_t* xy, uint8_t* inf) {
-  using Fd = Field<typename C::Fp>;
-  constexpr int NW = C::Fp::NW;
-  const Affine<C> a = Ec<C>::to_affine(p);
-  uint32_t* o = reinterpret_cast<uint32_t*>(xy);
-  if (a.inf) {
-    memset(o, 0, 2 * NW * 4);
-    *inf = 1;
-    return;
-  }
-  Fd::to_words(Fd::from_mont(a.x), o);
-  Fd::to_words(Fd::from_mont(a.y), o + NW);
-  *inf = 0;
+XYZZ<C> host_point(const uint64_t* xy, uint8_t inf) {
+  return Ec<C>::from_affine(affine_from_words<C>(reinterpret_cast<const uint32_t*>(xy), inf != 0));
 }
 
 // sum_s 2^(s * sb) P_s over the slice results, from the top slice down
@@ -267,7 +181,7 @@ XYZZ<C> recombine_slices(const uint64_t* xy, const uint8_t* inf, uint32_t ns, ui
   XYZZ<C> acc = Ec<C>::infinity();
   for (uint32_t s = ns; s-- > 0;) {
     for (uint32_t d = 0; d < sb; ++d) acc = Ec<C>::dbl(acc);
-    acc = Ec<C>::add(acc, point_from_words<C>(xy + (size_t)s * PW64, inf[s]));
+    acc = Ec<C>::add(acc, host_point<C>(xy + (size_t)s * PW64, inf[s]));
   }
   return acc;
 }
@@ -320,8 +234,8 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
   const size_t o_pxy = reserve(K * PT_BYTES), o_pinf = reserve(proof_inf ? K : 0), o_cxy = reserve(n_comm * PT_BYTES),
                o_cinf = reserve(comm_inf ? n_comm : 0), o_recs = reserve(K * rb), o_vals = reserve(M * 32),
                o_r = reserve(K * 32), o_s = reserve(K * 32), o_slice = reserve(K * 32), o_cidx = reserve(K * 4),
-               o_perm = reserve(K * 4), o_off = reserve((n_comm + 1) * 4), o_wtab = reserve((size_t)VER_TAB * 32),
-               o_rtab = reserve((size_t)VER_TAB * 32), o_part = reserve((size_t)sum_threads * 32),
+               o_perm = reserve(K * 4), o_off = reserve((n_comm + 1) * 4), o_wtab = reserve((size_t)POW_TAB * 32),
+               o_rtab = reserve((size_t)POW_TAB * 32), o_part = reserve((size_t)sum_threads * 32),
                o_cpart = reserve(n_comm * nsp * 32), o_T = reserve(l * 32), o_coef = reserve(n_comm * 32),
                o_bad = reserve(4);
   int rc = ensure_buf(c, c->ver_tmp, total);
@@ -352,11 +266,8 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
   KZG_VER_HIP(hipMemcpyAsync(d_cxy, comm_xy, n_comm * PT_BYTES, hipMemcpyHostToDevice, st));
   if (comm_inf) KZG_VER_HIP(hipMemcpyAsync(d_cinf, comm_inf, n_comm, hipMemcpyHostToDevice, st));
   KZG_VER_HIP(hipMemsetAsync(d_bad, 0, 4, st));
-  hipLaunchKernelGGL(ver_import_kernel<C>, dim3((uint32_t)((K + 255) / 256)), dim3(256), 0, st, d_pxy, d_pinf, d_recs,
-                     K, d_bad);
-  hipLaunchKernelGGL(ver_import_kernel<C>, dim3((uint32_t)((n_comm + 255) / 256)), dim3(256), 0, st, d_cxy, d_cinf,
-                     cs->recs, n_comm, d_bad);
-  KZG_VER_HIP(hipGetLastError());
+  if ((rc = g1_import(c, d_pxy, d_pinf, K, /*range=*/true, d_recs, d_bad))) return fail(rc);
+  if ((rc = g1_import(c, d_cxy, d_cinf, n_comm, /*range=*/true, cs->recs, d_bad))) return fail(rc);
   uint32_t bad = 0;
   KZG_VER_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
   // the claims travel while the points are checked
@@ -370,11 +281,9 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
 
   // ---- weights and the fold of the values
   const Fe<F> rho = mont_from_words<F>(rho_words);
-  Fe<F> w_hi = w, rho_hi = rho;
-  for (uint32_t q = 0; q < VER_TLOG; ++q) { w_hi = Fd::sqr(w_hi); rho_hi = Fd::sqr(rho_hi); }
-  const dim3 tab_grid((VER_TAB + 255) / 256), k_grid((uint32_t)((K + 255) / 256));
-  hipLaunchKernelGGL(ver_pow_table_kernel<F>, tab_grid, dim3(256), 0, st, fr_arg<F>(w), fr_arg<F>(w_hi), d_wtab);
-  hipLaunchKernelGGL(ver_pow_table_kernel<F>, tab_grid, dim3(256), 0, st, fr_arg<F>(rho), fr_arg<F>(rho_hi), d_rtab);
+  const dim3 k_grid((uint32_t)((K + 255) / 256));
+  if ((rc = fr_pow_table(c, fr_arg<F>(w), d_wtab))) return fail(rc);
+  if ((rc = fr_pow_table(c, fr_arg<F>(rho), d_rtab))) return fail(rc);
   hipLaunchKernelGGL(ver_weights_kernel<F>, k_grid, dim3(256), 0, st, (uint32_t)K, log_l, d_cidx, d_wtab, d_rtab, d_r,
                      d_s);
   KZG_VER_HIP(hipGetLastError());
@@ -424,11 +333,11 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
 
   const XYZZ<C> R = recombine_slices<C>(h_xy.data(), h_inf.data(), ns, sb);
   const XYZZ<C> S = recombine_slices<C>(h_xy.data() + (size_t)ns * PW64, h_inf.data() + ns, ns, sb);
-  XYZZ<C> Tp = point_from_words<C>(h_xy.data() + (size_t)2 * ns * PW64, h_inf[2 * ns]);
+  XYZZ<C> Tp = host_point<C>(h_xy.data() + (size_t)2 * ns * PW64, h_inf[2 * ns]);
   Tp.y = Field<Fp>::neg(Tp.y);                        // -O = O: y = 0 stays 0
-  const XYZZ<C> Cc = point_from_words<C>(h_xy.data() + (size_t)(2 * ns + 1) * PW64, h_inf[2 * ns + 1]);
-  point_to_words<C>(Ec<C>::add(Ec<C>::add(Cc, Tp), S), out_xy, out_inf);
-  point_to_words<C>(R, out_xy + PW64, out_inf + 1);
+  const XYZZ<C> Cc = host_point<C>(h_xy.data() + (size_t)(2 * ns + 1) * PW64, h_inf[2 * ns + 1]);
+  out_inf[0] = affine_to_words<C>(Ec<C>::to_affine(Ec<C>::add(Ec<C>::add(Cc, Tp), S)), reinterpret_cast<uint32_t*>(out_xy));
+  out_inf[1] = affine_to_words<C>(Ec<C>::to_affine(R), reinterpret_cast<uint32_t*>(out_xy + PW64));
   srs_free(cs);
   return KZG_OK;
 }
@@ -439,11 +348,8 @@ int verify_cosets(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const
                   const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
                   const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy, const uint8_t* proof_inf,
                   size_t K, const uint32_t* rho_words, uint64_t* out_xy, uint8_t* out_inf) {
-  return c->curve == 0 ? verify_cosets_t<Bn254>(c, mono, log_N, log_l, w_words, comm_xy, comm_inf, n_comm, comm_idx,
-                                                coset_idx, values, proof_xy, proof_inf, K, rho_words, out_xy, out_inf)
-                       : verify_cosets_t<Bls12_381>(c, mono, log_N, log_l, w_words, comm_xy, comm_inf, n_comm,
-                                                    comm_idx, coset_idx, values, proof_xy, proof_inf, K, rho_words,
-                                                    out_xy, out_inf);
+  return KZG_BY_CURVE(c, verify_cosets_t, c, mono, log_N, log_l, w_words, comm_xy, comm_inf, n_comm, comm_idx, coset_idx,
+                      values, proof_xy, proof_inf, K, rho_words, out_xy, out_inf);
 }
 
 }  // namespace kzg

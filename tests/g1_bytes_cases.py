@@ -1,14 +1,40 @@
 """Shared inputs of the compressed-point tests (a plain helper module, no fixtures): the golden vectors and the seeded
 subgroup matrix, with every expected verdict taken from kzg_snark_amd/curve.py's single-point helpers ([r] P = O)."""
+import ctypes
 import json
 import os
 import random
+import subprocess
 from functools import lru_cache
 
 from kzg_snark_amd import curve as C
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CURVE_IDS = {"bn254": 0, "bls12_381": 1}
+SHIM_DIR = os.path.join(HERE, "shim")
+SHIM_SRC = os.path.join(SHIM_DIR, "g1_bytes_shim.cpp")
+
+
+@lru_cache(maxsize=None)
+def build_shim(audit=False):
+    """csrc/g1_bytes.h and g1_words.h compiled for the host (tests/shim/g1_bytes_shim.cpp), loaded"""
+    kind = "audit" if audit else "plain"
+    so = os.path.join(SHIM_DIR, f"libg1_bytes_shim_{kind}.so")
+    subprocess.run(["g++", "-O0" if audit else "-O1", "-std=c++17", *(["-DKZG_AUDIT"] if audit else []), "-shared", "-fPIC",
+                    SHIM_SRC, "-o", so], check=True)
+    return ctypes.CDLL(so)
+
+
+def words(x, nw):
+    """x as nw little-endian 32-bit words"""
+    return (ctypes.c_uint32 * nw)(*[(x >> (32 * i)) & 0xffffffff for i in range(nw)])
+
+
+def key_point_with_x_plus_p(cv, k=3):
+    """(x + p, y) for the point [k] G1 = (x, y): not canonical, and the same point modulo p"""
+    G = C.g1_group(cv)
+    x, y, _ = G.multiply((cv.g1[0], cv.g1[1], 1), k)
+    return x + cv.p, y
 
 
 @lru_cache(maxsize=None)

@@ -1,6 +1,6 @@
-// Host-only test shim: kzg_snark_amd/csrc/g1_bytes.h (the text the gfx950 kernels of g1_bytes.hip compile) behind a
-// tiny C interface, so tests/test_g1_bytes_host.py can check the square root, the subgroup test and the byte formats
-// against Python integers without a GPU.  Built plain, with -DKZG_AUDIT (field.h's pre/postcondition hooks), and with
+// Host-only test shim: kzg_snark_amd/csrc/g1_bytes.h and, through it, g1_words.h (the text the gfx950 kernels compile)
+// behind a tiny C interface, so tests/test_g1_bytes_host.py can check the square root, the subgroup test, the byte
+// formats and the point <-> canonical-words codec against Python integers without a GPU.  Built plain, with -DKZG_AUDIT (field.h's pre/postcondition hooks), and with
 // -DG1_BYTES_SHIM_MAIN as a program of its own for the sanitizers.  Test infrastructure only.
 #include <stdio.h>
 #include <string.h>
@@ -58,6 +58,32 @@ extern "C" int gb_check(int curve, const uint32_t* xy, int inf) {
   return -1;
 }
 
+// g1_words.h's rule on canonical words x | y: 1 iff both coordinates are below p and the point is on the curve
+extern "C" int gb_import(int curve, const uint32_t* xy) {
+  if (curve == 0) { Fe<BnFp> x, y; return import_affine<Bn254>(xy, xy + BnFp::NW, x, y) ? 1 : 0; }
+  if (curve == 1) { Fe<BlsFp> x, y; return import_affine<Bls12_381>(xy, xy + BlsFp::NW, x, y) ? 1 : 0; }
+  return -1;
+}
+// affine_to_words of affine_from_words: out = the words of (xy, inf) taken modulo p; returns the infinity flag
+extern "C" int gb_words_round_trip(int curve, const uint32_t* xy, int inf, uint32_t* out) {
+  if (curve == 0) return affine_to_words<Bn254>(affine_from_words<Bn254>(xy, inf != 0), out) ? 1 : 0;
+  if (curve == 1) return affine_to_words<Bls12_381>(affine_from_words<Bls12_381>(xy, inf != 0), out) ? 1 : 0;
+  return -1;
+}
+// What kzg_srs_load_g1 asks of a finite key point, written out on its own (not through g1_words.h): the curve
+// equation on the coordinates taken modulo p, no range check.  1 = the key is accepted.
+template <class C>
+static int do_key_rule(const uint32_t* xy) {
+  using Fd = Field<typename C::Fp>;
+  return Ec<C>::on_curve(Fd::reduce(Fd::to_mont(Fd::from_words(xy))),
+                         Fd::reduce(Fd::to_mont(Fd::from_words(xy + C::Fp::NW)))) ? 1 : 0;
+}
+extern "C" int gb_key_rule(int curve, const uint32_t* xy) {
+  if (curve == 0) return do_key_rule<Bn254>(xy);
+  if (curve == 1) return do_key_rule<Bls12_381>(xy);
+  return -1;
+}
+
 #ifdef KZG_AUDIT_ON
 extern "C" void gb_audit_reset() { audit::state() = audit::State{0, "", "", 0, false}; }
 extern "C" unsigned long long gb_audit_read(char* fn, char* what, int cap, int* line) {
@@ -72,7 +98,9 @@ extern "C" unsigned long long gb_audit_read(char* fn, char* what, int cap, int* 
 #ifdef G1_BYTES_SHIM_MAIN
 // The drivers above on inputs made here: k G (k = 1..6, both signs of y by negation) encoded, decoded with the
 // subgroup test and compared; infinity; malformed blobs; square roots of 0, 1, squares and their negatives (p = 3
-// mod 4: exactly one of a, -a is a square) with all-ones limbs; on BLS12-381 the order-3 point (0, 2).
+// mod 4: exactly one of a, -a is a square) with all-ones limbs; on BLS12-381 the order-3 point (0, 2); the
+// canonical-words codec of g1_words.h at its edges (x = p, y = p, x = p - 1, all-ones words, a flagged infinity with
+// stray words) and the key-loading rule on x + p.
 static int fails = 0;
 #define EXPECT(c) do { if (!(c)) { ++fails; printf("FAILED line %d: %s\n", __LINE__, #c); } } while (0)
 
@@ -131,6 +159,31 @@ static void self_test(int curve, const uint32_t* gen_xy) {
   uint32_t one[NW] = {1}, zw[NW] = {0}, rw[NW];
   EXPECT(gb_sqrt(curve, zw, rw) == 1 && rw[0] == 0);
   EXPECT(gb_sqrt(curve, one, rw) == 1);
+  // g1_words.h: the rule, the round trip and the key-loading rule on the generator and around p
+  {
+    uint32_t pw[NW], q[2 * NW], back[2 * NW];
+    for (int k = 0; k < NW; ++k) pw[k] = F::PW[k];
+    EXPECT(gb_import(curve, gen_xy) == 1 && gb_key_rule(curve, gen_xy) == 1);
+    EXPECT(gb_words_round_trip(curve, gen_xy, 0, back) == 0 && memcmp(back, gen_xy, sizeof(back)) == 0);
+    memcpy(q, gen_xy, sizeof(q)); memcpy(q, pw, sizeof(pw));                       // x = p
+    EXPECT(gb_import(curve, q) == 0);
+    memcpy(q, gen_xy, sizeof(q)); memcpy(q + NW, pw, sizeof(pw));                  // y = p
+    EXPECT(gb_import(curve, q) == 0);
+    memcpy(q, gen_xy, sizeof(q)); memcpy(q, pw, sizeof(pw)); q[0] -= 1;            // (p - 1, y): in range, off the curve
+    EXPECT(words_below_p<F>(q) && words_below_p<F>(q + NW) && gb_import(curve, q) == 0 && gb_key_rule(curve, q) == 0);
+    memset(q, 0xff, sizeof(q));                                                    // all-ones words
+    EXPECT(gb_import(curve, q) == 0);
+    EXPECT(gb_words_round_trip(curve, q, 1, back) == 1);                           // the flag wins over stray words
+    for (int k = 0; k < 2 * NW; ++k) EXPECT(back[k] == 0);
+    // x + p (there is room: p < 2^255, p < 2^382): the rule refuses it, the round trip and key loading take it as x
+    memcpy(q, gen_xy, sizeof(q));
+    uint64_t carry = 0;
+    for (int k = 0; k < NW; ++k) { carry += (uint64_t)q[k] + pw[k]; q[k] = (uint32_t)carry; carry >>= 32; }
+    EXPECT(carry == 0 && !words_below_p<F>(q));
+    EXPECT(gb_import(curve, q) == 0);
+    EXPECT(gb_key_rule(curve, q) == 1);
+    EXPECT(gb_words_round_trip(curve, q, 0, back) == 0 && memcmp(back, gen_xy, sizeof(back)) == 0);
+  }
   if (curve == 1) {                                       // (0, 2): order 3, on the curve y^2 = x^3 + 4
     uint32_t xy[2 * NW] = {0};
     xy[NW] = 2;

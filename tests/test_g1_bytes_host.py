@@ -10,7 +10,8 @@ import subprocess
 
 import pytest
 
-from g1_bytes_cases import CURVE_IDS, golden, golden_failures, golden_points, subgroup_matrix
+from g1_bytes_cases import (CURVE_IDS, build_shim, golden, golden_failures, golden_points, key_point_with_x_plus_p,
+                            subgroup_matrix)
 from kzg_snark_amd import curve as C
 from limb_patterns import adversarial, header_layout
 
@@ -123,10 +124,7 @@ class Shim:
 @pytest.fixture(scope="module", params=["plain", "audit"])
 def shim(request):
     audit = request.param == "audit"
-    so = os.path.join(SHIM_DIR, f"libg1_bytes_shim_{request.param}.so")
-    subprocess.run(["g++", "-O0" if audit else "-O1", "-std=c++17", *(["-DKZG_AUDIT"] if audit else []), "-shared", "-fPIC", SRC, "-o", so],
-                   check=True)
-    return Shim(ctypes.CDLL(so), audit)
+    return Shim(build_shim(audit), audit)
 
 
 @pytest.mark.parametrize("name", ["bls12_381", "bn254"])
@@ -200,8 +198,47 @@ def test_encode_and_decode_of_every_golden_vector(shim, name):
     shim.assert_clean()
 
 
+@pytest.mark.parametrize("name", ["bls12_381", "bn254"])
+def test_words_codec_of_g1_words_h(shim, name):
+    """import_affine (the rule: both coordinates below p, on the curve), affine_to_words o affine_from_words, and the
+    rule of key loading (the curve equation alone, modulo p) at the edges of the canonical range."""
+    cv, cid = C.CURVES[name], CURVE_IDS[name]
+    p = cv.p
+    nw = (p.bit_length() + 31) // 32
+    gx, gy = cv.g1
+
+    def xy(x, y):
+        return shim.words(x | (y << (32 * nw)), 2 * nw)
+
+    def round_trip(x, y, inf=0):
+        out = (U32 * (2 * nw))()
+        flag = shim.lib.gb_words_round_trip(cid, xy(x, y), inf, out)
+        v = shim.val(out)
+        return flag, v & ((1 << (32 * nw)) - 1), v >> (32 * nw)
+
+    ones = (1 << (32 * nw)) - 1
+    assert shim.lib.gb_import(cid, xy(gx, gy)) == 1 and round_trip(gx, gy) == (0, gx, gy)
+    assert shim.lib.gb_import(cid, xy(p, gy)) == 0                              # x = p
+    assert shim.lib.gb_import(cid, xy(gx, p)) == 0                              # y = p
+    assert ((p - 1) ** 3 + cv.b - gy * gy) % p != 0
+    assert shim.lib.gb_import(cid, xy(p - 1, gy)) == 0                          # in range, off the curve
+    assert shim.lib.gb_key_rule(cid, xy(p - 1, gy)) == 0
+    assert shim.lib.gb_import(cid, xy(ones, ones)) == 0                         # all-ones words
+    assert round_trip(ones, ones, inf=1) == (1, 0, 0)                           # the flag wins over stray words
+    assert round_trip(ones, ones) == (0, ones % p, ones % p)                    # unchecked: modulo p
+    # x + p fits the words; the rule refuses it, key loading takes it for x (the expectation of the GPU test
+    # test_key_loading_and_compression_differ_on_a_coordinate_above_p)
+    x2, y2 = key_point_with_x_plus_p(cv)
+    assert x2 < 1 << (32 * nw)
+    assert shim.lib.gb_import(cid, xy(x2 - p, y2)) == 1 and shim.lib.gb_import(cid, xy(x2, y2)) == 0
+    assert shim.lib.gb_key_rule(cid, xy(x2, y2)) == 1
+    assert round_trip(x2, y2) == (0, x2 - p, y2)
+    shim.assert_clean()
+
+
 def test_shim_under_address_and_undefined_behaviour_sanitizers(tmp_path):
-    """g1_bytes_shim.cpp with its own main(): encode / decode / subgroup test / square roots on both curves, built with
+    """g1_bytes_shim.cpp with its own main(): encode / decode / subgroup test / square roots / the canonical-words codec
+    on both curves, built with
     -DKZG_AUDIT and -fsanitize=address,undefined (no recovery, static runtimes) and run as a program of its own.  Exit
     status 0 = no sanitizer report, no audit violation, every check of the program passed."""
     exe = str(tmp_path / "g1_bytes_shim_san")

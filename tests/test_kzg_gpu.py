@@ -791,3 +791,37 @@ def test_commit_at_the_bin_counts_of_larger_polynomials(native, kzgs, log_n):
         got = tuple(native.limbs_to_ints(xy.reshape(2, 6)))
         assert inf[0] == 0 and got == O.normalize(O.commit_trapdoor(coeffs, tau, cv), cv), (log_n, variant)
     srs.close()
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_key_loading_and_compression_differ_on_a_coordinate_above_p(native, curve):
+    """A 4-point key whose point 2 has x replaced by x + p (it fits the words: p < 2^255, p < 2^382).  Loading a key
+    checks the curve equation on the coordinates taken modulo p and nothing else, so kzg_srs_load_g1 answers what the
+    host build of that expression answers (tests/shim: gb_key_rule); every other entry point applies the rule of
+    csrc/g1_words.h, which refuses a coordinate >= p: kzg_g1_compress of the same points is KZG_ERR_ARG."""
+    from g1_bytes_cases import CURVE_IDS, build_shim, words
+    p = O.curve(curve).p
+    ctx = native.get_context(curve)
+    L = ctx.fp_limbs
+    gen = ctx.srs_generate(native.int_to_words(0x5eed), 4)
+    xy, inf = gen.export()
+    gen.close()
+    x, y = native.limbs_to_ints(xy[2].reshape(2, L))
+    assert x + p < 1 << (64 * L)
+    bad = xy.copy()
+    bad[2, :L] = native.int_to_words(x + p, L)
+    accepted = build_shim().gb_key_rule(CURVE_IDS[curve], words((x + p) | (y << (64 * L)), 4 * L))
+    assert accepted in (0, 1)
+    if accepted:
+        srs = ctx.srs_load_g1(bad, inf)
+        xy2, inf2 = srs.export()                               # stored modulo p: the key that was meant
+        srs.close()
+        assert np.array_equal(xy2, xy) and not inf2.any()
+    else:
+        with pytest.raises(native.NativeError) as e:
+            ctx.srs_load_g1(bad, inf)
+        assert e.value.code == -1
+    with pytest.raises(native.NativeError) as e:
+        ctx.g1_compress(bad, inf)
+    assert e.value.code == -1                                  # KZG_ERR_ARG
+    assert ctx.g1_compress(xy, inf).shape == (4, ctx.g1_bytes)

@@ -18,7 +18,7 @@ HEADER = os.path.join(ROOT, "include", "kzg_mi355x.h")
 CURVES = ["bls12_381", "bn254"]
 SMALL_SHAPES = [(8, 16, 1), (8, 16, 2), (8, 32, 4), (16, 16, 4), (4, 16, 4), (8, 16, 8)]      # (n, N, l)
 NEW_SYMBOLS = ["kzg_recover_cosets", "kzg_recover_cosets_device"]
-NEW_KERNELS = ["rec_pow_table_kernel", "rec_leaf_kernel", "rec_pair_mul_kernel", "rec_expand_kernel",
+NEW_KERNELS = ["fr_pow_table_kernel", "rec_leaf_kernel", "rec_pair_mul_kernel", "rec_expand_kernel",
                "rec_to_mont_kernel", "rec_scatter_kernel", "rec_shift_kernel", "rec_divide_kernel", "rec_finish_kernel"]
 
 
