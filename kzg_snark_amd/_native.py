@@ -191,6 +191,29 @@ def _as_vp(a):
     return ctypes.cast(a, ctypes.c_void_p)
 
 
+def _fr(v):
+    """one Fr scalar (anything int() takes) -> pointer to its 4 canonical words"""
+    return _as_vp(int_to_words(int(v)))
+
+
+def _inf_arg(inf, n, who):
+    """infinity flags beside n points: None, or contiguous uint8[n]; `who` names the call and the pair in the message"""
+    if inf is None:
+        return None
+    inf = np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1)
+    if inf.size != n:
+        raise ValueError(f"{who} differ in length")
+    return inf
+
+
+def result_buffers(limbs, shape=(), evals=None):
+    """Zeroed host arrays an entry point writes its results into: (xy uint64[*shape, 2*limbs], inf uint8[*shape],
+    ev uint64[*evals] or None).  shape () is one point: xy uint64[2*limbs], inf uint8[1]."""
+    shape = tuple(shape)
+    return (np.zeros(shape + (2 * limbs,), dtype=np.uint64), np.zeros(shape or 1, dtype=np.uint8),
+            None if evals is None else np.zeros(evals, dtype=np.uint64))
+
+
 class Context:
     """One engine context: one curve, one GPU, one stream (kzg_ctx)."""
 
@@ -230,6 +253,12 @@ class Context:
         if rc != 0:
             msg = lib().kzg_last_error(self._h)
             raise NativeError(rc, msg.decode() if msg else "")
+
+    def _handle(self, fn, *args):
+        """fn(ctx, *args, &handle), checked: the new handle"""
+        h = ctypes.c_void_p()
+        self._check(fn(self._h, *args, ctypes.byref(h)))
+        return h
 
     def set_stream(self, stream_ptr):
         self._check(lib().kzg_ctx_set_stream(self._h, ctypes.c_void_p(stream_ptr or 0)))
@@ -313,19 +342,15 @@ class Context:
         assert xy.dtype == np.uint64 and xy.flags.c_contiguous and xy.shape[1] == 2 * self.fp_limbs
         if inf is not None:
             assert inf.dtype == np.uint8 and inf.size == n and inf.flags.c_contiguous
-        h = ctypes.c_void_p()
-        self._check(lib().kzg_srs_load_g1(self._h, _as_vp(xy), _as_vp(inf), n, ctypes.byref(h)))
-        return Srs(self, h, n)
+        return Srs(self, self._handle(lib().kzg_srs_load_g1, _as_vp(xy), _as_vp(inf), n), n)
 
     def srs_load_g1_compressed(self, blobs, check_subgroup=True):
         """blobs: uint8[n, g1_bytes] compressed points (include/kzg_mi355x.h: the byte formats); decompressed and
         expanded on the device.  A point that does not decompress (or, with check_subgroup, lies outside the
         subgroup) raises NativeError naming the first such index."""
         blobs = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(-1, self.g1_bytes)
-        h = ctypes.c_void_p()
-        self._check(lib().kzg_srs_load_g1_compressed(self._h, _as_vp(blobs), blobs.shape[0], int(bool(check_subgroup)),
-                                                     ctypes.byref(h)))
-        return Srs(self, h, blobs.shape[0])
+        return Srs(self, self._handle(lib().kzg_srs_load_g1_compressed, _as_vp(blobs), blobs.shape[0],
+                                      int(bool(check_subgroup))), blobs.shape[0])
 
     # ---- compressed points and subgroup membership
     @property
@@ -337,10 +362,7 @@ class Context:
         """affine points (uint64[n, 2*fp_limbs], uint8[n] flags or None) -> uint8[n, g1_bytes]"""
         xy = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, 2 * self.fp_limbs)
         n = xy.shape[0]
-        if inf is not None:
-            inf = np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1)
-            if inf.size != n:
-                raise ValueError("g1_compress: inf and xy differ in length")
+        inf = _inf_arg(inf, n, "g1_compress: inf and xy")
         out = np.zeros((n, self.g1_bytes), dtype=np.uint8)
         self._check(lib().kzg_g1_compress(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(out)))
         return out
@@ -367,79 +389,52 @@ class Context:
         curve, 3 on the curve but outside the subgroup"""
         xy = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, 2 * self.fp_limbs)
         n = xy.shape[0]
-        if inf is not None:
-            inf = np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1)
-            if inf.size != n:
-                raise ValueError("g1_check_subgroup: inf and xy differ in length")
+        inf = _inf_arg(inf, n, "g1_check_subgroup: inf and xy")
         status = np.zeros(n, dtype=np.uint8)
         self._check(lib().kzg_g1_check_subgroup(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(status)))
         return status
 
     def srs_generate(self, tau_words, n, start=0):
-        h = ctypes.c_void_p()
-        self._check(lib().kzg_srs_generate_range(self._h, _as_vp(tau_words), start, n, ctypes.byref(h)))
-        return Srs(self, h, n)
+        return Srs(self, self._handle(lib().kzg_srs_generate_range, _as_vp(tau_words), start, n), n)
 
     def srs_generate_strided(self, tau_words, start, n, run_len, inner_stride, outer_stride):
         """point i = tau^(start + (i // run_len) * outer_stride + (i % run_len) * inner_stride) * G1"""
-        h = ctypes.c_void_p()
-        self._check(lib().kzg_srs_generate_strided(self._h, _as_vp(tau_words), start, n, run_len, inner_stride,
-                                                   outer_stride, ctypes.byref(h)))
-        return Srs(self, h, n)
+        return Srs(self, self._handle(lib().kzg_srs_generate_strided, _as_vp(tau_words), start, n, run_len,
+                                      inner_stride, outer_stride), n)
 
     # ---- evaluation form (Lagrange keys over the domain {w^i}, n = 2^log_n)
     def srs_generate_lagrange(self, tau_words, log_n, w):
         """[L_i(tau) G1], i < 2^log_n: the Lagrange key from the secret."""
-        h = ctypes.c_void_p()
-        self._check(lib().kzg_srs_generate_lagrange(self._h, _as_vp(tau_words), int(log_n),
-                                                    _as_vp(int_to_words(int(w))), ctypes.byref(h)))
+        h = self._handle(lib().kzg_srs_generate_lagrange, _as_vp(tau_words), int(log_n), _fr(w))
         return Srs(self, h, 1 << int(log_n), basis=(int(log_n), int(w)))
 
     def srs_lagrange(self, monomial, log_n, w):
         """The Lagrange key from the first 2^log_n points of a monomial key (inverse NTT over G1)."""
-        h = ctypes.c_void_p()
-        self._check(lib().kzg_srs_lagrange(self._h, monomial._h, int(log_n), _as_vp(int_to_words(int(w))),
-                                           ctypes.byref(h)))
+        h = self._handle(lib().kzg_srs_lagrange, monomial._h, int(log_n), _fr(w))
         return Srs(self, h, 1 << int(log_n), basis=(int(log_n), int(w)))
 
     def open_evals(self, srs, vals, lens, stride, z_words, xi_words, device=False):
         """Opening from value vectors (uint64[k, stride, 4] host array, or a device pointer with device=True)
         against a Lagrange key: (out_xy, out_inf, eval)."""
-        k = len(lens)
-        lens_a = np.asarray(lens, dtype=np.uint64)
-        out_xy = np.zeros(2 * self.fp_limbs, dtype=np.uint64)
-        out_inf = np.zeros(1, dtype=np.uint8)
-        ev = np.zeros(4, dtype=np.uint64)
-        fn = lib().kzg_open_evals_device if device else lib().kzg_open_evals
-        self._check(fn(self._h, srs._h, _as_vp(vals), _as_vp(lens_a), k, stride, _as_vp(z_words),
-                       _as_vp(xi_words), _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev)))
-        return out_xy, out_inf, ev
+        return self._open("kzg_open_evals", srs, vals, lens, stride, z_words, xi_words, device)
 
     def open_evals_device_async(self, srs, d_vals, lens, stride, z_words, xi_words, out_xy, out_inf, eval_out):
         """Pipelined opening from values: the outputs (numpy arrays the caller keeps alive) are filled by the time
         commit_flush() returns -- the slot rules of open_device_async."""
-        lens_a = np.asarray(lens, dtype=np.uint64)
-        _check_out(out_xy, np.uint64, 2 * self.fp_limbs, "out_xy")
-        _check_out(out_inf, np.uint8, 1, "out_inf")
-        _check_out(eval_out, np.uint64, 4, "eval_out")
-        self._check(lib().kzg_open_evals_device_async(self._h, srs._h, _as_vp(d_vals), _as_vp(lens_a), len(lens),
-                                                      stride, _as_vp(z_words), _as_vp(xi_words), _as_vp(out_xy),
-                                                      _as_vp(out_inf), _as_vp(eval_out)))
-        self._inflight.append((srs, out_xy, out_inf, eval_out))
+        self._open_async(lib().kzg_open_evals_device_async, srs, d_vals, lens, stride, z_words, xi_words, out_xy,
+                         out_inf, eval_out)
 
     def eval_lagrange(self, log_n, w, n, d_vals, z):
         """p(z) of the interpolant of n device-resident values over {w^i} (barycentric, z in the domain included)."""
         out = np.zeros(4, dtype=np.uint64)
-        self._check(lib().kzg_fr_eval_lagrange(self._h, int(log_n), _as_vp(int_to_words(int(w))), n, _as_vp(d_vals),
-                                               _as_vp(int_to_words(int(z))), _as_vp(out)))
+        self._check(lib().kzg_fr_eval_lagrange(self._h, int(log_n), _fr(w), n, _as_vp(d_vals), _fr(z), _as_vp(out)))
         return int.from_bytes(out.tobytes(), "little")
 
     # ---- every proof on a domain (FK20)
     def domain_table(self, monomial, log_n):
         """The FK20 table of the first 2^log_n points of a monomial key."""
-        h = ctypes.c_void_p()
-        self._check(lib().kzg_domain_table_create(self._h, monomial._h, int(log_n), ctypes.byref(h)))
-        return DomainTable(self, h, 1 << int(log_n))
+        return DomainTable(self, self._handle(lib().kzg_domain_table_create, monomial._h, int(log_n)),
+                           1 << int(log_n))
 
     def open_domain(self, table, polys, lens, stride, w, device=False, evals=True):
         """All n proofs of each of len(lens) coefficient vectors (uint64[b, stride, 4] host array, or a device pointer
@@ -447,20 +442,16 @@ class Context:
         None)."""
         b, n = len(lens), table.n
         lens_a = np.asarray(lens, dtype=np.uint64)
-        out_xy = np.zeros((b, n, 2 * self.fp_limbs), dtype=np.uint64)
-        out_inf = np.zeros((b, n), dtype=np.uint8)
-        ev = np.zeros((b, n, 4), dtype=np.uint64) if evals else None
+        out = result_buffers(self.fp_limbs, (b, n), (b, n, 4) if evals else None)
         fn = lib().kzg_open_domain_device if device else lib().kzg_open_domain
-        self._check(fn(self._h, table._h, _as_vp(polys), _as_vp(lens_a), b, stride, _as_vp(int_to_words(int(w))),
-                       _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev) if evals else None))
-        return out_xy, out_inf, ev
+        self._check(fn(self._h, table._h, _as_vp(polys), _as_vp(lens_a), b, stride, _fr(w), *map(_as_vp, out)))
+        return out
 
     # ---- coset openings (FK20 multi-reveal, and one coset by division)
     def coset_table(self, monomial, log_n, log_l):
         """The coset table of the first 2^log_n points of a monomial key for cosets of 2^log_l points."""
-        h = ctypes.c_void_p()
-        self._check(lib().kzg_coset_table_create(self._h, monomial._h, int(log_n), int(log_l), ctypes.byref(h)))
-        return DomainTable(self, h, 1 << int(log_n), 1 << int(log_l))
+        return DomainTable(self, self._handle(lib().kzg_coset_table_create, monomial._h, int(log_n), int(log_l)),
+                           1 << int(log_n), 1 << int(log_l))
 
     def open_cosets(self, table, polys, lens, stride, log_N, w, device=False, evals=True):
         """The N/l coset proofs of each of len(lens) coefficient vectors (uint64[b, stride, 4] host array, or a device
@@ -469,27 +460,22 @@ class Context:
         b, l = len(lens), table.l
         cosets = (1 << int(log_N)) // l
         lens_a = np.asarray(lens, dtype=np.uint64)
-        out_xy = np.zeros((b, cosets, 2 * self.fp_limbs), dtype=np.uint64)
-        out_inf = np.zeros((b, cosets), dtype=np.uint8)
-        ev = np.zeros((b, cosets, l, 4), dtype=np.uint64) if evals else None
+        out = result_buffers(self.fp_limbs, (b, cosets), (b, cosets, l, 4) if evals else None)
         fn = lib().kzg_open_cosets_device if device else lib().kzg_open_cosets
-        self._check(fn(self._h, table._h, _as_vp(polys), _as_vp(lens_a), b, stride, int(log_N),
-                       _as_vp(int_to_words(int(w))), _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev) if evals else None))
-        return out_xy, out_inf, ev
+        self._check(fn(self._h, table._h, _as_vp(polys), _as_vp(lens_a), b, stride, int(log_N), _fr(w),
+                       *map(_as_vp, out)))
+        return out
 
     def open_coset(self, srs, polys, lens, stride, log_l, h, zeta, xi, device=False):
         """One coset proof of the xi-combination of len(lens) polynomials at h * zeta^k, k < 2^log_l:
         (out_xy uint64[2*fp_limbs], out_inf uint8[1], values uint64[l, 4])."""
         k = len(lens)
         lens_a = np.asarray(lens, dtype=np.uint64)
-        out_xy = np.zeros(2 * self.fp_limbs, dtype=np.uint64)
-        out_inf = np.zeros(1, dtype=np.uint8)
-        ev = np.zeros((1 << int(log_l), 4), dtype=np.uint64)
+        out = result_buffers(self.fp_limbs, evals=(1 << int(log_l), 4))
         fn = lib().kzg_open_coset_device if device else lib().kzg_open_coset
-        self._check(fn(self._h, srs._h, _as_vp(polys), _as_vp(lens_a), k, stride, int(log_l),
-                       _as_vp(int_to_words(int(h))), _as_vp(int_to_words(int(zeta))), _as_vp(int_to_words(int(xi))),
-                       _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev)))
-        return out_xy, out_inf, ev
+        self._check(fn(self._h, srs._h, _as_vp(polys), _as_vp(lens_a), k, stride, int(log_l), _fr(h), _fr(zeta),
+                       _fr(xi), *map(_as_vp, out)))
+        return out
 
     # ---- bulk verification
     def verify_cosets(self, srs, log_N, log_l, w, comm_xy, comm_inf, comm_idx, coset_idx, values, proof_xy, proof_inf,
@@ -507,20 +493,13 @@ class Context:
         values = np.ascontiguousarray(values, dtype=np.uint64)
         if coset_idx.size != K or proof_xy.shape[0] != K or values.size != K * l * 4:
             raise ValueError("verify_cosets: comm_idx, coset_idx, values and proofs describe different numbers of cells")
-        if comm_inf is not None:
-            comm_inf = np.ascontiguousarray(comm_inf, dtype=np.uint8).reshape(-1)
-            if comm_inf.size != comm_xy.shape[0]:
-                raise ValueError("verify_cosets: comm_inf and comm_xy differ in length")
-        if proof_inf is not None:
-            proof_inf = np.ascontiguousarray(proof_inf, dtype=np.uint8).reshape(-1)
-            if proof_inf.size != K:
-                raise ValueError("verify_cosets: proof_inf and proof_xy differ in length")
-        out_xy = np.zeros((2, P), dtype=np.uint64)
-        out_inf = np.zeros(2, dtype=np.uint8)
-        self._check(lib().kzg_verify_cosets(self._h, srs._h, int(log_N), int(log_l), _as_vp(int_to_words(int(w))),
-                                            _as_vp(comm_xy), _as_vp(comm_inf), comm_xy.shape[0], _as_vp(comm_idx),
-                                            _as_vp(coset_idx), _as_vp(values), _as_vp(proof_xy), _as_vp(proof_inf), K,
-                                            _as_vp(int_to_words(int(rho))), _as_vp(out_xy), _as_vp(out_inf)))
+        comm_inf = _inf_arg(comm_inf, comm_xy.shape[0], "verify_cosets: comm_inf and comm_xy")
+        proof_inf = _inf_arg(proof_inf, K, "verify_cosets: proof_inf and proof_xy")
+        out_xy, out_inf, _ = result_buffers(self.fp_limbs, (2,))
+        self._check(lib().kzg_verify_cosets(self._h, srs._h, int(log_N), int(log_l), _fr(w), _as_vp(comm_xy),
+                                            _as_vp(comm_inf), comm_xy.shape[0], _as_vp(comm_idx), _as_vp(coset_idx),
+                                            _as_vp(values), _as_vp(proof_xy), _as_vp(proof_inf), K, _fr(rho),
+                                            _as_vp(out_xy), _as_vp(out_inf)))
         # the library retires every pipeline slot before it returns, as kzg_commit_flush does
         self._inflight.clear()
         return out_xy, out_inf
@@ -535,7 +514,7 @@ class Context:
         coset_idx = np.ascontiguousarray(coset_idx, dtype=np.uint32).reshape(-1)
         K, b = coset_idx.size, int(b)
         ok = np.zeros(max(b, 1), dtype=np.uint8)
-        w_words = _as_vp(int_to_words(int(w)))
+        w_words = _fr(w)
         if d_coeffs is not None:
             self._check(lib().kzg_recover_cosets_device(self._h, int(log_n), int(log_N), int(log_l), w_words,
                                                         _as_vp(coset_idx), K, _as_vp(values), b, _as_vp(d_coeffs),
@@ -550,24 +529,19 @@ class Context:
         return coeffs[:b], ok[:b]
 
     # ---- commit / open on host buffers
-    def commit(self, srs, scalars, lens, stride):
-        """scalars: uint64[n_polys, stride, 4]; lens: per-polynomial coefficient counts."""
-        n_polys = len(lens)
+    def _commit(self, fn, srs, scalars, lens, stride):
         lens_a = np.asarray(lens, dtype=np.uint64)
-        out_xy = np.zeros((n_polys, 2 * self.fp_limbs), dtype=np.uint64)
-        out_inf = np.zeros(n_polys, dtype=np.uint8)
-        self._check(lib().kzg_commit(self._h, srs._h, _as_vp(scalars), _as_vp(lens_a), n_polys, stride,
-                                     _as_vp(out_xy), _as_vp(out_inf)))
+        out_xy, out_inf, _ = result_buffers(self.fp_limbs, (len(lens),))
+        self._check(fn(self._h, srs._h, _as_vp(scalars), _as_vp(lens_a), len(lens), stride, _as_vp(out_xy),
+                       _as_vp(out_inf)))
         return out_xy, out_inf
 
+    def commit(self, srs, scalars, lens, stride):
+        """scalars: uint64[n_polys, stride, 4]; lens: per-polynomial coefficient counts."""
+        return self._commit(lib().kzg_commit, srs, scalars, lens, stride)
+
     def commit_device(self, srs, d_scalars, lens, stride):
-        n_polys = len(lens)
-        lens_a = np.asarray(lens, dtype=np.uint64)
-        out_xy = np.zeros((n_polys, 2 * self.fp_limbs), dtype=np.uint64)
-        out_inf = np.zeros(n_polys, dtype=np.uint8)
-        self._check(lib().kzg_commit_device(self._h, srs._h, _as_vp(d_scalars), _as_vp(lens_a), n_polys,
-                                            stride, _as_vp(out_xy), _as_vp(out_inf)))
-        return out_xy, out_inf
+        return self._commit(lib().kzg_commit_device, srs, d_scalars, lens, stride)
 
     def commit_device_async(self, srs, d_scalars, lens, stride, out_xy, out_inf):
         """Pipelined commit: results land in the caller's out_xy / out_inf (numpy, kept alive by the
@@ -589,29 +563,32 @@ class Context:
             # the library retires every slot in kzg_commit_flush, also on error: nothing points at these any more
             self._inflight.clear()
 
-    def open(self, srs, polys, lens, stride, z_words, xi_words, device=False):
-        k = len(lens)
+    def _open(self, name, srs, data, lens, stride, z_words, xi_words, device):
+        """kzg_open / kzg_open_evals (`name`), or its _device form: (out_xy, out_inf, eval)"""
         lens_a = np.asarray(lens, dtype=np.uint64)
-        out_xy = np.zeros(2 * self.fp_limbs, dtype=np.uint64)
-        out_inf = np.zeros(1, dtype=np.uint8)
-        ev = np.zeros(4, dtype=np.uint64)
-        fn = lib().kzg_open_device if device else lib().kzg_open
-        self._check(fn(self._h, srs._h, _as_vp(polys), _as_vp(lens_a), k, stride, _as_vp(z_words),
-                       _as_vp(xi_words), _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev)))
-        return out_xy, out_inf, ev
+        out = result_buffers(self.fp_limbs, evals=4)
+        fn = getattr(lib(), name + "_device" if device else name)
+        self._check(fn(self._h, srs._h, _as_vp(data), _as_vp(lens_a), len(lens), stride, _as_vp(z_words),
+                       _as_vp(xi_words), *map(_as_vp, out)))
+        return out
 
+    def open(self, srs, polys, lens, stride, z_words, xi_words, device=False):
+        return self._open("kzg_open", srs, polys, lens, stride, z_words, xi_words, device)
 
-    def open_device_async(self, srs, d_polys, lens, stride, z_words, xi_words, out_xy, out_inf, eval_out):
-        """Pipelined open: out_xy (uint64[2*fp_limbs]), out_inf (uint8[1]) and eval_out (uint64[4]) -- numpy arrays
-        the caller keeps alive -- are filled by the time commit_flush() returns."""
+    def _open_async(self, fn, srs, d_data, lens, stride, z_words, xi_words, out_xy, out_inf, eval_out):
         lens_a = np.asarray(lens, dtype=np.uint64)
         _check_out(out_xy, np.uint64, 2 * self.fp_limbs, "out_xy")
         _check_out(out_inf, np.uint8, 1, "out_inf")
         _check_out(eval_out, np.uint64, 4, "eval_out")
-        self._check(lib().kzg_open_device_async(self._h, srs._h, _as_vp(d_polys), _as_vp(lens_a), len(lens), stride,
-                                                _as_vp(z_words), _as_vp(xi_words), _as_vp(out_xy), _as_vp(out_inf),
-                                                _as_vp(eval_out)))
-        self._inflight.append((srs, out_xy, out_inf, eval_out))
+        self._check(fn(self._h, srs._h, _as_vp(d_data), _as_vp(lens_a), len(lens), stride, _as_vp(z_words),
+                       _as_vp(xi_words), _as_vp(out_xy), _as_vp(out_inf), _as_vp(eval_out)))
+        self._inflight.append((srs, out_xy, out_inf, eval_out))          # after KZG_OK, as in commit_device_async
+
+    def open_device_async(self, srs, d_polys, lens, stride, z_words, xi_words, out_xy, out_inf, eval_out):
+        """Pipelined open: out_xy (uint64[2*fp_limbs]), out_inf (uint8[1]) and eval_out (uint64[4]) -- numpy arrays
+        the caller keeps alive -- are filled by the time commit_flush() returns."""
+        self._open_async(lib().kzg_open_device_async, srs, d_polys, lens, stride, z_words, xi_words, out_xy, out_inf,
+                         eval_out)
 
     # ---- device vector / polynomial primitives (device pointers, canonical elements)
     def vec_op(self, op, n, d_a, d_b, d_out):
@@ -627,8 +604,7 @@ class Context:
                                              _as_vp(sc), _as_vp(d_out)))
 
     def vec_mul_powers(self, n, d_a, s, c0, d_out):
-        self._check(lib().kzg_fr_vec_mul_powers(self._h, n, _as_vp(d_a), _as_vp(int_to_words(int(s))),
-                                                _as_vp(int_to_words(int(c0))), _as_vp(d_out)))
+        self._check(lib().kzg_fr_vec_mul_powers(self._h, n, _as_vp(d_a), _fr(s), _fr(c0), _as_vp(d_out)))
 
     def vec_inverse(self, n, d_a, d_out):
         self._check(lib().kzg_fr_vec_inverse(self._h, n, _as_vp(d_a), _as_vp(d_out)))
@@ -638,7 +614,7 @@ class Context:
 
     def poly_eval(self, n, d_a, z):
         out = np.zeros(4, dtype=np.uint64)
-        self._check(lib().kzg_fr_poly_eval(self._h, n, _as_vp(d_a), _as_vp(int_to_words(int(z))), _as_vp(out)))
+        self._check(lib().kzg_fr_poly_eval(self._h, n, _as_vp(d_a), _fr(z), _as_vp(out)))
         return int.from_bytes(out.tobytes(), "little")
 
     # ---- sharded open (device pointers)
@@ -650,17 +626,34 @@ class Context:
         return h
 
     def open_shard_finish(self, srs, z_words, carry_words, first_rank):
-        out_xy = np.zeros(2 * self.fp_limbs, dtype=np.uint64)
-        out_inf = np.zeros(1, dtype=np.uint8)
-        ev = np.zeros(4, dtype=np.uint64)
+        out = result_buffers(self.fp_limbs, evals=4)
         self._check(lib().kzg_open_shard_finish(self._h, srs._h, _as_vp(z_words), _as_vp(carry_words),
-                                                int(bool(first_rank)), _as_vp(out_xy), _as_vp(out_inf), _as_vp(ev)))
-        return out_xy, out_inf, ev
+                                                int(bool(first_rank)), *map(_as_vp, out)))
+        return out
 
 
-class Srs:
+class _Handle:
+    """A device object of one context; `_free` names the ABI function that releases it.  Closing after the context
+    has closed is a no-op (kzg_ctx_destroy has released everything the context owned)."""
+    _free = None
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            getattr(lib(), self._free)(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Srs(_Handle):
     """Device-resident commitment key (kzg_srs): the reference's `ck` list.  basis: None for a monomial key
     ([tau^i] G1), (log_n, w) for a Lagrange key over the domain {w^i} ([L_i(tau)] G1)."""
+
+    _free = "kzg_srs_free"
 
     def __init__(self, ctx, h, n, basis=None):
         self.ctx = ctx
@@ -682,21 +675,12 @@ class Srs:
         self.ctx._check(lib().kzg_srs_export_compressed(self.ctx._h, self._h, start, count, _as_vp(out)))
         return out
 
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            lib().kzg_srs_free(self._h)
-        self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DomainTable:
+class DomainTable(_Handle):
     """FK20 table of one monomial key, domain size n and coset size l (kzg_domain_table; l = 1 from domain_table):
     2n affine points on the device."""
+
+    _free = "kzg_domain_table_free"
 
     def __init__(self, ctx, h, n, l=1):
         self.ctx = ctx
@@ -704,31 +688,16 @@ class DomainTable:
         self.n = n
         self.l = l
 
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            lib().kzg_domain_table_free(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def g1_sum(curve_type, points):
     """Sum of G1 points given as facade tuples (x, y, 1) / (1, 1, 0), on the host in the library's C++ (kzg_g1_sum):
-    microseconds per point where the pure-Python group law takes tens -- the add-up of the ranks' partial results."""
+    microseconds per point where the pure-Python group law takes tens -- the add-up of the ranks' partial results.
+    The points must be NORMALISED: the coordinates of a point whose z is neither 0 nor 1 are taken as they stand."""
     cid = CURVE_IDS[curve_type]
     L = lib().kzg_fp_limbs(cid)
-    n = len(points)
-    inf = np.array([1 if int(p[2]) == 0 else 0 for p in points], dtype=np.uint8)
-    coords = []
-    for p, f in zip(points, inf):
-        coords += [0, 0] if f else [int(p[0]), int(p[1])]
-    xy = ints_to_limbs(coords, L).reshape(n, 2 * L) if n else np.zeros((0, 2 * L), dtype=np.uint64)
-    out_xy, out_inf = np.zeros(2 * L, dtype=np.uint64), np.zeros(1, dtype=np.uint8)
-    rc = lib().kzg_g1_sum(cid, _as_vp(np.ascontiguousarray(xy)), _as_vp(inf), n, _as_vp(out_xy), _as_vp(out_inf))
+    xy, inf = points_to_limbs(points, L)
+    out_xy, out_inf, _ = result_buffers(L)
+    rc = lib().kzg_g1_sum(cid, _as_vp(xy), _as_vp(inf), len(inf), _as_vp(out_xy), _as_vp(out_inf))
     if rc != 0:
         raise NativeError(rc, "kzg_g1_sum: a coordinate is not reduced or a point is not on the curve")
     return limbs_to_points(out_xy, out_inf)[0]
@@ -806,6 +775,26 @@ def limbs_to_ints(arr):
         return _pyconv.bytes_to_ints(a.reshape(-1).view(np.uint8), nb)
     raw = a.tobytes()
     return [int.from_bytes(raw[i:i + nb], "little") for i in range(0, len(raw), nb)]
+
+
+def points_to_limbs(points, limbs, normalize=None):
+    """Facade point tuples -> the C layout (xy uint64[n, 2*limbs] C-contiguous, inf uint8[n]); the one place where they
+    become C arrays.  z == 0: flag 1 and zero coordinates; z == 1: the coordinates as given; any other z:
+    normalize(point) when a callable is given (curve.normalize), the coordinates as given when it is None."""
+    points = list(points)
+    inf = np.zeros(len(points), dtype=np.uint8)
+    coords = []
+    for i, pt in enumerate(points):
+        x, y, z = (int(c) for c in pt)
+        if z == 0:
+            inf[i] = 1
+            x = y = 0
+        elif z != 1 and normalize is not None:
+            x, y, z = normalize((x, y, z))
+        coords += [x, y]
+    if not coords:
+        return np.zeros((0, 2 * limbs), dtype=np.uint64), inf
+    return np.ascontiguousarray(ints_to_limbs(coords, limbs).reshape(len(points), 2 * limbs)), inf
 
 
 def limbs_to_points(xy, inf):

@@ -18,12 +18,40 @@ depends on py_ecc's operation order; equality there is `eq`, here plain `==` wor
 too.  There is no CPU fallback for commit/open/setup: they raise
 _native.NativeUnavailable without the shared library and a GPU."""
 from collections.abc import Sequence
+from contextlib import contextmanager
 
 import numpy as np
 
 from . import _native
 from . import curve as _curve
 from .field import GF, Polynomial, PolynomialRing
+
+
+def _lru_get(cache, key, capacity, fresh, make, close):
+    """cache[key], moved to most recently used, when fresh(entry) says it still stands; else make(), stored in its
+    place once close() has released least recently used entries down to capacity - 1.  A stale entry is dropped,
+    not closed: its holder may still use it."""
+    hit = cache.get(key)
+    if hit is not None and fresh(hit):
+        cache[key] = cache.pop(key)                                # most recently used last
+        return hit
+    entry = make()
+    cache.pop(key, None)
+    while len(cache) >= capacity:
+        close(cache.pop(next(iter(cache))))
+    cache[key] = entry
+    return entry
+
+
+@contextmanager
+def _bad_input_is_value_error():
+    """the library's KZG_ERR_ARG (-1: an input it refuses, named in the message) as the facade's ValueError"""
+    try:
+        yield
+    except _native.NativeError as e:
+        if e.code == -1:
+            raise ValueError(str(e)) from e
+        raise
 
 
 class CommitmentKey(Sequence):
@@ -156,30 +184,14 @@ class KZG:
         if isinstance(ck, CommitmentKey):
             return ck
         fp = self._fingerprint(ck)
-        hit = self._loaded.get(id(ck))
-        if hit and hit[1] == fp:
-            self._loaded[id(ck)] = self._loaded.pop(id(ck))       # most recently used last
-            return hit[0]
-        ctx = self._context()
-        L = ctx.fp_limbs
-        n = len(ck)
-        coords, inf = [], np.zeros(n, dtype=np.uint8)
-        for i, pt in enumerate(ck):
-            x, y, z = self._g1.normalize(tuple(int(c) for c in pt))
-            if z == 0:
-                inf[i] = 1
-                x = y = 0
-            coords.append(x)
-            coords.append(y)
-        xy = _native.ints_to_limbs(coords, L).reshape(n, 2 * L)
-        key = CommitmentKey(ctx, ctx.srs_load_g1(np.ascontiguousarray(xy), inf))
-        self._loaded.pop(id(ck), None)
-        while len(self._loaded) >= self._KEY_CACHE:                # evict the least recently used table
-            _, (old, _) = next(iter(self._loaded.items()))
-            del self._loaded[next(iter(self._loaded))]
-            old.srs.close()
-        self._loaded[id(ck)] = (key, fp)
-        return key
+
+        def load():
+            ctx = self._context()
+            xy, inf = _native.points_to_limbs(ck, ctx.fp_limbs, self._g1.normalize)
+            return CommitmentKey(ctx, ctx.srs_load_g1(xy, inf)), fp
+
+        return _lru_get(self._loaded, id(ck), self._KEY_CACHE, lambda e: e[1] == fp, load,
+                        lambda e: e[0].srs.close())[0]
 
     def _coeffs(self, poly):
         """Coefficient ints of a polynomial given as a list, our Polynomial, or any
@@ -215,13 +227,31 @@ class KZG:
 
     _points = staticmethod(_native.limbs_to_points)
 
+    def _canon(self, v):
+        """a scalar argument (z, xi, h: an int or a field element) as its canonical int (kzg.py:144-145)"""
+        return int(self.Fq(v))
+
+    def _tau(self, tau):
+        """the secret of a setup: the one given (reproducible tests), else sampled (kzg.py:67), as an int mod r"""
+        if tau is None:
+            tau = self.Fq.random_element()
+        return int(tau) % self.curve_order
+
+    @staticmethod
+    def _upload(ctx, arr):
+        """A host array of canonical words as an int64 tensor on the context's GPU.  The context runs on its own
+        stream ("stream ordering"), so the device is synchronised before the engine may read it --
+        and whatever else torch had queued, a zero fill of a result tensor say."""
+        import torch
+        d = torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).to(f"cuda:{ctx.device}", non_blocking=False)
+        torch.cuda.synchronize(ctx.device)
+        return d
+
     # ---- the scheme -----------------------------------------------------------------
     def setup(self, max_degree, tau=None):
         """kzg.py:56-78.  `tau` may be supplied for reproducible tests (the reference
         samples it at :67 and discards it; so do we when it is not given)."""
-        if tau is None:
-            tau = self.Fq.random_element()
-        tau = int(tau) % self.curve_order
+        tau = self._tau(tau)
         ctx = self._context()
         srs = ctx.srs_generate(_native.int_to_words(tau), int(max_degree) + 1)      # kzg.py:69-72
         tau_G2 = self.multiply(self.G2, tau)                                         # kzg.py:75
@@ -271,12 +301,8 @@ class KZG:
                 blobs = np.frombuffer(f.read(n * ctx.g1_bytes), dtype=np.uint8)
                 if blobs.size != n * ctx.g1_bytes:
                     raise ValueError("SRS file is shorter than its header says")
-                try:
+                with _bad_input_is_value_error():
                     return CommitmentKey(ctx, ctx.srs_load_g1_compressed(blobs.reshape(n, ctx.g1_bytes), check_subgroup))
-                except _native.NativeError as e:
-                    if e.code == -1:
-                        raise ValueError(str(e)) from e
-                    raise
             xy = np.frombuffer(f.read(n * 2 * L * 8), dtype="<u8").reshape(n, 2 * L).astype(np.uint64)
             inf = np.frombuffer(f.read(n), dtype=np.uint8).copy()
         return CommitmentKey(ctx, ctx.srs_load_g1(np.ascontiguousarray(xy), inf))
@@ -286,12 +312,8 @@ class KZG:
         """points: a list of point tuples, or (xy, inf) arrays in the C layout -> list of bytes objects (48 bytes each
         on bls12_381, ZCash's format; 32 on bn254, gnark's).  A point off the curve raises ValueError."""
         xy, inf = self._g1_arrays(points, "points")
-        try:
+        with _bad_input_is_value_error():
             out = self._context().g1_compress(xy, inf)
-        except _native.NativeError as e:
-            if e.code == -1:
-                raise ValueError(str(e)) from e
-            raise
         return [row.tobytes() for row in out]
 
     def decompress_g1(self, blobs, check_subgroup=True, strict=True):
@@ -345,8 +367,7 @@ class KZG:
         """kzg.py:122-159."""
         key = self._key(ck)
         coeffs = [self._coeffs(p) for p in polynomials]
-        z = int(self.Fq(z))                                                           # kzg.py:144
-        xi = int(self.Fq(xi))                                                         # kzg.py:145
+        z, xi = self._canon(z), self._canon(xi)                                       # kzg.py:144-145
         arr, lens, stride = self._pack(coeffs)
         try:
             xy, inf, _ = self._context().open(key.srs, arr, lens, stride, _native.int_to_words(z),
@@ -437,9 +458,7 @@ class KZG:
         """setup() in the Lagrange basis of {w^i}, i < n: (LagrangeKey [L_i(tau) G1], tau G2).  w defaults to
         Fq.root_of_unity(n), the root of plonk/encoder.py:49."""
         log_n, w = self._domain(n, w)
-        if tau is None:
-            tau = self.Fq.random_element()
-        tau = int(tau) % self.curve_order
+        tau = self._tau(tau)
         ctx = self._context()
         srs = ctx.srs_generate_lagrange(_native.int_to_words(tau), log_n, w)
         return LagrangeKey(ctx, srs, 1 << log_n, w), self.multiply(self.G2, tau)
@@ -470,8 +489,7 @@ class KZG:
         if not isinstance(lk, LagrangeKey):
             raise TypeError("open_evaluations needs a LagrangeKey (setup_lagrange / lagrange_key)")
         vals = self._value_lists(value_lists, lk.n)
-        z = int(self.Fq(z))
-        xi = int(self.Fq(xi))
+        z, xi = self._canon(z), self._canon(xi)
         arr, lens, stride = self._pack(vals)
         xy, inf, _ = self._context().open_evals(lk.srs, arr, lens, stride, _native.int_to_words(z),
                                                 _native.int_to_words(xi))
@@ -493,27 +511,41 @@ class KZG:
                 raise ValueError("w is not a root of unity of power-of-two order")
             log_n, w = self._domain(n, w)
         vals = self._value_lists([values], 1 << log_n)[0]
-        z = int(self.Fq(z))
+        z = self._canon(z)
         if not len(vals):
             return self.Fq(0)
-        import torch
         ctx = self._context()
-        arr = np.ascontiguousarray(vals if isinstance(vals, np.ndarray) else _native.ints_to_limbs(vals))
-        d = torch.from_numpy(arr.view(np.int64)).to(f"cuda:{ctx.device}", non_blocking=False)
-        torch.cuda.synchronize(ctx.device)
+        d = self._upload(ctx, vals if isinstance(vals, np.ndarray) else _native.ints_to_limbs(vals))
         return self.Fq(ctx.eval_lagrange(log_n, w, len(vals), d.data_ptr(), z))
 
     # ---- every proof on a domain at once (FK20: Feist-Khovratovich, "Fast amortized KZG proofs", 2020) -------------
     _DOMAIN_MAX = 1 << 20
 
-    def domain_table(self, ck, n):
-        """The FK20 table of the first n points of a monomial key (CommitmentKey or list of points) for domain size n
-        (a power of two, 2 <= n <= 2^20).  Built on the device; tables of a CommitmentKey are cached per (key, n)."""
-        if isinstance(ck, (LagrangeKey, DomainTable)):
-            raise TypeError("domain_table needs a monomial key (setup / load_key / a list of points)")
+    def _domain_size(self, n):
         n = int(n)
         if n < 2 or n & (n - 1) or n > self._DOMAIN_MAX:
             raise ValueError(f"domain size {n} is not a power of two in [2, 2^20]")
+        return n
+
+    @staticmethod
+    def _monomial_key(ck, who):
+        if isinstance(ck, (LagrangeKey, DomainTable)):
+            raise TypeError(f"{who} needs a monomial key (setup / load_key / a list of points)")
+
+    @staticmethod
+    def _table_n(table, n, l=None):
+        """a given domain size n (None: not given) and coset size l (None: not asked) against a table's: its n"""
+        if n is not None and int(n) != table.n:
+            raise ValueError(f"n = {n} differs from the table's domain size {table.n}")
+        if l is not None and l != table.l:
+            raise ValueError(f"l = {l} differs from the table's coset size {table.l}")
+        return table.n
+
+    def domain_table(self, ck, n):
+        """The FK20 table of the first n points of a monomial key (CommitmentKey or list of points) for domain size n
+        (a power of two, 2 <= n <= 2^20).  Built on the device; tables of a CommitmentKey are cached per (key, n)."""
+        self._monomial_key(ck, "domain_table")
+        n = self._domain_size(n)
         if len(ck) < n:
             raise ValueError(f"commitment key of {len(ck)} points is shorter than the domain ({n})")
         key = self._key(ck)
@@ -522,17 +554,8 @@ class KZG:
             ctx, ctx.domain_table(key.srs, n.bit_length() - 1), n))
 
     def _table_cached(self, key, cache_key, make):
-        hit = self._tables.get(cache_key)
-        if hit and hit[0] is key:
-            self._tables[cache_key] = self._tables.pop(cache_key)           # most recently used last
-            return hit[1]
-        table = make()
-        self._tables.pop(cache_key, None)
-        while len(self._tables) >= self._TABLE_CACHE:
-            old = next(iter(self._tables))
-            self._tables.pop(old)[1].table.close()
-        self._tables[cache_key] = (key, table)
-        return table
+        return _lru_get(self._tables, cache_key, self._TABLE_CACHE, lambda e: e[0] is key, lambda: (key, make()),
+                        lambda e: e[1].table.close())[1]
 
     def _fk20_call(self, who, ck_or_table, polynomials, n, w, l=None, N=None):
         """Host-side checks of open_domain* (l is None) and open_cosets*, `who` in the messages, before any device
@@ -547,18 +570,12 @@ class KZG:
         coeffs = [self._coeffs(p) for p in polynomials]
         longest = max((len(c) for c in coeffs), default=0)
         if isinstance(ck_or_table, DomainTable):
-            if n is not None and int(n) != ck_or_table.n:
-                raise ValueError(f"n = {n} differs from the table's domain size {ck_or_table.n}")
-            if cosets and l != ck_or_table.l:
-                raise ValueError(f"l = {l} differs from the table's coset size {ck_or_table.l}")
-            n = ck_or_table.n
+            n = self._table_n(ck_or_table, n, l)
         elif n is None:
             n = max(2, 2 * l) if cosets else 2
             while n < longest:
                 n *= 2
-        n = int(n)
-        if n < 2 or n & (n - 1) or n > self._DOMAIN_MAX:
-            raise ValueError(f"domain size {n} is not a power of two in [2, 2^20]")
+        n = self._domain_size(n)
         if cosets and l > n // 2:
             raise ValueError(f"coset size {l} exceeds n/2 = {n // 2}")
         if longest > n:
@@ -577,10 +594,8 @@ class KZG:
         arr, lens, stride = self._pack(coeffs)
         length = max(max(lens, default=0), 1)
         import torch
-        dev = f"cuda:{ctx.device}"
-        d_in = torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).to(dev, non_blocking=False)
-        d_comb = torch.zeros((length, 4), dtype=torch.int64, device=dev)
-        torch.cuda.synchronize(ctx.device)
+        d_comb = torch.zeros((length, 4), dtype=torch.int64, device=f"cuda:{ctx.device}")
+        d_in = self._upload(ctx, arr)                     # its synchronise covers the zero fill above as well
         ptrs = [d_in.data_ptr() + j * stride * 32 for j in range(len(coeffs))]
         scalars, x = [], xi
         for _ in coeffs:
@@ -593,7 +608,7 @@ class KZG:
         """open(ck, polynomials, w^i, xi) for every i < n at once: a list of n proofs.  The xi^(j+1) combination runs
         on the device (as in open), then FK20 on the combined polynomial.  w defaults to Fq.root_of_unity(n)."""
         coeffs, n, _, _, w = self._fk20_call("open_domain", ck_or_table, polynomials, n, w)
-        xi = int(self.Fq(xi))
+        xi = self._canon(xi)
         table = ck_or_table if isinstance(ck_or_table, DomainTable) else self.domain_table(ck_or_table, n)
         ctx = self._context()
         d_comb, length = self._combine_on_device(ctx, coeffs, xi)
@@ -624,11 +639,8 @@ class KZG:
     def coset_table(self, ck, n, l):
         """The coset table of the first n points of a monomial key for cosets of l points (powers of two, 2 <= n <=
         2^20, l <= n/2).  Built on the device; cached per (key, n, l) beside domain_table's tables."""
-        if isinstance(ck, (LagrangeKey, DomainTable)):
-            raise TypeError("coset_table needs a monomial key (setup / load_key / a list of points)")
-        n = int(n)
-        if n < 2 or n & (n - 1) or n > self._DOMAIN_MAX:
-            raise ValueError(f"domain size {n} is not a power of two in [2, 2^20]")
+        self._monomial_key(ck, "coset_table")
+        n = self._domain_size(n)
         log_l = self._log2_exact(l, "coset size")
         if (1 << log_l) > n // 2:
             raise ValueError(f"coset size {l} exceeds n/2 = {n // 2}")
@@ -647,7 +659,7 @@ class KZG:
         N/l proofs of the xi^(j+1) combination (combined on the device, as in open_domain).  w defaults to
         Fq.root_of_unity(N), N to n."""
         coeffs, n, l, log_N, w = self._fk20_call("open_cosets", ck_or_table, polynomials, n, w, l, N)
-        xi = int(self.Fq(xi))
+        xi = self._canon(xi)
         table = self._coset_table_for(ck_or_table, n, l)
         ctx = self._context()
         d_comb, length = self._combine_on_device(ctx, coeffs, xi)
@@ -668,11 +680,13 @@ class KZG:
         proofs = [self._points(xy[j], inf[j]) for j in range(len(coeffs))]
         if not with_values:
             return proofs
-        cosets = (1 << log_N) // l
+        return proofs, self._cell_values(ev, len(coeffs), (1 << log_N) // l, l)
+
+    @staticmethod
+    def _cell_values(ev, b, cosets, l):
+        """uint64[b, cosets, l, 4] words -> values[j][i][k], ints"""
         ints = _native.limbs_to_ints(np.ascontiguousarray(ev).reshape(-1, 4))
-        values = [[[ints[(j * cosets + i) * l + k] for k in range(l)] for i in range(cosets)]
-                  for j in range(len(coeffs))]
-        return proofs, values
+        return [[[ints[(j * cosets + i) * l + k] for k in range(l)] for i in range(cosets)] for j in range(b)]
 
     # ---- coset recovery: the polynomial back from any n/l of its N/l cosets (recover_cells_and_kzg_proofs of EIP-7594)
     def _recover_call(self, coset_indices, values, l, n, N, w):
@@ -739,9 +753,7 @@ class KZG:
         if isinstance(ck_or_table, LagrangeKey):
             raise TypeError("recover_cosets_and_open needs a monomial key or a coset table, not a LagrangeKey")
         if isinstance(ck_or_table, DomainTable):
-            if n is not None and int(n) != ck_or_table.n:
-                raise ValueError(f"n = {n} differs from the table's domain size {ck_or_table.n}")
-            n = ck_or_table.n
+            n = self._table_n(ck_or_table, n)
         elif n is None:
             n = int(N) // 2 if N is not None else len(coset_indices) * int(l)
         idx, arr, b, log_n, log_N, log_l, w = self._recover_call(coset_indices, values, l, n, N, w)
@@ -751,17 +763,12 @@ class KZG:
         table = self._coset_table_for(ck_or_table, n, l)
         ctx = self._context()
         import torch
-        dev = f"cuda:{ctx.device}"
-        d_vals = torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).to(dev)
-        d_coeffs = torch.empty((b, n, 4), dtype=torch.int64, device=dev)
-        torch.cuda.synchronize(ctx.device)
+        d_coeffs = torch.empty((b, n, 4), dtype=torch.int64, device=f"cuda:{ctx.device}")
+        d_vals = self._upload(ctx, arr)
         _, ok = ctx.recover_cosets(log_n, log_N, log_l, w, idx, d_vals.data_ptr(), b, d_coeffs=d_coeffs.data_ptr())
         self._first_inconsistent(ok, n)
         xy, inf, ev = ctx.open_cosets(table.table, d_coeffs.data_ptr(), [n] * b, n, log_N, w, device=True, evals=True)
-        proofs = [self._points(xy[j], inf[j]) for j in range(b)]
-        cosets = (1 << log_N) // l
-        ints = _native.limbs_to_ints(np.ascontiguousarray(ev).reshape(-1, 4))
-        return proofs, [[[ints[(j * cosets + i) * l + k] for k in range(l)] for i in range(cosets)] for j in range(b)]
+        return [self._points(xy[j], inf[j]) for j in range(b)], self._cell_values(ev, b, (1 << log_N) // l, l)
 
     def _coset_root(self, l, zeta):
         """zeta for cosets of l points: Fq.root_of_unity(l) by default; a given one must be a primitive l-th root."""
@@ -781,15 +788,14 @@ class KZG:
         """ONE proof for the values of the xi^(j+1) combination at the l points h zeta^k (zeta defaults to
         Fq.root_of_unity(l)): the commitment of (p - rho) / (X^l - h^l), rho = p mod (X^l - h^l).  l = 1 is open() at
         z = h.  with_values: (proof, [combined(h zeta^k) for k < l])."""
-        if isinstance(ck, (LagrangeKey, DomainTable)):
-            raise TypeError("open_coset needs a monomial key (setup / load_key / a list of points)")
+        self._monomial_key(ck, "open_coset")
         log_l, zeta = self._coset_root(l, zeta)
         if log_l > self._COSET_MAX_LOG_L:
             raise ValueError(f"coset size {l} exceeds 2^{self._COSET_MAX_LOG_L}")
-        h = int(self.Fq(h))
+        h = self._canon(h)
         if h == 0:
             raise ValueError("h must be non-zero")
-        xi = int(self.Fq(xi))
+        xi = self._canon(xi)
         coeffs = [self._coeffs(p) for p in polynomials]
         if len(coeffs) > 64:
             raise ValueError("at most 64 polynomials per opening")
@@ -903,20 +909,7 @@ class KZG:
             if inf is not None and inf.size != xy.shape[0]:
                 raise ValueError(f"{what}: {inf.size} infinity flags for {xy.shape[0]} points")
             return xy, inf
-        points = list(points)
-        n = len(points)
-        inf = np.zeros(n, dtype=np.uint8)
-        coords = []
-        for i, pt in enumerate(points):
-            x, y, z = (int(c) for c in pt)
-            if z == 0:
-                inf[i] = 1
-                x = y = 0
-            elif z != 1:
-                x, y, z = self._g1.normalize((x, y, z))
-            coords += [x, y]
-        xy = _native.ints_to_limbs(coords, L).reshape(n, 2 * L) if n else np.zeros((0, 2 * L), dtype=np.uint64)
-        return np.ascontiguousarray(xy), inf
+        return _native.points_to_limbs(points, L, self._g1.normalize)
 
     def verify_cosets(self, ck, rk_l, commitments, commitment_indices, coset_indices, values, proofs, l, N, w=None,
                       r=None, check_subgroup=False):
@@ -930,8 +923,7 @@ class KZG:
         False when one lies outside the prime-order subgroup: for a point T of the cofactor torsion pi + T satisfies
         the pairing equation whenever pi does, so a verifier of untrusted proofs wants it.  The default skips the
         test (as check / batch_check do)."""
-        if isinstance(ck, (LagrangeKey, DomainTable)):
-            raise TypeError("verify_cosets needs a monomial key (setup / load_key / a list of points)")
+        self._monomial_key(ck, "verify_cosets")
         l = 1 << self._log2_exact(l, "coset size")
         N = int(N)
         if N < 2 or N & (N - 1) or N > self._VERIFY_MAX_N:

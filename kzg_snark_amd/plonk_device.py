@@ -95,8 +95,8 @@ class DeviceAlgebra:
 
     def result_buffers(self, k, evals=False):
         """host arrays a pipelined commit of k polynomials (or, with evals, one opening: k = 1) fills by the flush"""
-        out = (np.zeros((k, 2 * self.ctx.fp_limbs), dtype=np.uint64), np.zeros(k, dtype=np.uint8))
-        return out + (np.zeros(4, dtype=np.uint64),) if evals else out
+        out = _native.result_buffers(self.ctx.fp_limbs, (k,), 4 if evals else None)
+        return out if evals else out[:2]
 
     # ---- element-wise
     def op(self, kind, a, b):

@@ -210,3 +210,102 @@ def test_int_marshalling_helper_matches_the_python_forms():
     assert limbs.shape == (1000, 4) and limbs.dtype == np.uint64 and limbs.flags.writeable
     assert _native.limbs_to_ints(limbs) == vals
     assert _native.limbs_to_ints(limbs[::2]) == vals[::2]                                          # non-contiguous input
+
+
+def _mixed_points(name):
+    """infinity, z == 1 points and generator multiples scaled by z = 4 (as test_point_helpers_match_oracle builds one)"""
+    cv = C.CURVES[name]
+    G = C.g1_group(cv)
+    g = (cv.g1[0], cv.g1[1], 1)
+    aff = [G.multiply(g, k) for k in (1, 2, 7, 11, 12345)]
+    scaled = [(p[0] * 4 % cv.p, p[1] * 4 % cv.p, 4) for p in aff[2:]]
+    return G, cv, [aff[0], (1, 1, 0), scaled[0], aff[1], scaled[1], (1, 1, 0), scaled[2], aff[4]]
+
+
+def _restated_limbs(points, limbs):
+    """(x, y, 1) / z == 0 tuples -> the C layout, by int.to_bytes per coordinate"""
+    import numpy as np
+    nb = 8 * limbs
+    raw = b"".join((0 if z == 0 else c).to_bytes(nb, "little") for x, y, z in points for c in (x, y))
+    return (np.frombuffer(raw, dtype="<u8").reshape(len(points), 2 * limbs),
+            np.array([1 if z == 0 else 0 for _, _, z in points], dtype=np.uint8))
+
+
+@pytest.mark.parametrize("name,limbs", [("bn254", 4), ("bls12_381", 6)])
+def test_points_to_limbs_against_a_restatement(name, limbs):
+    """The one statement of "facade tuples -> C layout": z == 0 flagged with zero coordinates, z == 1 as given, any
+    other z through `normalize` when one is given and as given when it is None."""
+    import numpy as np
+    from kzg_snark_amd import _native
+    from kzg_snark_amd.kzg import KZG
+    G, cv, pts = _mixed_points(name)
+    assert (cv.p.bit_length() + 63) // 64 == limbs
+    other_z = [i for i, p in enumerate(pts) if p[2] not in (0, 1)]
+    assert len(other_z) == 3
+
+    xy, inf = _native.points_to_limbs(pts, limbs, G.normalize)
+    want_xy, want_inf = _restated_limbs([G.normalize(p) for p in pts], limbs)
+    assert xy.dtype == np.uint64 and xy.shape == (len(pts), 2 * limbs) and xy.flags.c_contiguous
+    assert inf.dtype == np.uint8 and np.array_equal(inf, want_inf) and inf.sum() == 2
+    assert np.array_equal(xy, want_xy)
+    assert not xy[inf == 1].any()                                  # (1, 1, 0) leaves zero coordinates
+    for i in other_z:                                              # the scaled points are their z == 1 forms
+        assert _native.limbs_to_ints(xy[i].reshape(2, limbs)) == list(G.normalize(pts[i])[:2])
+
+    raw_xy, raw_inf = _native.points_to_limbs(pts, limbs)          # normalize=None: coordinates as given
+    want_raw, _ = _restated_limbs(pts, limbs)
+    assert np.array_equal(raw_xy, want_raw) and np.array_equal(raw_inf, want_inf)
+    for i in other_z:
+        assert _native.limbs_to_ints(raw_xy[i].reshape(2, limbs)) == list(pts[i][:2])
+        assert not np.array_equal(raw_xy[i], xy[i])
+    keep = [i for i in range(len(pts)) if i not in other_z]
+    assert np.array_equal(raw_xy[keep], xy[keep])
+
+    for norm in (None, G.normalize):
+        e_xy, e_inf = _native.points_to_limbs([], limbs, norm)
+        assert e_xy.shape == (0, 2 * limbs) and e_xy.dtype == np.uint64 and e_xy.flags.c_contiguous
+        assert e_inf.shape == (0,) and e_inf.dtype == np.uint8
+
+    # KZG._g1_arrays: the list branch is points_to_limbs with the group's normalize ...
+    kzg = KZG(name)
+    a_xy, a_inf = kzg._g1_arrays(pts, "points")
+    assert np.array_equal(a_xy, xy) and np.array_equal(a_inf, inf) and a_xy.flags.c_contiguous
+    # ... and the array branch hands (xy, inf) on, or names the mismatch
+    b_xy, b_inf = kzg._g1_arrays((xy, inf), "points")
+    assert np.array_equal(b_xy, xy) and np.array_equal(b_inf, inf)
+    assert kzg._g1_arrays((xy, None), "points")[1] is None
+    with pytest.raises(ValueError) as err:
+        kzg._g1_arrays((xy, inf[:-1]), "proofs")
+    assert str(err.value) == f"proofs: {len(pts) - 1} infinity flags for {len(pts)} points"
+
+
+def test_lru_helper_touches_inserts_and_closes_what_it_evicts():
+    """The cache rule of KZG._key and KZG._table_cached at capacity 2: insert a, b; touch a; insert c -> b closed
+    exactly once, a and c kept, a before c."""
+    from kzg_snark_amd.kzg import _lru_get
+
+    class Entry:
+        def __init__(self, name):
+            self.name, self.closed = name, 0
+
+        def close(self):
+            self.closed += 1
+
+    cache, made = {}, []
+
+    def get(name, fresh=True):
+        def make():
+            made.append(name)
+            return Entry(name)
+        return _lru_get(cache, name, 2, lambda e: fresh, make, Entry.close)
+
+    a, b = get("a"), get("b")
+    assert list(cache) == ["a", "b"] and made == ["a", "b"]
+    assert get("a") is a and list(cache) == ["b", "a"] and made == ["a", "b"]          # a touch makes nothing
+    c = get("c")
+    assert list(cache) == ["a", "c"] and cache["a"] is a and cache["c"] is c
+    assert (a.closed, b.closed, c.closed) == (0, 1, 0)
+    # an entry that no longer stands is replaced in place, and is not closed (its holder may still use it)
+    a2 = get("a", fresh=False)
+    assert a2 is not a and list(cache) == ["c", "a"] and cache["a"] is a2
+    assert (a.closed, b.closed, c.closed, a2.closed) == (0, 1, 0, 0)

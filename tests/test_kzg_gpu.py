@@ -112,6 +112,32 @@ def test_commit_with_plain_list_key_duplicates_and_infinity(kzgs, curve):
 
 
 @pytest.mark.parametrize("curve", CURVES)
+def test_commit_with_a_list_key_of_unnormalised_points(kzgs, curve):
+    """A list-form key whose points come with z outside {0, 1}: (x z, y z, z) is the point (x, y, 1), the rule of
+    _native.points_to_limbs that _key, in_subgroup, compress_g1 and verify_cosets share."""
+    cv = O.curve(curve)
+    kzg = kzgs[curve]
+    g = O.from_affine(cv.g1)
+    pts = [O.multiply(g, k, cv) for k in (1, 2, 3, 5)] + [O.Z1()] + [O.multiply(g, k, cv) for k in (8, 13, 21)]
+    flat = []
+    for p in pts:
+        n = O.normalize(p, cv)
+        flat.append((1, 1, 0) if n is None else (n[0], n[1], 1))
+    ck = list(flat)
+    for i, z in ((1, 4), (5, cv.p - 1), (7, 0x123456789abcdef0fedcba9876543211)):
+        x, y, _ = flat[i]
+        ck[i] = (x * z % cv.p, y * z % cv.p, z)
+    assert sum(1 for p in ck if p[2] not in (0, 1)) == 3 and sum(1 for p in ck if p[2] == 0) == 1
+    rng = random.Random(17)
+    polys = [[rng.randrange(cv.r) for _ in range(8)], [1] * 8, [cv.r - 1, 0, 7, 0, 3, 2, 0, 5]]
+    got = kzg.commit(ck, polys)
+    want = O.commit(pts, polys, cv)
+    assert [aff(p) for p in got] == [O.normalize(w, cv) for w in want]
+    assert got == kzg.commit(flat, polys)
+    assert kzg.in_subgroup(ck).all() and kzg.compress_g1(ck) == kzg.compress_g1(flat)
+
+
+@pytest.mark.parametrize("curve", CURVES)
 def test_open_matches_oracle(kzgs, small_keys, curve):
     cv = O.curve(curve)
     kzg = kzgs[curve]
