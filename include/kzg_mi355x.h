@@ -82,7 +82,9 @@ int kzg_ctx_synchronize(kzg_ctx* ctx);
  *   "open_direct_tiles"  tile count up to which every tile sums all tile aggregates above it (default 1024)
  *   "open_domain_chunk"  vectors per chunk of kzg_open_domain*, 1..1024 (default: as many as ~2 GiB of scratch holds)
  *   "open_cosets_chunk"  vectors per chunk of kzg_open_cosets*, 1..1024 (default: as many as ~2 GiB of scratch holds)
- *   "recover_chunk"      vectors per chunk of kzg_recover_cosets*, 1..1024 (default: as many as ~2 GiB of scratch holds) */
+ *   "recover_chunk"      vectors per chunk of kzg_recover_cosets*, 1..1024 (default: as many as ~2 GiB of scratch holds)
+ *   "eval_batch_chunk"   vectors per chunk of kzg_fr_eval_lagrange_batch*, 1..65535, the most one launch indexes
+ *                        (default: as many as ~1 GiB of scratch holds, at most 65535) */
 int kzg_ctx_set_tuning(kzg_ctx* ctx, const char* key, int64_t value);
 
 /* ---- NTT: replaces fft_ff (fft_ff.py:3-37) and ifft_ff (fft_ff.py:39-58) -------------
@@ -327,6 +329,29 @@ int kzg_verify_cosets(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uin
                       const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
                       const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy,
                       const uint8_t* proof_inf, size_t K, const uint64_t rho[4], uint64_t* out_xy, uint8_t* out_inf);
+/* ---- bulk verification at arbitrary points: K single-point claims folded into ONE pairing equation
+ * Claim k < K: the polynomial of commitment C[c_k] takes the value y_k at z_k -- ANY element of Fr, what kzg_open,
+ * kzg_open_evals and an EIP-4844 blob proof open at -- with proof pi_k.  With weights r_k = rho^(k+1) (the rule of
+ * kzg_verify_cosets and the facade's batch_check):
+ *     L = sum_j (sum_(k: c_k = j) r_k) C[j]  -  (sum_k r_k y_k) G1  +  sum_k (r_k z_k) pi_k
+ *     R = sum_k r_k pi_k
+ * and every claim holds (up to the soundness error of the random combination) iff e(L, G2) = e(R, [tau] G2).  G1 is
+ * the curve's generator, the point a generated key starts with: the call takes no key.  out_xy / out_inf: L, then R,
+ * kzg_verify_cosets' output format; the caller does the two pairings.  This is the fold of
+ * verify_blob_kzg_proof_batch (EIP-4844) once the blobs' values y_k are known (kzg_fr_eval_lagrange_batch).
+ *   comm_xy / comm_inf   n_comm commitments (1 <= n_comm <= 2^16), comm_idx[k] = c_k < n_comm
+ *   z, y       [K][4] canonical limbs each, reduced by the caller;  proof_xy / proof_inf: the K proofs
+ * K <= 2^21; K = 0 is KZG_OK with both points at infinity.  KZG_ERR_ARG, before any scalar multiplication runs: a
+ * size or an index out of range, a proof or commitment with a coordinate >= p or off the curve (kzg_verify_cosets'
+ * rule).  Membership in the prime-order subgroup is not part of this call (kzg_g1_check_subgroup; the facade's
+ * verify_points / verify_blobs with check_subgroup=True).
+ * Every (point, scalar) pair is one lane of one kernel: a 4-bit fixed-window ladder over a per-lane table of the
+ * point's multiples, the lanes of a workgroup summed in LDS, the workgroups' partial points by a second kernel.  The
+ * call does NOT use the commit pipeline: results of kzg_commit_device_async / kzg_open_device_async still pending are
+ * neither retired nor disturbed.  Host pointers in, host results out; synchronises the context's stream. */
+int kzg_verify_points(kzg_ctx* ctx, const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm,
+                      const uint32_t* comm_idx, const uint64_t* z, const uint64_t* y, const uint64_t* proof_xy,
+                      const uint8_t* proof_inf, size_t K, const uint64_t rho[4], uint64_t* out_xy, uint8_t* out_inf);
 /* ---- coset recovery: b polynomials of degree < n back from their values on any K >= n/l cosets ------------------
  * The domain {w^t, t < N}, N = 2^log_N, has C = N/l cosets of l = 2^log_l points in kzg_open_cosets' numbering
  * (coset i = {w^(i + k C), k < l}, the roots of X^l - u^i, u = w^l).  K distinct cosets are given, M are missing:
@@ -435,6 +460,23 @@ int kzg_fr_poly_eval(kzg_ctx* ctx, size_t n, const void* d_a, const uint64_t z[4
  * KZG_ERR_DEGREE) at z, z in H included: p(z) of the interpolant.  Device-resident values; synchronises. */
 int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size_t len, const void* d_vals,
                          const uint64_t z[4], uint64_t out[4]);
+/* The same for b value vectors over ONE domain, vector j at its own point z_j (z_j in H included): out[j] is
+ * kzg_fr_eval_lagrange's result for vector j and z_j -- the claimed values of a batch of blobs at their challenges.
+ *   vals   [b][stride][4] canonical limbs, vector j holds lens[j] <= 2^log_n values (missing ones zero)
+ *   z, out [b][4] canonical limbs (z reduced by the caller)
+ * KZG_ERR_DEGREE for a lens[j] above 2^log_n; KZG_ERR_ARG for lens[j] > stride, log_n outside [1, 24] or a w that is
+ * not a primitive 2^log_n-th root.  b = 0 is KZG_OK with no work.  The launch count does not depend on b: per chunk
+ * of vectors (tuning key "eval_batch_chunk") the denominators z_j - w^i of the whole block, one batch inversion, one
+ * reduction pass and one finishing kernel that forms (z_j^n - 1)/n on the device.  The host form takes host pointers
+ * and synchronises; the _device form takes device pointers (32-byte aligned), enqueues on the context's stream and
+ * does not wait for its own work.  It is not free of host waits: the lengths travel through one pinned array of the
+ * context, so a call first waits until the PREVIOUS call's copy of its lengths has left that array (and with it for
+ * whatever was queued on the stream before that copy), and a call that needs more scratch than any before it
+ * reallocates, which synchronises the device. */
+int kzg_fr_eval_lagrange_batch(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], const uint64_t* vals,
+                               const size_t* lens, size_t b, size_t stride, const uint64_t* z, uint64_t* out);
+int kzg_fr_eval_lagrange_batch_device(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], const void* d_vals,
+                                      const size_t* lens, size_t b, size_t stride, const void* d_z, void* d_out);
 /* ---- measurement hooks (bench.py) -----------------------------------------------------------
  * When enabled, the library brackets its kernels with HIP events on the stream each one runs on.
  * Span names: "ntt_pass", "msm_partition1", "msm_partition2", "msm_order", "msm_accumulate",
@@ -447,13 +489,15 @@ int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size
  * the context's stream; its MSMs also report under the msm_* names), "recover_cosets" (ONE per kzg_recover_cosets*:
  * the product tree and every chunk), "g1_decompress" (ONE per kzg_g1_decompress*, and one per
  * kzg_srs_load_g1_compressed: the decoding, with the subgroup test when asked for), "g1_subgroup" (ONE per
- * kzg_g1_check_subgroup).  kzg_prof_read synchronises the
+ * kzg_g1_check_subgroup), "verify_points" (ONE per kzg_verify_points: the whole call), "eval_lagrange_batch" (ONE per
+ * kzg_fr_eval_lagrange_batch*: every chunk).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.
  * Two names are not spans: "msm_accumulate_shader_mhz" and "ntt_pass_shader_mhz" return (in *total_ms) the shader
  * clock in MHz the accumulate / NTT kernel ran at since the last reset -- s_memtime over s_memrealtime ticks of its
  * first wave -- and *count = 1 when a launch has reported, 0 otherwise; "ntt_tile_log" returns log2 of the LDS
  * tile the last two-pass transform took; "verify_device_bytes" the bytes of device memory the last kzg_verify_cosets
- * asked for (commit-pipeline slots not included); "recover_leaf" the number of linear factors one leaf of
+ * asked for (commit-pipeline slots not included); "verify_points_device_bytes" the bytes the last kzg_verify_points
+ * carved out of its scratch buffer; "recover_leaf" the number of linear factors one leaf of
  * kzg_recover_cosets' product tree multiplies out; "msm_accumulate_tail_us" and "msm_accumulate_exit_spread_us"
  * return, in microseconds averaged over the *count accumulate launches since the last reset, how long after the
  * MEAN exit of its waves the last wave of a launch left (the time its SIMDs stand half empty or idle) and how long

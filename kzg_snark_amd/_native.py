@@ -102,6 +102,12 @@ SIGNATURES = {
                                              _vp, _vp, _vp, _vp, _vp, _vp]),
     "kzg_verify_cosets": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_size_t,
                                          _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "kzg_verify_points": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp,
+                                         _vp, _vp]),
+    "kzg_fr_eval_lagrange_batch": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_size_t,
+                                                  ctypes.c_size_t, _vp, _vp]),
+    "kzg_fr_eval_lagrange_batch_device": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_size_t,
+                                                         ctypes.c_size_t, _vp, _vp]),
     "kzg_recover_cosets": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
                                           ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
     "kzg_g1_compress": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
@@ -430,6 +436,27 @@ class Context:
         self._check(lib().kzg_fr_eval_lagrange(self._h, int(log_n), _fr(w), n, _as_vp(d_vals), _fr(z), _as_vp(out)))
         return int.from_bytes(out.tobytes(), "little")
 
+    def eval_lagrange_batch(self, log_n, w, vals, lens, stride, z, d_out=None):
+        """p_j(z_j) of the interpolants of len(lens) value vectors over {w^i}, vector j at its own point.  Host form
+        (d_out None): vals uint64[b, stride, 4], z uint64[b, 4] -> uint64[b, 4].  Device form: vals, z and d_out are
+        device pointers (32-byte aligned); enqueued on the context's stream without waiting for the call's own work
+        (the host may wait for the previous call's copy of its lengths), returns None."""
+        lens_a = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+        b = lens_a.size
+        if d_out is not None:
+            self._check(lib().kzg_fr_eval_lagrange_batch_device(self._h, int(log_n), _fr(w), _as_vp(vals),
+                                                                _as_vp(lens_a), b, int(stride), _as_vp(z),
+                                                                _as_vp(d_out)))
+            return None
+        vals = np.ascontiguousarray(vals, dtype=np.uint64)
+        z = np.ascontiguousarray(z, dtype=np.uint64)
+        if vals.size != b * int(stride) * 4 or z.size != b * 4:
+            raise ValueError("eval_lagrange_batch: vals is not [b][stride][4] or z is not [b][4]")
+        out = np.zeros((b, 4), dtype=np.uint64)
+        self._check(lib().kzg_fr_eval_lagrange_batch(self._h, int(log_n), _fr(w), _as_vp(vals), _as_vp(lens_a), b,
+                                                     int(stride), _as_vp(z), _as_vp(out)))
+        return out
+
     # ---- every proof on a domain (FK20)
     def domain_table(self, monomial, log_n):
         """The FK20 table of the first 2^log_n points of a monomial key."""
@@ -502,6 +529,28 @@ class Context:
                                             _as_vp(out_xy), _as_vp(out_inf)))
         # the library retires every pipeline slot before it returns, as kzg_commit_flush does
         self._inflight.clear()
+        return out_xy, out_inf
+
+    def verify_points(self, comm_xy, comm_inf, comm_idx, z, y, proof_xy, proof_inf, rho):
+        """The two G1 points (L, R) of the rho-weighted combination of K claims at arbitrary points: (xy
+        uint64[2, 2*fp_limbs], inf uint8[2]); the claims hold iff e(L, G2) = e(R, [tau] G2).  comm_xy
+        uint64[n_comm, 2*fp_limbs] with comm_inf uint8[n_comm] or None; comm_idx uint32[K]; z, y uint64[K, 4];
+        proof_xy uint64[K, 2*fp_limbs] with proof_inf uint8[K] or None.  Pending pipeline results stay pending."""
+        P = 2 * self.fp_limbs
+        comm_idx = np.ascontiguousarray(comm_idx, dtype=np.uint32).reshape(-1)
+        K = comm_idx.size
+        comm_xy = np.ascontiguousarray(comm_xy, dtype=np.uint64).reshape(-1, P)
+        proof_xy = np.ascontiguousarray(proof_xy, dtype=np.uint64).reshape(-1, P)
+        z = np.ascontiguousarray(z, dtype=np.uint64)
+        y = np.ascontiguousarray(y, dtype=np.uint64)
+        if proof_xy.shape[0] != K or z.size != K * 4 or y.size != K * 4:
+            raise ValueError("verify_points: comm_idx, z, y and proofs describe different numbers of claims")
+        comm_inf = _inf_arg(comm_inf, comm_xy.shape[0], "verify_points: comm_inf and comm_xy")
+        proof_inf = _inf_arg(proof_inf, K, "verify_points: proof_inf and proof_xy")
+        out_xy, out_inf, _ = result_buffers(self.fp_limbs, (2,))
+        self._check(lib().kzg_verify_points(self._h, _as_vp(comm_xy), _as_vp(comm_inf), comm_xy.shape[0],
+                                            _as_vp(comm_idx), _as_vp(z), _as_vp(y), _as_vp(proof_xy),
+                                            _as_vp(proof_inf), K, _fr(rho), _as_vp(out_xy), _as_vp(out_inf)))
         return out_xy, out_inf
 
     # ---- coset recovery

@@ -161,9 +161,12 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
   ntt_free_domains(c);
   msm_free_work(c);
   for (DevBuf* b : {&c->ntt_scratch, &c->io, &c->scan_tmp, &c->lagr_tmp, &c->dom_tmp, &c->ver_tmp, &c->rec_tmp,
+                    &c->vpt_tmp,
                     &c->poly_tmp[0], &c->poly_tmp[1], &c->poly_tmp[2], &c->poly_tmp[3]})
     hipFree(b->p);
   hipFree(c->clk_probe);
+  if (c->eval_lens_pin) hipHostFree(c->eval_lens_pin);
+  if (c->eval_lens_ev) hipEventDestroy(c->eval_lens_ev);
   for (auto s : c->aux_streams) hipStreamDestroy(s);
   for (auto e : c->aux_events) hipEventDestroy(e);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -222,6 +225,9 @@ int kzg_ctx_set_tuning(kzg_ctx* ctx, const char* key, int64_t value) {
   } else if (k == "recover_chunk") {
     if (value < 0 || value > 1024) return set_err(c, KZG_ERR_ARG, "recover_chunk: 0 .. 1024");
     c->tune_recover_chunk = (int)value;
+  } else if (k == "eval_batch_chunk") {
+    if (value < 0 || value > 65535) return set_err(c, KZG_ERR_ARG, "eval_batch_chunk: 0 .. 65535");
+    c->tune_eval_batch_chunk = (int)value;
   } else {
     return set_err(c, KZG_ERR_ARG, "kzg_ctx_set_tuning: unknown key");
   }
@@ -664,6 +670,14 @@ int kzg_verify_cosets(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uin
                        out_xy, out_inf);
 }
 
+int kzg_verify_points(kzg_ctx* ctx, const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm,
+                      const uint32_t* comm_idx, const uint64_t* z, const uint64_t* y, const uint64_t* proof_xy,
+                      const uint8_t* proof_inf, size_t K, const uint64_t rho[4], uint64_t* out_xy, uint8_t* out_inf) {
+  KZG_ENTER(!rho || !out_xy || !out_inf || !comm_xy || (K && (!comm_idx || !z || !y || !proof_xy)));
+  return verify_points(c, comm_xy, comm_inf, n_comm, comm_idx, z, y, proof_xy, proof_inf, K,
+                       reinterpret_cast<const uint32_t*>(rho), out_xy, out_inf);
+}
+
 int kzg_recover_cosets(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
                        const uint32_t* coset_idx, size_t K, const uint64_t* values, size_t b, uint64_t* out_coeffs,
                        uint8_t* out_consistent) {
@@ -733,6 +747,34 @@ int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size
                           reinterpret_cast<const uint32_t*>(z), out);
 }
 
+int kzg_fr_eval_lagrange_batch_device(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], const void* d_vals,
+                                      const size_t* lens, size_t b, size_t stride, const void* d_z, void* d_out) {
+  KZG_ENTER(false);
+  if (!w || (b && (!d_vals || !lens || !d_z || !d_out))) return KZG_ERR_ARG;
+  return fr_eval_lagrange_batch(c, log_n, reinterpret_cast<const uint32_t*>(w), static_cast<const uint32_t*>(d_vals),
+                                lens, b, stride, static_cast<const uint32_t*>(d_z), static_cast<uint32_t*>(d_out));
+}
+
+int kzg_fr_eval_lagrange_batch(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], const uint64_t* vals,
+                               const size_t* lens, size_t b, size_t stride, const uint64_t* z, uint64_t* out) {
+  KZG_ENTER(false);
+  if (!w || (b && (!vals || !lens || !z || !out))) return KZG_ERR_ARG;
+  if (b == 0) return KZG_OK;
+  if (stride == 0 || b > ((size_t)1 << 40) / stride) return set_err(c, KZG_ERR_ARG, "kzg_fr_eval_lagrange_batch: b * stride too large");
+  // staged as [values | points | results]
+  const size_t vb = b * stride * 32, zb = b * 32;
+  int rc = ensure_buf(c, c->io, vb + 2 * zb);
+  if (rc) return rc;
+  char* d = static_cast<char*>(c->io.p);
+  KZG_HIP(c, hipMemcpyAsync(d, vals, vb, hipMemcpyHostToDevice, c->stream));
+  KZG_HIP(c, hipMemcpyAsync(d + vb, z, zb, hipMemcpyHostToDevice, c->stream));
+  rc = kzg_fr_eval_lagrange_batch_device(ctx, log_n, w, d, lens, b, stride, d + vb, d + vb + zb);
+  if (rc) return rc;
+  KZG_HIP(c, hipMemcpyAsync(out, d + vb + zb, zb, hipMemcpyDeviceToHost, c->stream));
+  KZG_HIP(c, hipStreamSynchronize(c->stream));
+  return KZG_OK;
+}
+
 int kzg_prof_enable(kzg_ctx* ctx, int on) {
   if (!ctx) return KZG_ERR_ARG;
   Ctx* c = &ctx->c;
@@ -768,6 +810,11 @@ int kzg_prof_read(kzg_ctx* ctx, const char* name, double* total_ms, uint64_t* co
   if (std::string(name) == "verify_device_bytes") {   // not a span: device memory the last kzg_verify_cosets asked for
     *total_ms = (double)c->ver_last_bytes;
     *count = c->ver_last_bytes ? 1 : 0;
+    return KZG_OK;
+  }
+  if (std::string(name) == "verify_points_device_bytes") {   // not a span: what the last kzg_verify_points carved out
+    *total_ms = (double)c->vpt_last_bytes;
+    *count = c->vpt_last_bytes ? 1 : 0;
     return KZG_OK;
   }
   if (std::string(name) == "recover_leaf") {   // not a span: linear factors per leaf of kzg_recover_cosets' product tree

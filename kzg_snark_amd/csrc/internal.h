@@ -1,6 +1,6 @@
 // internal.h -- library-private declarations shared by the translation units of
 // libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, msm_prep.hip, poly.hip, lagrange.hip, domain.hip, verify.hip,
-// recover.hip, g1_bytes.hip): the context, error and profiling plumbing, the dispatch by curve (KZG_BY_CURVE,
+// recover.hip, g1_bytes.hip, verify_points.hip): the context, error and profiling plumbing, the dispatch by curve (KZG_BY_CURVE,
 // KZG_BY_FR) and the entry points of ntt.hip and poly.hip.  Shared device helpers live in fr_util.h (one Fr element,
 // the power-table lookup), g1_util.h (word arrays, XYZZ points), g1_words.h (point <-> canonical words) and
 // srs_rec.h (key records).
@@ -79,8 +79,15 @@ struct Ctx {
   DevBuf dom_tmp;         // domain.hip: G1 transform buffers and the Fr vectors of one chunk of kzg_open_domain
   DevBuf ver_tmp;         // verify.hip: staged claims, proof records, weights, power tables, partial sums
   DevBuf rec_tmp;         // recover.hip: power tables, the product tree, Z and its inverses, one chunk of vectors
+  DevBuf vpt_tmp;         // verify_points.hip: staged claims, weights, power table, partial sums and partial points
   size_t ver_last_bytes = 0;              // what the last kzg_verify_cosets carved out of ver_tmp (kzg_prof_read)
+  size_t vpt_last_bytes = 0;              // what the last kzg_verify_points carved out of vpt_tmp (kzg_prof_read)
   uint32_t ver_lds_attr_set = 0;          // per ver_cell_kernel instantiation, as ntt_lds_attr_set
+  // kzg_fr_eval_lagrange_batch*: the vector lengths travel from this pinned array; the event marks the last copy out
+  // of it, waited for before the array is rewritten (the caller's own array need not outlive the call)
+  uint32_t* eval_lens_pin = nullptr;
+  size_t eval_lens_cap = 0;
+  hipEvent_t eval_lens_ev = nullptr;
   size_t open_shard_n = 0;                // slice length between kzg_open_shard_begin / _finish
   uint32_t open_shard_tb = 0;             // tile width the slice's aggregates were formed with
   // kzg_ctx_set_tuning: 0 = the library's own choice
@@ -90,6 +97,7 @@ struct Ctx {
   int tune_open_domain_chunk = 0;         // vectors per chunk of kzg_open_domain
   int tune_open_cosets_chunk = 0;         // vectors per chunk of kzg_open_cosets
   int tune_recover_chunk = 0;             // vectors per chunk of kzg_recover_cosets
+  int tune_eval_batch_chunk = 0;          // vectors per chunk of kzg_fr_eval_lagrange_batch
   int last_ntt_tile_log = 0;              // what the last transform used (kzg_prof_read "ntt_tile_log")
   void* msm_work = nullptr;               // MsmWork (msm.hip)
   bool prof_on = false;

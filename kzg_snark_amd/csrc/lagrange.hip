@@ -191,6 +191,90 @@ __global__ __launch_bounds__(256) void lagr_quotient_kernel(uint32_t n, const ui
   store_words<F>(q + (size_t)i * 8, r);
 }
 
+// ---- batched evaluation: b vectors over one domain, vector j at its own point ------------------------------------
+
+constexpr uint32_t BATCH_MAXG = 32;   // workgroups per vector of the batched reduction pass
+
+// d[j n + i] = z_j - w^i over the whole block of cb vectors (z_j canonical words, standard form)
+template <class F>
+__global__ __launch_bounds__(256) void lagr_batch_denom_kernel(uint32_t log_n, size_t total, const uint32_t* wpow,
+                                                               const uint32_t* z, uint32_t* d) {
+  using Fd = Field<F>;
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const size_t j = e >> log_n, i = e & (((size_t)1 << log_n) - 1);
+  store_words<F>(d + e * 8, Fd::sub(load_words<F>(z + j * 8), load_words<F>(wpow + i * 8)));
+}
+
+// lagr_sums_kernel with the vector index in the grid (blockIdx.y), without T (only the quotient needs it):
+// part[j][g] = [S | E] of workgroup g over vector j, Montgomery limbs
+template <class F>
+__global__ __launch_bounds__(SUM_TB) void lagr_batch_sums_kernel(uint32_t n, size_t stride, const uint32_t* lens,
+                                                                 const uint32_t* vals, const uint32_t* wpow,
+                                                                 const uint32_t* inv, uint32_t* part) {
+  using Fd = Field<F>;
+  __shared__ uint32_t red[SUM_TB / 64][2 * LG_FRN];
+  const uint32_t j = blockIdx.y, plen = lens[j];
+  const uint32_t* P = vals + (size_t)j * stride * 8;
+  const uint32_t* iv_j = inv + (size_t)j * n * 8;
+  Fe<F> S = Fd::zero(), E = Fd::zero();
+  const uint32_t step = gridDim.x * blockDim.x;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < plen; i += step) {    // P_i = 0 from plen on
+    const Fe<F> iv = load_words<F>(iv_j + (size_t)i * 8);
+    const Fe<F> p = Fd::to_mont(load_words<F>(P + (size_t)i * 8));
+    if (Fd::is_zero(iv)) {
+      E = Fd::add(E, p);
+    } else {
+      const Fe<F> u = Fd::mul(Fd::to_mont(load_words<F>(wpow + (size_t)i * 8)), Fd::to_mont(iv));
+      S = Fd::add(S, Fd::mul(p, u));
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    S = Fd::add(S, shfl_xor_fe<F>(S, m));
+    E = Fd::add(E, shfl_xor_fe<F>(E, m));
+  }
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    store_limbs<F>(&red[wave][0], S);
+    store_limbs<F>(&red[wave][LG_FRN], E);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (uint32_t q = 1; q < SUM_TB / 64; ++q) {
+      S = Fd::add(S, load_limbs<F>(&red[q][0]));
+      E = Fd::add(E, load_limbs<F>(&red[q][LG_FRN]));
+    }
+    uint32_t* o = part + ((size_t)j * gridDim.x + blockIdx.x) * 2 * LG_FRN;
+    store_limbs<F>(o, S);
+    store_limbs<F>(o + LG_FRN, E);
+  }
+}
+
+// One wave per vector: out[j] = (z_j^n - 1)/n * S + E, canonical words; ninv = n^-1 (Montgomery)
+template <class F>
+__global__ __launch_bounds__(64) void lagr_batch_value_kernel(uint32_t log_n, uint32_t groups, const uint32_t* part,
+                                                              const uint32_t* z, FrArg ninv, uint32_t* out) {
+  using Fd = Field<F>;
+  const uint32_t j = blockIdx.x;
+  Fe<F> S = Fd::zero(), E = Fd::zero();
+  for (uint32_t g = threadIdx.x; g < groups; g += 64) {
+    const uint32_t* q = part + ((size_t)j * groups + g) * 2 * LG_FRN;
+    S = Fd::add(S, load_limbs<F>(q));
+    E = Fd::add(E, load_limbs<F>(q + LG_FRN));
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    S = Fd::add(S, shfl_xor_fe<F>(S, m));
+    E = Fd::add(E, shfl_xor_fe<F>(E, m));
+  }
+  if (threadIdx.x != 0) return;
+  Fe<F> zn = Fd::to_mont(load_words<F>(z + (size_t)j * 8));
+  for (uint32_t q = 0; q < log_n; ++q) zn = Fd::sqr(zn);
+  const Fe<F> cz = Fd::mul(Fd::sub(zn, Fd::one()), arg_fe<F>(ninv));
+  store_words<F>(out + (size_t)j * 8, Fd::from_mont(Fd::reduce(Fd::add(Fd::mul(cz, S), E))));
+}
+
 // ---- G1 inverse NTT -------------------------------------------------------------------------------
 
 // buf[bitrev(i)] = record i of window 0
@@ -428,6 +512,68 @@ int fr_eval_lagrange_t(Ctx* c, uint32_t log_n, const uint32_t* w_words, size_t l
   return KZG_OK;
 }
 
+constexpr size_t BATCH_SCRATCH_BYTES = (size_t)1 << 30;   // denominators and inverses of one chunk of vectors
+constexpr size_t BATCH_MAX_CHUNK = 65535;                 // the vector index is blockIdx.y
+
+template <class F>
+int fr_eval_lagrange_batch_t(Ctx* c, uint32_t log_n, const uint32_t* w_words, const uint32_t* d_vals,
+                             const size_t* lens, size_t b, size_t stride, const uint32_t* d_z, uint32_t* d_out) {
+  if (log_n < 1 || log_n > LG_MAX_LOG)
+    return set_err(c, KZG_ERR_ARG, "kzg_fr_eval_lagrange_batch: log_n must be in [1, 24]");
+  if (!primitive_root<F>(mont_from_words<F>(w_words), log_n))
+    return set_err(c, KZG_ERR_ARG, "kzg_fr_eval_lagrange_batch: w is not a primitive root");
+  const size_t n = (size_t)1 << log_n;
+  for (size_t j = 0; j < b; ++j) {
+    if (lens[j] > n) return set_err(c, KZG_ERR_DEGREE, "value vector longer than the domain");
+    if (lens[j] > stride) return set_err(c, KZG_ERR_ARG, "kzg_fr_eval_lagrange_batch: lens[j] > stride");
+  }
+  if (b == 0) return KZG_OK;
+  if (((reinterpret_cast<uintptr_t>(d_vals) | reinterpret_cast<uintptr_t>(d_z) | reinterpret_cast<uintptr_t>(d_out)) & 31u))
+    return set_err(c, KZG_ERR_ARG, "kzg_fr_eval_lagrange_batch: misaligned device pointer");
+  size_t chunk = c->tune_eval_batch_chunk > 0 ? (size_t)c->tune_eval_batch_chunk
+                                              : std::max<size_t>(1, BATCH_SCRATCH_BYTES / (n * 64));
+  chunk = std::min<size_t>({chunk, b, BATCH_MAX_CHUNK});
+  const uint32_t groups = std::min<uint32_t>(BATCH_MAXG, (uint32_t)((n + SUM_TB - 1) / SUM_TB));
+  // [w^i: n | den: chunk n | inv: chunk n | partial sums | lens: b]
+  const size_t part_bytes = (chunk * groups * 2 * LG_FRN * 4 + 31) / 32 * 32;
+  int rc = ensure_buf(c, c->lagr_tmp, n * 32 + chunk * n * 64 + part_bytes + b * 4);
+  if (rc) return rc;
+  uint32_t* d_wpow = static_cast<uint32_t*>(c->lagr_tmp.p);
+  uint32_t* d_den = d_wpow + n * 8;
+  uint32_t* d_inv = d_den + chunk * n * 8;
+  uint32_t* d_part = d_inv + chunk * n * 8;
+  uint32_t* d_lens = d_part + part_bytes / 4;
+  // the lengths: through the context's pinned array (an earlier call's copy out of it has to be over first)
+  if (c->eval_lens_ev) KZG_HIP(c, hipEventSynchronize(c->eval_lens_ev));
+  else KZG_HIP(c, hipEventCreateWithFlags(&c->eval_lens_ev, hipEventDisableTiming));
+  if (c->eval_lens_cap < b) {
+    if (c->eval_lens_pin) KZG_HIP(c, hipHostFree(c->eval_lens_pin));
+    c->eval_lens_pin = nullptr;
+    c->eval_lens_cap = 0;
+    KZG_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->eval_lens_pin), b * 4, hipHostMallocDefault));
+    c->eval_lens_cap = b;
+  }
+  for (size_t j = 0; j < b; ++j) c->eval_lens_pin[j] = (uint32_t)lens[j];
+  ProfScope ps(c, "eval_lagrange_batch");
+  KZG_HIP(c, hipMemcpyAsync(d_lens, c->eval_lens_pin, b * 4, hipMemcpyHostToDevice, c->stream));
+  KZG_HIP(c, hipEventRecord(c->eval_lens_ev, c->stream));
+  if ((rc = launch_wpow<F>(c, (uint32_t)n, w_words, d_wpow))) return rc;
+  const FrArg ninv = fr_arg<F>(Field<F>::reduce(inv_pow2<F>(log_n)));
+  for (size_t j0 = 0; j0 < b; j0 += chunk) {
+    const size_t cb = std::min(chunk, b - j0), total = cb * n;
+    hipLaunchKernelGGL(lagr_batch_denom_kernel<F>, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, c->stream, log_n,
+                       total, d_wpow, d_z + j0 * 8, d_den);
+    KZG_HIP(c, hipGetLastError());
+    if ((rc = fr_vec_inverse(c, total, d_den, d_inv))) return rc;
+    hipLaunchKernelGGL(lagr_batch_sums_kernel<F>, dim3(groups, (uint32_t)cb), dim3(SUM_TB), 0, c->stream, (uint32_t)n,
+                       stride, d_lens + j0, d_vals + j0 * stride * 8, d_wpow, d_inv, d_part);
+    hipLaunchKernelGGL(lagr_batch_value_kernel<F>, dim3((uint32_t)cb), dim3(64), 0, c->stream, log_n, groups, d_part,
+                       d_z + j0 * 8, ninv, d_out + j0 * 8);
+    KZG_HIP(c, hipGetLastError());
+  }
+  return KZG_OK;
+}
+
 }  // namespace
 
 int fr_pow_table(Ctx* c, const FrArg& base, uint32_t* d_tab) { return KZG_BY_FR(c, pow_table_t, c, base, d_tab); }
@@ -445,6 +591,10 @@ int open_evals_device(Ctx* c, const Srs* s, const uint32_t* d_vals, const size_t
 int fr_eval_lagrange(Ctx* c, uint32_t log_n, const uint32_t* w_words, size_t len, const uint32_t* d_vals,
                      const uint32_t* z_words, uint64_t* out) {
   return KZG_BY_FR(c, fr_eval_lagrange_t, c, log_n, w_words, len, d_vals, z_words, out);
+}
+int fr_eval_lagrange_batch(Ctx* c, uint32_t log_n, const uint32_t* w_words, const uint32_t* d_vals, const size_t* lens,
+                           size_t b, size_t stride, const uint32_t* d_z, uint32_t* d_out) {
+  return KZG_BY_FR(c, fr_eval_lagrange_batch_t, c, log_n, w_words, d_vals, lens, b, stride, d_z, d_out);
 }
 
 }  // namespace kzg

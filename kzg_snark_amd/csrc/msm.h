@@ -56,6 +56,11 @@ int open_evals_device(Ctx* c, const Srs* s, const uint32_t* d_vals, const size_t
                       uint64_t* eval_out, bool sync);
 int fr_eval_lagrange(Ctx* c, uint32_t log_n, const uint32_t* w_words, size_t len, const uint32_t* d_vals,
                      const uint32_t* z_words, uint64_t* out);
+// b vectors over one domain, vector j (lens[j] values at d_vals + j * stride elements) at its own point d_z[j]:
+// d_out[j] = fr_eval_lagrange's result.  Device pointers; a fixed number of launches per chunk, no wait for the call's
+// own work (the host may wait for the previous call's copy of its lengths, and for a reallocation of the scratch).
+int fr_eval_lagrange_batch(Ctx* c, uint32_t log_n, const uint32_t* w_words, const uint32_t* d_vals, const size_t* lens,
+                           size_t b, size_t stride, const uint32_t* d_z, uint32_t* d_out);
 
 // domain.hip: the radix-2 G1 transform in XYZZ, in place, one launch per level: `nvec` vectors of 2^log_len points
 // (vector j at point j << log_len), bit-reversed in, natural out, unscaled; root a primitive 2^log_len-th root of
@@ -108,6 +113,26 @@ int verify_cosets(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const
                   const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
                   const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy, const uint8_t* proof_inf,
                   size_t K, const uint32_t* rho_words, uint64_t* out_xy, uint8_t* out_inf);
+
+// verify.hip: d_coef[j] = sum of d_r[d_perm[q]], q in [d_off[j], d_off[j + 1]): the per-commitment sums of the weights
+// over the cells grouped by commitment.  d_cpart: n_comm * ver_commsum_shares(n_comm) elements of scratch.  Two launches.
+__attribute__((visibility("hidden")))   // library-private: not in the exported symbol list
+size_t ver_commsum_shares(size_t n_comm);
+__attribute__((visibility("hidden")))   // library-private: not in the exported symbol list
+int ver_commitment_sums(Ctx* c, const uint32_t* d_r, const uint32_t* d_perm, const uint32_t* d_off, size_t n_comm,
+                        uint32_t* d_cpart, uint32_t* d_coef);
+// d_out[j] = sum_(q < cnt) d_part[q * cols + j], j < cols (ver_colsum_final_kernel).  One launch.
+__attribute__((visibility("hidden")))   // library-private: not in the exported symbol list
+int ver_column_sums(Ctx* c, uint32_t cols, uint32_t cnt, const uint32_t* d_part, uint32_t* d_out);
+
+// verify_points.hip: the two G1 points (L, R) of a random linear combination of K claims at arbitrary points
+// 
+int verify_points(Ctx* c, const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
+                  const uint64_t* z, const uint64_t* y, const uint64_t* proof_xy, const uint8_t* proof_inf, size_t K,
+                  const uint32_t* rho_words, uint64_t* out_xy, uint8_t* out_inf);
+// msm.hip: the curve's generator, canonical affine limbs x | y (what a generated key starts with)
+__attribute__((visibility("hidden")))   // library-private: not in the exported symbol list
+const uint64_t* g1_generator_limbs(int curve);
 
 // recover.hip: b coefficient vectors of n elements from their values on K of the N/l cosets.
 // coset_idx and out_consistent in host memory; values / coeffs in host (host_ptrs) or device memory.  Synchronises.

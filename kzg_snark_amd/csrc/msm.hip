@@ -630,6 +630,8 @@ static const uint64_t GEN_BLS[12] = {
     0x0caa232946c5e7e1ull, 0xd03cc744a2888ae4ull, 0x00db18cb2c04b3edull, 0xfcf5e095d5d00af6ull,
     0xa09e30ed741d8ae4ull, 0x08b3f481e3aaa0f1ull};
 
+const uint64_t* g1_generator_limbs(int curve) { return curve == 0 ? GEN_BN254 : GEN_BLS; }
+
 template <class C>
 static int srs_generate_t(Ctx* c, const uint32_t* tau_words, size_t start, size_t n, Srs** out, size_t run_len,
                           size_t inner_stride, size_t outer_stride, const uint32_t* d_scalars = nullptr) {

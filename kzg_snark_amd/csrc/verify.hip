@@ -228,7 +228,7 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
   const size_t M = K << log_l, rb = srs_rec_bytes(c->curve);
   const uint32_t log_e = std::max(log_l, VER_MIN_TILE_LOG);
   const uint32_t sum_threads = std::max<uint32_t>((uint32_t)l, VER_SUM_THREADS);
-  const uint32_t nsp = n_comm >= VER_COMM_SPLIT ? 1 : VER_COMM_SPLIT;
+  const uint32_t nsp = (uint32_t)ver_commsum_shares(n_comm);
   size_t total = 0;
   auto reserve = [&](size_t bytes) { const size_t o = total; total += (bytes + 255) / 256 * 256; return o; };
   const size_t o_pxy = reserve(K * PT_BYTES), o_pinf = reserve(proof_inf ? K : 0), o_cxy = reserve(n_comm * PT_BYTES),
@@ -300,11 +300,8 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
   hipLaunchKernelGGL(ver_colsum_kernel<F>, dim3(sum_threads / 256), dim3(256), 0, st, M, d_vals, d_part);
   hipLaunchKernelGGL(ver_colsum_final_kernel<F>, dim3((uint32_t)l), dim3(64), 0, st, (uint32_t)l,
                      sum_threads >> log_l, d_part, d_T);
-  hipLaunchKernelGGL(ver_commsum_kernel<F>, dim3((uint32_t)n_comm, nsp), dim3(256), 0, st, d_r, d_perm, d_off,
-                     (uint32_t)n_comm, d_cpart);
-  hipLaunchKernelGGL(ver_colsum_final_kernel<F>, dim3((uint32_t)n_comm), dim3(64), 0, st, (uint32_t)n_comm, nsp,
-                     d_cpart, d_coef);
   KZG_VER_HIP(hipGetLastError());
+  if ((rc = ver_commitment_sums(c, d_r, d_perm, d_off, n_comm, d_cpart, d_coef))) return fail(rc);
 
   // ---- the MSMs: 2 x ns slice vectors over the proofs, T over the key, the weights over the commitments
   Srs pv;
@@ -342,7 +339,35 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
   return KZG_OK;
 }
 
+template <class F>
+int commitment_sums_t(Ctx* c, const uint32_t* d_r, const uint32_t* d_perm, const uint32_t* d_off, size_t n_comm,
+                      uint32_t* d_cpart, uint32_t* d_coef) {
+  const uint32_t nsp = (uint32_t)ver_commsum_shares(n_comm);
+  hipLaunchKernelGGL(ver_commsum_kernel<F>, dim3((uint32_t)n_comm, nsp), dim3(256), 0, c->stream, d_r, d_perm, d_off,
+                     (uint32_t)n_comm, d_cpart);
+  hipLaunchKernelGGL(ver_colsum_final_kernel<F>, dim3((uint32_t)n_comm), dim3(64), 0, c->stream, (uint32_t)n_comm, nsp,
+                     d_cpart, d_coef);
+  KZG_HIP(c, hipGetLastError());
+  return KZG_OK;
+}
+
+template <class F>
+int column_sums_t(Ctx* c, uint32_t cols, uint32_t cnt, const uint32_t* d_part, uint32_t* d_out) {
+  hipLaunchKernelGGL(ver_colsum_final_kernel<F>, dim3(cols), dim3(64), 0, c->stream, cols, cnt, d_part, d_out);
+  KZG_HIP(c, hipGetLastError());
+  return KZG_OK;
+}
+
 }  // namespace
+
+size_t ver_commsum_shares(size_t n_comm) { return n_comm >= VER_COMM_SPLIT ? 1 : VER_COMM_SPLIT; }
+int ver_commitment_sums(Ctx* c, const uint32_t* d_r, const uint32_t* d_perm, const uint32_t* d_off, size_t n_comm,
+                        uint32_t* d_cpart, uint32_t* d_coef) {
+  return KZG_BY_FR(c, commitment_sums_t, c, d_r, d_perm, d_off, n_comm, d_cpart, d_coef);
+}
+int ver_column_sums(Ctx* c, uint32_t cols, uint32_t cnt, const uint32_t* d_part, uint32_t* d_out) {
+  return KZG_BY_FR(c, column_sums_t, c, cols, cnt, d_part, d_out);
+}
 
 int verify_cosets(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const uint32_t* w_words,
                   const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,

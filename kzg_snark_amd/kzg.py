@@ -10,6 +10,7 @@ commit and open -- executed by the gfx950 engine through the C ABI.
     check(rk, commitments, z, evaluations, proof, xi) -> bool            kzg.py:161
     batch_check(rk, commitments_list, z_list, evaluations_list, proof_list, xi_list, r=None)   kzg.py:213
     verify_cosets / verify_domain: any number of coset (or single-point) claims folded on the device, two pairings
+    verify_points / verify_blobs: the same for claims at arbitrary points (blob proofs), evaluate_evaluations_each
     compress_g1 / decompress_g1 / in_subgroup: 48- / 32-byte points and subgroup membership, on the device
 
 Points are py_ecc-shaped 3-tuples, always normalised: (x, y, 1), infinity (1, 1, 0).
@@ -495,21 +496,24 @@ class KZG:
                                                 _native.int_to_words(xi))
         return self._points(xy, inf)[0]
 
+    def _eval_domain(self, lk_or_w):
+        """(log_n, w) of a LagrangeKey, or of the root w itself (the domain size is its multiplicative order)"""
+        if isinstance(lk_or_w, LagrangeKey):
+            return lk_or_w.log_n, lk_or_w.w
+        r = self.curve_order
+        w = int(lk_or_w) % r
+        n, x = 1, w
+        while x != 1 and n < (1 << 40):
+            x = x * x % r
+            n *= 2
+        if x != 1:
+            raise ValueError("w is not a root of unity of power-of-two order")
+        return self._domain(n, w)
+
     def evaluate_evaluations(self, lk_or_w, values, z):
         """p(z) for the interpolant of values over {w^i} (barycentric, on the device; z in the domain included).
         lk_or_w: a LagrangeKey, or the root w itself (the domain size is then its multiplicative order)."""
-        if isinstance(lk_or_w, LagrangeKey):
-            log_n, w = lk_or_w.log_n, lk_or_w.w
-        else:
-            r = self.curve_order
-            w = int(lk_or_w) % r
-            n, x = 1, w
-            while x != 1 and n < (1 << 40):
-                x = x * x % r
-                n *= 2
-            if x != 1:
-                raise ValueError("w is not a root of unity of power-of-two order")
-            log_n, w = self._domain(n, w)
+        log_n, w = self._eval_domain(lk_or_w)
         vals = self._value_lists([values], 1 << log_n)[0]
         z = self._canon(z)
         if not len(vals):
@@ -517,6 +521,20 @@ class KZG:
         ctx = self._context()
         d = self._upload(ctx, vals if isinstance(vals, np.ndarray) else _native.ints_to_limbs(vals))
         return self.Fq(ctx.eval_lagrange(log_n, w, len(vals), d.data_ptr(), z))
+
+    def evaluate_evaluations_each(self, lk_or_w, value_lists, z_list):
+        """[p_j(z_j)]: evaluate_evaluations for every vector of value_lists at its own point, in one batch on the
+        device (kzg_fr_eval_lagrange_batch: a fixed number of launches whatever the count)."""
+        log_n, w = self._eval_domain(lk_or_w)
+        vals = self._value_lists(value_lists, 1 << log_n)
+        zs = [self._canon(z) for z in z_list]
+        if len(zs) != len(vals):
+            raise ValueError(f"{len(vals)} value vectors but {len(zs)} points")
+        if not vals:
+            return []
+        arr, lens, stride = self._pack(vals)
+        out = self._context().eval_lagrange_batch(log_n, w, arr, lens, stride, _native.ints_to_limbs(zs))
+        return [self.Fq(v) for v in _native.limbs_to_ints(out)]
 
     # ---- every proof on a domain at once (FK20: Feist-Khovratovich, "Fast amortized KZG proofs", 2020) -------------
     _DOMAIN_MAX = 1 << 20
@@ -991,3 +1009,66 @@ class KZG:
         return self.verify_cosets(ck, rk, [commitment], np.zeros(count, dtype=np.int64),
                                   np.arange(count, dtype=np.int64), values, proofs, 1, N, w=w, r=r,
                                   check_subgroup=check_subgroup)
+
+    # ---- bulk verification at arbitrary points (device): blob batches into the two G1 points of one pairing equation --
+    @staticmethod
+    def _verification_key(rk, who):
+        if not (isinstance(rk, (tuple, list)) and len(rk) == 3 and isinstance(rk[0], tuple)):
+            raise TypeError(f"{who}: rk must be a G2 point (setup's tau G2)")
+
+    def verify_points(self, rk, commitments, commitment_indices, z_list, evaluations, proofs, r=None,
+                      check_subgroup=False):
+        """Claim k: the polynomial of commitments[commitment_indices[k]] takes the value evaluations[k] at z_list[k]
+        -- any field element, the output of open / open_evaluations with xi = 1 or an EIP-4844 blob proof -- with proof
+        proofs[k].  All claims are combined with weights r^(k+1) (r sampled when not given, as in batch_check) into two
+        G1 points on the device (kzg_verify_points), then pairing(G2, L) == pairing(rk, R) with rk = tau G2.
+        proofs / commitments: lists of point tuples or (xy, inf) arrays in the C layout.  A point off the curve: False.
+        No claims: True.  check_subgroup: as in verify_cosets."""
+        self._verification_key(rk, "verify_points")
+        order = self.curve_order
+        comm_idx = np.ascontiguousarray(commitment_indices, dtype=np.int64).reshape(-1)
+        K = comm_idx.size
+        pxy, pinf = self._g1_arrays(proofs, "proofs")
+        cxy, cinf = self._g1_arrays(commitments, "commitments")
+        zs = [int(v) % order for v in z_list]
+        ys = [int(v) % order for v in evaluations]
+        if len(zs) != K or len(ys) != K or pxy.shape[0] != K:
+            raise ValueError("commitment_indices, z_list, evaluations and proofs must describe the same number of claims")
+        if K > (1 << 21):
+            raise ValueError("at most 2^21 claims per call")
+        if not 1 <= cxy.shape[0] <= (1 << 16):
+            raise ValueError("between 1 and 2^16 commitments per call")
+        if K and (comm_idx.min() < 0 or comm_idx.max() >= cxy.shape[0]):
+            raise ValueError("commitment index out of range")
+        rho = int(self.Fq(self.Fq.random_element() if r is None else r))
+        if K == 0:
+            return True
+        ctx = self._context()
+        if check_subgroup and (ctx.g1_check_subgroup(cxy, cinf).any() or ctx.g1_check_subgroup(pxy, pinf).any()):
+            return False
+        try:
+            xy, inf = ctx.verify_points(cxy, cinf, comm_idx.astype(np.uint32), _native.ints_to_limbs(zs),
+                                        _native.ints_to_limbs(ys), pxy, pinf, rho)
+        except _native.NativeError as e:
+            if e.code == -1 and "not on the curve" in str(e):
+                return False
+            raise
+        L_pt, R_pt = self._points(xy, inf)
+        return self.pairing(self.G2, L_pt) == self.pairing(rk, R_pt)
+
+    def verify_blobs(self, lk_or_w, rk, commitments, value_lists, z_list, proofs, r=None, check_subgroup=False):
+        """A batch of blobs: value_lists[j] (values over the domain of lk_or_w) against commitments[j] at the challenge
+        z_list[j] with proof proofs[j] -- verify_blob_kzg_proof_batch of EIP-4844 with the challenges given (the hash
+        that derives them is the protocol's).  The claimed values are computed on the device
+        (evaluate_evaluations_each), then verify_points."""
+        self._verification_key(rk, "verify_blobs")
+        value_lists, z_list = list(value_lists), list(z_list)
+        commitments = self._g1_arrays(commitments, "commitments")          # converted once: verify_points takes (xy, inf)
+        proofs = self._g1_arrays(proofs, "proofs")
+        if not (len(value_lists) == len(z_list) == commitments[0].shape[0] == proofs[0].shape[0]):
+            raise ValueError("commitments, value_lists, z_list and proofs must describe the same number of blobs")
+        if not value_lists:
+            return True
+        ys = self.evaluate_evaluations_each(lk_or_w, value_lists, z_list)
+        return self.verify_points(rk, commitments, np.arange(len(ys), dtype=np.int64), z_list, [int(v) for v in ys],
+                                  proofs, r=r, check_subgroup=check_subgroup)
