@@ -90,6 +90,7 @@ struct Ctx {
   hipEvent_t eval_lens_ev = nullptr;
   size_t open_shard_n = 0;                // slice length between kzg_open_shard_begin / _finish
   uint32_t open_shard_tb = 0;             // tile width the slice's aggregates were formed with
+  bool open_shard_begun = false;          // a kzg_open_shard_begin has left a slice (an empty one included)
   // kzg_ctx_set_tuning: 0 = the library's own choice
   int tune_ntt_tile_log = 0;              // LDS tile of the transform (8..12)
   int tune_open_tb = 0;                   // threads per tile of the opening's scan (128 | 256)

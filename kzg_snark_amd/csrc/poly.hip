@@ -584,6 +584,7 @@ int open_shard_begin_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, size
   if (rc) return rc;
   c->open_shard_n = n;
   c->open_shard_tb = 0;
+  c->open_shard_begun = true;
   if (n == 0) return KZG_OK;
   if ((rc = ensure_buf(c, c->poly_tmp[0], (2 * (n + 1) + 1) * 32))) return rc;
   uint32_t* d_comb = static_cast<uint32_t*>(c->poly_tmp[0].p);
@@ -624,6 +625,8 @@ int open_shard_finish_t(Ctx* c, const uint32_t* z_words, const uint32_t* carry_w
   memset(eval_out, 0, 32);
   *d_vec_out = nullptr;
   *vec_len = 0;
+  // a context that never began a slice holds n = 0, which is also what an empty slice leaves: told apart here
+  if (!c->open_shard_begun) return set_err(c, KZG_ERR_ARG, "kzg_open_shard_finish without kzg_open_shard_begin");
   const size_t n = c->open_shard_n;
   if (n == 0) return KZG_OK;
   uint32_t* d_comb = static_cast<uint32_t*>(c->poly_tmp[0].p);
