@@ -436,6 +436,36 @@ int kzg_g1_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, 
 int kzg_srs_load_g1_compressed(kzg_ctx* ctx, const uint8_t* bytes, size_t n, int check_subgroup, kzg_srs** out);
 int kzg_srs_export_compressed(kzg_ctx* ctx, const kzg_srs* srs, size_t start, size_t count, uint8_t* out_bytes);
 
+/* ---- EIP-4844 blobs as bytes: device intake and SHA-256 challenges ---------------------------------
+ * A blob is n = 2^log_n field elements of 32 big-endian bytes each; b blobs lie one after the other ([b][n][32]).
+ *   kzg_blob_to_fr          every element checked < r and written as four canonical little-endian limbs:
+ *                           out_vals[j][i] = element i of blob j, or out_vals[j][bitrev_log_n(i)] when bit_reversed != 0
+ *                           (EIP-4844 keeps a blob in bit-reversed order over the domain: the output is then in natural
+ *                           order, what kzg_commit / kzg_open_evals / kzg_fr_eval_lagrange_batch take against a Lagrange
+ *                           key).  A non-canonical element is not an error of the call: the verdict is in out_status,
+ *                           one byte per blob, 0 ok, 1 some element >= r (as with kzg_g1_decompress); such an element is
+ *                           written as zeros.
+ *   kzg_blob_challenges     out_z[j] = SHA-256("FSBLOBVERIFY_V1_" | n as 16 bytes big-endian | blob j | commitment j)
+ *                           read as a 256-bit big-endian number mod r, canonical limbs: compute_challenge of EIP-4844.
+ *                           commitments: [b][G] bytes, G the size of a compressed point (48 on BLS12-381, 32 on BN254;
+ *                           BN254 has no standard for this hash: the same construction over its own r and point bytes).
+ *                           The bytes are hashed as given: neither the elements' canonicity nor the commitment's
+ *                           validity is looked at, the hash is defined on bytes.  One lane per blob, 64-byte blocks,
+ *                           n/2 + 2 compressions per blob.
+ * Ranges: 1 <= log_n <= 24 and b * 2^log_n <= 2^26 elements per call, otherwise KZG_ERR_ARG; b = 0 is KZG_OK with no
+ * work.  The host forms take host pointers and synchronise.  The _device forms take device pointers (16-byte aligned;
+ * d_vals and d_z 32-byte aligned; d_status b bytes), enqueue on the context's stream and do not wait.  Both run on the
+ * context's stream alone: results of kzg_commit_device_async / kzg_open_device_async still pending are neither retired
+ * nor disturbed. */
+int kzg_blob_to_fr(kzg_ctx* ctx, uint32_t log_n, const uint8_t* blobs, size_t b, int bit_reversed, uint64_t* out_vals,
+                   uint8_t* out_status);
+int kzg_blob_to_fr_device(kzg_ctx* ctx, uint32_t log_n, const void* d_blobs, size_t b, int bit_reversed, void* d_vals,
+                          void* d_status);
+int kzg_blob_challenges(kzg_ctx* ctx, uint32_t log_n, const uint8_t* blobs, const uint8_t* commitments, size_t b,
+                        uint64_t* out_z);
+int kzg_blob_challenges_device(kzg_ctx* ctx, uint32_t log_n, const void* d_blobs, const void* d_commitments, size_t b,
+                               void* d_z);
+
 /* ---- device vector / polynomial primitives over Fr ------------------------------------------------
  * What the reference's callers do with Sage's dense polynomials between the transforms and the
  * commitments (plonk/prover.py:243-316: accumulator ratios, products, division by Z_H on a coset),
@@ -490,7 +520,8 @@ int kzg_fr_eval_lagrange_batch_device(kzg_ctx* ctx, uint32_t log_n, const uint64
  * the product tree and every chunk), "g1_decompress" (ONE per kzg_g1_decompress*, and one per
  * kzg_srs_load_g1_compressed: the decoding, with the subgroup test when asked for), "g1_subgroup" (ONE per
  * kzg_g1_check_subgroup), "verify_points" (ONE per kzg_verify_points: the whole call), "eval_lagrange_batch" (ONE per
- * kzg_fr_eval_lagrange_batch*: every chunk).  kzg_prof_read synchronises the
+ * kzg_fr_eval_lagrange_batch*: every chunk), "blob_intake" (ONE per kzg_blob_to_fr*) and "blob_challenge" (ONE per
+ * kzg_blob_challenges*).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.
  * Two names are not spans: "msm_accumulate_shader_mhz" and "ntt_pass_shader_mhz" return (in *total_ms) the shader
  * clock in MHz the accumulate / NTT kernel ran at since the last reset -- s_memtime over s_memrealtime ticks of its

@@ -118,6 +118,10 @@ SIGNATURES = {
     "kzg_srs_export_compressed": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "kzg_recover_cosets_device": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
                                                  ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
+    "kzg_blob_to_fr": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp]),
+    "kzg_blob_to_fr_device": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp]),
+    "kzg_blob_challenges": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, ctypes.c_size_t, _vp]),
+    "kzg_blob_challenges_device": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 
@@ -399,6 +403,42 @@ class Context:
         status = np.zeros(n, dtype=np.uint8)
         self._check(lib().kzg_g1_check_subgroup(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(status)))
         return status
+
+    # ---- EIP-4844 blobs as bytes
+    def blob_to_fr(self, blobs, log_n, bit_reversed=True):
+        """uint8[b, 32 << log_n] big-endian elements -> (values uint64[b, n, 4] canonical limbs, status uint8[b]);
+        bit_reversed: element i lands at bitrev(i) (a blob in EIP-4844's order comes out in natural domain order).
+        status 1: some element of the blob is >= r (written as zeros)."""
+        size = 32 << int(log_n)
+        blobs = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(-1, size)
+        b = blobs.shape[0]
+        vals = np.zeros((b, 1 << int(log_n), 4), dtype=np.uint64)
+        status = np.zeros(b, dtype=np.uint8)
+        self._check(lib().kzg_blob_to_fr(self._h, int(log_n), _as_vp(blobs), b, int(bool(bit_reversed)), _as_vp(vals),
+                                         _as_vp(status)))
+        return vals, status
+
+    def blob_to_fr_device(self, d_blobs, log_n, b, bit_reversed, d_vals, d_status):
+        """The same on device pointers, enqueued on the context's stream (no synchronisation)."""
+        self._check(lib().kzg_blob_to_fr_device(self._h, int(log_n), _as_vp(d_blobs), int(b), int(bool(bit_reversed)),
+                                                _as_vp(d_vals), _as_vp(d_status)))
+
+    def blob_challenges(self, blobs, commitments, log_n):
+        """uint8[b, 32 << log_n] blobs and uint8[b, g1_bytes] commitments -> uint64[b, 4]: the challenges
+        SHA-256("FSBLOBVERIFY_V1_" | n | blob | commitment) mod r, hashed on the device, one lane per blob."""
+        blobs = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(-1, 32 << int(log_n))
+        commitments = np.ascontiguousarray(commitments, dtype=np.uint8).reshape(-1, self.g1_bytes)
+        b = blobs.shape[0]
+        if commitments.shape[0] != b:
+            raise ValueError("blob_challenges: blobs and commitments differ in number")
+        z = np.zeros((b, 4), dtype=np.uint64)
+        self._check(lib().kzg_blob_challenges(self._h, int(log_n), _as_vp(blobs), _as_vp(commitments), b, _as_vp(z)))
+        return z
+
+    def blob_challenges_device(self, d_blobs, d_commitments, log_n, b, d_z):
+        """The same on device pointers, enqueued on the context's stream (no synchronisation)."""
+        self._check(lib().kzg_blob_challenges_device(self._h, int(log_n), _as_vp(d_blobs), _as_vp(d_commitments),
+                                                     int(b), _as_vp(d_z)))
 
     def srs_generate(self, tau_words, n, start=0):
         return Srs(self, self._handle(lib().kzg_srs_generate_range, _as_vp(tau_words), start, n), n)

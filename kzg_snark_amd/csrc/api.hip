@@ -392,6 +392,30 @@ int kzg_g1_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, 
   return g1_check_subgroup(c, xy, inf, n, out_status);
 }
 
+int kzg_blob_to_fr(kzg_ctx* ctx, uint32_t log_n, const uint8_t* blobs, size_t b, int bit_reversed, uint64_t* out_vals,
+                   uint8_t* out_status) {
+  KZG_ENTER(b && (!blobs || !out_vals || !out_status));
+  return blob_to_fr(c, log_n, blobs, b, bit_reversed, out_vals, out_status);
+}
+
+int kzg_blob_to_fr_device(kzg_ctx* ctx, uint32_t log_n, const void* d_blobs, size_t b, int bit_reversed, void* d_vals,
+                          void* d_status) {
+  KZG_ENTER(b && (!d_blobs || !d_vals || !d_status));
+  return blob_to_fr_device(c, log_n, d_blobs, b, bit_reversed, d_vals, d_status);
+}
+
+int kzg_blob_challenges(kzg_ctx* ctx, uint32_t log_n, const uint8_t* blobs, const uint8_t* commitments, size_t b,
+                        uint64_t* out_z) {
+  KZG_ENTER(b && (!blobs || !commitments || !out_z));
+  return blob_challenges(c, log_n, blobs, commitments, b, out_z);
+}
+
+int kzg_blob_challenges_device(kzg_ctx* ctx, uint32_t log_n, const void* d_blobs, const void* d_commitments, size_t b,
+                               void* d_z) {
+  KZG_ENTER(b && (!d_blobs || !d_commitments || !d_z));
+  return blob_challenges_device(c, log_n, d_blobs, d_commitments, b, d_z);
+}
+
 size_t kzg_srs_size(const kzg_srs* srs) { return srs ? srs->s->n : 0; }
 
 void kzg_srs_free(kzg_srs* srs) {

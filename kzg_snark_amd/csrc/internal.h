@@ -1,6 +1,6 @@
 // internal.h -- library-private declarations shared by the translation units of
 // libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, msm_prep.hip, poly.hip, lagrange.hip, domain.hip, verify.hip,
-// recover.hip, g1_bytes.hip, verify_points.hip): the context, error and profiling plumbing, the dispatch by curve (KZG_BY_CURVE,
+// recover.hip, g1_bytes.hip, verify_points.hip, blob.hip): the context, error and profiling plumbing, the dispatch by curve (KZG_BY_CURVE,
 // KZG_BY_FR) and the entry points of ntt.hip and poly.hip.  Shared device helpers live in fr_util.h (one Fr element,
 // the power-table lookup), g1_util.h (word arrays, XYZZ points), g1_words.h (point <-> canonical words) and
 // srs_rec.h (key records).

@@ -152,6 +152,17 @@ int g1_check_subgroup(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, 
 int srs_load_g1_compressed(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, Srs** out);
 int srs_export_compressed(Ctx* c, const Srs* s, size_t start, size_t count, uint8_t* out_bytes);
 
+// blob.hip: EIP-4844 blobs as bytes; the contracts are those of the kzg_* entry points of the same
+// names.  b = 0 does nothing; log_n outside [1, 24] or more than 2^26 elements is KZG_ERR_ARG.
+int blob_to_fr(Ctx* c, uint32_t log_n, const uint8_t* blobs, size_t b, int bit_reversed, uint64_t* out_vals,
+               uint8_t* out_status);
+int blob_to_fr_device(Ctx* c, uint32_t log_n, const void* d_blobs, size_t b, int bit_reversed, void* d_vals,
+                      void* d_status);
+int blob_challenges(Ctx* c, uint32_t log_n, const uint8_t* blobs, const uint8_t* commitments, size_t b,
+                    uint64_t* out_z);
+int blob_challenges_device(Ctx* c, uint32_t log_n, const void* d_blobs, const void* d_commitments, size_t b,
+                           void* d_z);
+
 int open_shard_begin_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                             const uint32_t* z_words, const uint32_t* xi_words, uint64_t* chunk_eval_out);
 int open_shard_finish_device(Ctx* c, const uint32_t* z_words, const uint32_t* carry_words, int first_rank,

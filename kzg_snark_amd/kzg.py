@@ -12,6 +12,8 @@ commit and open -- executed by the gfx950 engine through the C ABI.
     verify_cosets / verify_domain: any number of coset (or single-point) claims folded on the device, two pairings
     verify_points / verify_blobs: the same for claims at arbitrary points (blob proofs), evaluate_evaluations_each
     compress_g1 / decompress_g1 / in_subgroup: 48- / 32-byte points and subgroup membership, on the device
+    blob_to_kzg_commitment / compute_blob_kzg_proof / verify_blob_kzg_proof_batch: EIP-4844's calls, bytes in and out
+    (blob_to_values / blob_challenges: the device intake of blob bytes and the SHA-256 challenges on their own)
 
 Points are py_ecc-shaped 3-tuples, always normalised: (x, y, 1), infinity (1, 1, 0).
 The reference returns un-normalised projective triples whose representative
@@ -1072,3 +1074,187 @@ class KZG:
         ys = self.evaluate_evaluations_each(lk_or_w, value_lists, z_list)
         return self.verify_points(rk, commitments, np.arange(len(ys), dtype=np.int64), z_list, [int(v) for v in ys],
                                   proofs, r=r, check_subgroup=check_subgroup)
+
+    # ---- EIP-4844 blobs as bytes (device intake, SHA-256 challenges on the device): the spec's calls by name ------------
+    #      A blob is n elements of 32 big-endian bytes in bit-reversed order over the domain; commitments and proofs are
+    #      compressed points (compress_g1's formats).  blobs: a list of bytes objects or a uint8[b, 32 n] array;
+    #      commitments / proofs: lists of bytes objects or uint8[b, G] arrays.
+    _FS_DOMAIN = b"FSBLOBVERIFY_V1_"               # the domain of the blob challenge (hashed on the device)
+    _RHO_DOMAIN = b"RCKZGBATCH___V1_"              # the domain of the batch's weight base (hashed here)
+
+    @staticmethod
+    def _byte_rows(rows, size, what):
+        """a list of bytes objects or a uint8[b, size] array -> uint8[b, size]; ValueError names the first row of another
+        size"""
+        if isinstance(rows, np.ndarray):
+            arr = np.ascontiguousarray(rows, dtype=np.uint8)
+            if arr.ndim != 2 or arr.shape[1] != size:
+                raise ValueError(f"{what}: an array of shape {arr.shape}, expected (b, {size})")
+            return arr if arr.flags.writeable else arr.copy()          # torch uploads writable arrays only
+        rows = [bytes(x) for x in rows]
+        for i, x in enumerate(rows):
+            if len(x) != size:
+                raise ValueError(f"{what} {i}: {len(x)} bytes, expected {size}")
+        return np.frombuffer(bytearray(b"".join(rows)), dtype=np.uint8).reshape(len(rows), size)     # writable
+
+    def _blob_size(self, n):
+        """log_n of a blob of n elements: a power of two in [2, 2^24]"""
+        n = int(n)
+        if n < 2 or n & (n - 1) or n > (1 << 24):
+            raise ValueError(f"blob size {n} is not a power of two in [2, 2^24]")
+        return n.bit_length() - 1
+
+    def _first_bad_element(self, blob_row, j):
+        """the ValueError of a blob whose status is 1: its first element >= r, found on the host"""
+        r, raw = self.curve_order, blob_row.tobytes()
+        i = next(i for i in range(len(raw) // 32) if int.from_bytes(raw[32 * i:32 * i + 32], "big") >= r)
+        return ValueError(f"blob {j}: element {i} is not below the field modulus")
+
+    def blob_to_values(self, blobs, n, bit_reversed=True, strict=True):
+        """The field elements of b blobs of n elements: a uint64[b, n, 4] array of canonical limbs, in natural domain
+        order when the blobs are bit-reversed (EIP-4844's order; bit_reversed=False keeps the order of the bytes) --
+        the form commit_evaluations / open_evaluations take.  Checked and permuted on the device (kzg_blob_to_fr).
+        strict: the first blob holding an element >= r raises ValueError naming the blob and its first such element;
+        strict=False returns (values, status), status uint8[b] with 1 for such a blob (its elements >= r read as 0)."""
+        log_n = self._blob_size(n)
+        arr = self._byte_rows(blobs, 32 << log_n, "blob")
+        with _bad_input_is_value_error():
+            vals, status = self._context().blob_to_fr(arr, log_n, bit_reversed)
+        if not strict:
+            return vals, status
+        bad = np.flatnonzero(status)
+        if bad.size:
+            raise self._first_bad_element(arr[int(bad[0])], int(bad[0]))
+        return vals
+
+    def blob_challenges(self, blobs, commitments, n):
+        """[z_j]: SHA-256("FSBLOBVERIFY_V1_" | n as 16 bytes | blob_j | commitment_j) mod r, compute_challenge of
+        EIP-4844, one lane per blob on the device (kzg_blob_challenges).  The bytes are hashed as given."""
+        log_n = self._blob_size(n)
+        ctx = self._context()
+        arr = self._byte_rows(blobs, 32 << log_n, "blob")
+        comm = self._byte_rows(commitments, ctx.g1_bytes, "commitment")
+        if comm.shape[0] != arr.shape[0]:
+            raise ValueError(f"{arr.shape[0]} blobs but {comm.shape[0]} commitments")
+        if not arr.shape[0]:
+            return []
+        with _bad_input_is_value_error():
+            z = ctx.blob_challenges(arr, comm, log_n)
+        return [self.Fq(v) for v in _native.limbs_to_ints(z)]
+
+    @staticmethod
+    def _lagrange_key(lk, who):
+        if not isinstance(lk, LagrangeKey):
+            raise TypeError(f"{who} needs a LagrangeKey (setup_lagrange / lagrange_key)")
+
+    def blob_to_kzg_commitment(self, lk, blobs):
+        """blob_to_kzg_commitment of EIP-4844 for every blob: a list of compressed commitments (bytes).  Intake on the
+        device, the commit pipeline on the Lagrange key, compression on the device.  A blob with an element >= r
+        raises ValueError."""
+        self._lagrange_key(lk, "blob_to_kzg_commitment")
+        vals = self.blob_to_values(blobs, lk.n)
+        b = vals.shape[0]
+        if not b:
+            return []
+        ctx = self._context()
+        xy, inf = ctx.commit(lk.srs, vals, [lk.n] * b, lk.n)
+        return [row.tobytes() for row in ctx.g1_compress(xy, inf)]
+
+    def compute_blob_kzg_proof(self, lk, blobs, commitments):
+        """compute_blob_kzg_proof of EIP-4844 for every blob: a list of compressed proofs (bytes).  The blobs are
+        uploaded once; challenges z_j and values come from the device (kzg_blob_challenges_device, kzg_blob_to_fr_device),
+        then one evaluation-form opening per blob at z_j with xi = 1, queued through the commit pipeline
+        (kzg_open_evals_device_async).  A blob with an element >= r raises ValueError."""
+        self._lagrange_key(lk, "compute_blob_kzg_proof")
+        n, log_n = lk.n, self._blob_size(lk.n)
+        ctx = self._context()
+        arr = self._byte_rows(blobs, 32 * n, "blob")
+        comm = self._byte_rows(commitments, ctx.g1_bytes, "commitment")
+        b = arr.shape[0]
+        if comm.shape[0] != b:
+            raise ValueError(f"{b} blobs but {comm.shape[0]} commitments")
+        if not b:
+            return []
+        import torch
+        dev = f"cuda:{ctx.device}"
+        d_vals = torch.empty((b, n, 4), dtype=torch.int64, device=dev)
+        d_z = torch.empty((b, 4), dtype=torch.int64, device=dev)
+        d_status = torch.empty(b, dtype=torch.uint8, device=dev)
+        d_blobs, d_comm = self._upload(ctx, arr), self._upload(ctx, comm)
+        with _bad_input_is_value_error():
+            ctx.blob_to_fr_device(d_blobs.data_ptr(), log_n, b, True, d_vals.data_ptr(), d_status.data_ptr())
+            ctx.blob_challenges_device(d_blobs.data_ptr(), d_comm.data_ptr(), log_n, b, d_z.data_ptr())
+        ctx.synchronize()
+        bad = np.flatnonzero(d_status.cpu().numpy())
+        if bad.size:
+            raise self._first_bad_element(arr[int(bad[0])], int(bad[0]))
+        z = np.ascontiguousarray(d_z.cpu().numpy().view(np.uint64))
+        one = _native.int_to_words(1)
+        out = [_native.result_buffers(ctx.fp_limbs, evals=4) for _ in range(b)]
+        try:
+            for j in range(b):
+                ctx.open_evals_device_async(lk.srs, d_vals.data_ptr() + j * n * 32, [n], n, z[j], one, *out[j])
+        finally:
+            ctx.commit_flush()
+        xy = np.stack([o[0] for o in out])
+        inf = np.concatenate([o[1] for o in out])
+        return [row.tobytes() for row in ctx.g1_compress(xy, inf)]
+
+    def _blob_batch_rho(self, n, commitments, zs, ys, proofs):
+        """SHA-256("RCKZGBATCH___V1_" | n as 8 bytes | b as 8 bytes | per blob: commitment | z | y | proof) mod r --
+        160 b bytes, on the host.  commitments / proofs: rows of bytes; zs, ys: ints."""
+        import hashlib
+        h = hashlib.sha256(self._RHO_DOMAIN + int(n).to_bytes(8, "big") + len(zs).to_bytes(8, "big"))
+        for c, z, y, p in zip(commitments, zs, ys, proofs):
+            h.update(bytes(c) + int(z).to_bytes(32, "big") + int(y).to_bytes(32, "big") + bytes(p))
+        return int.from_bytes(h.digest(), "big") % self.curve_order
+
+    def verify_blob_kzg_proof_batch(self, lk_or_w, rk, blobs, commitments, proofs):
+        """verify_blob_kzg_proof_batch of EIP-4844: do proofs[j] open commitments[j] to the value of blobs[j] at its
+        challenge, for every j?  lk_or_w: a LagrangeKey or the domain's root w (as in verify_blobs); rk: setup's tau G2.
+        The blobs are uploaded once and stay on the device: intake, challenges and the values y_j = p_j(z_j)
+        (kzg_blob_to_fr_device, kzg_blob_challenges_device, kzg_fr_eval_lagrange_batch_device); only z and y come back.
+        Commitments and proofs are decompressed with the subgroup test on the device.  The claims are folded by
+        kzg_verify_points with the weights rho^(k+1), rho = SHA-256("RCKZGBATCH___V1_" | n | b | per blob:
+        commitment | z | y | proof) mod r: the protocol fixes the verdict, not the weights (the specification's
+        rho^k differ by the common factor rho).  Two pairings.
+        False, not an exception: an element >= r, a malformed point, a point off the curve or outside the subgroup, a
+        wrong proof.  ValueError: mismatched counts or sizes.  No blobs: True."""
+        self._verification_key(rk, "verify_blob_kzg_proof_batch")
+        log_n, w = self._eval_domain(lk_or_w)
+        n = 1 << log_n
+        self._blob_size(n)
+        ctx = self._context()
+        G = ctx.g1_bytes
+        arr = self._byte_rows(blobs, 32 * n, "blob")
+        comm = self._byte_rows(commitments, G, "commitment")
+        prf = self._byte_rows(proofs, G, "proof")
+        b = arr.shape[0]
+        if comm.shape[0] != b or prf.shape[0] != b:
+            raise ValueError("blobs, commitments and proofs must describe the same number of blobs")
+        if not b:
+            return True
+        import torch
+        dev = f"cuda:{ctx.device}"
+        d_vals = torch.empty((b, n, 4), dtype=torch.int64, device=dev)
+        d_zy = torch.empty((2, b, 4), dtype=torch.int64, device=dev)
+        d_status = torch.empty(b, dtype=torch.uint8, device=dev)
+        d_blobs, d_comm = self._upload(ctx, arr), self._upload(ctx, comm)
+        d_z, d_y = d_zy.data_ptr(), d_zy.data_ptr() + b * 32
+        with _bad_input_is_value_error():
+            ctx.blob_to_fr_device(d_blobs.data_ptr(), log_n, b, True, d_vals.data_ptr(), d_status.data_ptr())
+            ctx.blob_challenges_device(d_blobs.data_ptr(), d_comm.data_ptr(), log_n, b, d_z)
+            ctx.eval_lagrange_batch(log_n, w, d_vals.data_ptr(), [n] * b, n, d_z, d_out=d_y)
+        ctx.synchronize()
+        if d_status.cpu().numpy().any():
+            return False
+        zy = np.ascontiguousarray(d_zy.cpu().numpy().view(np.uint64))
+        xy, inf, status = ctx.g1_decompress(np.concatenate([comm, prf]), check_subgroup=True)
+        if status.any():
+            return False
+        zs, ys = _native.limbs_to_ints(zy[0]), _native.limbs_to_ints(zy[1])
+        rho = self._blob_batch_rho(n, comm, zs, ys, prf)
+        out_xy, out_inf = ctx.verify_points(xy[:b], inf[:b], np.arange(b, dtype=np.uint32), zy[0], zy[1], xy[b:],
+                                            inf[b:], rho)
+        L_pt, R_pt = self._points(out_xy, out_inf)
+        return self.pairing(self.G2, L_pt) == self.pairing(rk, R_pt)
