@@ -507,6 +507,34 @@ int kzg_fr_eval_lagrange_batch(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4]
                                const size_t* lens, size_t b, size_t stride, const uint64_t* z, uint64_t* out);
 int kzg_fr_eval_lagrange_batch_device(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], const void* d_vals,
                                       const size_t* lens, size_t b, size_t stride, const void* d_z, void* d_out);
+/* ---- pairing-product checks: the verdict on the device -------------------------------------------
+ * m equations of k pairs each, row-major [m][k]: is the product over i < k of e(P_i, Q_i) one?  e is the optimal-ate
+ * pairing of the context's curve.  A G1 point is laid out as everywhere else (x | y, FP_LIMBS canonical limbs each,
+ * with an infinity byte; g1_inf may be NULL: no point is infinity); a G2 point is x.c0, x.c1, y.c0, y.c1 (a
+ * coordinate is c0 + c1 i), FP_LIMBS canonical limbs each, with an infinity byte (g2_inf may be NULL likewise).
+ * An infinity byte wins over the coordinates beside it and drops its pair from the product.
+ * out_status[e], a verdict and not an error (as kzg_blob_to_fr's):
+ *   0  the product is one      1  it is not
+ *   2  a finite point of the equation has a coordinate >= p, is off the curve (G1) or off the twist (G2)
+ * An equation whose points are all infinity has the product one.  Membership in the prime-order subgroups is NOT part
+ * of these calls: kzg_g1_check_subgroup tests G1 points, G2 points (the verification keys) come from the caller's
+ * setup.  Input outside the subgroups yields status 0 or 1, no error.
+ *   kzg_pairing_check        the statuses alone: what a verifier needs after kzg_verify_cosets / kzg_verify_points,
+ *                            one equation [(L, G2), (-R, [tau] G2)].
+ *   kzg_pairing_product      also the value of every product raised to c = kzg_pairing_gt_multiple(curve) (the final
+ *                            exponentiation computes c (p^12 - 1) / r; c = 1 on BN254, 3 on BLS12-381; r does not
+ *                            divide c, so "is one" is unchanged): out_gt[e] is the six Fp2 coefficients of
+ *                            1, w, ..., w^5 in Fp12 = Fp2[w]/(w^6 - xi), xi = 9 + i (BN254) or 1 + i (BLS12-381),
+ *                            each c0 | c1 in FP_LIMBS canonical limbs -- [m][12][FP_LIMBS]; zeros for status 2.
+ * 1 <= k <= 16 and m <= 2^20, otherwise KZG_ERR_ARG before anything is queued; m = 0 is KZG_OK with no work.  Host
+ * pointers in and out; the calls synchronise the context's stream.  They do not touch the commit pipeline: results
+ * pending from kzg_commit_device_async / kzg_open_device_async stay pending and undisturbed. */
+int kzg_pairing_check(kzg_ctx* ctx, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                      const uint8_t* g2_inf, size_t m, size_t k, uint8_t* out_status);
+int kzg_pairing_product(kzg_ctx* ctx, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                        const uint8_t* g2_inf, size_t m, size_t k, uint64_t* out_gt, uint8_t* out_status);
+int kzg_pairing_gt_multiple(int curve);
+
 /* ---- measurement hooks (bench.py) -----------------------------------------------------------
  * When enabled, the library brackets its kernels with HIP events on the stream each one runs on.
  * Span names: "ntt_pass", "msm_partition1", "msm_partition2", "msm_order", "msm_accumulate",
@@ -520,8 +548,8 @@ int kzg_fr_eval_lagrange_batch_device(kzg_ctx* ctx, uint32_t log_n, const uint64
  * the product tree and every chunk), "g1_decompress" (ONE per kzg_g1_decompress*, and one per
  * kzg_srs_load_g1_compressed: the decoding, with the subgroup test when asked for), "g1_subgroup" (ONE per
  * kzg_g1_check_subgroup), "verify_points" (ONE per kzg_verify_points: the whole call), "eval_lagrange_batch" (ONE per
- * kzg_fr_eval_lagrange_batch*: every chunk), "blob_intake" (ONE per kzg_blob_to_fr*) and "blob_challenge" (ONE per
- * kzg_blob_challenges*).  kzg_prof_read synchronises the
+ * kzg_fr_eval_lagrange_batch*: every chunk), "blob_intake" (ONE per kzg_blob_to_fr*), "blob_challenge" (ONE per
+ * kzg_blob_challenges*) and "pairing" (ONE per kzg_pairing_check / kzg_pairing_product: copies and kernel).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.
  * Two names are not spans: "msm_accumulate_shader_mhz" and "ntt_pass_shader_mhz" return (in *total_ms) the shader
  * clock in MHz the accumulate / NTT kernel ran at since the last reset -- s_memtime over s_memrealtime ticks of its

@@ -118,6 +118,9 @@ SIGNATURES = {
     "kzg_srs_export_compressed": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "kzg_recover_cosets_device": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
                                                  ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
+    "kzg_pairing_check": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
+    "kzg_pairing_product": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
+    "kzg_pairing_gt_multiple": (ctypes.c_int, [ctypes.c_int]),
     "kzg_blob_to_fr": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp]),
     "kzg_blob_to_fr_device": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp]),
     "kzg_blob_challenges": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, ctypes.c_size_t, _vp]),
@@ -403,6 +406,39 @@ class Context:
         status = np.zeros(n, dtype=np.uint8)
         self._check(lib().kzg_g1_check_subgroup(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(status)))
         return status
+
+    # ---- pairing-product checks
+    def _pairing_args(self, g1_xy, g1_inf, g2_xy, g2_inf, k, who):
+        L = self.fp_limbs
+        k = int(k)
+        g1_xy = np.ascontiguousarray(g1_xy, dtype=np.uint64).reshape(-1, 2 * L)
+        g2_xy = np.ascontiguousarray(g2_xy, dtype=np.uint64).reshape(-1, 4 * L)
+        n = g1_xy.shape[0]
+        if g2_xy.shape[0] != n or k < 1 or n % k:
+            raise ValueError(f"{who}: {n} G1 points and {g2_xy.shape[0]} G2 points do not make equations of {k} pairs")
+        g1_inf = _inf_arg(g1_inf, n, f"{who}: g1_inf and g1_xy")
+        g2_inf = _inf_arg(g2_inf, n, f"{who}: g2_inf and g2_xy")
+        return g1_xy, g1_inf, g2_xy, g2_inf, n // k, k
+
+    def pairing_check(self, g1_xy, g1_inf, g2_xy, g2_inf, k):
+        """m equations of k pairs, row-major: g1_xy uint64[m * k, 2*fp_limbs] (x | y), g2_xy uint64[m * k, 4*fp_limbs]
+        (x.c0 | x.c1 | y.c0 | y.c1), flags uint8[m * k] or None -> status uint8[m]: 0 the product of the k pairings is
+        one, 1 it is not, 2 a malformed point.  Pending pipeline results stay pending."""
+        g1_xy, g1_inf, g2_xy, g2_inf, m, k = self._pairing_args(g1_xy, g1_inf, g2_xy, g2_inf, k, "pairing_check")
+        status = np.zeros(m, dtype=np.uint8)
+        self._check(lib().kzg_pairing_check(self._h, _as_vp(g1_xy), _as_vp(g1_inf), _as_vp(g2_xy), _as_vp(g2_inf), m, k,
+                                            _as_vp(status)))
+        return status
+
+    def pairing_product(self, g1_xy, g1_inf, g2_xy, g2_inf, k):
+        """The same with the values: (gt uint64[m, 12, fp_limbs], status uint8[m]); gt[e] is the product of equation e
+        to the power PAIRING_GT_MULTIPLE[curve], six Fp2 tower coefficients c0 | c1, zeros where the status is 2."""
+        g1_xy, g1_inf, g2_xy, g2_inf, m, k = self._pairing_args(g1_xy, g1_inf, g2_xy, g2_inf, k, "pairing_product")
+        status = np.zeros(m, dtype=np.uint8)
+        gt = np.zeros((m, 12, self.fp_limbs), dtype=np.uint64)
+        self._check(lib().kzg_pairing_product(self._h, _as_vp(g1_xy), _as_vp(g1_inf), _as_vp(g2_xy), _as_vp(g2_inf), m,
+                                              k, _as_vp(gt), _as_vp(status)))
+        return gt, status
 
     # ---- EIP-4844 blobs as bytes
     def blob_to_fr(self, blobs, log_n, bit_reversed=True):
@@ -790,6 +826,55 @@ def g1_sum(curve_type, points):
     if rc != 0:
         raise NativeError(rc, "kzg_g1_sum: a coordinate is not reduced or a point is not on the curve")
     return limbs_to_points(out_xy, out_inf)[0]
+
+
+class _GtMultiple:
+    """PAIRING_GT_MULTIPLE[curve name or id]: the c of kzg_pairing_product, whose values are e(P, Q)^c with e the
+    pairing raised to (p^12 - 1) / r (csrc/fp_tower.h states c per curve; read from the library)."""
+
+    def __getitem__(self, curve):
+        cid = CURVE_IDS[curve] if isinstance(curve, str) else int(curve)
+        c = lib().kzg_pairing_gt_multiple(cid)
+        if c <= 0:
+            raise KeyError(curve)
+        return c
+
+
+PAIRING_GT_MULTIPLE = _GtMultiple()
+
+
+def g2_points_to_limbs(points, limbs):
+    """G2 facade tuples ((x0, x1), (y0, y1), (1, 0)) / infinity with z = (0, 0) -> the C layout (xy uint64[n, 4*limbs]:
+    x.c0 | x.c1 | y.c0 | y.c1, inf uint8[n]).  The points must be normalised."""
+    points = list(points)
+    inf = np.zeros(len(points), dtype=np.uint8)
+    coords = []
+    for i, pt in enumerate(points):
+        z = pt[2]
+        if z == 0 or tuple(z) == (0, 0):
+            inf[i] = 1
+            coords += [0, 0, 0, 0]
+        else:
+            if tuple(z) != (1, 0):
+                raise ValueError("G2 points must be normalised")
+            coords += [int(pt[0][0]), int(pt[0][1]), int(pt[1][0]), int(pt[1][1])]
+    if not coords:
+        return np.zeros((0, 4 * limbs), dtype=np.uint64), inf
+    return np.ascontiguousarray(ints_to_limbs(coords, limbs).reshape(len(points), 4 * limbs)), inf
+
+
+def gt_to_tuple(gt_row, curve_type):
+    """one value of kzg_pairing_product (uint64[12, fp_limbs]) -> the 12-tuple kzg_snark_amd/pairing.py returns:
+    coefficient k of the tower value (a_k + b_k i) becomes entries k = a_k - shift b_k and k + 6 = b_k (its embed_fp2)"""
+    from .pairing import _CURVES
+    pc = _CURVES[curve_type]
+    v = limbs_to_ints(np.ascontiguousarray(gt_row).reshape(12, -1))
+    out = [0] * 12
+    for k in range(6):
+        a, b = v[2 * k], v[2 * k + 1]
+        out[k] = (a - pc.shift * b) % pc.p
+        out[k + 6] = b % pc.p
+    return tuple(out)
 
 
 _contexts = {}

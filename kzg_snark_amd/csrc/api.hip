@@ -161,7 +161,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
   ntt_free_domains(c);
   msm_free_work(c);
   for (DevBuf* b : {&c->ntt_scratch, &c->io, &c->scan_tmp, &c->lagr_tmp, &c->dom_tmp, &c->ver_tmp, &c->rec_tmp,
-                    &c->vpt_tmp,
+                    &c->vpt_tmp, &c->pair_tmp,
                     &c->poly_tmp[0], &c->poly_tmp[1], &c->poly_tmp[2], &c->poly_tmp[3]})
     hipFree(b->p);
   hipFree(c->clk_probe);
@@ -391,6 +391,20 @@ int kzg_g1_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, 
   KZG_ENTER(n && (!xy || !out_status));
   return g1_check_subgroup(c, xy, inf, n, out_status);
 }
+
+int kzg_pairing_check(kzg_ctx* ctx, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                      const uint8_t* g2_inf, size_t m, size_t k, uint8_t* out_status) {
+  KZG_ENTER(m && (!g1_xy || !g2_xy || !out_status));
+  return pairing_product(c, g1_xy, g1_inf, g2_xy, g2_inf, m, k, nullptr, out_status);
+}
+
+int kzg_pairing_product(kzg_ctx* ctx, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                        const uint8_t* g2_inf, size_t m, size_t k, uint64_t* out_gt, uint8_t* out_status) {
+  KZG_ENTER(m && (!g1_xy || !g2_xy || !out_gt || !out_status));
+  return pairing_product(c, g1_xy, g1_inf, g2_xy, g2_inf, m, k, out_gt, out_status);
+}
+
+int kzg_pairing_gt_multiple(int curve) { return pairing_gt_multiple(curve); }
 
 int kzg_blob_to_fr(kzg_ctx* ctx, uint32_t log_n, const uint8_t* blobs, size_t b, int bit_reversed, uint64_t* out_vals,
                    uint8_t* out_status) {

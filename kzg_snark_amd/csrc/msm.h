@@ -163,6 +163,12 @@ int blob_challenges(Ctx* c, uint32_t log_n, const uint8_t* blobs, const uint8_t*
 int blob_challenges_device(Ctx* c, uint32_t log_n, const void* d_blobs, const void* d_commitments, size_t b,
                            void* d_z);
 
+// pairing.hip: m pairing-product equations of k pairs each; the contract is that of
+// kzg_pairing_check (out_gt == nullptr) and kzg_pairing_product.  m = 0 does nothing.
+int pairing_product(Ctx* c, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy, const uint8_t* g2_inf,
+                    size_t m, size_t k, uint64_t* out_gt, uint8_t* out_status);
+int pairing_gt_multiple(int curve);
+
 int open_shard_begin_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                             const uint32_t* z_words, const uint32_t* xi_words, uint64_t* chunk_eval_out);
 int open_shard_finish_device(Ctx* c, const uint32_t* z_words, const uint32_t* carry_words, int first_rank,

@@ -10,6 +10,7 @@ commit and open -- executed by the gfx950 engine through the C ABI.
     check(rk, commitments, z, evaluations, proof, xi) -> bool            kzg.py:161
     batch_check(rk, commitments_list, z_list, evaluations_list, proof_list, xi_list, r=None)   kzg.py:213
     verify_cosets / verify_domain: any number of coset (or single-point) claims folded on the device, two pairings
+    pairing_check / pairing_product: pairing-product equations on the device, the verdict the verifiers below end with
     verify_points / verify_blobs: the same for claims at arbitrary points (blob proofs), evaluate_evaluations_each
     compress_g1 / decompress_g1 / in_subgroup: 48- / 32-byte points and subgroup membership, on the device
     blob_to_kzg_commitment / compute_blob_kzg_proof / verify_blob_kzg_proof_batch: EIP-4844's calls, bytes in and out
@@ -917,6 +918,61 @@ class KZG:
         lhs += [self.neg(p) for p in self._rho_commitment_terms(ck, rho_sum)]
         return self.pairing(self.G2, self._sum_g1(lhs)) == self.pairing(rk_l, self._sum_g1(rhs))
 
+    # ---- pairing-product checks on the device (kzg_pairing_check / kzg_pairing_product) ----------------
+    _PAIRING_MAX_PAIRS = 16
+
+    def _pairing_arrays(self, pairs, who):
+        """one equation [(G1 point, G2 point), ...] or a list of equations -> (single, g1 xy, g1 inf, g2 xy, g2 inf, k)
+        in the C layout; every equation of a call has the same number k of pairs, 1 <= k <= 16"""
+        pairs = list(pairs)
+        single = bool(pairs) and len(pairs[0]) == 2 and len(pairs[0][0]) == 3 and not isinstance(pairs[0][0][0], (tuple, list))
+        eqs = [pairs] if single else [list(e) for e in pairs]
+        if not eqs:
+            return single, None, None, None, None, 0
+        k = len(eqs[0])
+        if not 1 <= k <= self._PAIRING_MAX_PAIRS:
+            raise ValueError(f"{who}: an equation has between 1 and {self._PAIRING_MAX_PAIRS} pairs, not {k}")
+        if any(len(e) != k for e in eqs) or any(len(pr) != 2 for e in eqs for pr in e):
+            raise ValueError(f"{who}: every equation of a call needs the same number of (G1, G2) pairs")
+        L = (self._cv.p.bit_length() + 63) // 64
+        g1_xy, g1_inf = _native.points_to_limbs([pr[0] for e in eqs for pr in e], L, self._g1.normalize)
+        g2_xy, g2_inf = _native.g2_points_to_limbs([self._g2.normalize(pr[1]) for e in eqs for pr in e], L)
+        return single, g1_xy, g1_inf, g2_xy, g2_inf, k
+
+    def pairing_check(self, pairs):
+        """Is the product of e(P_i, Q_i) over the pairs (P_i in G1, Q_i in G2) of an equation one?  pairs: one equation
+        as a list of (G1_point, G2_point) -> bool, or a list of equations (the same number of pairs each, at most 16)
+        -> a list of bools, one wave of the device per equation.  A malformed point (a coordinate >= p, off its curve
+        or twist) gives False.  Membership in the prime-order subgroups is not tested (in_subgroup does it for G1)."""
+        single, g1_xy, g1_inf, g2_xy, g2_inf, k = self._pairing_arrays(pairs, "pairing_check")
+        if k == 0:
+            return []
+        status = self._context().pairing_check(g1_xy, g1_inf, g2_xy, g2_inf, k)
+        out = [int(st) == 0 for st in status]
+        return out[0] if single else out
+
+    def pairing_product(self, pairs):
+        """The value of the product: the 12-tuple pairing() returns, raised to c = _native.PAIRING_GT_MULTIPLE[curve] (1 on
+        BN254, 3 on BLS12-381) -- for one equation, or a list of them for a list of equations.  ValueError for a
+        malformed point."""
+        single, g1_xy, g1_inf, g2_xy, g2_inf, k = self._pairing_arrays(pairs, "pairing_product")
+        if k == 0:
+            return []
+        gt, status = self._context().pairing_product(g1_xy, g1_inf, g2_xy, g2_inf, k)
+        if (status == 2).any():
+            raise ValueError(f"pairing_product: equation {int(np.flatnonzero(status == 2)[0])} has a malformed point")
+        out = [_native.gt_to_tuple(row, self.curve_type) for row in gt]
+        return out[0] if single else out
+
+    def _verdict(self, L_pt, R_pt, g2_right, pairing, who):
+        """e(L, G2) == e(R, g2_right): pairing = "device": one kzg_pairing_check on [(L, G2), (-R, g2_right)];
+        "host": the two pure-Python pairings of pairing.py.  The verdicts are the same."""
+        if pairing == "device":
+            return self.pairing_check([(L_pt, self.G2), (self.neg(R_pt), g2_right)])
+        if pairing == "host":
+            return self.pairing(self.G2, L_pt) == self.pairing(g2_right, R_pt)
+        raise ValueError(f"{who}: pairing must be \"device\" or \"host\", not {pairing!r}")
+
     # ---- bulk verification (device): K claims folded into the two G1 points of one pairing equation -----------------
     _VERIFY_MAX_N = 1 << 21
 
@@ -932,7 +988,7 @@ class KZG:
         return _native.points_to_limbs(points, L, self._g1.normalize)
 
     def verify_cosets(self, ck, rk_l, commitments, commitment_indices, coset_indices, values, proofs, l, N, w=None,
-                      r=None, check_subgroup=False):
+                      r=None, check_subgroup=False, pairing="device"):
         """Cell k claims: the polynomial of commitments[commitment_indices[k]] takes the l values values[k][t] at
         w^(coset_indices[k] + t N/l), t < l, with proof proofs[k] -- open_cosets' numbering; l = 1: single points.
         All claims are combined with weights r^(k+1) (r sampled when not given, as in batch_check) into two G1 points
@@ -942,7 +998,10 @@ class KZG:
         check_subgroup=True first runs commitments and proofs through kzg_g1_check_subgroup on the device and returns
         False when one lies outside the prime-order subgroup: for a point T of the cofactor torsion pi + T satisfies
         the pairing equation whenever pi does, so a verifier of untrusted proofs wants it.  The default skips the
-        test (as check / batch_check do)."""
+        test (as check / batch_check do).  pairing: "device" ends with one kzg_pairing_check on [(L, G2), (-R, rk_l)],
+        "host" with the two Python pairings; the verdict is the same."""
+        if pairing not in ("device", "host"):
+            raise ValueError(f"verify_cosets: pairing must be \"device\" or \"host\", not {pairing!r}")
         self._monomial_key(ck, "verify_cosets")
         l = 1 << self._log2_exact(l, "coset size")
         N = int(N)
@@ -997,9 +1056,10 @@ class KZG:
                 return False
             raise
         L_pt, R_pt = self._points(xy, inf)
-        return self.pairing(self.G2, L_pt) == self.pairing(rk_l, R_pt)
+        return self._verdict(L_pt, R_pt, rk_l, pairing, "verify_cosets")
 
-    def verify_domain(self, ck, rk, commitment, values, proofs, N=None, w=None, r=None, check_subgroup=False):
+    def verify_domain(self, ck, rk, commitment, values, proofs, N=None, w=None, r=None, check_subgroup=False,
+                      pairing="device"):
         """The whole output of open_domain at once: proofs[i] opens `commitment` to values[i] at w^i, i < N (N defaults
         to the number of proofs); rk is setup's tau G2.  verify_cosets with l = 1 (check_subgroup: as there)."""
         if isinstance(values, np.ndarray) and values.dtype == np.uint64:
@@ -1010,7 +1070,7 @@ class KZG:
         N = count if N is None else int(N)
         return self.verify_cosets(ck, rk, [commitment], np.zeros(count, dtype=np.int64),
                                   np.arange(count, dtype=np.int64), values, proofs, 1, N, w=w, r=r,
-                                  check_subgroup=check_subgroup)
+                                  check_subgroup=check_subgroup, pairing=pairing)
 
     # ---- bulk verification at arbitrary points (device): blob batches into the two G1 points of one pairing equation --
     @staticmethod
@@ -1019,13 +1079,15 @@ class KZG:
             raise TypeError(f"{who}: rk must be a G2 point (setup's tau G2)")
 
     def verify_points(self, rk, commitments, commitment_indices, z_list, evaluations, proofs, r=None,
-                      check_subgroup=False):
+                      check_subgroup=False, pairing="device"):
         """Claim k: the polynomial of commitments[commitment_indices[k]] takes the value evaluations[k] at z_list[k]
         -- any field element, the output of open / open_evaluations with xi = 1 or an EIP-4844 blob proof -- with proof
         proofs[k].  All claims are combined with weights r^(k+1) (r sampled when not given, as in batch_check) into two
         G1 points on the device (kzg_verify_points), then pairing(G2, L) == pairing(rk, R) with rk = tau G2.
         proofs / commitments: lists of point tuples or (xy, inf) arrays in the C layout.  A point off the curve: False.
-        No claims: True.  check_subgroup: as in verify_cosets."""
+        No claims: True.  check_subgroup, pairing: as in verify_cosets."""
+        if pairing not in ("device", "host"):
+            raise ValueError(f"verify_points: pairing must be \"device\" or \"host\", not {pairing!r}")
         self._verification_key(rk, "verify_points")
         order = self.curve_order
         comm_idx = np.ascontiguousarray(commitment_indices, dtype=np.int64).reshape(-1)
@@ -1056,9 +1118,10 @@ class KZG:
                 return False
             raise
         L_pt, R_pt = self._points(xy, inf)
-        return self.pairing(self.G2, L_pt) == self.pairing(rk, R_pt)
+        return self._verdict(L_pt, R_pt, rk, pairing, "verify_points")
 
-    def verify_blobs(self, lk_or_w, rk, commitments, value_lists, z_list, proofs, r=None, check_subgroup=False):
+    def verify_blobs(self, lk_or_w, rk, commitments, value_lists, z_list, proofs, r=None, check_subgroup=False,
+                     pairing="device"):
         """A batch of blobs: value_lists[j] (values over the domain of lk_or_w) against commitments[j] at the challenge
         z_list[j] with proof proofs[j] -- verify_blob_kzg_proof_batch of EIP-4844 with the challenges given (the hash
         that derives them is the protocol's).  The claimed values are computed on the device
@@ -1073,7 +1136,7 @@ class KZG:
             return True
         ys = self.evaluate_evaluations_each(lk_or_w, value_lists, z_list)
         return self.verify_points(rk, commitments, np.arange(len(ys), dtype=np.int64), z_list, [int(v) for v in ys],
-                                  proofs, r=r, check_subgroup=check_subgroup)
+                                  proofs, r=r, check_subgroup=check_subgroup, pairing=pairing)
 
     # ---- EIP-4844 blobs as bytes (device intake, SHA-256 challenges on the device): the spec's calls by name ------------
     #      A blob is n elements of 32 big-endian bytes in bit-reversed order over the domain; commitments and proofs are
@@ -1209,7 +1272,7 @@ class KZG:
             h.update(bytes(c) + int(z).to_bytes(32, "big") + int(y).to_bytes(32, "big") + bytes(p))
         return int.from_bytes(h.digest(), "big") % self.curve_order
 
-    def verify_blob_kzg_proof_batch(self, lk_or_w, rk, blobs, commitments, proofs):
+    def verify_blob_kzg_proof_batch(self, lk_or_w, rk, blobs, commitments, proofs, pairing="device"):
         """verify_blob_kzg_proof_batch of EIP-4844: do proofs[j] open commitments[j] to the value of blobs[j] at its
         challenge, for every j?  lk_or_w: a LagrangeKey or the domain's root w (as in verify_blobs); rk: setup's tau G2.
         The blobs are uploaded once and stay on the device: intake, challenges and the values y_j = p_j(z_j)
@@ -1217,9 +1280,12 @@ class KZG:
         Commitments and proofs are decompressed with the subgroup test on the device.  The claims are folded by
         kzg_verify_points with the weights rho^(k+1), rho = SHA-256("RCKZGBATCH___V1_" | n | b | per blob:
         commitment | z | y | proof) mod r: the protocol fixes the verdict, not the weights (the specification's
-        rho^k differ by the common factor rho).  Two pairings.
+        rho^k differ by the common factor rho).  Two pairings: on the device in one kzg_pairing_check
+        (pairing="device"), or pairing.py's on the host ("host"); the verdict is the same.
         False, not an exception: an element >= r, a malformed point, a point off the curve or outside the subgroup, a
         wrong proof.  ValueError: mismatched counts or sizes.  No blobs: True."""
+        if pairing not in ("device", "host"):
+            raise ValueError(f"verify_blob_kzg_proof_batch: pairing must be \"device\" or \"host\", not {pairing!r}")
         self._verification_key(rk, "verify_blob_kzg_proof_batch")
         log_n, w = self._eval_domain(lk_or_w)
         n = 1 << log_n
@@ -1257,4 +1323,4 @@ class KZG:
         out_xy, out_inf = ctx.verify_points(xy[:b], inf[:b], np.arange(b, dtype=np.uint32), zy[0], zy[1], xy[b:],
                                             inf[b:], rho)
         L_pt, R_pt = self._points(out_xy, out_inf)
-        return self.pairing(self.G2, L_pt) == self.pairing(rk, R_pt)
+        return self._verdict(L_pt, R_pt, rk, pairing, "verify_blob_kzg_proof_batch")

@@ -1,14 +1,18 @@
 """Host-side optimal-ate pairing for BN254 and BLS12-381 -- what the reference gets from
 py_ecc's `pairing` (bound at kzg.py:27-35, called as pairing(G2_point, G1_point) at
-kzg.py:208-209 and :285-286).  Verification is O(1): two pairings per check /
-batch_check, not data-parallel, so it stays on the host (SURVEY.md section 2 row 4,
-section 8f N3).
+kzg.py:208-209 and :285-286).  This is the host STATEMENT of the pairing: KZG.pairing, check,
+batch_check, check_coset and batch_check_cosets run it (no GPU needed), and the device pairing
+(csrc/fp_tower.h, kzg_pairing_check / kzg_pairing_product) is tested against its
+values integer by integer; the device verifiers end on the device by default and run this file
+with pairing="host".
 
 Fp12 is the polynomial ring Fp[w]/(w^12 - a*w^6 - b) (BN254: w^6 = 9 + i;
 BLS12-381: w^6 = 1 + u), elements are 12-coefficient lists; G2 points are
 untwisted into E(Fp12) and the Miller loop runs with affine line functions.
 Written from the textbook definitions; results are only ever compared with each
-other (GT equality), never with py_ecc's representation."""
+other (GT equality), never with py_ecc's representation.  On BLS12-381 (u < 0) the loop runs
+over |u| without the final conjugation: the value is the inverse of the textbook one, a bilinear
+non-degenerate pairing all the same, and the device computes this value."""
 
 _BN_P = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 _BLS_P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab

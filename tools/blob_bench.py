@@ -6,7 +6,9 @@ Per b, alternating in one process:
     device_ms      kzg_blob_to_fr_device + kzg_blob_challenges_device on the resident bytes, until z is on the host
     host_hash_ms   hashlib.sha256 over the same blobs, one core: the challenges on the host
     host_intake_ms a numpy intake of the same blobs: byte swap, comparison with r, bit-reversal permutation
-    verify_ms      KZG.verify_blob_kzg_proof_batch end to end from bytes, its two pure-Python pairings included
+    verify_ms      KZG.verify_blob_kzg_proof_batch(pairing="host") end to end from bytes, its two pure-Python pairings
+                   included
+    verify_device_ms   the same call with pairing="device": the verdict from one kzg_pairing_check
     pairings_ms    those two pairings alone (what verify_ms spends after the device is done)
 
     python tools/blob_bench.py [--out DIR] [--reps 5] [--blobs 6,64,1024]
@@ -99,19 +101,22 @@ def main():
             ctx.synchronize()
             return _native.limbs_to_ints(d_z.cpu().numpy().view(np.uint64))
 
-        t = {k: [] for k in ("upload_ms", "device_ms", "host_hash_ms", "host_intake_ms", "verify_ms", "pairings_ms")}
+        t = {k: [] for k in ("upload_ms", "device_ms", "host_hash_ms", "host_intake_ms", "verify_ms", "pairings_ms",
+                             "verify_device_ms")}
         for rep in range(a.reps + 1):
             ms_u, (d_blobs, d_comms) = timed(upload)
             ms_d, z_dev = timed(lambda: device(d_blobs, d_comms))
             ms_h, z_host = timed(lambda: host_hash(blobs, comms))
             ms_i, (vals_host, bad_host) = timed(lambda: host_intake(blobs))
-            ms_v, ok = timed(lambda: kzg.verify_blob_kzg_proof_batch(lk, rk, blobs, comms, proofs))
+            ms_v, ok = timed(lambda: kzg.verify_blob_kzg_proof_batch(lk, rk, blobs, comms, proofs, pairing="host"))
+            ms_vd, ok_dev = timed(lambda: kzg.verify_blob_kzg_proof_batch(lk, rk, blobs, comms, proofs, pairing="device"))
             ms_p, _ = timed(lambda: (kzg.pairing(kzg.G2, kzg.G1), kzg.pairing(rk, kzg.G1)))
             assert z_dev == z_host, f"{b} blobs: the device's challenges differ from hashlib's"
             assert np.array_equal(d_vals.cpu().numpy().view(np.uint64), vals_host) and not bad_host.any()
             assert not d_status.cpu().numpy().any() and ok is True, f"{b} blobs: the batch does not verify"
+            assert ok_dev is True, f"{b} blobs: the batch does not verify with the pairing on the device"
             if rep:
-                for k, v in zip(t, (ms_u, ms_d, ms_h, ms_i, ms_v, ms_p)):
+                for k, v in zip(t, (ms_u, ms_d, ms_h, ms_i, ms_v, ms_p, ms_vd)):
                     t[k].append(v)
         m = {k: statistics.median(v) for k, v in t.items()}
         res["blobs"][str(b)] = {
@@ -123,7 +128,8 @@ def main():
         }
         print(f"{b} blobs: upload {m['upload_ms']:.2f} ms, device {m['device_ms']:.2f} ms, hashlib "
               f"{m['host_hash_ms']:.2f} ms, numpy intake {m['host_intake_ms']:.2f} ms, verify {m['verify_ms']:.1f} ms "
-              f"(pairings {m['pairings_ms']:.1f} ms)", file=sys.stderr, flush=True)
+              f"(pairings {m['pairings_ms']:.1f} ms), with the device pairing {m['verify_device_ms']:.1f} ms",
+              file=sys.stderr, flush=True)
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         with open(os.path.join(a.out, "blob_bench.json"), "w") as f:
