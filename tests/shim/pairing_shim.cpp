@@ -2,7 +2,8 @@
 // interface, with the lanes of a wave replaced by HostLanes' loop around the same interpreter and program, so tests/test_pairing_host.py can compare the tower
 // arithmetic and whole pairings with kzg_snark_amd/pairing.py's integers without a GPU.  Field elements cross the
 // interface as raw limbs in Montgomery form (N words each), so a test chooses the limb image of an operand; points
-// and pairing values cross as canonical 32-bit words, the C ABI's format.  Built plain, with -DKZG_AUDIT (field.h's
+// and pairing values cross as canonical 32-bit words, the C ABI's format.  LockstepLanes is a second exchange that
+// holds a phase to fp_tower.h's contract (no lane reads or writes what another lane of the phase writes).  Built plain, with -DKZG_AUDIT (field.h's
 // pre/postcondition hooks), and with -DPAIRING_SHIM_MAIN as a program of its own for the sanitizers.  Test
 // infrastructure only.
 #include <stdio.h>
@@ -106,6 +107,86 @@ extern "C" int ps_equation(int curve, const uint32_t* g1, const uint8_t* g1_inf,
   return -1;
 }
 
+// The lockstep exchange: a phase with the semantics fp_tower.h's contract assumes -- every lane of a phase starts from
+// the state the phase began with, so a body that reads a slot another lane of the same phase writes sees the OLD value
+// (HostLanes shows it the new one to every later lane, the wave shows it either).  each() snapshots the shared state,
+// and per lane restores the snapshot, runs body(t), and moves the words body(t) changed into the post-state, which it
+// installs after the last lane.  A word changed by two different lanes of one phase is a conflict.  `reverse` runs
+// body(n - 1), ..., body(0): nothing changes under the contract.  Only PairingShared is exchanged: what a body writes
+// elsewhere (out_gt) is written by one lane per word.
+template <class C>
+struct LockstepLanes {
+  using Sh = PairingShared<C>;
+  static constexpr size_t WORDS = sizeof(Sh) / sizeof(uint32_t);
+  static_assert(sizeof(Sh) % sizeof(uint32_t) == 0 && alignof(Sh) == alignof(uint32_t), "PairingShared is 32-bit words");
+  Sh* sh;
+  bool reverse;
+  uint32_t* snap;
+  uint32_t* post;
+  int* owner;
+  unsigned long long conflicts = 0, phases = 0, widest = 0;
+
+  LockstepLanes(Sh* s, bool rev) : sh(s), reverse(rev), snap(new uint32_t[WORDS]), post(new uint32_t[WORDS]),
+                                   owner(new int[WORDS]) {}
+  ~LockstepLanes() { delete[] snap; delete[] post; delete[] owner; }
+  LockstepLanes(const LockstepLanes&) = delete;
+  LockstepLanes& operator=(const LockstepLanes&) = delete;
+
+  template <class Fn>
+  void each(int n, Fn fn) {
+    ++phases;
+    if ((unsigned long long)n > widest) widest = (unsigned long long)n;
+    memcpy(snap, sh, sizeof(Sh));
+    memcpy(post, sh, sizeof(Sh));
+    for (size_t w = 0; w < WORDS; ++w) owner[w] = -1;
+    uint32_t* live = reinterpret_cast<uint32_t*>(sh);     // every member of PairingShared is an array of uint32_t
+    for (int i = 0; i < n; ++i) {
+      const int t = reverse ? n - 1 - i : i;
+      fn(t);                                              // on the snapshot: the words lane t changed are put back below
+      for (size_t w = 0; w < WORDS; ++w) {
+        if (live[w] == snap[w]) continue;
+        if (owner[w] >= 0 && owner[w] != t) ++conflicts;
+        owner[w] = t;
+        post[w] = live[w];
+        live[w] = snap[w];
+      }
+    }
+    memcpy(sh, post, sizeof(Sh));
+  }
+  static uint32_t uniform(uint32_t v) { return v; }
+};
+
+template <class C>
+static int do_equation_lockstep(bool reverse, const uint32_t* g1, const uint8_t* g1_inf, const uint32_t* g2,
+                                const uint8_t* g2_inf, int k, uint32_t* out_gt, unsigned long long* info) {
+  PairingShared<C>* sh = new PairingShared<C>();
+  int st;
+  {
+    LockstepLanes<C> x(sh, reverse);
+    st = Tower<C>::equation(x, sh, g1, g1_inf, g2, g2_inf, k, out_gt);
+    if (info) { info[0] = x.conflicts; info[1] = x.phases; info[2] = x.widest; }
+  }
+  delete sh;
+  return st;
+}
+static int equation_lockstep(bool reverse, int curve, const uint32_t* g1, const uint8_t* g1_inf, const uint32_t* g2,
+                             const uint8_t* g2_inf, int k, uint32_t* out_gt, unsigned long long* info) {
+  if (k < 1 || k > PAIRING_MAX_PAIRS) return -1;
+  if (curve == 0) return do_equation_lockstep<Bn254>(reverse, g1, g1_inf, g2, g2_inf, k, out_gt, info);
+  if (curve == 1) return do_equation_lockstep<Bls12_381>(reverse, g1, g1_inf, g2, g2_inf, k, out_gt, info);
+  return -1;
+}
+// ps_equation through the lockstep exchange; info (may be null): conflicts, phases, the lanes of the widest phase
+extern "C" int ps_equation_lockstep(int curve, const uint32_t* g1, const uint8_t* g1_inf, const uint32_t* g2,
+                                    const uint8_t* g2_inf, int k, uint32_t* out_gt, unsigned long long* info) {
+  return equation_lockstep(false, curve, g1, g1_inf, g2, g2_inf, k, out_gt, info);
+}
+// the same with the lanes of every phase in reverse order
+extern "C" int ps_equation_lockstep_reverse(int curve, const uint32_t* g1, const uint8_t* g1_inf, const uint32_t* g2,
+                                            const uint8_t* g2_inf, int k, uint32_t* out_gt, unsigned long long* info) {
+  return equation_lockstep(true, curve, g1, g1_inf, g2, g2_inf, k, out_gt, info);
+}
+
 #ifdef KZG_AUDIT_ON
 extern "C" void ps_audit_reset(int lift) { audit::state() = audit::State{0, "", "", 0, lift != 0}; }
 extern "C" unsigned long long ps_audit_read(char* fn, char* what, int cap, int* line) {
@@ -118,7 +199,8 @@ extern "C" unsigned long long ps_audit_read(char* fn, char* what, int cap, int* 
 #endif
 
 #ifdef PAIRING_SHIM_MAIN
-// The drivers above on inputs made here: e(G1, G2) is not one; e(G1, G2) e(-G1, G2) is; an infinity flag skips a pair;
+// The drivers above on inputs made here: e(G1, G2) is not one; e(G1, G2) e(-G1, G2) is, through the lockstep exchange
+// as well (its snapshots and merges run under the sanitizers here); an infinity flag skips a pair;
 // a G2 point off the twist and a coordinate equal to p give status 2 and a zeroed value; a a^-1 = 1, (a^p)^p = a^(p^2),
 // a sparse product equals the full one, on tower values made from the limbs of p.
 static int fails = 0;
@@ -135,6 +217,12 @@ static void self_test(int curve, const uint32_t* g1, const uint32_t* neg_y, cons
   memcpy(q, g2, 16 * NW); memcpy(q + 4 * NW, g2, 16 * NW);
   EXPECT(ps_equation(curve, p1, nullptr, q, nullptr, 1, gt) == 1);
   EXPECT(ps_equation(curve, p1, nullptr, q, nullptr, 2, gt2) == 0 && gt2[0] == 1 && gt2[1] == 0 && gt2[2 * NW] == 0);
+  // the same equation through the lockstep exchange: no word written twice in a phase, the widest phase is an Fp12
+  // product's 36 lanes, and the value is the sequential one
+  unsigned long long info[3] = {9, 0, 0};
+  memset(gt2, 0xff, sizeof(gt2));
+  EXPECT(ps_equation_lockstep(curve, p1, nullptr, q, nullptr, 2, gt2, info) == 0 && gt2[0] == 1 && gt2[1] == 0 &&
+         gt2[2 * NW] == 0 && info[0] == 0 && info[1] > 1000 && info[2] == 36);
   inf[1] = 1;
   EXPECT(ps_equation(curve, p1, inf, q, nullptr, 2, gt2) == 1 && memcmp(gt, gt2, sizeof(gt)) == 0);
   inf[0] = 1;

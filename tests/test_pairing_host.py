@@ -3,7 +3,9 @@ the lanes of a wave replaced by a loop) against kzg_snark_amd/pairing.py's integ
 by operation, then whole pairings.  A tower value sum (a_k + b_k i) w^k is pairing.py's coefficient list with entry
 k = a_k - shift b_k and entry k + 6 = b_k (its embed_fp2), so values are compared integer by integer.  The shim runs
 plain and with -DKZG_AUDIT (field.h's column and precondition hooks must stay silent, with every multiplier returning
-the representative in [p, 2p)), and once as a program of its own under the address and undefined-behaviour sanitizers."""
+the representative in [p, 2p)), and once as a program of its own under the address and undefined-behaviour sanitizers.
+Whole equations also run through the shim's lockstep exchange, which holds every phase to the header's contract (no lane
+reads or writes what another lane of the phase writes) at the pair counts whose phases pass a wave's 64 lanes."""
 import ctypes
 import os
 import random
@@ -197,18 +199,25 @@ def words(ints, nw):
     return (U32 * len(flat))(*flat)
 
 
-def equation(shim, lay, pairs):
-    """pairs: [(G1 tuple, G2 tuple)] -> (status, pairing.py-shaped value)"""
+def equation(shim, lay, pairs, entry="ps_equation"):
+    """pairs: [(G1 tuple, G2 tuple)] -> (status, pairing.py-shaped value); a point at infinity (z = 0) travels as its
+    flag beside zero coordinates, and the flag arrays are NULL when no point of their side is one.  entry: ps_equation
+    (HostLanes), or ps_equation_lockstep / ps_equation_lockstep_reverse, which add (conflicts, phases, widest phase)."""
     nw = lay.nw
-    g1 = words([c for P, _ in pairs for c in (P[0], P[1])], nw)
-    g2 = words([c for _, Q in pairs for c in (Q[0][0], Q[0][1], Q[1][0], Q[1][1])], nw)
+    inf1 = [P[2] == 0 for P, _ in pairs]
+    inf2 = [Q[2] in (0, (0, 0)) for _, Q in pairs]
+    g1 = words([0 if f else c for (P, _), f in zip(pairs, inf1) for c in (P[0], P[1])], nw)
+    g2 = words([0 if f else c for (_, Q), f in zip(pairs, inf2) for c in (Q[0][0], Q[0][1], Q[1][0], Q[1][1])], nw)
+    flags = [(ctypes.c_uint8 * len(pairs))(*f) if any(f) else None for f in (inf1, inf2)]
     out = (U32 * (12 * nw))()
-    st = shim.lib.ps_equation(lay.cid, g1, None, g2, None, len(pairs), out)
+    info = (ctypes.c_ulonglong * 3)(99, 0, 0)
+    extra = () if entry == "ps_equation" else (info,)
+    st = getattr(shim.lib, entry)(lay.cid, g1, flags[0], g2, flags[1], len(pairs), out, *extra)
     v = [sum(int(out[i * nw + j]) << (32 * j) for j in range(nw)) for i in range(12)]
     val = [0] * 12
     for k in range(6):
         val[k], val[k + 6] = (v[2 * k] - lay.shift * v[2 * k + 1]) % lay.p, v[2 * k + 1]
-    return st, tuple(val)
+    return (st, tuple(val), *([tuple(info)] if extra else []))
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -230,8 +239,112 @@ def test_pairing_values_and_bilinearity(shim, name):
     shim.assert_clean()
 
 
+# ---- the phase contract: whole equations through the shim's lockstep exchange -----------------------------------------
+# fp_tower.h: "a body never reads a slot that another lane writes in the same phase".  HostLanes cannot see a violation
+# (the later lane reads the new value and the result is whatever the author saw); on the wave it is a race.  Under
+# LockstepLanes every lane of a phase starts from the state the phase began with, so a body that reads a neighbour's
+# write computes with the old value and the equation's value leaves pairing.py's; two lanes that write one word are
+# counted.  The per-pair product phases are k * jobs lanes wide, jobs up to 6: past the 64 lanes of a wave from k = 11
+# (66, the 6-job phases) and, for the 5-job phase, from k = 13 (65) -- the widest phase reported back shows the run was
+# that wide.  Equations close by the trapdoor: (a_i G1, b_i G2) and one closing pair -(sum a_i b_i - S) G1, G2 give
+# e(G1, G2)^S.
+HOST_POOL = 8
+
+
+class HostPool:
+    def __init__(self, name):
+        self.cv = cv = C.CURVES[name]
+        self.G1, self.G2 = C.g1_group(cv), C.g2_group(cv)
+        self.g1, self.g2 = (cv.g1[0], cv.g1[1], 1), (cv.g2[0], cv.g2[1], (1, 0))
+        rng = random.Random(97 + CURVE_IDS[name])
+        self.a = [rng.randrange(1, cv.r) for _ in range(HOST_POOL)]
+        self.b = [rng.randrange(1, cv.r) for _ in range(HOST_POOL)]
+        self.A = [self.G1.multiply(self.g1, a) for a in self.a]
+        self.B = [self.G2.multiply(self.g2, b) for b in self.b]
+        self.S = rng.randrange(1, cv.r)
+        self._host = {}
+
+    def picks(self, k):                          # the indices (i, j) of the k - 1 pairs before the closing one
+        return [(t % HOST_POOL, (3 * t + 1) % HOST_POOL) for t in range(k - 1)]
+
+    def closed(self, k, delta=0, skip1=(), skip2=()):
+        """k pairs with the product e(G1, G2)^delta: pair t is (a_i G1, b_j G2), with G1 at infinity for t in skip1 and
+        G2 for t in skip2, and the last pair closes the ones that are left"""
+        idx = self.picks(k)
+        total = sum(self.a[i] * self.b[j] for t, (i, j) in enumerate(idx) if t not in skip1 and t not in skip2)
+        pairs = [(self.G1.Z if t in skip1 else self.A[i], self.G2.Z if t in skip2 else self.B[j])
+                 for t, (i, j) in enumerate(idx)]
+        return pairs + [(self.G1.neg(self.G1.multiply(self.g1, (total - delta) % self.cv.r)), self.g2)]
+
+    def host(self, P, Q):                        # pairing.py's value, computed once per pair of points
+        if (P, Q) not in self._host:
+            self._host[P, Q] = list(PR.pairing(Q, P, self.cv))
+        return self._host[P, Q]
+
+
+@lru_cache(maxsize=None)
+def host_pool(name):
+    return HostPool(name)
+
+
+def run_lockstep(shim, lay, pairs, status, value, widest=None):
+    """the equation under LockstepLanes, lanes in both orders: no word written by two lanes of a phase, and the status
+    and value that pairing.py's algebra gives -- which HostLanes' loop gives too"""
+    k = len(pairs)
+    widest = (36 if k <= 6 else 6 * k) if widest is None else widest
+    value = tuple(value)
+    st, val, (conflicts, phases, wide) = equation(shim, lay, pairs, "ps_equation_lockstep")
+    assert conflicts == 0 and st == status and val == value, (k, conflicts, st)
+    assert wide == widest and phases > 1000, (k, wide, phases)
+    rst, rval, (rconflicts, rphases, rwide) = equation(shim, lay, pairs, "ps_equation_lockstep_reverse")
+    assert (rconflicts, rst, rval, rphases, rwide) == (0, st, val, phases, wide), (k, rconflicts, rst)
+    assert equation(shim, lay, pairs) == (st, val), k
+    shim.assert_clean()
+
+
+@pytest.mark.parametrize("k", [1, 2, 11, 13, 16])
+@pytest.mark.parametrize("name", NAMES)
+def test_phase_contract_under_lockstep_lanes(shim, name, k):
+    lay, pool = layout(name), host_pool(name)
+    K = lay.K
+    c = shim.lib.ps_gt_multiple(lay.cid)
+    if k == 1:
+        P, Q = pool.A[0], pool.B[1]
+        run_lockstep(shim, lay, [(P, Q)], 1, K.pow(pool.host(P, Q), c))
+    else:
+        run_lockstep(shim, lay, pool.closed(k), 0, K.one)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_phase_contract_with_skipped_pairs(shim, name):
+    lay, pool = layout(name), host_pool(name)
+    K = lay.K
+    c = shim.lib.ps_gt_multiple(lay.cid)
+    k = 11
+    # pair 0 skipped by its G1 flag, pair 5 by its G2 flag, the closing pair sums the live ones: idle lanes inside the
+    # 66-lane phases, among them lane 0 and lanes of the wrapped range's pair
+    run_lockstep(shim, lay, pool.closed(k, skip1=(0,), skip2=(5,)), 0, K.one)
+    # only the last pair live (lanes 60 .. 65 of a 6-job phase): its pairing, as at k = 1
+    P, Q = pool.A[0], pool.B[1]
+    alone = [(pool.G1.Z, pool.B[t % HOST_POOL]) if t % 2 else (pool.A[t % HOST_POOL], pool.G2.Z) for t in range(k - 1)]
+    run_lockstep(shim, lay, alone + [(P, Q)], 1, K.pow(pool.host(P, Q), c))
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_a_value_that_is_not_one_at_eleven_pairs(shim, name):
+    """the product of k = 11 pairs is E^(c S), E = pairing.py's e(G1, G2), S != 0: a value past k = 2 that one wrong
+    line or one pair's lost lane would change"""
+    lay, pool = layout(name), host_pool(name)
+    c = shim.lib.ps_gt_multiple(lay.cid)
+    E = pool.host(pool.g1, pool.g2)
+    want = lay.K.pow(E, c * pool.S % pool.cv.r)
+    assert want != lay.K.one
+    run_lockstep(shim, lay, pool.closed(11, delta=pool.S), 1, want)
+
+
 def test_shim_under_address_and_undefined_behaviour_sanitizers(tmp_path):
-    """pairing_shim.cpp with its own main(): pairings of the generators (e(G1, G2) e(-G1, G2) = 1, infinity flags,
+    """pairing_shim.cpp with its own main(): pairings of the generators (e(G1, G2) e(-G1, G2) = 1 -- under HostLanes and
+    under the lockstep exchange, whose snapshot code so runs under the sanitizers --, infinity flags,
     malformed points) and the tower operations on both curves, built with -DKZG_AUDIT and
     -fsanitize=address,undefined (no recovery, static runtimes) and run as a program of its own.  Exit status 0 = no
     sanitizer report, no audit violation, every check of the program passed."""
