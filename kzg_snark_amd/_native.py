@@ -674,8 +674,9 @@ class Context:
         lens_a = np.asarray(lens, dtype=np.uint64)
         _check_out(out_xy, np.uint64, len(lens) * 2 * self.fp_limbs, "out_xy")
         _check_out(out_inf, np.uint8, len(lens), "out_inf")
-        # the library adopts the host pointers only once the work is queued (msm.hip): on an error nothing points
-        # at these arrays, so they are recorded after the call has returned KZG_OK
+        # the library adopts the host pointers only once the work is queued, and every failure after that leaves
+        # through a flush (commit_t in msm.hip, kzg_commit in api.hip): when a call returns non-zero, no pipeline slot
+        # points at these arrays, so they are recorded after the call has returned KZG_OK
         self._check(lib().kzg_commit_device_async(self._h, srs._h, _as_vp(d_scalars), _as_vp(lens_a), len(lens),
                                                   stride, _as_vp(out_xy), _as_vp(out_inf)))
         self._inflight.append((srs, out_xy, out_inf))

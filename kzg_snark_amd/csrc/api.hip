@@ -470,14 +470,15 @@ int kzg_commit(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* scalars, const 
     if (lens[p] > srs->s->n) return set_err(c, KZG_ERR_DEGREE, "polynomial longer than the commitment key");
     if (lens[p] > stride) return set_err(c, KZG_ERR_ARG, "kzg_commit: lens[p] > stride");
   }
-  for (size_t p = 0; p < n_polys; ++p) {
+  for (size_t p = 0; p < n_polys && rc == KZG_OK; ++p) {
     if (lens[p])
-      KZG_HIP(c, hipMemcpyAsync(io + p * stride * 8, scalars + p * stride * 4, lens[p] * 32, hipMemcpyHostToDevice,
-                                c->stream));
-    rc = commit_device(c, srs->s, io + p * stride * 8, lens + p, 1, stride, out_xy + p * 2 * fpw, out_inf + p, false);
-    if (rc) { commit_flush(c); return rc; }
+      rc = KZG_HIP_RC(c, hipMemcpyAsync(io + p * stride * 8, scalars + p * stride * 4, lens[p] * 32,
+                                        hipMemcpyHostToDevice, c->stream));
+    if (rc == KZG_OK)
+      rc = commit_device(c, srs->s, io + p * stride * 8, lens + p, 1, stride, out_xy + p * 2 * fpw, out_inf + p, false);
   }
-  return commit_flush(c);
+  const int rc2 = commit_flush(c);                     // also on an error: nothing may point at out_xy / out_inf afterwards
+  return rc ? rc : rc2;
 }
 
 int kzg_open_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,

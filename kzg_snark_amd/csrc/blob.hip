@@ -70,7 +70,6 @@ __global__ __launch_bounds__(CHALLENGE_TB) void blob_challenge_kernel(const uint
   st_words<8>(z + (size_t)j * 8, w);
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // enqueue only
@@ -96,18 +95,18 @@ int challenge_launch(Ctx* c, uint32_t log_n, const uint32_t* d_blobs, const uint
 template <class F>
 int blob_to_fr_t(Ctx* c, uint32_t log_n, const uint8_t* blobs, size_t b, int bit_reversed, uint64_t* out_vals,
                  uint8_t* out_status) {
-  const size_t bytes = (b << log_n) * 32;                // staged as blobs | values | statuses
-  int rc = ensure_buf(c, c->io, 2 * bytes + up256(b));
+  const size_t bytes = (b << log_n) * 32;
+  uint32_t *d_blobs, *d_vals;
+  uint8_t* d_status;
+  int rc = carve(c, c->io,
+                 [&](Carve& ws) { d_blobs = ws.take(bytes);  d_vals = ws.take(bytes);  d_status = ws.take<uint8_t>(b); });
   if (rc) return rc;
-  char* d = static_cast<char*>(c->io.p);
   {
     ProfScope span(c, "blob_intake");
-    KZG_HIP(c, hipMemcpyAsync(d, blobs, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = intake_launch<F>(c, log_n, reinterpret_cast<const uint32_t*>(d), b, bit_reversed,
-                               reinterpret_cast<uint32_t*>(d + bytes), reinterpret_cast<uint8_t*>(d + 2 * bytes))))
-      return rc;
-    KZG_HIP(c, hipMemcpyAsync(out_vals, d + bytes, bytes, hipMemcpyDeviceToHost, c->stream));
-    KZG_HIP(c, hipMemcpyAsync(out_status, d + 2 * bytes, b, hipMemcpyDeviceToHost, c->stream));
+    KZG_HIP(c, hipMemcpyAsync(d_blobs, blobs, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = intake_launch<F>(c, log_n, d_blobs, b, bit_reversed, d_vals, d_status))) return rc;
+    KZG_HIP(c, hipMemcpyAsync(out_vals, d_vals, bytes, hipMemcpyDeviceToHost, c->stream));
+    KZG_HIP(c, hipMemcpyAsync(out_status, d_status, b, hipMemcpyDeviceToHost, c->stream));
   }
   KZG_HIP(c, hipStreamSynchronize(c->stream));
   return KZG_OK;
@@ -117,19 +116,17 @@ template <class C>
 int blob_challenges_t(Ctx* c, uint32_t log_n, const uint8_t* blobs, const uint8_t* commitments, size_t b,
                       uint64_t* out_z) {
   constexpr size_t G = G1Bytes<C>::SIZE;
-  const size_t bytes = (b << log_n) * 32, cb = up256(b * G);          // staged as blobs | commitments | challenges
-  int rc = ensure_buf(c, c->io, bytes + cb + b * 32);
+  const size_t bytes = (b << log_n) * 32;
+  uint32_t *d_blobs, *d_comms, *d_z;
+  int rc = carve(c, c->io,
+                 [&](Carve& ws) { d_blobs = ws.take(bytes);  d_comms = ws.take(b * G);  d_z = ws.take(b * 32); });
   if (rc) return rc;
-  char* d = static_cast<char*>(c->io.p);
   {
     ProfScope span(c, "blob_challenge");
-    KZG_HIP(c, hipMemcpyAsync(d, blobs, bytes, hipMemcpyHostToDevice, c->stream));
-    KZG_HIP(c, hipMemcpyAsync(d + bytes, commitments, b * G, hipMemcpyHostToDevice, c->stream));
-    if ((rc = challenge_launch<C>(c, log_n, reinterpret_cast<const uint32_t*>(d),
-                                  reinterpret_cast<const uint32_t*>(d + bytes), b,
-                                  reinterpret_cast<uint32_t*>(d + bytes + cb))))
-      return rc;
-    KZG_HIP(c, hipMemcpyAsync(out_z, d + bytes + cb, b * 32, hipMemcpyDeviceToHost, c->stream));
+    KZG_HIP(c, hipMemcpyAsync(d_blobs, blobs, bytes, hipMemcpyHostToDevice, c->stream));
+    KZG_HIP(c, hipMemcpyAsync(d_comms, commitments, b * G, hipMemcpyHostToDevice, c->stream));
+    if ((rc = challenge_launch<C>(c, log_n, d_blobs, d_comms, b, d_z))) return rc;
+    KZG_HIP(c, hipMemcpyAsync(out_z, d_z, b * 32, hipMemcpyDeviceToHost, c->stream));
   }
   KZG_HIP(c, hipStreamSynchronize(c->stream));
   return KZG_OK;

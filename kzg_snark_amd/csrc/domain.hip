@@ -357,32 +357,26 @@ int domain_table_t(Ctx* c, const Srs* mono, uint32_t log_n, uint32_t log_l, cons
   if (mono->n < n) return set_err(c, KZG_ERR_ARG, (std::string(fn) + ": monomial key shorter than the domain").c_str());
   const Fe<F> omega = dom_omega<C>(log_mm);
   if (!primitive_root<F>(omega, log_mm)) return set_err(c, KZG_ERR_ARG, (std::string(fn) + ": no 2m-th root").c_str());
-  DomainTable* t = new DomainTable();
+  DomainTablePtr t(new DomainTable());
   t->curve = c->curve;
   t->log_n = log_n;
   t->log_l = log_l;
   t->n = n;
-  uint32_t* d_buf = nullptr;
-  auto fail = [&](int code) { hipFree(d_buf); hipFree(t->d_tbl); delete t; return code; };
+  DevTmp<uint32_t> d_buf;
   if (hipMalloc(reinterpret_cast<void**>(&t->d_tbl), (size_t)nn * Tbl<C>::WORDS * 4) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&d_buf), (size_t)nn * xyzz_bytes<C>()) != hipSuccess)
-    return fail(set_err(c, KZG_ERR_ALLOC, "hipMalloc(domain table)"));
+      d_buf.alloc((size_t)nn * xyzz_bytes<C>()) != hipSuccess)
+    return set_err(c, KZG_ERR_ALLOC, "hipMalloc(domain table)");
   {
     ProfScope ps(c, span);
     hipLaunchKernelGGL(dom_load_key_kernel<C>, dim3((nn + 127) / 128), dim3(128), 0, c->stream, mono->recs, m, log_l,
-                       log_mm, d_buf);
-    int rc = launch_levels(c, d_buf, 1u << log_l, log_mm, fr_arg<F>(omega));
-    if (rc) return fail(rc);
-    hipLaunchKernelGGL(dom_finish_table_kernel<C>, dim3((nn + 63) / 64), dim3(64), 0, c->stream, d_buf, nn,
+                       log_mm, d_buf.get());
+    if (int rc = launch_levels(c, d_buf, 1u << log_l, log_mm, fr_arg<F>(omega))) return rc;
+    hipLaunchKernelGGL(dom_finish_table_kernel<C>, dim3((nn + 63) / 64), dim3(64), 0, c->stream, d_buf.get(), nn,
                        t->d_tbl);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, "domain table", e));
+    KZG_HIP(c, hipGetLastError());
   }
-  hipError_t e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, "domain table", e));
-  hipFree(d_buf);
-  d_buf = nullptr;
-  *out = t;
+  KZG_HIP(c, hipStreamSynchronize(c->stream));
+  *out = t.release();
   return KZG_OK;
 }
 

@@ -88,7 +88,6 @@ __global__ __launch_bounds__(256) void g1_compress_kernel(const uint32_t* xy, co
   st_words<NW>(bytes + i * NW, raw);
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline uint32_t blocks_of(size_t n) { return (uint32_t)((n + 255) / 256); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -118,16 +117,13 @@ struct Stage {
 template <class C>
 int stage(Ctx* c, size_t n, Stage* s) {
   constexpr size_t SIZE = G1Bytes<C>::SIZE;
-  const size_t b0 = up256(n * SIZE), b1 = up256(n * 2 * SIZE), b2 = up256(n);
-  int rc = ensure_buf(c, c->io, b0 + b1 + 2 * b2 + 256);
-  if (rc) return rc;
-  char* p = static_cast<char*>(c->io.p);
-  s->bytes = reinterpret_cast<uint32_t*>(p);
-  s->xy = reinterpret_cast<uint32_t*>(p + b0);
-  s->inf = reinterpret_cast<uint8_t*>(p + b0 + b1);
-  s->status = reinterpret_cast<uint8_t*>(p + b0 + b1 + b2);
-  s->bad = reinterpret_cast<uint32_t*>(p + b0 + b1 + 2 * b2);
-  return KZG_OK;
+  return carve(c, c->io, [&](Carve& ws) {
+    s->bytes = ws.take(n * SIZE);
+    s->xy = ws.take(n * 2 * SIZE);
+    s->inf = ws.take<uint8_t>(n);
+    s->status = ws.take<uint8_t>(n);
+    s->bad = ws.take(4);
+  });
 }
 
 template <class C>

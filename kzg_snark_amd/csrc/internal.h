@@ -3,7 +3,7 @@
 // recover.hip, g1_bytes.hip, verify_points.hip, blob.hip, pairing.hip): the context, error and profiling plumbing, the dispatch by curve (KZG_BY_CURVE,
 // KZG_BY_FR) and the entry points of ntt.hip and poly.hip.  Shared device helpers live in fr_util.h (one Fr element,
 // the power-table lookup), g1_util.h (word arrays, XYZZ points), g1_words.h (point <-> canonical words) and
-// srs_rec.h (key records).
+// srs_rec.h (key records); devmem.h owns device temporaries and carves the scratch buffers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "field.h"
+#include "devmem.h"
 
 namespace kzg {
 
@@ -45,11 +46,6 @@ struct ProfSpan {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
   double total_ms = 0;
   uint64_t count = 0;
-};
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
 };
 
 // words of Ctx::clk_probe
@@ -121,13 +117,15 @@ struct ProfScope {
   ProfScope(Ctx* ctx, const char* name, hipStream_t stream = nullptr);
   ~ProfScope();
 };
-int ensure_buf(Ctx* c, DevBuf& b, size_t bytes);
 
 #define KZG_HIP(c, call)                                         \
   do {                                                           \
     hipError_t e__ = (call);                                     \
     if (e__ != hipSuccess) return set_err((c), KZG_ERR_HIP, #call, e__); \
   } while (0)
+// the same as a value, KZG_OK or the recorded error, for a function that has to reach its own exit
+#define KZG_HIP_RC(c, call) hip_rc((c), (call), #call)
+inline int hip_rc(Ctx* c, hipError_t e, const char* what) { return e == hipSuccess ? KZG_OK : set_err(c, KZG_ERR_HIP, what, e); }
 
 // Call-through by the context's curve: fn<Bn254 | Bls12_381>(args) for code over the curve, fn<BnFr | BlsFr>(args) for
 // code over the scalar field alone.

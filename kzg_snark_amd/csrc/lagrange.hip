@@ -364,33 +364,27 @@ int srs_generate_lagrange_t(Ctx* c, const uint32_t* tau_words, uint32_t log_n, c
     return set_err(c, KZG_ERR_ARG, "Lagrange key: w is not a primitive root");
   const uint32_t n = 1u << log_n;
   ProfScope ps(c, "srs_lagrange");
-  uint32_t *d_wpow = nullptr, *d_tmp = nullptr;
-  auto cleanup = [&]() { hipFree(d_wpow); hipFree(d_tmp); };
-  if (hipMalloc(reinterpret_cast<void**>(&d_wpow), (size_t)n * 32) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&d_tmp), (size_t)n * 3 * 32) != hipSuccess) {
-    cleanup();
+  DevTmp<uint32_t> d_wpow, d_tmp;
+  if (d_wpow.alloc((size_t)n * 32) != hipSuccess || d_tmp.alloc((size_t)n * 3 * 32) != hipSuccess)
     return set_err(c, KZG_ERR_ALLOC, "hipMalloc(Lagrange key)");
-  }
   uint32_t *d_den = d_tmp, *d_inv = d_tmp + (size_t)n * 8, *d_sc = d_tmp + (size_t)n * 16;
   int rc = launch_wpow<F>(c, n, w_words, d_wpow);
-  if (rc) { cleanup(); return rc; }
+  if (rc) return rc;
   const Fe<F> ts = Fd::from_words(tau_words);
   bool in_domain = false;
   const Fe<F> cz = vanishing_over_n<F>(Fd::to_mont(ts), log_n, &in_domain);
   const uint32_t grid = (n + 255) / 256;
-  hipLaunchKernelGGL(lagr_denom_kernel<F>, dim3(grid), dim3(256), 0, c->stream, n, d_wpow, fr_arg<F>(ts), d_den);
-  if ((rc = fr_vec_inverse(c, n, d_den, d_inv))) { cleanup(); return rc; }
-  hipLaunchKernelGGL(lagr_basis_scalars_kernel<F>, dim3(grid), dim3(256), 0, c->stream, n, d_wpow, d_inv,
+  hipLaunchKernelGGL(lagr_denom_kernel<F>, dim3(grid), dim3(256), 0, c->stream, n, d_wpow.get(), fr_arg<F>(ts), d_den);
+  if ((rc = fr_vec_inverse(c, n, d_den, d_inv))) return rc;
+  hipLaunchKernelGGL(lagr_basis_scalars_kernel<F>, dim3(grid), dim3(256), 0, c->stream, n, d_wpow.get(), d_inv,
                      fr_arg<F>(cz), d_sc);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { cleanup(); return set_err(c, KZG_ERR_HIP, "Lagrange scalars", e); }
+  KZG_HIP(c, hipGetLastError());
   Srs* s = nullptr;
-  if ((rc = srs_generate_scalars(c, d_sc, n, &s))) { cleanup(); return rc; }   // synchronises
-  hipFree(d_tmp);
+  if ((rc = srs_generate_scalars(c, d_sc, n, &s))) return rc;   // synchronises
   s->basis = SRS_LAGRANGE;
   s->log_n = log_n;
   memcpy(s->w, w_words, 32);
-  s->d_wpow = d_wpow;
+  s->d_wpow = d_wpow.release();
   *out = s;
   return KZG_OK;
 }
@@ -406,37 +400,34 @@ int srs_lagrange_t(Ctx* c, const Srs* mono, uint32_t log_n, const uint32_t* w_wo
   if (mono->n < n) return set_err(c, KZG_ERR_ARG, "kzg_srs_lagrange: monomial key shorter than the domain");
   if (!primitive_root<F>(mont_from_words<F>(w_words), log_n))
     return set_err(c, KZG_ERR_ARG, "Lagrange key: w is not a primitive root");
-  Srs* s = nullptr;
+  SrsPtr s;
   int rc = srs_create(c, n, &s);
   if (rc) return rc;
-  uint32_t* d_buf = nullptr;
-  auto fail = [&](int code) { hipFree(d_buf); srs_free(s); return code; };
-  if (hipMalloc(reinterpret_cast<void**>(&s->d_wpow), (size_t)n * 32) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&d_buf), (size_t)n * 4 * C::Fp::N * 4) != hipSuccess)
-    return fail(set_err(c, KZG_ERR_ALLOC, "hipMalloc(Lagrange key)"));
   {
-    ProfScope ps(c, "srs_lagrange");
-    if ((rc = launch_wpow<F>(c, n, w_words, s->d_wpow))) return fail(rc);
-    const Fe<F> winv = Fd::inv(mont_from_words<F>(w_words));
-    LgWords ninv;
-    words_from_mont<F>(inv_pow2<F>(log_n), ninv.w);
-    hipLaunchKernelGGL(g1_intt_load_kernel<C>, dim3((n + 127) / 128), dim3(128), 0, c->stream, mono->recs, n, log_n,
-                       d_buf);
-    if ((rc = launch_levels(c, d_buf, 1, log_n, fr_arg<F>(winv)))) return fail(rc);
-    hipLaunchKernelGGL(g1_intt_finish_kernel<C>, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_buf, n, ninv,
-                       s->recs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, "G1 inverse NTT", e));
-  }
-  hipError_t e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, "G1 inverse NTT", e));
-  hipFree(d_buf);
-  d_buf = nullptr;
+    DevTmp<uint32_t> d_buf;
+    if (hipMalloc(reinterpret_cast<void**>(&s->d_wpow), (size_t)n * 32) != hipSuccess ||
+        d_buf.alloc((size_t)n * 4 * C::Fp::N * 4) != hipSuccess)
+      return set_err(c, KZG_ERR_ALLOC, "hipMalloc(Lagrange key)");
+    {
+      ProfScope ps(c, "srs_lagrange");
+      if ((rc = launch_wpow<F>(c, n, w_words, s->d_wpow))) return rc;
+      const Fe<F> winv = Fd::inv(mont_from_words<F>(w_words));
+      LgWords ninv;
+      words_from_mont<F>(inv_pow2<F>(log_n), ninv.w);
+      hipLaunchKernelGGL(g1_intt_load_kernel<C>, dim3((n + 127) / 128), dim3(128), 0, c->stream, mono->recs, n, log_n,
+                         d_buf.get());
+      if ((rc = launch_levels(c, d_buf, 1, log_n, fr_arg<F>(winv)))) return rc;
+      hipLaunchKernelGGL(g1_intt_finish_kernel<C>, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_buf.get(), n, ninv,
+                         s->recs);
+      KZG_HIP(c, hipGetLastError());
+    }
+    KZG_HIP(c, hipStreamSynchronize(c->stream));
+  }                                                      // the transform's buffer goes before the windows are built
   s->basis = SRS_LAGRANGE;
   s->log_n = log_n;
   memcpy(s->w, w_words, 32);
-  if ((rc = srs_finish_windows(c, s))) return fail(rc);
-  *out = s;
+  if ((rc = srs_finish_windows(c, s.get()))) return rc;
+  *out = s.release();
   return KZG_OK;
 }
 

@@ -22,6 +22,8 @@ struct Srs {
 constexpr int SRS_MONOMIAL = 0;
 constexpr int SRS_LAGRANGE = 1;
 
+void srs_free(Srs* s);
+using SrsPtr = Owned<Srs, srs_free>;            // a key under construction: freed unless release()d to the caller
 int srs_load(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, Srs** out);
 // the same from points already on the device: canonical words x | y per point, flags or null (g1_bytes.hip)
 int srs_load_device(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n, Srs** out);
@@ -36,11 +38,10 @@ __attribute__((visibility("hidden")))   // library-private: not in the exported 
 int g1_import(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n, bool range, uint32_t* d_recs,
               uint32_t* d_bad);
 int srs_export(Ctx* c, const Srs* s, size_t start, size_t count, uint64_t* xy, uint8_t* inf);
-void srs_free(Srs* s);
 // record i = scalars[i] * G1 (device vector of n canonical scalars), windows built; synchronises
 int srs_generate_scalars(Ctx* c, const uint32_t* d_scalars, size_t n, Srs** out);
 // an n-point key whose window-0 records the caller fills, then srs_finish_windows (synchronises)
-int srs_create(Ctx* c, size_t n, Srs** out);
+int srs_create(Ctx* c, size_t n, SrsPtr* out);
 int srs_finish_windows(Ctx* c, Srs* s);
 // `out` becomes a key of n points over caller-owned window-0 records and NO further window (nothing is allocated, the
 // caller keeps `recs` alive and never calls srs_free on it): good for commits whose scalars are all below
@@ -73,6 +74,7 @@ int launch_levels(Ctx* c, uint32_t* d_buf, uint32_t nvec, uint32_t log_len, cons
 struct DomainTable;
 int domain_table_create(Ctx* c, const Srs* mono, uint32_t log_n, DomainTable** out);
 void domain_table_free(DomainTable* t);
+using DomainTablePtr = Owned<DomainTable, domain_table_free>;
 size_t domain_table_size(const DomainTable* t);
 int open_domain(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host_polys, const size_t* lens, size_t b,
                 size_t stride, const uint32_t* w_words, uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out);

@@ -571,38 +571,37 @@ static int srs_build_windows(Ctx* c, Srs* s) {
   return KZG_OK;
 }
 
-static Srs* srs_alloc(Ctx* c, size_t n) {
-  Srs* s = new Srs();
+// an n-point key with its table of all windows, records unset
+static int srs_alloc(Ctx* c, size_t n, size_t rec_bytes, const char* bad_size, SrsPtr* out) {
+  if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, bad_size);
+  SrsPtr s(new Srs());
   s->n = n;
   s->curve = c->curve;
   s->win_bits = pick_win_bits(n);
   s->nwin = nwin_of(s->win_bits);
-  return s;
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->recs), (size_t)s->nwin * n * rec_bytes);
+  if (e != hipSuccess) return set_err(c, KZG_ERR_ALLOC, "hipMalloc(SRS table)", e);
+  *out = std::move(s);
+  return KZG_OK;
 }
 
 // the key from n affine points ALREADY ON THE DEVICE (canonical words x | y, flags or null; the caller keeps them
 // alive until this returns): import with the on-curve check, then the window multiples.  Synchronises.
 template <class C>
 static int srs_load_device_t(Ctx* c, const uint32_t* d_xy, const uint8_t* d_inf, size_t n, Srs** out) {
-  if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, "kzg_srs_load_g1: bad size");
-  Srs* s = srs_alloc(c, n);
-  const size_t table_bytes = (size_t)s->nwin * n * rec_bytes<C>();
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->recs), table_bytes);
-  if (e != hipSuccess) { delete s; return set_err(c, KZG_ERR_ALLOC, "hipMalloc(SRS table)", e); }
-  uint32_t* d_bad = nullptr;
-  auto fail = [&](int rc) { hipFree(d_bad); hipFree(s->recs); delete s; return rc; };
-  if (hipMalloc(reinterpret_cast<void**>(&d_bad), 4) != hipSuccess) return fail(set_err(c, KZG_ERR_ALLOC, "hipMalloc"));
-  hipMemsetAsync(d_bad, 0, 4, c->stream);
-  if (int rc = g1_import(c, d_xy, d_inf, n, /*range=*/false, s->recs, d_bad)) return fail(rc);
+  SrsPtr s;
+  int rc = srs_alloc(c, n, rec_bytes<C>(), "kzg_srs_load_g1: bad size", &s);
+  if (rc) return rc;
+  DevTmp<uint32_t> d_bad;
+  if (d_bad.alloc(4) != hipSuccess) return set_err(c, KZG_ERR_ALLOC, "hipMalloc");
+  KZG_HIP(c, hipMemsetAsync(d_bad, 0, 4, c->stream));
+  if ((rc = g1_import(c, d_xy, d_inf, n, /*range=*/false, s->recs, d_bad))) return rc;
   uint32_t bad = 0;
-  hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream);
-  e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, "srs import", e));
-  if (bad) return fail(set_err(c, KZG_ERR_ARG, "kzg_srs_load_g1: point not on the curve"));
-  hipFree(d_bad);
-  int rc = srs_build_windows<C>(c, s);
-  if (rc) { hipFree(s->recs); delete s; return rc; }
-  *out = s;
+  KZG_HIP(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
+  KZG_HIP(c, hipStreamSynchronize(c->stream));
+  if (bad) return set_err(c, KZG_ERR_ARG, "kzg_srs_load_g1: point not on the curve");
+  if ((rc = srs_build_windows<C>(c, s.get()))) return rc;
+  *out = s.release();
   return KZG_OK;
 }
 
@@ -610,16 +609,14 @@ template <class C>
 static int srs_load_t(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, Srs** out) {
   using F = typename C::Fp;
   if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, "kzg_srs_load_g1: bad size");
-  uint32_t* d_xy = nullptr; uint8_t* d_inf = nullptr;
+  DevTmp<uint32_t> d_xy;
+  DevTmp<uint8_t> d_inf;
   const size_t xy_bytes = n * 2 * F::NW * 4;
-  auto cleanup = [&]() { hipFree(d_xy); hipFree(d_inf); };
-  if (hipMalloc(reinterpret_cast<void**>(&d_xy), xy_bytes) != hipSuccess) return set_err(c, KZG_ERR_ALLOC, "hipMalloc");
-  if (inf && hipMalloc(reinterpret_cast<void**>(&d_inf), n) != hipSuccess) { cleanup(); return set_err(c, KZG_ERR_ALLOC, "hipMalloc"); }
-  hipMemcpyAsync(d_xy, xy, xy_bytes, hipMemcpyHostToDevice, c->stream);
-  if (inf) hipMemcpyAsync(d_inf, inf, n, hipMemcpyHostToDevice, c->stream);
-  const int rc = srs_load_device_t<C>(c, d_xy, d_inf, n, out);     // synchronises: the uploads are done with
-  cleanup();
-  return rc;
+  if (d_xy.alloc(xy_bytes) != hipSuccess || (inf && d_inf.alloc(n) != hipSuccess))
+    return set_err(c, KZG_ERR_ALLOC, "hipMalloc");
+  KZG_HIP(c, hipMemcpyAsync(d_xy, xy, xy_bytes, hipMemcpyHostToDevice, c->stream));
+  if (inf) KZG_HIP(c, hipMemcpyAsync(d_inf, inf, n, hipMemcpyHostToDevice, c->stream));
+  return srs_load_device_t<C>(c, d_xy, d_inf, n, out);             // synchronises: the uploads are done with
 }
 
 // the generators, canonical affine words x | y
@@ -638,34 +635,26 @@ static int srs_generate_t(Ctx* c, const uint32_t* tau_words, size_t start, size_
   using F = typename C::Fp;
   using Fr = typename C::Fr;
   const uint64_t* gen_xy = C::ID == 0 ? GEN_BN254 : GEN_BLS;
-  if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, "kzg_srs_generate: bad size");
-  Srs* s = srs_alloc(c, n);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->recs), (size_t)s->nwin * n * rec_bytes<C>());
-  if (e != hipSuccess) { delete s; return set_err(c, KZG_ERR_ALLOC, "hipMalloc(SRS table)", e); }
-  uint32_t *d_g = nullptr, *d_tab = nullptr, *d_tau = nullptr, *d_xy = nullptr, *d_bad = nullptr;
-  auto cleanup = [&]() { hipFree(d_g); hipFree(d_tab); hipFree(d_tau); hipFree(d_xy); hipFree(d_bad); };
-  auto fail = [&](int rc) { cleanup(); hipFree(s->recs); delete s; return rc; };
-  if (hipMalloc(reinterpret_cast<void**>(&d_g), rec_bytes<C>()) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&d_tab), 32 * 255 * rec_bytes<C>()) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&d_tau), Fr::N * 4) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&d_xy), 2 * F::NW * 4) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&d_bad), 4) != hipSuccess)
-    return fail(set_err(c, KZG_ERR_ALLOC, "hipMalloc"));
+  SrsPtr s;
+  int rc = srs_alloc(c, n, rec_bytes<C>(), "kzg_srs_generate: bad size", &s);
+  if (rc) return rc;
+  DevTmp<uint32_t> d_g, d_tab, d_tau, d_xy, d_bad;
+  if (d_g.alloc(rec_bytes<C>()) != hipSuccess || d_tab.alloc(32 * 255 * rec_bytes<C>()) != hipSuccess ||
+      d_tau.alloc(Fr::N * 4) != hipSuccess || d_xy.alloc(2 * F::NW * 4) != hipSuccess || d_bad.alloc(4) != hipSuccess)
+    return set_err(c, KZG_ERR_ALLOC, "hipMalloc");
   const Fe<Fr> tau = Field<Fr>::to_mont(Field<Fr>::from_words(tau_words));
-  hipMemcpy(d_tau, tau.l, Fr::N * 4, hipMemcpyHostToDevice);
-  hipMemcpy(d_xy, gen_xy, 2 * F::NW * 4, hipMemcpyHostToDevice);
-  hipMemsetAsync(d_bad, 0, 4, c->stream);
-  hipLaunchKernelGGL((g1_import_kernel<C, false>), dim3(1), dim3(64), 0, c->stream, d_xy, (const uint8_t*)nullptr, d_g,
-                     (size_t)1, d_bad);
-  hipLaunchKernelGGL(gen_table_kernel<C>, dim3(32), dim3(256), 0, c->stream, d_g, d_tab);
-  hipLaunchKernelGGL(srs_generate_kernel<C>, dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, c->stream, d_tab, d_tau,
-                     s->recs, start, n, run_len, inner_stride, outer_stride, d_scalars);
-  e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, "srs generate", e));
-  cleanup();
-  int rc = srs_build_windows<C>(c, s);
-  if (rc) { hipFree(s->recs); delete s; return rc; }
-  *out = s;
+  KZG_HIP(c, hipMemcpy(d_tau, tau.l, Fr::N * 4, hipMemcpyHostToDevice));
+  KZG_HIP(c, hipMemcpy(d_xy, gen_xy, 2 * F::NW * 4, hipMemcpyHostToDevice));
+  KZG_HIP(c, hipMemsetAsync(d_bad, 0, 4, c->stream));
+  hipLaunchKernelGGL((g1_import_kernel<C, false>), dim3(1), dim3(64), 0, c->stream, d_xy.get(),
+                     (const uint8_t*)nullptr, d_g.get(), (size_t)1, d_bad.get());
+  hipLaunchKernelGGL(gen_table_kernel<C>, dim3(32), dim3(256), 0, c->stream, d_g.get(), d_tab.get());
+  hipLaunchKernelGGL(srs_generate_kernel<C>, dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, c->stream, d_tab.get(),
+                     d_tau.get(), s->recs, start, n, run_len, inner_stride, outer_stride, d_scalars);
+  KZG_HIP(c, hipGetLastError());
+  KZG_HIP(c, hipStreamSynchronize(c->stream));
+  if ((rc = srs_build_windows<C>(c, s.get()))) return rc;
+  *out = s.release();
   return KZG_OK;
 }
 
@@ -685,15 +674,7 @@ int srs_generate_scalars(Ctx* c, const uint32_t* d_scalars, size_t n, Srs** out)
   static const uint32_t zero[8] = {0};
   return KZG_BY_CURVE(c, srs_generate_t, c, zero, 0, n, out, n ? n : 1, 1, 0, d_scalars);
 }
-int srs_create(Ctx* c, size_t n, Srs** out) {
-  const size_t rb = srs_rec_bytes(c->curve);
-  if (n == 0 || n * (size_t)16 >= (1ull << 31)) return set_err(c, KZG_ERR_ARG, "SRS: bad size");
-  Srs* s = srs_alloc(c, n);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->recs), (size_t)s->nwin * n * rb);
-  if (e != hipSuccess) { delete s; return set_err(c, KZG_ERR_ALLOC, "hipMalloc(SRS table)", e); }
-  *out = s;
-  return KZG_OK;
-}
+int srs_create(Ctx* c, size_t n, SrsPtr* out) { return srs_alloc(c, n, srs_rec_bytes(c->curve), "SRS: bad size", out); }
 int srs_finish_windows(Ctx* c, Srs* s) {
   return KZG_BY_CURVE(c, srs_build_windows, c, s);
 }
@@ -718,16 +699,16 @@ static int srs_export_t(Ctx* c, const Srs* s, size_t start, size_t count, uint64
   using F = typename C::Fp;
   if (start + count > s->n) return set_err(c, KZG_ERR_ARG, "kzg_srs_export: range");
   if (count == 0) return KZG_OK;
-  uint32_t* d_xy = nullptr; uint8_t* d_inf = nullptr;
-  KZG_HIP(c, hipMalloc(reinterpret_cast<void**>(&d_xy), count * 2 * F::NW * 4));
-  KZG_HIP(c, hipMalloc(reinterpret_cast<void**>(&d_inf), count));
+  DevTmp<uint32_t> d_xy;
+  DevTmp<uint8_t> d_inf;
+  KZG_HIP(c, d_xy.alloc(count * 2 * F::NW * 4));
+  KZG_HIP(c, d_inf.alloc(count));
   hipLaunchKernelGGL(srs_export_kernel<C>, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, c->stream, s->recs,
-                     start, count, d_xy, d_inf);
-  hipMemcpyAsync(xy, d_xy, count * 2 * F::NW * 4, hipMemcpyDeviceToHost, c->stream);
-  hipMemcpyAsync(inf, d_inf, count, hipMemcpyDeviceToHost, c->stream);
-  hipError_t e = hipStreamSynchronize(c->stream);
-  hipFree(d_xy); hipFree(d_inf);
-  if (e != hipSuccess) return set_err(c, KZG_ERR_HIP, "srs export", e);
+                     start, count, d_xy.get(), d_inf.get());
+  KZG_HIP(c, hipGetLastError());
+  KZG_HIP(c, hipMemcpyAsync(xy, d_xy, count * 2 * F::NW * 4, hipMemcpyDeviceToHost, c->stream));
+  KZG_HIP(c, hipMemcpyAsync(inf, d_inf, count, hipMemcpyDeviceToHost, c->stream));
+  KZG_HIP(c, hipStreamSynchronize(c->stream));
   return KZG_OK;
 }
 int srs_export(Ctx* c, const Srs* s, size_t start, size_t count, uint64_t* xy, uint8_t* inf) {
@@ -1027,6 +1008,8 @@ static int commit_t(Ctx* c, const Srs* s, const uint32_t* d_scalars, const size_
     if (lens[p] > s->n) return set_err(c, KZG_ERR_DEGREE, "polynomial longer than the commitment key");
     if (lens[p] > stride) return set_err(c, KZG_ERR_ARG, "kzg_commit: lens[p] > stride");
   }
+  // From here on every failure leaves through the flush below: when this returns non-zero, no slot -- of this call or
+  // of an earlier one with drain = false -- still holds a pointer into the caller's out_xy / out_inf / out_eval.
   int rc = KZG_OK;
   for (size_t p = 0; p < n_polys && rc == KZG_OK; ++p) {
     uint64_t* o = out_xy + p * 2 * (F::NW / 2);
@@ -1034,8 +1017,8 @@ static int commit_t(Ctx* c, const Srs* s, const uint32_t* d_scalars, const size_
       memset(o, 0, 2 * F::NW * 4);
       out_inf[p] = 1;
       if (d_eval && out_eval) {     // nothing to pipeline behind: fetch P(z) now
-        KZG_HIP(c, hipMemcpyAsync(out_eval, d_eval, 32, hipMemcpyDeviceToHost, c->stream));
-        KZG_HIP(c, hipStreamSynchronize(c->stream));
+        if ((rc = KZG_HIP_RC(c, hipMemcpyAsync(out_eval, d_eval, 32, hipMemcpyDeviceToHost, c->stream)))) break;
+        rc = KZG_HIP_RC(c, hipStreamSynchronize(c->stream));
       }
       continue;
     }
@@ -1047,9 +1030,10 @@ static int commit_t(Ctx* c, const Srs* s, const uint32_t* d_scalars, const size_
     if (d_eval && out_eval) {
       // P(z) rides with the slot: the copy is ordered on the context's stream BEFORE ev_in, which every stage of
       // this polynomial waits for, so it has landed when the slot's last event (ev_b) has
-      if (!sl.h_tb) KZG_HIP(c, hipHostMalloc(&sl.h_tb, MAX_NPART * 4 * 16 * 4 + 32));
-      KZG_HIP(c, hipMemcpyAsync(static_cast<char*>(sl.h_tb) + MAX_NPART * 4 * 16 * 4, d_eval, 32,
-                                hipMemcpyDeviceToHost, c->stream));
+      if (!sl.h_tb && (rc = KZG_HIP_RC(c, hipHostMalloc(&sl.h_tb, MAX_NPART * 4 * 16 * 4 + 32)))) break;
+      if ((rc = KZG_HIP_RC(c, hipMemcpyAsync(static_cast<char*>(sl.h_tb) + MAX_NPART * 4 * 16 * 4, d_eval, 32,
+                                             hipMemcpyDeviceToHost, c->stream))))
+        break;
       slot_eval = out_eval;
     }
     const uint32_t* sc = d_scalars + p * stride * 8;

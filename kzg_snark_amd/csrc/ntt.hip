@@ -362,6 +362,11 @@ __global__ void twist_table_kernel(uint32_t* out, const uint32_t* twA, const uin
   for (int j = 0; j < F::N; ++j) out[(size_t)idx * F::N + j] = r.l[j];
 }
 
+static void free_tables(NttDomain& d) {
+  for (uint32_t** t : {&d.d_stage, &d.d_twA, &d.d_twB, &d.d_scale, &d.d_twist}) { (void)hipFree(*t); *t = nullptr; }
+}
+
+// on failure the tables built so far stay in `d`: the caller frees them
 template <class F>
 int build_domain(Ctx* c, NttDomain& d) {
   using Fd = Field<F>;
@@ -384,8 +389,8 @@ int build_domain(Ctx* c, NttDomain& d) {
     jobs.push_back({&d.d_twA, pow2k(w, d.h), d.inverse ? ninv : Fd::one(), 1u << (log_n - d.h)});
     jobs.push_back({&d.d_twB, w, Fd::one(), 1u << d.h});
   }
-  uint32_t* d_tmp = nullptr;
-  KZG_HIP(c, hipMalloc(&d_tmp, 2 * F::N * 4));
+  DevTmp<uint32_t> d_tmp;
+  KZG_HIP(c, d_tmp.alloc(2 * F::N * 4));
   for (auto& j : jobs) {
     KZG_HIP(c, hipMalloc(j.dst, (size_t)j.count * F::N * 4));
     uint32_t hb[2 * F::N];
@@ -394,11 +399,10 @@ int build_domain(Ctx* c, NttDomain& d) {
     KZG_HIP(c, hipMemcpyAsync(d_tmp, hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
     KZG_HIP(c, hipStreamSynchronize(c->stream));   // hb is a stack buffer
     hipLaunchKernelGGL(pow_table_kernel<F>, dim3((j.count + 255) / 256), dim3(256), 0, c->stream, *j.dst,
-                       d_tmp, j.count);
+                       d_tmp.get(), j.count);
     KZG_HIP(c, hipGetLastError());
     KZG_HIP(c, hipStreamSynchronize(c->stream));
   }
-  KZG_HIP(c, hipFree(d_tmp));
   // The twist w^(t*v) comes from the two factor tables (e = t*v = hi * 2^h + lo: twA[hi] * twB[lo], 2 x 2^10 entries at
   // 2^20) -- one more multiplication per element than a full [N1][N2] table, but measured at the same time (112-115 us
   // either way at 2^20: the table's 36 MiB of reads per transform stalled as much as the multiplication costs) with
@@ -414,8 +418,9 @@ int build_domain(Ctx* c, NttDomain& d) {
     KZG_HIP(c, hipGetLastError());
     KZG_HIP(c, hipStreamSynchronize(c->stream));
     KZG_HIP(c, hipFree(d.d_twA));
+    d.d_twA = nullptr;
     KZG_HIP(c, hipFree(d.d_twB));
-    d.d_twA = d.d_twB = nullptr;
+    d.d_twB = nullptr;
   }
   // Last pass: a forward transform, and an inverse one whose n^-1 is already in the twist, end with the
   // plain reduction of the lazy value (d_scale stays null); only the single-pass inverse multiplies by
@@ -608,14 +613,13 @@ int get_domain(Ctx* c, uint32_t log_n, const uint32_t* w_words, int inverse, Ntt
         if (c->domains[i].last_use < c->domains[victim].last_use) victim = i;
       NttDomain& v = c->domains[victim];
       hipStreamSynchronize(c->stream);
-      hipFree(v.d_stage); hipFree(v.d_twA); hipFree(v.d_twB); hipFree(v.d_scale); hipFree(v.d_twist);
+      free_tables(v);
       c->domains.erase(c->domains.begin() + victim);
     }
     NttDomain d;
     d.log_n = log_n; d.inverse = inverse;
     memcpy(d.w, w_words, 32);
-    int rc = build_domain<F>(c, d);
-    if (rc) return rc;
+    if (int rc = build_domain<F>(c, d)) { free_tables(d); return rc; }   // a half-built domain: not kept, not leaked
     c->domains.push_back(d);
     dom = &c->domains.back();
   }
@@ -746,9 +750,7 @@ int ntt_rows_exchange_device(Ctx* c, const uint32_t* d_src, uint32_t* d_dst, uin
 }
 
 void ntt_free_domains(Ctx* c) {
-  for (auto& d : c->domains) {
-    hipFree(d.d_stage); hipFree(d.d_twA); hipFree(d.d_twB); hipFree(d.d_scale); hipFree(d.d_twist);
-  }
+  for (auto& d : c->domains) free_tables(d);
   c->domains.clear();
 }
 

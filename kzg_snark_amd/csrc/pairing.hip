@@ -45,25 +45,20 @@ __global__ __launch_bounds__(PAIRING_LANES) void pairing_kernel(const uint32_t* 
   if (threadIdx.x == 0) out_status[e] = (uint8_t)st;
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 template <class C>
 int pairing_t(Ctx* c, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy, const uint8_t* g2_inf,
               size_t m, size_t k, uint64_t* out_gt, uint8_t* out_status) {
   constexpr size_t FB = C::Fp::NW * 4;                  // bytes of a coordinate
   const size_t n = m * k;
-  const size_t b1 = up256(n * 2 * FB), b2 = up256(n * 4 * FB), bf = up256(n), bg = out_gt ? up256(m * 12 * FB) : 0,
-               bs = up256(m);
+  uint32_t *d_g1, *d_g2, *d_gt;
+  uint8_t *d_f1, *d_f2, *d_st;
   // its own buffer: the staging buffer and the pipeline's slots are not touched
-  int rc = ensure_buf(c, c->pair_tmp, b1 + b2 + 2 * bf + bg + bs);
+  int rc = carve(c, c->pair_tmp, [&](Carve& ws) {
+    d_g1 = ws.take(n * 2 * FB);  d_g2 = ws.take(n * 4 * FB);
+    d_f1 = ws.take<uint8_t>(n);  d_f2 = ws.take<uint8_t>(n);
+    d_gt = ws.take_if<uint32_t>(out_gt != nullptr, m * 12 * FB);  d_st = ws.take<uint8_t>(m);
+  });
   if (rc) return rc;
-  char* p = static_cast<char*>(c->pair_tmp.p);
-  uint32_t* d_g1 = reinterpret_cast<uint32_t*>(p);
-  uint32_t* d_g2 = reinterpret_cast<uint32_t*>(p + b1);
-  uint8_t* d_f1 = reinterpret_cast<uint8_t*>(p + b1 + b2);
-  uint8_t* d_f2 = d_f1 + bf;
-  uint32_t* d_gt = out_gt ? reinterpret_cast<uint32_t*>(p + b1 + b2 + 2 * bf) : nullptr;
-  uint8_t* d_st = reinterpret_cast<uint8_t*>(p + b1 + b2 + 2 * bf + bg);
   {
     ProfScope span(c, "pairing");
     KZG_HIP(c, hipMemcpyAsync(d_g1, g1_xy, n * 2 * FB, hipMemcpyHostToDevice, c->stream));

@@ -870,16 +870,15 @@ int open_coset_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* le
 int device_any_nonzero(Ctx* c, const uint32_t* d_words, size_t from, size_t to, bool* out) {
   *out = false;
   if (from >= to) return KZG_OK;
-  uint32_t* d_flag = nullptr;
-  KZG_HIP(c, hipMalloc(reinterpret_cast<void**>(&d_flag), 4));
-  hipMemsetAsync(d_flag, 0, 4, c->stream);
+  DevTmp<uint32_t> d_flag;
+  KZG_HIP(c, d_flag.alloc(4));
+  KZG_HIP(c, hipMemsetAsync(d_flag, 0, 4, c->stream));
   hipLaunchKernelGGL(any_nonzero_kernel, dim3((uint32_t)((to - from + 255) / 256)), dim3(256), 0, c->stream, d_words,
-                     from, to, d_flag);
+                     from, to, d_flag.get());
+  KZG_HIP(c, hipGetLastError());
   uint32_t f = 0;
-  hipMemcpyAsync(&f, d_flag, 4, hipMemcpyDeviceToHost, c->stream);
-  hipError_t e = hipStreamSynchronize(c->stream);
-  hipFree(d_flag);
-  if (e != hipSuccess) return set_err(c, KZG_ERR_HIP, "any_nonzero", e);
+  KZG_HIP(c, hipMemcpyAsync(&f, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+  KZG_HIP(c, hipStreamSynchronize(c->stream));
   *out = f != 0;
   return KZG_OK;
 }

@@ -234,21 +234,17 @@ int recover_t(Ctx* c, uint32_t log_n, uint32_t log_N, uint32_t log_l, const uint
   size_t chunk = c->tune_recover_chunk > 0 ? (size_t)c->tune_recover_chunk
                                            : std::max<size_t>(1, REC_SCRATCH_BYTES / per_vec);
   chunk = std::min<size_t>({chunk, b, REC_MAX_CHUNK});
-  size_t total = 0;
-  auto reserve = [&](size_t bytes) { const size_t o = total; total += (bytes + 255) / 256 * 256; return o; };
-  const size_t o_wtab = reserve((size_t)POW_TAB * 32), o_stab = reserve((size_t)POW_TAB * 32),
-               o_sitab = reserve((size_t)POW_TAB * 32), o_miss = reserve((size_t)m * 4), o_pos = reserve(C * 4),
-               o_a = reserve(cap_a * 32), o_b = reserve(cap_b * 32), o_v = reserve(C * 32), o_z = reserve(2 * C * 32),
-               o_zinv = reserve(C * 32), o_flag = reserve(b * 4), o_x = reserve(chunk * N * 32),
-               o_vals = reserve(host ? chunk * cells * 32 : 0), o_out = reserve(host ? chunk * n * 32 : 0);
-  int rc = ensure_buf(c, c->rec_tmp, total);
+  uint32_t *d_wtab, *d_stab, *d_sitab, *d_miss, *d_pos, *d_a, *d_b, *d_v, *d_zw, *d_zinv, *d_flag, *d_x, *d_vals, *d_out;
+  int rc = carve(c, c->rec_tmp, [&](Carve& ws) {
+    d_wtab = ws.take((size_t)POW_TAB * 32);  d_stab = ws.take((size_t)POW_TAB * 32);
+    d_sitab = ws.take((size_t)POW_TAB * 32);  d_miss = ws.take((size_t)m * 4);  d_pos = ws.take(C * 4);
+    d_a = ws.take(cap_a * 32);  d_b = ws.take(cap_b * 32);  d_v = ws.take(C * 32);
+    d_zw = ws.take(2 * C * 32);                                  // Z on the domain, then (d_zs) on its shift
+    d_zinv = ws.take(C * 32);  d_flag = ws.take(b * 4);  d_x = ws.take(chunk * N * 32);
+    d_vals = ws.take_if<uint32_t>(host, chunk * cells * 32);  d_out = ws.take_if<uint32_t>(host, chunk * n * 32);
+  });
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->rec_tmp.p);
-  auto u32 = [&](size_t o) { return reinterpret_cast<uint32_t*>(base + o); };
-  uint32_t *d_wtab = u32(o_wtab), *d_stab = u32(o_stab), *d_sitab = u32(o_sitab), *d_miss = u32(o_miss),
-           *d_pos = u32(o_pos), *d_a = u32(o_a), *d_b = u32(o_b), *d_v = u32(o_v), *d_zw = u32(o_z),
-           *d_zs = u32(o_z) + C * 8, *d_zinv = u32(o_zinv), *d_flag = u32(o_flag), *d_x = u32(o_x),
-           *d_vals = u32(o_vals), *d_out = u32(o_out);
+  uint32_t* d_zs = d_zw + C * 8;
 
   const Fe<F> s = fr_generator<Cv>(), s_inv = Fd::inv(s);                      // the multiplicative generator: s^N != 1
   Fe<F> s_l = s;

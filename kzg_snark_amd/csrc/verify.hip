@@ -29,6 +29,7 @@
 #include "g1_util.h"
 #include "msm.h"
 #include "g1_words.h"
+#include "ver_layout.h"
 
 namespace kzg {
 
@@ -211,122 +212,96 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
   memset(out_xy, 0, 2 * PT_BYTES);
   out_inf[0] = out_inf[1] = 1;
   if (K == 0) return KZG_OK;
-  // the cells grouped by commitment: a counting sort of the indices (and their range check)
+  // the cells grouped by commitment: a counting sort of the indices (and their range check, cell by cell)
   const uint32_t n_cosets = 1u << (log_N - log_l);
-  std::vector<uint32_t> off(n_comm + 1, 0), perm(K);
-  for (size_t k = 0; k < K; ++k) {
-    if (comm_idx[k] >= n_comm) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: commitment index out of range");
+  std::vector<uint32_t> off, perm;
+  const size_t k_bad = group_by_index(comm_idx, K, n_comm, off, perm);
+  for (size_t k = 0; k < k_bad; ++k)
     if (coset_idx[k] >= n_cosets) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: coset index out of range");
-    ++off[comm_idx[k] + 1];
-  }
-  for (size_t j = 0; j < n_comm; ++j) off[j + 1] += off[j];
-  {
-    std::vector<uint32_t> cur(off.begin(), off.end() - 1);
-    for (size_t k = 0; k < K; ++k) perm[cur[comm_idx[k]]++] = (uint32_t)k;
-  }
+  if (k_bad < K) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: commitment index out of range");
 
   const size_t M = K << log_l, rb = srs_rec_bytes(c->curve);
   const uint32_t log_e = std::max(log_l, VER_MIN_TILE_LOG);
   const uint32_t sum_threads = std::max<uint32_t>((uint32_t)l, VER_SUM_THREADS);
-  const uint32_t nsp = (uint32_t)ver_commsum_shares(n_comm);
+  VerifyWs d;
   size_t total = 0;
-  auto reserve = [&](size_t bytes) { const size_t o = total; total += (bytes + 255) / 256 * 256; return o; };
-  const size_t o_pxy = reserve(K * PT_BYTES), o_pinf = reserve(proof_inf ? K : 0), o_cxy = reserve(n_comm * PT_BYTES),
-               o_cinf = reserve(comm_inf ? n_comm : 0), o_recs = reserve(K * rb), o_vals = reserve(M * 32),
-               o_r = reserve(K * 32), o_s = reserve(K * 32), o_slice = reserve(K * 32), o_cidx = reserve(K * 4),
-               o_perm = reserve(K * 4), o_off = reserve((n_comm + 1) * 4), o_wtab = reserve((size_t)POW_TAB * 32),
-               o_rtab = reserve((size_t)POW_TAB * 32), o_part = reserve((size_t)sum_threads * 32),
-               o_cpart = reserve(n_comm * nsp * 32), o_T = reserve(l * 32), o_coef = reserve(n_comm * 32),
-               o_bad = reserve(4);
-  int rc = ensure_buf(c, c->ver_tmp, total);
+  int rc = carve(c, c->ver_tmp, [&](Carve& ws) {
+    d.layout(ws, K, n_comm, l, proof_inf != nullptr, comm_inf != nullptr, PT_BYTES, rb, POW_TAB, sum_threads,
+             ver_commsum_shares(n_comm));
+  }, &total);
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->ver_tmp.p);
-  auto u32 = [&](size_t o) { return reinterpret_cast<uint32_t*>(base + o); };
-  uint32_t *d_pxy = u32(o_pxy), *d_cxy = u32(o_cxy), *d_recs = u32(o_recs), *d_vals = u32(o_vals), *d_r = u32(o_r),
-           *d_s = u32(o_s), *d_slice = u32(o_slice), *d_cidx = u32(o_cidx), *d_perm = u32(o_perm), *d_off = u32(o_off),
-           *d_wtab = u32(o_wtab), *d_rtab = u32(o_rtab), *d_part = u32(o_part), *d_cpart = u32(o_cpart),
-           *d_T = u32(o_T), *d_coef = u32(o_coef), *d_bad = u32(o_bad);
-  uint8_t* d_pinf = proof_inf ? base + o_pinf : nullptr;
-  uint8_t* d_cinf = comm_inf ? base + o_cinf : nullptr;
 
-  Srs* cs = nullptr;                                 // the commitments as a key of their own (all windows)
+  SrsPtr cs;                                         // the commitments as a key of their own (all windows)
   if ((rc = srs_create(c, n_comm, &cs))) return rc;
   c->ver_last_bytes = total + (size_t)cs->nwin * n_comm * rb;
-  auto fail = [&](int code) { srs_free(cs); return code; };
-#define KZG_VER_HIP(call)                                                        \
-  do {                                                                           \
-    hipError_t e__ = (call);                                                     \
-    if (e__ != hipSuccess) return fail(set_err(c, KZG_ERR_HIP, #call, e__));     \
-  } while (0)
 
   ProfScope ps(c, "verify_cosets");
   hipStream_t st = c->stream;
-  KZG_VER_HIP(hipMemcpyAsync(d_pxy, proof_xy, K * PT_BYTES, hipMemcpyHostToDevice, st));
-  if (proof_inf) KZG_VER_HIP(hipMemcpyAsync(d_pinf, proof_inf, K, hipMemcpyHostToDevice, st));
-  KZG_VER_HIP(hipMemcpyAsync(d_cxy, comm_xy, n_comm * PT_BYTES, hipMemcpyHostToDevice, st));
-  if (comm_inf) KZG_VER_HIP(hipMemcpyAsync(d_cinf, comm_inf, n_comm, hipMemcpyHostToDevice, st));
-  KZG_VER_HIP(hipMemsetAsync(d_bad, 0, 4, st));
-  if ((rc = g1_import(c, d_pxy, d_pinf, K, /*range=*/true, d_recs, d_bad))) return fail(rc);
-  if ((rc = g1_import(c, d_cxy, d_cinf, n_comm, /*range=*/true, cs->recs, d_bad))) return fail(rc);
+  KZG_HIP(c, hipMemcpyAsync(d.pxy, proof_xy, K * PT_BYTES, hipMemcpyHostToDevice, st));
+  if (proof_inf) KZG_HIP(c, hipMemcpyAsync(d.pinf, proof_inf, K, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemcpyAsync(d.cxy, comm_xy, n_comm * PT_BYTES, hipMemcpyHostToDevice, st));
+  if (comm_inf) KZG_HIP(c, hipMemcpyAsync(d.cinf, comm_inf, n_comm, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemsetAsync(d.bad, 0, 4, st));
+  if ((rc = g1_import(c, d.pxy, d.pinf, K, /*range=*/true, d.recs, d.bad))) return rc;
+  if ((rc = g1_import(c, d.cxy, d.cinf, n_comm, /*range=*/true, cs->recs, d.bad))) return rc;
   uint32_t bad = 0;
-  KZG_VER_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+  KZG_HIP(c, hipMemcpyAsync(&bad, d.bad, 4, hipMemcpyDeviceToHost, st));
   // the claims travel while the points are checked
-  KZG_VER_HIP(hipMemcpyAsync(d_vals, values, M * 32, hipMemcpyHostToDevice, st));
-  KZG_VER_HIP(hipMemcpyAsync(d_cidx, coset_idx, K * 4, hipMemcpyHostToDevice, st));
-  KZG_VER_HIP(hipMemcpyAsync(d_perm, perm.data(), K * 4, hipMemcpyHostToDevice, st));
-  KZG_VER_HIP(hipMemcpyAsync(d_off, off.data(), (n_comm + 1) * 4, hipMemcpyHostToDevice, st));
-  KZG_VER_HIP(hipStreamSynchronize(st));
-  if (bad) return fail(set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: a proof or commitment has a coordinate >= p or is not on the curve"));
-  if ((rc = srs_finish_windows(c, cs))) return fail(rc);
+  KZG_HIP(c, hipMemcpyAsync(d.vals, values, M * 32, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemcpyAsync(d.cidx, coset_idx, K * 4, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemcpyAsync(d.perm, perm.data(), K * 4, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemcpyAsync(d.off, off.data(), (n_comm + 1) * 4, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipStreamSynchronize(st));
+  if (bad) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: a proof or commitment has a coordinate >= p or is not on the curve");
+  if ((rc = srs_finish_windows(c, cs.get()))) return rc;
 
   // ---- weights and the fold of the values
   const Fe<F> rho = mont_from_words<F>(rho_words);
   const dim3 k_grid((uint32_t)((K + 255) / 256));
-  if ((rc = fr_pow_table(c, fr_arg<F>(w), d_wtab))) return fail(rc);
-  if ((rc = fr_pow_table(c, fr_arg<F>(rho), d_rtab))) return fail(rc);
-  hipLaunchKernelGGL(ver_weights_kernel<F>, k_grid, dim3(256), 0, st, (uint32_t)K, log_l, d_cidx, d_wtab, d_rtab, d_r,
-                     d_s);
-  KZG_VER_HIP(hipGetLastError());
+  if ((rc = fr_pow_table(c, fr_arg<F>(w), d.wtab))) return rc;
+  if ((rc = fr_pow_table(c, fr_arg<F>(rho), d.rtab))) return rc;
+  hipLaunchKernelGGL(ver_weights_kernel<F>, k_grid, dim3(256), 0, st, (uint32_t)K, log_l, d.cidx, d.wtab, d.rtab, d.r,
+                     d.s);
+  KZG_HIP(c, hipGetLastError());
   const size_t lds_bytes = (size_t)32 << log_e;
   if (lds_bytes > 64 * 1024 && !c->ver_lds_attr_set) {   // > 64 KiB of dynamic LDS (gfx950: 160 KiB per CU); per device
-    KZG_VER_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ver_cell_kernel<F>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    KZG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(ver_cell_kernel<F>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     c->ver_lds_attr_set = 1;
   }
   const size_t ntiles = (M + ((size_t)1 << log_e) - 1) >> log_e;
   hipLaunchKernelGGL(ver_cell_kernel<F>, dim3((uint32_t)std::min<size_t>(ntiles, 4096)), dim3(256), lds_bytes, st,
-                     (uint32_t)K, log_l, log_N, log_e, d_cidx, d_wtab, d_rtab, fr_arg<F>(Fd::reduce(inv_pow2<F>(log_l))),
-                     d_vals);
-  hipLaunchKernelGGL(ver_colsum_kernel<F>, dim3(sum_threads / 256), dim3(256), 0, st, M, d_vals, d_part);
+                     (uint32_t)K, log_l, log_N, log_e, d.cidx, d.wtab, d.rtab, fr_arg<F>(Fd::reduce(inv_pow2<F>(log_l))),
+                     d.vals);
+  hipLaunchKernelGGL(ver_colsum_kernel<F>, dim3(sum_threads / 256), dim3(256), 0, st, M, d.vals, d.part);
   hipLaunchKernelGGL(ver_colsum_final_kernel<F>, dim3((uint32_t)l), dim3(64), 0, st, (uint32_t)l,
-                     sum_threads >> log_l, d_part, d_T);
-  KZG_VER_HIP(hipGetLastError());
-  if ((rc = ver_commitment_sums(c, d_r, d_perm, d_off, n_comm, d_cpart, d_coef))) return fail(rc);
+                     sum_threads >> log_l, d.part, d.T);
+  KZG_HIP(c, hipGetLastError());
+  if ((rc = ver_commitment_sums(c, d.r, d.perm, d.off, n_comm, d.cpart, d.coef))) return rc;
 
   // ---- the MSMs: 2 x ns slice vectors over the proofs, T over the key, the weights over the commitments
   Srs pv;
-  srs_window0_view(c, d_recs, K, &pv);
+  srs_window0_view(c, d.recs, K, &pv);
   const uint32_t sb = (uint32_t)pv.win_bits - 1, ns = (F::BITS + sb - 1) / sb;
   std::vector<uint64_t> h_xy((size_t)(2 * ns + 2) * PW64);
   std::vector<uint8_t> h_inf(2 * ns + 2);
   for (uint32_t v = 0; v < 2 && rc == KZG_OK; ++v) {
     for (uint32_t s = 0; s < ns && rc == KZG_OK; ++s) {
-      hipLaunchKernelGGL(ver_slice_kernel, k_grid, dim3(256), 0, st, (uint32_t)K, v ? d_s : d_r, s * sb, sb, d_slice);
+      hipLaunchKernelGGL(ver_slice_kernel, k_grid, dim3(256), 0, st, (uint32_t)K, v ? d.s : d.r, s * sb, sb, d.slice);
       // the pipeline takes its own copy of the scalars in stream order (or holds the stream until they are consumed):
-      // the next slice may overwrite d_slice
+      // the next slice may overwrite d.slice
       const size_t idx = (size_t)v * ns + s;
-      rc = commit_device(c, &pv, d_slice, &K, 1, K, h_xy.data() + idx * PW64, h_inf.data() + idx, /*drain=*/false);
+      rc = commit_device(c, &pv, d.slice, &K, 1, K, h_xy.data() + idx * PW64, h_inf.data() + idx, /*drain=*/false);
     }
   }
   if (rc == KZG_OK)
-    rc = commit_device(c, mono, d_T, &l, 1, l, h_xy.data() + (size_t)2 * ns * PW64, h_inf.data() + 2 * ns, false);
+    rc = commit_device(c, mono, d.T, &l, 1, l, h_xy.data() + (size_t)2 * ns * PW64, h_inf.data() + 2 * ns, false);
   if (rc == KZG_OK)
-    rc = commit_device(c, cs, d_coef, &n_comm, 1, n_comm, h_xy.data() + (size_t)(2 * ns + 1) * PW64,
+    rc = commit_device(c, cs.get(), d.coef, &n_comm, 1, n_comm, h_xy.data() + (size_t)(2 * ns + 1) * PW64,
                        h_inf.data() + 2 * ns + 1, false);
   const int rc2 = commit_flush(c);                    // also on an error: nothing may point at h_xy afterwards
   if (rc == KZG_OK) rc = rc2;
-  if (rc) return fail(rc);
-#undef KZG_VER_HIP
+  if (rc) return rc;
 
   const XYZZ<C> R = recombine_slices<C>(h_xy.data(), h_inf.data(), ns, sb);
   const XYZZ<C> S = recombine_slices<C>(h_xy.data() + (size_t)ns * PW64, h_inf.data() + ns, ns, sb);
@@ -335,7 +310,6 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
   const XYZZ<C> Cc = host_point<C>(h_xy.data() + (size_t)(2 * ns + 1) * PW64, h_inf[2 * ns + 1]);
   out_inf[0] = affine_to_words<C>(Ec<C>::to_affine(Ec<C>::add(Ec<C>::add(Cc, Tp), S)), reinterpret_cast<uint32_t*>(out_xy));
   out_inf[1] = affine_to_words<C>(Ec<C>::to_affine(R), reinterpret_cast<uint32_t*>(out_xy + PW64));
-  srs_free(cs);
   return KZG_OK;
 }
 

@@ -31,6 +31,7 @@
 #include "msm.h"
 #include "g1_words.h"
 #include "srs_rec.h"
+#include "ver_layout.h"
 
 namespace kzg {
 
@@ -234,90 +235,68 @@ int verify_points_t(Ctx* c, const uint64_t* comm_xy, const uint8_t* comm_inf, si
   out_inf[0] = out_inf[1] = 1;
   if (K == 0) return KZG_OK;
   // the claims grouped by commitment: a counting sort of the indices (and their range check)
-  std::vector<uint32_t> off(n_comm + 1, 0), perm(K);
-  for (size_t k = 0; k < K; ++k) {
-    if (comm_idx[k] >= n_comm) return set_err(c, KZG_ERR_ARG, "kzg_verify_points: commitment index out of range");
-    ++off[comm_idx[k] + 1];
-  }
-  for (size_t j = 0; j < n_comm; ++j) off[j + 1] += off[j];
-  {
-    std::vector<uint32_t> cur(off.begin(), off.end() - 1);
-    for (size_t k = 0; k < K; ++k) perm[cur[comm_idx[k]]++] = (uint32_t)k;
-  }
+  std::vector<uint32_t> off, perm;
+  if (group_by_index(comm_idx, K, n_comm, off, perm) < K)
+    return set_err(c, KZG_ERR_ARG, "kzg_verify_points: commitment index out of range");
 
-  const size_t n_short = n_comm + 1, rb = srs_rec_bytes(c->curve), nsp = ver_commsum_shares(n_comm);
+  const size_t n_short = n_comm + 1;
   const uint32_t nb = (uint32_t)((K + VPT_TB - 1) / VPT_TB), nc = (uint32_t)((n_short + VPT_TB - 1) / VPT_TB);
   // the workgroups split evenly over the fewest launches of at most VPT_LAUNCH_BLOCKS: no launch of a few workgroups
   // trails behind a full one with a whole ladder's latency of its own
   const uint32_t blocks = 2 * nb + nc, launches = (blocks + VPT_LAUNCH_BLOCKS - 1) / VPT_LAUNCH_BLOCKS;
   const uint32_t launch_blocks = (blocks + launches - 1) / launches;
-  size_t total = 0;
-  auto reserve = [&](size_t bytes) { const size_t o = total; total += (bytes + 255) / 256 * 256; return o; };
-  const size_t o_pxy = reserve(K * PT_BYTES), o_pinf = reserve(proof_inf ? K : 0), o_cxy = reserve(n_short * PT_BYTES),
-               o_cinf = reserve(comm_inf ? n_short : 0), o_precs = reserve(K * rb), o_crecs = reserve(n_short * rb),
-               o_z = reserve(K * 32), o_y = reserve(K * 32), o_r = reserve(K * 32), o_s = reserve(K * 32),
-               o_perm = reserve(K * 4), o_off = reserve((n_comm + 1) * 4), o_rtab = reserve((size_t)POW_TAB * 32),
-               o_ypart = reserve((size_t)VPT_WEIGHT_THREADS * 32), o_cpart = reserve(n_comm * nsp * 32),
-               o_coef = reserve(n_short * 32), o_partial = reserve((size_t)blocks * XYZZ_BYTES),
-               o_out = reserve(3 * XYZZ_BYTES), o_bad = reserve(4),
-               o_tab = reserve((size_t)VPT_TABLE * XYZZ_BYTES * launch_blocks * VPT_TB);
-  int rc = ensure_buf(c, c->vpt_tmp, total);
+  VerifyPointsWs d;
+  int rc = carve(c, c->vpt_tmp, [&](Carve& ws) {
+    d.layout(ws, K, n_comm, proof_inf != nullptr, comm_inf != nullptr, PT_BYTES, srs_rec_bytes(c->curve), POW_TAB,
+             VPT_WEIGHT_THREADS, ver_commsum_shares(n_comm), blocks, XYZZ_BYTES,
+             (size_t)VPT_TABLE * XYZZ_BYTES * launch_blocks * VPT_TB);
+  }, &c->vpt_last_bytes);
   if (rc) return rc;
-  c->vpt_last_bytes = total;
-  uint8_t* base = static_cast<uint8_t*>(c->vpt_tmp.p);
-  auto u32 = [&](size_t o) { return reinterpret_cast<uint32_t*>(base + o); };
-  uint32_t *d_pxy = u32(o_pxy), *d_cxy = u32(o_cxy), *d_precs = u32(o_precs), *d_crecs = u32(o_crecs), *d_z = u32(o_z),
-           *d_y = u32(o_y), *d_r = u32(o_r), *d_s = u32(o_s), *d_perm = u32(o_perm), *d_off = u32(o_off),
-           *d_rtab = u32(o_rtab), *d_ypart = u32(o_ypart), *d_cpart = u32(o_cpart), *d_coef = u32(o_coef),
-           *d_partial = u32(o_partial), *d_out = u32(o_out), *d_bad = u32(o_bad);
-  uint4* d_tab = reinterpret_cast<uint4*>(base + o_tab);
-  uint8_t* d_pinf = proof_inf ? base + o_pinf : nullptr;
-  uint8_t* d_cinf = comm_inf ? base + o_cinf : nullptr;
 
   ProfScope ps(c, "verify_points");
   hipStream_t st = c->stream;
-  KZG_HIP(c, hipMemcpyAsync(d_pxy, proof_xy, K * PT_BYTES, hipMemcpyHostToDevice, st));
-  if (proof_inf) KZG_HIP(c, hipMemcpyAsync(d_pinf, proof_inf, K, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemcpyAsync(d.pxy, proof_xy, K * PT_BYTES, hipMemcpyHostToDevice, st));
+  if (proof_inf) KZG_HIP(c, hipMemcpyAsync(d.pinf, proof_inf, K, hipMemcpyHostToDevice, st));
   // the commitments, then the generator as one more: its scalar is -sum r_k y_k
-  KZG_HIP(c, hipMemcpyAsync(d_cxy, comm_xy, n_comm * PT_BYTES, hipMemcpyHostToDevice, st));
-  KZG_HIP(c, hipMemcpyAsync(reinterpret_cast<uint8_t*>(d_cxy) + n_comm * PT_BYTES, g1_generator_limbs(c->curve),
+  KZG_HIP(c, hipMemcpyAsync(d.cxy, comm_xy, n_comm * PT_BYTES, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemcpyAsync(reinterpret_cast<uint8_t*>(d.cxy) + n_comm * PT_BYTES, g1_generator_limbs(c->curve),
                             PT_BYTES, hipMemcpyHostToDevice, st));
   if (comm_inf) {
-    KZG_HIP(c, hipMemcpyAsync(d_cinf, comm_inf, n_comm, hipMemcpyHostToDevice, st));
-    KZG_HIP(c, hipMemsetAsync(d_cinf + n_comm, 0, 1, st));
+    KZG_HIP(c, hipMemcpyAsync(d.cinf, comm_inf, n_comm, hipMemcpyHostToDevice, st));
+    KZG_HIP(c, hipMemsetAsync(d.cinf + n_comm, 0, 1, st));
   }
-  KZG_HIP(c, hipMemsetAsync(d_bad, 0, 4, st));
-  if ((rc = g1_import(c, d_pxy, d_pinf, K, /*range=*/true, d_precs, d_bad))) return rc;
-  if ((rc = g1_import(c, d_cxy, d_cinf, n_short, /*range=*/true, d_crecs, d_bad))) return rc;
+  KZG_HIP(c, hipMemsetAsync(d.bad, 0, 4, st));
+  if ((rc = g1_import(c, d.pxy, d.pinf, K, /*range=*/true, d.precs, d.bad))) return rc;
+  if ((rc = g1_import(c, d.cxy, d.cinf, n_short, /*range=*/true, d.crecs, d.bad))) return rc;
   uint32_t bad = 0;
-  KZG_HIP(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+  KZG_HIP(c, hipMemcpyAsync(&bad, d.bad, 4, hipMemcpyDeviceToHost, st));
   // the claims travel while the points are checked
-  KZG_HIP(c, hipMemcpyAsync(d_z, z, K * 32, hipMemcpyHostToDevice, st));
-  KZG_HIP(c, hipMemcpyAsync(d_y, y, K * 32, hipMemcpyHostToDevice, st));
-  KZG_HIP(c, hipMemcpyAsync(d_perm, perm.data(), K * 4, hipMemcpyHostToDevice, st));
-  KZG_HIP(c, hipMemcpyAsync(d_off, off.data(), (n_comm + 1) * 4, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemcpyAsync(d.z, z, K * 32, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemcpyAsync(d.y, y, K * 32, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemcpyAsync(d.perm, perm.data(), K * 4, hipMemcpyHostToDevice, st));
+  KZG_HIP(c, hipMemcpyAsync(d.off, off.data(), (n_comm + 1) * 4, hipMemcpyHostToDevice, st));
   KZG_HIP(c, hipStreamSynchronize(st));
   if (bad) return set_err(c, KZG_ERR_ARG, "kzg_verify_points: a proof or commitment has a coordinate >= p or is not on the curve");
 
   // ---- weights: r, s, the per-commitment sums and -sum r_k y_k as scalar n_comm
-  if ((rc = fr_pow_table(c, fr_arg<F>(mont_from_words<F>(rho_words)), d_rtab))) return rc;
-  hipLaunchKernelGGL(vpt_weights_kernel<F>, dim3(VPT_WEIGHT_THREADS / 256), dim3(256), 0, st, (uint32_t)K, d_rtab, d_z,
-                     d_y, d_r, d_s, d_ypart);
+  if ((rc = fr_pow_table(c, fr_arg<F>(mont_from_words<F>(rho_words)), d.rtab))) return rc;
+  hipLaunchKernelGGL(vpt_weights_kernel<F>, dim3(VPT_WEIGHT_THREADS / 256), dim3(256), 0, st, (uint32_t)K, d.rtab, d.z,
+                     d.y, d.r, d.s, d.ypart);
   KZG_HIP(c, hipGetLastError());
-  if ((rc = ver_commitment_sums(c, d_r, d_perm, d_off, n_comm, d_cpart, d_coef))) return rc;
-  if ((rc = ver_column_sums(c, 1, VPT_WEIGHT_THREADS, d_ypart, d_coef + n_comm * 8))) return rc;
+  if ((rc = ver_commitment_sums(c, d.r, d.perm, d.off, n_comm, d.cpart, d.coef))) return rc;
+  if ((rc = ver_column_sums(c, 1, VPT_WEIGHT_THREADS, d.ypart, d.coef + n_comm * 8))) return rc;
 
   // ---- the ladders, VPT_LAUNCH_BLOCKS workgroups at a time over one table, and the fold of their partial points
   const VptGrid g{(uint32_t)K, nb, (uint32_t)n_short};
   for (uint32_t b0 = 0; b0 < blocks; b0 += launch_blocks) {
     hipLaunchKernelGGL(vpt_ladder_kernel<C>, dim3(std::min(launch_blocks, blocks - b0)), dim3(VPT_TB), 0, st, g, b0,
-                       d_precs, d_crecs, d_r, d_s, d_coef, d_tab, d_partial);
+                       d.precs, d.crecs, d.r, d.s, d.coef, static_cast<uint4*>(d.tab), d.partial);
     KZG_HIP(c, hipGetLastError());
   }
-  hipLaunchKernelGGL(vpt_fold_kernel<C>, dim3(3), dim3(VPT_TB), 0, st, nb, nc, d_partial, d_out);
+  hipLaunchKernelGGL(vpt_fold_kernel<C>, dim3(3), dim3(VPT_TB), 0, st, nb, nc, d.partial, d.out);
   KZG_HIP(c, hipGetLastError());
   uint32_t h_out[3 * 4 * Fp::N];
-  KZG_HIP(c, hipMemcpyAsync(h_out, d_out, sizeof(h_out), hipMemcpyDeviceToHost, st));
+  KZG_HIP(c, hipMemcpyAsync(h_out, d.out, sizeof(h_out), hipMemcpyDeviceToHost, st));
   KZG_HIP(c, hipStreamSynchronize(st));
 
   const XYZZ<C> R = point_from_limbs<C>(h_out), S = point_from_limbs<C>(h_out + 4 * Fp::N),
