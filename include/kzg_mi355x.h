@@ -383,12 +383,21 @@ int kzg_recover_cosets_device(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint
  * shard.  kzg_open_shard_begin combines the slices (sum xi^(i+1) p_i) and returns the slice
  * polynomial's value H_g = sum_j c_(lo_g+j) z^j.  The ranks exchange the H_g (one field element
  * each); rank g's carry is S_(hi_g) = sum_(g' > g) H_g' * z^(lo_g' - hi_g).  kzg_open_shard_finish
- * lets the carry enter the scan above the slice's top coefficient and commits the quotient slice
- * (it continues from what _begin left on the device: no other open on this context in between):
+ * lets the carry enter the scan above the slice's top coefficient and commits the quotient slice:
  *   first_rank != 0: coefficients S_1 .. S_(hi-1) against key points 0 ..      (eval_out = P(z))
  *   otherwise      : coefficients S_lo .. S_(hi-1) against key points lo-1 ..   -- the caller's shard
  *                    must therefore START at global index lo_g - 1 (kzg_srs_generate_range).
- * The partial points of all ranks add up to the opening proof. */
+ * The partial points of all ranks add up to the opening proof.
+ * Between the two calls the context HOLDS the slice: one per context, the last _begin's (an empty slice, every
+ * length 0, is one).  _finish continues from exactly what _begin left:
+ *   - it must be given _begin's z; another z is KZG_ERR_ARG and the slice stays held;
+ *   - tuning changed after _begin (kzg_ctx_set_tuning) has no effect on it;
+ *   - it does not consume the slice: it may be repeated, with the same result for the same carry.
+ * The slice is KEPT across commits (pipelined ones too), key generation, kzg_fr_poly_eval, the kzg_fr_vec_*
+ * primitives and kzg_ctx_set_tuning.  It is DROPPED by kzg_open, kzg_open_device[_async], kzg_open_coset[_device]
+ * (they work in the same buffers; only an opening of nothing but empty polynomials leaves them alone) and by a
+ * _begin that fails: _finish is then KZG_ERR_ARG ("another opening has used the context"), as it is, with its own
+ * message, on a context that never began. */
 int kzg_open_shard_begin(kzg_ctx* ctx, const void* d_polys, const size_t* lens, size_t k, size_t stride,
                          const uint64_t z[4], const uint64_t xi[4], uint64_t* chunk_eval_out);
 int kzg_open_shard_finish(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t z[4], const uint64_t carry[4],

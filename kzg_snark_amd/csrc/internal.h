@@ -58,6 +58,22 @@ enum : int {
   CLK_WORDS = 16
 };
 
+// The shape of one two-pass tile scan (poly.hip): all that its fill and eval launches need, free of the field
+// template so that a context can keep it.
+struct TileShape {
+  size_t n = 0;                                   // coefficients
+  uint32_t tb = 0, ntiles = 0, nsuper = 0;        // nsuper = 0: every tile sums all aggregates above it
+  uint32_t *G = nullptr, *H = nullptr, *A = nullptr, *zinv = nullptr, *W = nullptr;      // the carve of the scan buffer
+  uint32_t z[9] = {0}, z_inv[9] = {0};            // Montgomery limbs
+};
+// The slice between kzg_open_shard_begin and kzg_open_shard_finish.  HELD covers the slices without tiles too
+// (shape.tb = 0): the empty one (shape.n = 0) and z = 0, whose finish is a copy.
+struct OpenSlice {
+  enum State { NEVER, HELD, LOST } state = NEVER;   // LOST: another opening took the two buffers since
+  uint32_t z_words[8] = {0};                        // begin's z, canonical: finish must be given the same
+  TileShape shape;
+};
+
 struct Ctx {
   int curve = 0;
   int device = 0;
@@ -70,7 +86,7 @@ struct Ctx {
   DevBuf ntt_scratch;     // pass-1 output of two-pass transforms
   DevBuf io;              // staging for the host-pointer entry points
   DevBuf poly_tmp[4];     // open(): combined polynomial + suffix values; scratch of the vector primitives
-  DevBuf scan_tmp;        // open(): chunk values, tile aggregates, power tables (kept between the shard calls)
+  DevBuf scan_tmp;        // open(): chunk values, tile aggregates, power tables (open_slice holds their carve)
   DevBuf lagr_tmp;        // lagrange.hip: combined values, denominators, inverses, quotient, partial sums
   DevBuf dom_tmp;         // domain.hip: G1 transform buffers and the Fr vectors of one chunk of kzg_open_domain
   DevBuf ver_tmp;         // verify.hip: staged claims, proof records, weights, power tables, partial sums
@@ -85,9 +101,7 @@ struct Ctx {
   uint32_t* eval_lens_pin = nullptr;
   size_t eval_lens_cap = 0;
   hipEvent_t eval_lens_ev = nullptr;
-  size_t open_shard_n = 0;                // slice length between kzg_open_shard_begin / _finish
-  uint32_t open_shard_tb = 0;             // tile width the slice's aggregates were formed with
-  bool open_shard_begun = false;          // a kzg_open_shard_begin has left a slice (an empty one included)
+  OpenSlice open_slice;                   // what kzg_open_shard_begin left in poly_tmp[0] and scan_tmp for _finish
   // kzg_ctx_set_tuning: 0 = the library's own choice
   int tune_ntt_tile_log = 0;              // LDS tile of the transform (8..12)
   int tune_open_tb = 0;                   // threads per tile of the opening's scan (128 | 256)

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace kzg {
@@ -390,19 +391,38 @@ __global__ __launch_bounds__(TB) void tile_eval_kernel(uint32_t ntiles, const ui
 //   eval             S_0
 //   quot[0 .. cap)   S_1, S_2, ...        => [eval, quot...] is the contiguous vector S_0, S_1, ...
 // scan_tmp: g (9 words per chunk), H (per tile, + 1), A (per group of 64 tiles), zinv (TB + 1), W (per tile).
-template <class F>
-struct TilePlan {
-  uint32_t tb = 0, ntiles = 0, ntab = 0, nsuper = 0;        // nsuper = 0: every tile sums all aggregates above it
+// A plan is the TileShape (internal.h: all that a fill or eval launch needs, and what the sharded opening keeps from
+// begin to finish) and what pass 1 alone needs:
+struct TilePass1 {
+  uint32_t ntab = 0;                                          // table workgroups at the head of the grid
   TileScanArgs ts;
-  FrArg z;                                                    // Montgomery form
-  Fe<F> z_inv;                                                // Montgomery form
-  uint32_t *G = nullptr, *H = nullptr, *A = nullptr, *zinv = nullptr, *W = nullptr;
 };
+
+// The two buffers hold one opening at a time.  Every opening but kzg_open_shard_finish takes them through here, and
+// that ends the slice a kzg_open_shard_begin holds in them: finish then refuses.
+struct OpenBufs { DevBuf &vec, &scan; };
+static OpenBufs claim_open_bufs(Ctx* c) {
+  if (c->open_slice.state == OpenSlice::HELD) c->open_slice.state = OpenSlice::LOST;
+  return {c->poly_tmp[0], c->scan_tmp};
+}
+// vec sized for n coefficients, by the layout above: the combination, and S_0 with the quotient behind it
+static int open_vectors(Ctx* c, DevBuf& vec, size_t n, uint32_t** d_comb, uint32_t** d_eval) {
+  if (int rc = ensure_buf(c, vec, (2 * (n + 1) + 1) * 32)) return rc;
+  *d_comb = static_cast<uint32_t*>(vec.p);
+  *d_eval = *d_comb + (n + 1) * 8;
+  return KZG_OK;
+}
 
 static bool words_are_zero(const uint32_t* w) {
   uint32_t acc = 0;
   for (int i = 0; i < 8; ++i) acc |= w[i];
   return acc == 0;
+}
+
+// fn(std::integral_constant<uint32_t, TB>) for the tile width tb, one of 128 and 256
+template <class Fn>
+static int by_tile_width(uint32_t tb, Fn&& fn) {
+  return tb == 128 ? fn(std::integral_constant<uint32_t, 128>{}) : fn(std::integral_constant<uint32_t, 256>{});
 }
 
 // Tile width: 256 threads (2048 coefficients, 65 KiB of LDS in the fill) when the GPU is the opening's; 128 threads
@@ -415,18 +435,19 @@ static uint32_t open_tile_threads(Ctx* c) {
   return msm_accumulate_in_flight(c) ? 128u : 256u;
 }
 
+// the plan of a scan over n coefficients at z != 0 in tiles of tb threads, carved out of buf (with_chunks = false: no g)
 template <class F>
-int tile_plan(Ctx* c, size_t n, const uint32_t* z_words, uint32_t tb, TilePlan<F>* p, DevBuf* buf = nullptr,
+int tile_plan(Ctx* c, size_t n, const uint32_t* z_words, uint32_t tb, DevBuf& buf, TileShape* s, TilePass1* p,
               bool with_chunks = true) {
   using Fd = Field<F>;
   const uint32_t T = tb * SC, tk = T / TILE_ITER;
-  p->tb = tb;
-  p->ntiles = (uint32_t)((n + T - 1) / T);
-  p->ntab = (std::max(tb + 1, p->ntiles) + tk - 1) / tk;
+  s->tb = tb, s->n = n;
+  s->ntiles = (uint32_t)((n + T - 1) / T);
+  p->ntab = (std::max(tb + 1, s->ntiles) + tk - 1) / tk;
   const uint32_t direct_max = c->tune_open_direct_max > 0 ? (uint32_t)c->tune_open_direct_max : TILE_DIRECT_MAX;
-  p->nsuper = p->ntiles > direct_max ? (p->ntiles + SG - 1) / SG : 0;
+  s->nsuper = s->ntiles > direct_max ? (s->ntiles + SG - 1) / SG : 0;
   const Fe<F> z = Fd::to_mont(Fd::from_words(z_words));
-  p->z = fr_arg<F>(z);
+  memcpy(s->z, z.l, F::N * 4);
   Fe<F> zj = Fd::one();
   for (uint32_t j = 0; j < SC; ++j) { memcpy(&p->ts.zs[j * F::N], zj.l, F::N * 4); zj = Fd::mul(zj, z); }
   const Fe<F> z8 = zj;
@@ -437,85 +458,95 @@ int tile_plan(Ctx* c, size_t n, const uint32_t* z_words, uint32_t tb, TilePlan<F
   for (uint32_t j = 0; j < 16; ++j) { memcpy(&p->ts.zq_hi[j * F::N], zj.l, F::N * 4); zj = Fd::mul(zj, z128); }
   Fe<F> g = z128;                                             // z^(8 * 16) -> z^(8 * tb) = z^T
   for (uint32_t q = 16; q < tb; q <<= 1) g = Fd::mul(g, g);
-  for (uint32_t s = 0; s < TILE_GW; ++s) { memcpy(&p->ts.gw[s * F::N], g.l, F::N * 4); g = Fd::mul(g, g); }
-  p->z_inv = Fd::inv(z);
-  g = p->z_inv;
+  for (uint32_t q = 0; q < TILE_GW; ++q) { memcpy(&p->ts.gw[q * F::N], g.l, F::N * 4); g = Fd::mul(g, g); }
+  g = Fd::inv(z);
+  memcpy(s->z_inv, g.l, F::N * 4);
   for (uint32_t q = 0; q < SC_LOG; ++q) g = Fd::mul(g, g);    // z^-8
-  for (uint32_t s = 0; s < 9; ++s) { memcpy(&p->ts.ginv[s * F::N], g.l, F::N * 4); g = Fd::mul(g, g); }
-  const size_t chunk_words = with_chunks ? (size_t)p->ntiles * tb : 0;
-  const size_t words = (chunk_words + (p->ntiles + 1) + (p->nsuper + 1) + (tb + 1) + p->ntiles) * F::N;
-  DevBuf& b = buf ? *buf : c->scan_tmp;
-  int rc = ensure_buf(c, b, words * 4);
+  for (uint32_t q = 0; q < 9; ++q) { memcpy(&p->ts.ginv[q * F::N], g.l, F::N * 4); g = Fd::mul(g, g); }
+  const size_t chunk_words = with_chunks ? (size_t)s->ntiles * tb : 0;
+  const size_t words = (chunk_words + (s->ntiles + 1) + (s->nsuper + 1) + (tb + 1) + s->ntiles) * F::N;
+  int rc = ensure_buf(c, buf, words * 4);
   if (rc) return rc;
-  p->G = static_cast<uint32_t*>(b.p);
-  p->H = p->G + chunk_words * F::N;
-  p->A = p->H + (size_t)(p->ntiles + 1) * F::N;
-  p->zinv = p->A + (size_t)(p->nsuper + 1) * F::N;
-  p->W = p->zinv + (size_t)(tb + 1) * F::N;
+  s->G = static_cast<uint32_t*>(buf.p);
+  s->H = s->G + chunk_words * F::N;
+  s->A = s->H + (size_t)(s->ntiles + 1) * F::N;
+  s->zinv = s->A + (size_t)(s->nsuper + 1) * F::N;
+  s->W = s->zinv + (size_t)(tb + 1) * F::N;
   return KZG_OK;
+}
+
+// the weights xi^(i+1) (kzg.py:148-150) and the lengths of k polynomials, into a LincombArgs or a TileLincomb
+template <class F, class Args>
+Args lincomb_args(const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride, const uint32_t* xi_words) {
+  using Fd = Field<F>;
+  Args la{};
+  la.polys = d_polys; la.stride = stride; la.k = (uint32_t)k;
+  const Fe<F> xi = Fd::to_mont(Fd::from_words(xi_words));
+  Fe<F> xp = Fd::one();
+  for (size_t i = 0; i < k; ++i) {
+    xp = Fd::mul(xp, xi);
+    memcpy(&la.xipow[i * F::N], xp.l, F::N * 4);
+    la.lens[i] = (uint32_t)lens[i];
+  }
+  return la;
+}
+// weight one over a single vector of n elements
+template <class F>
+TileLincomb lincomb_of_one(const uint32_t* d_vec, size_t n) {
+  TileLincomb la{};
+  la.polys = d_vec; la.stride = n; la.k = 1; la.lens[0] = (uint32_t)n;
+  const Fe<F> one = Field<F>::one();
+  memcpy(&la.xipow[0], one.l, F::N * 4);
+  return la;
 }
 
 // plain combination: out[t] = sum_i xi^(i+1) p_i[t]  (any k <= 64)
 template <class F>
 int launch_lincomb(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                    const uint32_t* xi_words, uint32_t* d_out, size_t n) {
-  using Fd = Field<F>;
-  LincombArgs la{};
-  la.polys = d_polys; la.stride = stride; la.k = (uint32_t)k;
-  const Fe<F> xi = Fd::to_mont(Fd::from_words(xi_words));
-  Fe<F> xp = Fd::one();
-  for (size_t i = 0; i < k; ++i) {
-    xp = Fd::mul(xp, xi);                                   // xi^(i+1): kzg.py:148-150
-    memcpy(&la.xipow[i * F::N], xp.l, F::N * 4);
-    la.lens[i] = (uint32_t)lens[i];
-  }
-  hipLaunchKernelGGL(lincomb_kernel<F>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, la, d_out,
-                     (uint32_t)n);
-  KZG_HIP(c, hipGetLastError());
-  return KZG_OK;
+  hipLaunchKernelGGL(lincomb_kernel<F>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream,
+                     (lincomb_args<F, LincombArgs>(d_polys, lens, k, stride, xi_words)), d_out, (uint32_t)n);
+  return KZG_HIP_RC(c, hipGetLastError());
 }
 
-// pass 1: combination + chunk / tile aggregates + tables.  More than TILE_MAXK polynomials are combined first and
-// pass 1 then runs over the combination itself (weight one).
-template <class F, uint32_t TB>
-int launch_tile_combine(Ctx* c, const TilePlan<F>& p, const uint32_t* d_polys, const size_t* lens, size_t k,
-                        size_t stride, const uint32_t* xi_words, uint32_t* d_comb, size_t n) {
-  using Fd = Field<F>;
-  TileLincomb la{};
-  if (k > TILE_MAXK) {
-    int rc = launch_lincomb<F>(c, d_polys, lens, k, stride, xi_words, d_comb, n);
-    if (rc) return rc;
-    la.polys = d_comb; la.stride = n; la.k = 1; la.lens[0] = (uint32_t)n;
-    const Fe<F> one = Fd::one();
-    memcpy(&la.xipow[0], one.l, F::N * 4);
-  } else {
-    la.polys = d_polys; la.stride = stride; la.k = (uint32_t)k;
-    const Fe<F> xi = Fd::to_mont(Fd::from_words(xi_words));
-    Fe<F> xp = Fd::one();
-    for (size_t i = 0; i < k; ++i) {
-      xp = Fd::mul(xp, xi);                                 // xi^(i+1): kzg.py:148-150
-      memcpy(&la.xipow[i * F::N], xp.l, F::N * 4);
-      la.lens[i] = (uint32_t)lens[i];
-    }
-  }
-  hipLaunchKernelGGL((tile_combine_kernel<F, TB, TILE_ITER>), dim3(p.ntiles + p.ntab), dim3(TB * SC / TILE_ITER), 0,
-                     c->stream, la, p.ts, d_comb, (uint32_t)n, p.ntiles, p.G, p.H, p.zinv, p.W);
+// pass 1: combination + chunk / tile aggregates + tables.  STORE = false: the aggregates and tables alone.
+template <class F, uint32_t TB, bool STORE = true>
+int launch_tile_combine(Ctx* c, const TileShape& s, const TilePass1& p, const TileLincomb& la, uint32_t* d_comb) {
+  hipLaunchKernelGGL((tile_combine_kernel<F, TB, TILE_ITER, STORE>), dim3(s.ntiles + p.ntab),
+                     dim3(TB * SC / TILE_ITER), 0, c->stream, la, p.ts, d_comb, (uint32_t)s.n, s.ntiles,
+                     STORE ? s.G : (uint32_t*)nullptr, s.H, s.zinv, s.W);
   KZG_HIP(c, hipGetLastError());
-  if (p.nsuper) {
-    hipLaunchKernelGGL(tile_group_kernel<F>, dim3(p.nsuper), dim3(64), 0, c->stream, p.H, p.W, p.ntiles, p.A);
-    KZG_HIP(c, hipGetLastError());
-  }
-  return KZG_OK;
+  if (s.nsuper) hipLaunchKernelGGL(tile_group_kernel<F>, dim3(s.nsuper), dim3(64), 0, c->stream, s.H, s.W, s.ntiles, s.A);
+  return KZG_HIP_RC(c, hipGetLastError());
+}
+// pass 1 of an opening.  More than TILE_MAXK polynomials are combined first and pass 1 then runs over the combination
+// itself (weight one).
+template <class F, uint32_t TB>
+int launch_open_combine(Ctx* c, const TileShape& s, const TilePass1& p, const uint32_t* d_polys, const size_t* lens,
+                        size_t k, size_t stride, const uint32_t* xi_words, uint32_t* d_comb) {
+  if (k <= TILE_MAXK)
+    return launch_tile_combine<F, TB>(c, s, p, lincomb_args<F, TileLincomb>(d_polys, lens, k, stride, xi_words), d_comb);
+  int rc = launch_lincomb<F>(c, d_polys, lens, k, stride, xi_words, d_comb, s.n);
+  return rc ? rc : launch_tile_combine<F, TB>(c, s, p, lincomb_of_one<F>(d_comb, s.n), d_comb);
 }
 
+// pass 2.  hv: the aggregate of a virtual tile above the last one (sharded open), or null
 template <class F, uint32_t TB>
-int launch_tile_fill(Ctx* c, const TilePlan<F>& p, const uint32_t* d_comb, size_t n, const FrArg* hv, uint32_t* d_S) {
-  FrArg none{};
-  hipLaunchKernelGGL((tile_fill_kernel<F, TB>), dim3(p.ntiles), dim3(TB), 0, c->stream, d_comb, (uint32_t)n, p.ntiles,
-                     p.G, p.H, p.nsuper ? p.A : (const uint32_t*)nullptr, p.nsuper, hv ? *hv : none, hv ? 1u : 0u, p.z,
-                     p.zinv, p.W, d_S);
-  KZG_HIP(c, hipGetLastError());
-  return KZG_OK;
+int launch_tile_fill(Ctx* c, const TileShape& s, const uint32_t* d_comb, const FrArg* hv, uint32_t* d_S) {
+  FrArg none{}, z;
+  memcpy(z.l, s.z, sizeof(z.l));
+  hipLaunchKernelGGL((tile_fill_kernel<F, TB>), dim3(s.ntiles), dim3(TB), 0, c->stream, d_comb, (uint32_t)s.n, s.ntiles,
+                     s.G, s.H, s.nsuper ? s.A : (const uint32_t*)nullptr, s.nsuper, hv ? *hv : none, hv ? 1u : 0u, z,
+                     s.zinv, s.W, d_S);
+  return KZG_HIP_RC(c, hipGetLastError());
+}
+
+// S_0 alone from the aggregates of pass 1
+template <class F, uint32_t TB>
+int launch_tile_eval(Ctx* c, const TileShape& s, uint32_t* d_out) {
+  hipLaunchKernelGGL((tile_eval_kernel<F, TB>), dim3(1), dim3(TB), 0, c->stream, s.ntiles, s.H,
+                     s.nsuper ? s.A : (const uint32_t*)nullptr, s.nsuper, s.W, d_out);
+  return KZG_HIP_RC(c, hipGetLastError());
 }
 
 template <class F>
@@ -545,22 +576,21 @@ int open_quotient_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t 
   int rc = check_open_args<F>(c, lens, k, stride, &n);
   if (rc) return rc;
   if (n == 0) return KZG_OK;     // all polynomials zero: witness 0, evaluation 0
-  if ((rc = ensure_buf(c, c->poly_tmp[0], (2 * (n + 1) + 1) * 32))) return rc;
-  uint32_t* d_comb = static_cast<uint32_t*>(c->poly_tmp[0].p);
-  uint32_t* d_eval = d_comb + (n + 1) * 8;
+  const OpenBufs bufs = claim_open_bufs(c);
+  uint32_t *d_comb, *d_eval;
+  if ((rc = open_vectors(c, bufs.vec, n, &d_comb, &d_eval))) return rc;
   {
     ProfScope ps(c, "open_poly");
     if (words_are_zero(z_words)) {         // S_j = c_j: the combination IS the vector of suffix values
       if ((rc = launch_lincomb<F>(c, d_polys, lens, k, stride, xi_words, d_eval, n))) return rc;
     } else {
-      TilePlan<F> p;
-      const uint32_t tb = open_tile_threads(c);
-      if ((rc = tile_plan<F>(c, n, z_words, tb, &p))) return rc;
-      rc = tb == 128 ? launch_tile_combine<F, 128>(c, p, d_polys, lens, k, stride, xi_words, d_comb, n)
-                     : launch_tile_combine<F, 256>(c, p, d_polys, lens, k, stride, xi_words, d_comb, n);
-      if (rc) return rc;
-      rc = tb == 128 ? launch_tile_fill<F, 128>(c, p, d_comb, n, nullptr, d_eval)
-                     : launch_tile_fill<F, 256>(c, p, d_comb, n, nullptr, d_eval);
+      TileShape s;
+      TilePass1 p;
+      if ((rc = tile_plan<F>(c, n, z_words, open_tile_threads(c), bufs.scan, &s, &p))) return rc;
+      rc = by_tile_width(s.tb, [&](auto w) {
+        return launch_open_combine<F, w>(c, s, p, d_polys, lens, k, stride, xi_words, d_comb);
+      });
+      if (!rc) rc = by_tile_width(s.tb, [&](auto w) { return launch_tile_fill<F, w>(c, s, d_comb, nullptr, d_eval); });
       if (rc) return rc;
     }
   }
@@ -579,40 +609,34 @@ template <class F>
 int open_shard_begin_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                        const uint32_t* z_words, const uint32_t* xi_words, uint64_t* chunk_eval_out) {
   memset(chunk_eval_out, 0, 32);
+  const OpenBufs bufs = claim_open_bufs(c);      // first: a begin that fails leaves no slice
   size_t n = 0;
   int rc = check_open_args<F>(c, lens, k, stride, &n);
   if (rc) return rc;
-  c->open_shard_n = n;
-  c->open_shard_tb = 0;
-  c->open_shard_begun = true;
-  if (n == 0) return KZG_OK;
-  if ((rc = ensure_buf(c, c->poly_tmp[0], (2 * (n + 1) + 1) * 32))) return rc;
-  uint32_t* d_comb = static_cast<uint32_t*>(c->poly_tmp[0].p);
-  uint32_t* d_eval = d_comb + (n + 1) * 8;
-  {
+  OpenSlice held;                                // shape.tb = 0: the empty slice, or z = 0
+  held.state = OpenSlice::HELD;
+  held.shape.n = n;
+  memcpy(held.z_words, z_words, 32);
+  uint32_t *d_comb = nullptr, *d_eval = nullptr;
+  if (n && (rc = open_vectors(c, bufs.vec, n, &d_comb, &d_eval))) return rc;
+  if (n) {
     ProfScope ps(c, "open_shard_poly");
     if (words_are_zero(z_words)) {         // slice(0) = its constant coefficient
       if ((rc = launch_lincomb<F>(c, d_polys, lens, k, stride, xi_words, d_comb, n))) return rc;
-      KZG_HIP(c, hipMemcpyAsync(chunk_eval_out, d_comb, 32, hipMemcpyDeviceToHost, c->stream));
+      d_eval = d_comb;
     } else {
-      TilePlan<F> p;
-      const uint32_t tb = open_tile_threads(c);
-      if ((rc = tile_plan<F>(c, n, z_words, tb, &p))) return rc;
-      rc = tb == 128 ? launch_tile_combine<F, 128>(c, p, d_polys, lens, k, stride, xi_words, d_comb, n)
-                     : launch_tile_combine<F, 256>(c, p, d_polys, lens, k, stride, xi_words, d_comb, n);
+      TilePass1 p;
+      if ((rc = tile_plan<F>(c, n, z_words, open_tile_threads(c), bufs.scan, &held.shape, &p))) return rc;
+      rc = by_tile_width(held.shape.tb, [&](auto w) {
+        int r = launch_open_combine<F, w>(c, held.shape, p, d_polys, lens, k, stride, xi_words, d_comb);
+        return r ? r : launch_tile_eval<F, w>(c, held.shape, d_eval);
+      });
       if (rc) return rc;
-      if (tb == 128)
-        hipLaunchKernelGGL((tile_eval_kernel<F, 128>), dim3(1), dim3(128), 0, c->stream, p.ntiles, p.H,
-                           p.nsuper ? p.A : (const uint32_t*)nullptr, p.nsuper, p.W, d_eval);
-      else
-        hipLaunchKernelGGL((tile_eval_kernel<F, 256>), dim3(1), dim3(256), 0, c->stream, p.ntiles, p.H,
-                           p.nsuper ? p.A : (const uint32_t*)nullptr, p.nsuper, p.W, d_eval);
-      KZG_HIP(c, hipGetLastError());
-      c->open_shard_tb = tb;
-      KZG_HIP(c, hipMemcpyAsync(chunk_eval_out, d_eval, 32, hipMemcpyDeviceToHost, c->stream));
     }
+    KZG_HIP(c, hipMemcpyAsync(chunk_eval_out, d_eval, 32, hipMemcpyDeviceToHost, c->stream));
   }
-  KZG_HIP(c, hipStreamSynchronize(c->stream));
+  if (n) KZG_HIP(c, hipStreamSynchronize(c->stream));
+  c->open_slice = held;
   return KZG_OK;
 }
 
@@ -625,44 +649,42 @@ int open_shard_finish_t(Ctx* c, const uint32_t* z_words, const uint32_t* carry_w
   memset(eval_out, 0, 32);
   *d_vec_out = nullptr;
   *vec_len = 0;
-  // a context that never began a slice holds n = 0, which is also what an empty slice leaves: told apart here
-  if (!c->open_shard_begun) return set_err(c, KZG_ERR_ARG, "kzg_open_shard_finish without kzg_open_shard_begin");
-  const size_t n = c->open_shard_n;
+  // the slice is trusted as begin left it: no plan is made here, and the tuning of the moment has no say
+  const OpenSlice& held = c->open_slice;
+  if (held.state == OpenSlice::NEVER) return set_err(c, KZG_ERR_ARG, "kzg_open_shard_finish without kzg_open_shard_begin");
+  if (held.state == OpenSlice::LOST)
+    return set_err(c, KZG_ERR_ARG, "kzg_open_shard_finish: another opening has used the context since kzg_open_shard_begin");
+  if (memcmp(z_words, held.z_words, 32))
+    return set_err(c, KZG_ERR_ARG, "kzg_open_shard_finish: z differs from the z of kzg_open_shard_begin");
+  const TileShape& s = held.shape;
+  const size_t n = s.n;
   if (n == 0) return KZG_OK;
-  uint32_t* d_comb = static_cast<uint32_t*>(c->poly_tmp[0].p);
-  uint32_t* d_eval = d_comb + (n + 1) * 8;
-  int rc;
+  uint32_t *d_comb, *d_eval;
+  int rc = open_vectors(c, c->poly_tmp[0], n, &d_comb, &d_eval);      // as begin sized it: nothing is allocated
+  if (rc) return rc;
   {
     ProfScope ps(c, "open_shard_poly");
-    if (words_are_zero(z_words)) {         // S_j = c_j for every j below the slice's end
+    if (s.tb == 0) {                       // z = 0: S_j = c_j for every j below the slice's end
       KZG_HIP(c, hipMemcpyAsync(d_eval, d_comb, n * 32, hipMemcpyDeviceToDevice, c->stream));
     } else {
-      const uint32_t tb = c->open_shard_tb;
-      if (tb != 128 && tb != 256) return set_err(c, KZG_ERR_ARG, "kzg_open_shard_finish without kzg_open_shard_begin");
-      TilePlan<F> p;
-      if ((rc = tile_plan<F>(c, n, z_words, tb, &p))) return rc;       // same z, same tiles: same buffers and tables
       // virtual tile `ntiles`: its aggregate is S at index ntiles * T, i.e. carry * z^-(ntiles * T - n)
-      const size_t gap = (size_t)p.ntiles * tb * SC - n;
-      Fe<F> hv = Fd::from_words(carry_words), zi = p.z_inv;
+      const size_t gap = (size_t)s.ntiles * s.tb * SC - n;
+      Fe<F> hv = Fd::from_words(carry_words), zi;
+      memcpy(zi.l, s.z_inv, F::N * 4);
       for (size_t e = gap; e; e >>= 1) {
         if (e & 1) hv = Fd::mul(hv, zi);
         zi = Fd::mul(zi, zi);
       }
       const FrArg hva = fr_arg<F>(hv);
-      rc = tb == 128 ? launch_tile_fill<F, 128>(c, p, d_comb, n, &hva, d_eval)
-                     : launch_tile_fill<F, 256>(c, p, d_comb, n, &hva, d_eval);
-      if (rc) return rc;
+      if ((rc = by_tile_width(s.tb, [&](auto w) { return launch_tile_fill<F, w>(c, s, d_comb, &hva, d_eval); }))) return rc;
     }
   }
   KZG_HIP(c, hipMemcpyAsync(eval_out, d_eval, 32, hipMemcpyDeviceToHost, c->stream));
   KZG_HIP(c, hipStreamSynchronize(c->stream));
-  if (first_rank) {            // S_0 is the evaluation; the quotient slice is S_1 .. S_(n-1)
-    *d_vec_out = d_eval + 8;
-    *vec_len = n - 1;
-  } else {                     // S_lo is the quotient coefficient lo-1: commit S_lo .. S_(hi-1)
-    *d_vec_out = d_eval;
-    *vec_len = n;
-  }
+  // first rank: S_0 is the evaluation, the quotient slice is S_1 .. S_(n-1); otherwise S_lo is the quotient
+  // coefficient lo-1: commit S_lo .. S_(hi-1)
+  *d_vec_out = d_eval + (first_rank ? 8 : 0);
+  *vec_len = n - (first_rank ? 1 : 0);
   return KZG_OK;
 }
 
@@ -783,11 +805,12 @@ int open_coset_quotient_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, s
   if (n == 0) return KZG_OK;     // all polynomials zero: quotient 0, every value 0
   const uint32_t rows = (uint32_t)((n + l - 1) >> log_l);
   const size_t padded = (size_t)rows << log_l;
-  if ((rc = ensure_buf(c, c->poly_tmp[0], padded * 32))) return rc;
+  const OpenBufs bufs = claim_open_bufs(c);
+  if ((rc = ensure_buf(c, bufs.vec, padded * 32))) return rc;
   size_t agg = 0;                                             // aggregates of every level of the blocked scan
   for (uint32_t r = rows; r > 1; r = (r + CS_R - 1) / CS_R) agg += (size_t)((r + CS_R - 1) / CS_R) << log_l;
-  if ((rc = ensure_buf(c, c->scan_tmp, (agg + 1) * 32))) return rc;
-  uint32_t* d_S = static_cast<uint32_t*>(c->poly_tmp[0].p);
+  if ((rc = ensure_buf(c, bufs.scan, (agg + 1) * 32))) return rc;
+  uint32_t* d_S = static_cast<uint32_t*>(bufs.vec.p);
   const Fe<F> h = Fd::to_mont(Fd::from_words(h_words));
   Fe<F> a = h;
   for (uint32_t q = 0; q < log_l; ++q) a = Fd::sqr(a);        // a = h^l
@@ -795,7 +818,7 @@ int open_coset_quotient_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, s
   {
     ProfScope ps(c, "open_coset_poly");
     if ((rc = launch_lincomb<F>(c, d_polys, lens, k, stride, xi_words, d_S, padded))) return rc;   // zero-padded rows
-    if ((rc = coset_scan_level<F>(c, d_S, rows, log_l, a, static_cast<uint32_t*>(c->scan_tmp.p)))) return rc;
+    if ((rc = coset_scan_level<F>(c, d_S, rows, log_l, a, static_cast<uint32_t*>(bufs.scan.p)))) return rc;
     KZG_HIP(c, hipMemcpyAsync(rho.data(), d_S, std::min(l, n) * 32, hipMemcpyDeviceToHost, c->stream));
   }
   KZG_HIP(c, hipStreamSynchronize(c->stream));
@@ -1166,7 +1189,6 @@ int vec_prefix_product_t(Ctx* c, size_t n, const uint32_t* a, uint32_t* out) {
 // one-workgroup sum of the aggregates -- two launches (rounds 1-3 collapsed chunks of 8 level by level: seven)
 template <class F>
 int poly_eval_t(Ctx* c, size_t n, const uint32_t* a, const uint32_t* z_words, uint64_t* out) {
-  using Fd = Field<F>;
   memset(out, 0, 32);
   if (n == 0) return KZG_OK;
   if (n >= (1ull << 31) - 1) return set_err(c, KZG_ERR_ARG, "vector too long");
@@ -1175,23 +1197,14 @@ int poly_eval_t(Ctx* c, size_t n, const uint32_t* a, const uint32_t* z_words, ui
     KZG_HIP(c, hipStreamSynchronize(c->stream));
     return KZG_OK;
   }
-  TilePlan<F> p;
-  int rc = tile_plan<F>(c, n, z_words, 256, &p, &c->poly_tmp[2], /*with_chunks=*/false);
+  TileShape s;                                  // its own plan in its own buffers: an opening's slice stays
+  TilePass1 p;
+  int rc = tile_plan<F>(c, n, z_words, 256, c->poly_tmp[2], &s, &p, /*with_chunks=*/false);
   if (rc) return rc;
   if ((rc = ensure_buf(c, c->poly_tmp[3], 32))) return rc;
   uint32_t* d_val = static_cast<uint32_t*>(c->poly_tmp[3].p);
-  TileLincomb la{};
-  la.polys = a; la.stride = n; la.k = 1; la.lens[0] = (uint32_t)n;
-  const Fe<F> one = Fd::one();
-  memcpy(&la.xipow[0], one.l, F::N * 4);
-  hipLaunchKernelGGL((tile_combine_kernel<F, 256, TILE_ITER, false>), dim3(p.ntiles + p.ntab), dim3(256 * SC / TILE_ITER),
-                     0, c->stream, la, p.ts, (uint32_t*)nullptr, (uint32_t)n, p.ntiles, (uint32_t*)nullptr, p.H, p.zinv,
-                     p.W);
-  if (p.nsuper)
-    hipLaunchKernelGGL(tile_group_kernel<F>, dim3(p.nsuper), dim3(64), 0, c->stream, p.H, p.W, p.ntiles, p.A);
-  hipLaunchKernelGGL((tile_eval_kernel<F, 256>), dim3(1), dim3(256), 0, c->stream, p.ntiles, p.H,
-                     p.nsuper ? p.A : (const uint32_t*)nullptr, p.nsuper, p.W, d_val);
-  KZG_HIP(c, hipGetLastError());
+  if ((rc = launch_tile_combine<F, 256, false>(c, s, p, lincomb_of_one<F>(a, n), nullptr))) return rc;
+  if ((rc = launch_tile_eval<F, 256>(c, s, d_val))) return rc;
   KZG_HIP(c, hipMemcpyAsync(out, d_val, 32, hipMemcpyDeviceToHost, c->stream));
   KZG_HIP(c, hipStreamSynchronize(c->stream));
   return KZG_OK;

@@ -21,7 +21,8 @@ once ntiles > open_direct_tiles, else 0):
   ragged ends      [700, e), k = 1 .. 64          2    >500    0      128    middle (k <= 16 and k > 16)
   special points   n = 2053 | 2447 | 500      2 | 2 | 1  2043 | 1649 | 1548  0  256 (the library's choice)
   special points   z = 0                         the copy route of both calls, no tiles
-  pending commits  n = 1500 | 1600 | 500         the library's choice (128 while an accumulate kernel is in flight)"""
+  pending commits  n = 1500 | 1600 | 500         the library's choice (128 while an accumulate kernel is in flight)
+  grouping changed n = 1500 | 1600 | 500      2 | 2 | 1  >= 448    1 | 0    128    begin with direct 1, finish with 0, and back"""
 import random
 
 import numpy as np
@@ -361,6 +362,154 @@ def test_shard_finish_continues_the_last_begin(envs, curve):
         if stage == "begin2":
             ctx.open_shard_begin(t.data_ptr(), lens, stride, native.int_to_words(oz), native.int_to_words(oxi))
     play_ranks(env, polys, xi, z, STATE_BOUNDS, hook=hook, fresh_keys=True)
+
+
+@pytest.mark.parametrize("direct_begin,direct_finish", [(0, 1), (1, 0)])
+@pytest.mark.parametrize("curve", CURVES)
+def test_shard_finish_uses_the_grouping_begin_recorded(envs, curve, direct_begin, direct_finish):
+    """`open_direct_tiles` changed between begin and finish, width 128 (slices of two, two and one tiles: with the
+    value 1 the two-tile slices sum through one group aggregate, with 0 they do not).  A begin on another slice with
+    grouping on runs first, so that a foreign group aggregate lies where finish would look for one; finish fills
+    from the shape begin left, whatever the tuning says by then."""
+    env = envs[curve]
+    native, ctx = env.native, env.ctx
+    polys, z, xi = state_case(env)
+    other, oz, oxi = state_case(env, seed=9)
+    t, lens, stride = upload(native, other, 100, 2900)
+
+    def hook(stage, g):
+        if stage == "begin2":
+            ctx.set_tuning("open_direct_tiles", 1)
+            ctx.open_shard_begin(t.data_ptr(), lens, stride, native.int_to_words(oz), native.int_to_words(oxi))
+            ctx.set_tuning("open_direct_tiles", direct_begin)
+        else:
+            ctx.set_tuning("open_direct_tiles", direct_finish)
+    try:
+        ctx.set_tuning("open_tile_threads", 128)
+        play_ranks(env, polys, xi, z, STATE_BOUNDS, hook=hook)
+    finally:
+        reset_tuning(ctx)
+
+
+def refused_finish(env, key, z, first_rank):
+    """finish is KZG_ERR_ARG -> the message"""
+    native = env.native
+    with pytest.raises(native.NativeError) as e:
+        env.ctx.open_shard_finish(key, native.int_to_words(z), native.int_to_words(7), first_rank)
+    assert e.value.code == KZG_ERR_ARG
+    return str(e.value)
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_shard_finish_with_another_z_is_refused(envs, curve):
+    """finish must be given begin's z: another one is an argument error whose message names z, the slice stays, and
+    the same finish with begin's z returns the restated result."""
+    env = envs[curve]
+    polys, z, xi = state_case(env)
+
+    def hook(stage, g):
+        if stage == "finish":
+            key = env.shard(g, STATE_BOUNDS[g], STATE_BOUNDS[g + 1])
+            for wrong in ((z + 1) % env.r, 0):
+                assert "z differs" in refused_finish(env, key, wrong, g == 0)
+    play_ranks(env, polys, xi, z, STATE_BOUNDS, hook=hook)
+
+
+@pytest.mark.parametrize("between", ["open", "open_coset"])
+@pytest.mark.parametrize("curve", CURVES)
+def test_shard_finish_after_another_opening_is_refused(envs, curve, between):
+    """kzg_open_device / kzg_open_coset_device between begin and finish overwrite what begin left: finish is an
+    argument error that says so (not the "never begun" one), and the context then completes a sharded opening."""
+    env = envs[curve]
+    native, ctx, r = env.native, env.ctx, env.r
+    polys, z, xi = state_case(env)
+    zw, xw = native.int_to_words(z), native.int_to_words(xi)
+    t, lens, stride = upload(native, polys, 0, 1500)
+    ctx.open_shard_begin(t.data_ptr(), lens, stride, zw, xw)
+    if between == "open":
+        key = ctx.srs_generate(env.tw, 1600)
+        ev = ctx.open(key, t.data_ptr(), lens, stride, zw, xw, device=True)[2]
+        assert native.limbs_to_ints(ev.reshape(1, 4))[0] == O.poly_eval(O.combine([p[:1500] for p in polys], xi, r), z, r)
+    else:
+        key = ctx.srs_generate(env.tw, 64)
+        t64, lens64, stride64 = upload(native, polys, 0, 64)
+        ctx.open_coset(key, t64.data_ptr(), lens64, stride64, 1, 5, r - 1, xi, device=True)
+    try:
+        msg = refused_finish(env, key, z, True)
+        assert "another opening" in msg and "without kzg_open_shard_begin" not in msg
+    finally:
+        key.close()
+    play_ranks(env, polys, xi, z, STATE_BOUNDS)
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_shard_slice_is_kept_across_other_calls(envs, curve):
+    """kzg_fr_poly_eval (3000 coefficients: two tiles of 2048, its own plan in its own buffers), a prefix product of
+    100 elements and a change of `open_tile_threads` between begin and finish: each gives its own result and the
+    slice stands.  (Key generation and commits in between: test_shard_finish_continues_the_last_begin,
+    test_shard_begin_beside_pending_async_commits.)"""
+    import torch
+    env = envs[curve]
+    native, ctx, r = env.native, env.ctx, env.r
+    polys, z, xi = state_case(env)
+    rng = random.Random(77)
+    vec = [rng.randrange(r) for _ in range(3000)]
+    d_vec = upload(native, [vec], 0, 3000)[0]
+    pz = rng.randrange(2, r)
+    want_eval = O.poly_eval(vec, pz, r)
+    want_prefix, acc = [], 1
+    for y in vec[:100]:
+        want_prefix.append(acc)
+        acc = acc * y % r
+    d_out = torch.zeros((100, 4), dtype=torch.int64, device="cuda:0")
+
+    def hook(stage, g):
+        if stage == "finish":
+            assert ctx.poly_eval(3000, d_vec.data_ptr(), pz) == want_eval
+            ctx.vec_prefix_product(100, d_vec.data_ptr(), d_out.data_ptr())
+            ctx.synchronize()
+            assert native.limbs_to_ints(d_out.cpu().numpy().view(np.uint64)) == want_prefix
+            ctx.set_tuning("open_tile_threads", 256 if g % 2 else 128)
+    try:
+        play_ranks(env, polys, xi, z, STATE_BOUNDS, hook=hook)
+    finally:
+        reset_tuning(ctx)
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_shard_begin_that_fails_leaves_no_slice(envs, curve):
+    """A begin refused for its arguments (lens[0] > stride) after a good begin: the earlier slice is gone, finish is
+    an argument error."""
+    env = envs[curve]
+    native, ctx = env.native, env.ctx
+    polys, z, xi = state_case(env)
+    zw, xw = native.int_to_words(z), native.int_to_words(xi)
+    t, lens, stride = upload(native, polys, 0, 1500)
+    ctx.open_shard_begin(t.data_ptr(), lens, stride, zw, xw)
+    with pytest.raises(native.NativeError) as e:
+        ctx.open_shard_begin(t.data_ptr(), [stride + 1, lens[1]], stride, zw, xw)
+    assert e.value.code == KZG_ERR_ARG
+    refused_finish(env, env.shard(0, 0, 1500), z, True)
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_shard_finish_twice_after_one_begin(envs, curve):
+    """finish does not consume the slice: every rank finishes twice after its one begin, and both calls return the
+    same eval_out and point -- the restated ones."""
+    env = envs[curve]
+    native, ctx = env.native, env.ctx
+    polys, z, xi = state_case(env)
+    want = restate_sharded_open(polys, xi, z, STATE_BOUNDS, env.tau, env.r)
+    first = []
+
+    def hook(stage, g):
+        if stage == "finish":
+            key = env.shard(g, STATE_BOUNDS[g], STATE_BOUNDS[g + 1])
+            xy, inf, ev = ctx.open_shard_finish(key, native.int_to_words(z), native.int_to_words(want.carry[g]), g == 0)
+            first.append((native.limbs_to_ints(ev.reshape(1, 4))[0],
+                          None if inf[0] else tuple(native.limbs_to_ints(xy.reshape(2, ctx.fp_limbs)))))
+    second = play_ranks(env, polys, xi, z, STATE_BOUNDS, want=want, hook=hook)
+    assert first == [(ev, pt) for _, ev, pt in second]
 
 
 @pytest.mark.parametrize("curve", CURVES)
