@@ -329,6 +329,18 @@ int kzg_verify_cosets(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uin
                       const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
                       const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy,
                       const uint8_t* proof_inf, size_t K, const uint64_t rho[4], uint64_t* out_xy, uint8_t* out_inf);
+/* The same fold with the values as they travel in EIP-7594: cells [K][l][32], every element 32
+ * big-endian bytes in host memory.  bit_reversed != 0: element t of a cell is value bitrev_log_l(t) of its coset, the
+ * order of a cell of the specification; 0: natural order, as `values`.  The bytes are uploaded once and
+ * kzg_blob_to_fr's kernel writes them into the workspace's value array (log_n = log_l, b = K); from there the call IS
+ * kzg_verify_cosets, arguments, ranges and errors included.  An element >= r is a verdict, not an error:
+ * *out_status = 1, both points at infinity and KZG_OK (nothing is folded); otherwise *out_status = 0.
+ * "verify_device_bytes" then counts the staged bytes and the cells' status bytes as well. */
+int kzg_verify_cosets_bytes(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
+                            const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
+                            const uint32_t* coset_idx, const uint8_t* cells, int bit_reversed, const uint64_t* proof_xy,
+                            const uint8_t* proof_inf, size_t K, const uint64_t rho[4], uint64_t* out_xy,
+                            uint8_t* out_inf, uint8_t* out_status);
 /* ---- bulk verification at arbitrary points: K single-point claims folded into ONE pairing equation
  * Claim k < K: the polynomial of commitment C[c_k] takes the value y_k at z_k -- ANY element of Fr, what kzg_open,
  * kzg_open_evals and an EIP-4844 blob proof open at -- with proof pi_k.  With weights r_k = rho^(k+1) (the rule of
@@ -461,6 +473,12 @@ int kzg_srs_export_compressed(kzg_ctx* ctx, const kzg_srs* srs, size_t start, si
  *                           The bytes are hashed as given: neither the elements' canonicity nor the commitment's
  *                           validity is looked at, the hash is defined on bytes.  One lane per blob, 64-byte blocks,
  *                           n/2 + 2 compressions per blob.
+ *   kzg_fr_to_blob          the intake's inverse: out_bytes[j][i] = the 32 big-endian bytes of
+ *                           vals[j][i], or of vals[j][bitrev_log_n(i)] when bit_reversed != 0.  vals: [b][n][4] limbs;
+ *                           out_status[j] = 1 if some element of row j is >= r, and that element's bytes are zeros.
+ *                           One row of N natural-order evaluations with bit_reversed != 0 gives the N/l cells of
+ *                           EIP-7594 one after the other: cell c is the coset bitrev(c) of kzg_open_cosets, element t
+ *                           of a cell its value bitrev_log_l(t).  _device: d_vals 32-byte, d_bytes 16-byte aligned.
  * Ranges: 1 <= log_n <= 24 and b * 2^log_n <= 2^26 elements per call, otherwise KZG_ERR_ARG; b = 0 is KZG_OK with no
  * work.  The host forms take host pointers and synchronise.  The _device forms take device pointers (16-byte aligned;
  * d_vals and d_z 32-byte aligned; d_status b bytes), enqueue on the context's stream and do not wait.  Both run on the
@@ -469,6 +487,10 @@ int kzg_srs_export_compressed(kzg_ctx* ctx, const kzg_srs* srs, size_t start, si
 int kzg_blob_to_fr(kzg_ctx* ctx, uint32_t log_n, const uint8_t* blobs, size_t b, int bit_reversed, uint64_t* out_vals,
                    uint8_t* out_status);
 int kzg_blob_to_fr_device(kzg_ctx* ctx, uint32_t log_n, const void* d_blobs, size_t b, int bit_reversed, void* d_vals,
+                          void* d_status);
+int kzg_fr_to_blob(kzg_ctx* ctx, uint32_t log_n, const uint64_t* vals, size_t b, int bit_reversed, uint8_t* out_bytes,
+                   uint8_t* out_status);
+int kzg_fr_to_blob_device(kzg_ctx* ctx, uint32_t log_n, const void* d_vals, size_t b, int bit_reversed, void* d_bytes,
                           void* d_status);
 int kzg_blob_challenges(kzg_ctx* ctx, uint32_t log_n, const uint8_t* blobs, const uint8_t* commitments, size_t b,
                         uint64_t* out_z);
@@ -557,7 +579,7 @@ int kzg_pairing_gt_multiple(int curve);
  * the product tree and every chunk), "g1_decompress" (ONE per kzg_g1_decompress*, and one per
  * kzg_srs_load_g1_compressed: the decoding, with the subgroup test when asked for), "g1_subgroup" (ONE per
  * kzg_g1_check_subgroup), "verify_points" (ONE per kzg_verify_points: the whole call), "eval_lagrange_batch" (ONE per
- * kzg_fr_eval_lagrange_batch*: every chunk), "blob_intake" (ONE per kzg_blob_to_fr*), "blob_challenge" (ONE per
+ * kzg_fr_eval_lagrange_batch*: every chunk), "blob_intake" (ONE per kzg_blob_to_fr*), "blob_output" (ONE per kzg_fr_to_blob*), "blob_challenge" (ONE per
  * kzg_blob_challenges*) and "pairing" (ONE per kzg_pairing_check / kzg_pairing_product: copies and kernel).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.
  * Two names are not spans: "msm_accumulate_shader_mhz" and "ntt_pass_shader_mhz" return (in *total_ms) the shader

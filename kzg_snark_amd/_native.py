@@ -123,6 +123,11 @@ SIGNATURES = {
     "kzg_pairing_gt_multiple": (ctypes.c_int, [ctypes.c_int]),
     "kzg_blob_to_fr": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp]),
     "kzg_blob_to_fr_device": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp]),
+    "kzg_fr_to_blob": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp]),
+    "kzg_fr_to_blob_device": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp]),
+    "kzg_verify_cosets_bytes": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp,
+                                               ctypes.c_size_t, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_size_t,
+                                               _vp, _vp, _vp, _vp]),
     "kzg_blob_challenges": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, ctypes.c_size_t, _vp]),
     "kzg_blob_challenges_device": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, ctypes.c_size_t, _vp]),
 }
@@ -459,6 +464,24 @@ class Context:
         self._check(lib().kzg_blob_to_fr_device(self._h, int(log_n), _as_vp(d_blobs), int(b), int(bool(bit_reversed)),
                                                 _as_vp(d_vals), _as_vp(d_status)))
 
+    def fr_to_blob(self, vals, log_n, bit_reversed=True):
+        """The inverse of blob_to_fr: uint64[b, n, 4] canonical limbs -> (uint8[b, 32 << log_n] big-endian elements,
+        status uint8[b]); bit_reversed: byte element i is value bitrev(i).  status 1: some element of the row is >= r
+        (its bytes are zeros)."""
+        n = 1 << int(log_n)
+        vals = np.ascontiguousarray(vals, dtype=np.uint64).reshape(-1, n, 4)
+        b = vals.shape[0]
+        out = np.zeros((b, 32 * n), dtype=np.uint8)
+        status = np.zeros(b, dtype=np.uint8)
+        self._check(lib().kzg_fr_to_blob(self._h, int(log_n), _as_vp(vals), b, int(bool(bit_reversed)), _as_vp(out),
+                                         _as_vp(status)))
+        return out, status
+
+    def fr_to_blob_device(self, d_vals, log_n, b, bit_reversed, d_bytes, d_status):
+        """The same on device pointers, enqueued on the context's stream (no synchronisation)."""
+        self._check(lib().kzg_fr_to_blob_device(self._h, int(log_n), _as_vp(d_vals), int(b), int(bool(bit_reversed)),
+                                                _as_vp(d_bytes), _as_vp(d_status)))
+
     def blob_challenges(self, blobs, commitments, log_n):
         """uint8[b, 32 << log_n] blobs and uint8[b, g1_bytes] commitments -> uint64[b, 4]: the challenges
         SHA-256("FSBLOBVERIFY_V1_" | n | blob | commitment) mod r, hashed on the device, one lane per blob."""
@@ -606,6 +629,33 @@ class Context:
         # the library retires every pipeline slot before it returns, as kzg_commit_flush does
         self._inflight.clear()
         return out_xy, out_inf
+
+    def verify_cosets_bytes(self, srs, log_N, log_l, w, comm_xy, comm_inf, comm_idx, coset_idx, cells, proof_xy,
+                            proof_inf, rho, bit_reversed=True):
+        """verify_cosets with the values as cells of 32-byte big-endian elements (uint8[K, 32 * l]; bit_reversed:
+        element t of a cell is value bitrev(t) of its coset): (xy, inf, status).  status 1: some element is >= r, both
+        points are then at infinity."""
+        P = 2 * self.fp_limbs
+        comm_idx = np.ascontiguousarray(comm_idx, dtype=np.uint32).reshape(-1)
+        coset_idx = np.ascontiguousarray(coset_idx, dtype=np.uint32).reshape(-1)
+        K, l = comm_idx.size, 1 << int(log_l)
+        comm_xy = np.ascontiguousarray(comm_xy, dtype=np.uint64).reshape(-1, P)
+        proof_xy = np.ascontiguousarray(proof_xy, dtype=np.uint64).reshape(-1, P)
+        cells = np.ascontiguousarray(cells, dtype=np.uint8)
+        if coset_idx.size != K or proof_xy.shape[0] != K or cells.size != K * l * 32:
+            raise ValueError("verify_cosets_bytes: comm_idx, coset_idx, cells and proofs describe different numbers "
+                             "of cells")
+        comm_inf = _inf_arg(comm_inf, comm_xy.shape[0], "verify_cosets_bytes: comm_inf and comm_xy")
+        proof_inf = _inf_arg(proof_inf, K, "verify_cosets_bytes: proof_inf and proof_xy")
+        out_xy, out_inf, _ = result_buffers(self.fp_limbs, (2,))
+        status = np.zeros(1, dtype=np.uint8)
+        self._check(lib().kzg_verify_cosets_bytes(self._h, srs._h, int(log_N), int(log_l), _fr(w), _as_vp(comm_xy),
+                                                  _as_vp(comm_inf), comm_xy.shape[0], _as_vp(comm_idx),
+                                                  _as_vp(coset_idx), _as_vp(cells), int(bool(bit_reversed)),
+                                                  _as_vp(proof_xy), _as_vp(proof_inf), K, _fr(rho), _as_vp(out_xy),
+                                                  _as_vp(out_inf), _as_vp(status)))
+        self._inflight.clear()
+        return out_xy, out_inf, int(status[0])
 
     def verify_points(self, comm_xy, comm_inf, comm_idx, z, y, proof_xy, proof_inf, rho):
         """The two G1 points (L, R) of the rho-weighted combination of K claims at arbitrary points: (xy

@@ -418,6 +418,18 @@ int kzg_blob_to_fr_device(kzg_ctx* ctx, uint32_t log_n, const void* d_blobs, siz
   return blob_to_fr_device(c, log_n, d_blobs, b, bit_reversed, d_vals, d_status);
 }
 
+int kzg_fr_to_blob(kzg_ctx* ctx, uint32_t log_n, const uint64_t* vals, size_t b, int bit_reversed, uint8_t* out_bytes,
+                   uint8_t* out_status) {
+  KZG_ENTER(b && (!vals || !out_bytes || !out_status));
+  return fr_to_blob(c, log_n, vals, b, bit_reversed, out_bytes, out_status);
+}
+
+int kzg_fr_to_blob_device(kzg_ctx* ctx, uint32_t log_n, const void* d_vals, size_t b, int bit_reversed, void* d_bytes,
+                          void* d_status) {
+  KZG_ENTER(b && (!d_vals || !d_bytes || !d_status));
+  return fr_to_blob_device(c, log_n, d_vals, b, bit_reversed, d_bytes, d_status);
+}
+
 int kzg_blob_challenges(kzg_ctx* ctx, uint32_t log_n, const uint8_t* blobs, const uint8_t* commitments, size_t b,
                         uint64_t* out_z) {
   KZG_ENTER(b && (!blobs || !commitments || !out_z));
@@ -707,6 +719,18 @@ int kzg_verify_cosets(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uin
   return verify_cosets(c, monomial->s, log_N, log_l, reinterpret_cast<const uint32_t*>(w), comm_xy, comm_inf, n_comm,
                        comm_idx, coset_idx, values, proof_xy, proof_inf, K, reinterpret_cast<const uint32_t*>(rho),
                        out_xy, out_inf);
+}
+
+int kzg_verify_cosets_bytes(kzg_ctx* ctx, const kzg_srs* monomial, uint32_t log_N, uint32_t log_l, const uint64_t w[4],
+                            const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
+                            const uint32_t* coset_idx, const uint8_t* cells, int bit_reversed, const uint64_t* proof_xy,
+                            const uint8_t* proof_inf, size_t K, const uint64_t rho[4], uint64_t* out_xy,
+                            uint8_t* out_inf, uint8_t* out_status) {
+  KZG_ENTER(!monomial || !w || !rho || !out_xy || !out_inf || !out_status || !comm_xy || (K && (!comm_idx ||
+            !coset_idx || !cells || !proof_xy)));
+  return verify_cosets_bytes(c, monomial->s, log_N, log_l, reinterpret_cast<const uint32_t*>(w), comm_xy, comm_inf,
+                             n_comm, comm_idx, coset_idx, cells, bit_reversed, proof_xy, proof_inf, K,
+                             reinterpret_cast<const uint32_t*>(rho), out_xy, out_inf, out_status);
 }
 
 int kzg_verify_points(kzg_ctx* ctx, const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm,

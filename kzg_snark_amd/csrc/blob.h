@@ -1,6 +1,7 @@
 // blob.h -- an EIP-4844 blob as bytes, one blob (or one element) at a time: the canonicity check of a 32-byte
-// big-endian field element and the Fiat-Shamir challenge of a blob and its commitment.  Shared by the
-// kernels of blob.hip and the host (tests/shim/blob_shim.cpp compiles this text with g++), like g1_bytes.h.
+// big-endian field element, its inverse (limbs back to bytes) and the Fiat-Shamir challenge of a blob
+// and its commitment.  Shared by the kernels of blob.hip and the host (tests/shim/blob_shim.cpp and
+// cells_shim.cpp compile this text with g++), like g1_bytes.h.
 //
 // The challenge of blob j is the SHA-256 digest, reduced mod r, of
 //     "FSBLOBVERIFY_V1_" | n as 16 bytes big-endian | blob (n * 32 bytes) | commitment (G bytes)
@@ -42,6 +43,16 @@ static KZG_HD bool blob_element(const uint32_t raw[8], uint32_t w[8]) {
   const bool ok = words_below_p<F>(w);
 #pragma unroll
   for (int k = 0; k < 8; ++k) w[k] = ok ? w[k] : 0u;
+  return ok;
+}
+
+// The inverse: w[8] canonical little-endian words -> raw[8], the 32 big-endian bytes as they are stored.  true iff the
+// number is below r; otherwise raw is all zeros.
+template <class F>
+static KZG_HD bool blob_output_element(const uint32_t w[8], uint32_t raw[8]) {
+  const bool ok = words_below_p<F>(w);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) raw[k] = ok ? sha_bswap32(w[7 - k]) : 0u;
   return ok;
 }
 

@@ -1,15 +1,18 @@
-// blob.hip -- EIP-4844 blobs as bytes on the device: two kernels around the single-blob functions of
-// blob.h, and the host drivers behind kzg_blob_to_fr* and kzg_blob_challenges*.
+// blob.hip -- EIP-4844 blobs as bytes on the device: three kernels around the single-blob
+// functions of blob.h, and the host drivers behind kzg_blob_to_fr*, kzg_fr_to_blob* and kzg_blob_challenges*.
 //
 //   intake      blob_intake_kernel: one lane per field element.  Two 16-byte loads, the byte swap into canonical
 //               little-endian words, the comparison with r and two 16-byte stores, to the element's own place or to
 //               the bit-reversed one.  An element >= r is stored as zeros and sets its blob's status byte: every such
 //               lane stores the same 1, so a plain store serves and the status bytes are zeroed first on the stream.
+//   output      blob_output_kernel: the intake's inverse, one lane per field element.  Two 16-byte loads from the
+//               element's own place or the bit-reversed one, the comparison with r, the byte swap and two 16-byte
+//               stores.  An element >= r leaves zero bytes and sets its row's status byte, as in the intake.
 //   challenge   blob_challenge_kernel: one lane per blob (the hash is sequential within a blob, independent across
 //               blobs).  The lanes of a wave read addresses a whole blob apart, so every block is a gather of four
 //               16-byte pieces per lane; blob.h asks for the pieces of the next block before it compresses this one.
 //               State, two message windows and the temporaries stay in registers: no scratch, no LDS.
-// Both run on the context's stream alone: pending results of the commit pipeline are neither retired nor disturbed.
+// All run on the context's stream alone: pending results of the commit pipeline are neither retired nor disturbed.
 #include <algorithm>
 #include <string>
 #include "internal.h"
@@ -39,6 +42,23 @@ __global__ __launch_bounds__(256) void blob_intake_kernel(const uint32_t* blobs,
     const bool ok = blob_element<F>(raw, w);
     const uint32_t at = bit_reversed ? bitrev(i, log_n) : i;
     st_words<8>(vals + ((j << log_n) + at) * 8, w);
+    if (!ok) status[j] = 1;
+  }
+}
+
+// out[j][i] = the 32 big-endian bytes of vals[j][i or bitrev(i)]; status[j] = 1 if one of row j's elements is >= r
+template <class F>
+__global__ __launch_bounds__(256) void blob_output_kernel(const uint32_t* vals, size_t total, uint32_t log_n,
+                                                          int bit_reversed, uint32_t* out, uint8_t* status) {
+  const size_t step = (size_t)gridDim.x * blockDim.x;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += step) {
+    const size_t j = idx >> log_n;
+    const uint32_t i = (uint32_t)(idx & (((size_t)1 << log_n) - 1));
+    const uint32_t at = bit_reversed ? bitrev(i, log_n) : i;
+    uint32_t w[8], raw[8];
+    ld_words<8>(vals + ((j << log_n) + at) * 8, w);
+    const bool ok = blob_output_element<F>(w, raw);
+    st_words<8>(out + idx * 8, raw);
     if (!ok) status[j] = 1;
   }
 }
@@ -84,6 +104,17 @@ int intake_launch(Ctx* c, uint32_t log_n, const uint32_t* d_blobs, size_t b, int
   KZG_HIP(c, hipGetLastError());
   return KZG_OK;
 }
+template <class F>
+int output_launch(Ctx* c, uint32_t log_n, const uint32_t* d_vals, size_t b, int bit_reversed, uint32_t* d_out,
+                  uint8_t* d_status) {
+  const size_t total = b << log_n;
+  const uint32_t blocks = (uint32_t)std::min<size_t>((total + 255) / 256, 8192);
+  KZG_HIP(c, hipMemsetAsync(d_status, 0, b, c->stream));
+  hipLaunchKernelGGL(blob_output_kernel<F>, dim3(blocks), dim3(256), 0, c->stream, d_vals, total, log_n, bit_reversed,
+                     d_out, d_status);
+  KZG_HIP(c, hipGetLastError());
+  return KZG_OK;
+}
 template <class C>
 int challenge_launch(Ctx* c, uint32_t log_n, const uint32_t* d_blobs, const uint32_t* d_comms, size_t b, uint32_t* d_z) {
   hipLaunchKernelGGL(blob_challenge_kernel<C>, dim3((uint32_t)((b + CHALLENGE_TB - 1) / CHALLENGE_TB)),
@@ -106,6 +137,26 @@ int blob_to_fr_t(Ctx* c, uint32_t log_n, const uint8_t* blobs, size_t b, int bit
     KZG_HIP(c, hipMemcpyAsync(d_blobs, blobs, bytes, hipMemcpyHostToDevice, c->stream));
     if ((rc = intake_launch<F>(c, log_n, d_blobs, b, bit_reversed, d_vals, d_status))) return rc;
     KZG_HIP(c, hipMemcpyAsync(out_vals, d_vals, bytes, hipMemcpyDeviceToHost, c->stream));
+    KZG_HIP(c, hipMemcpyAsync(out_status, d_status, b, hipMemcpyDeviceToHost, c->stream));
+  }
+  KZG_HIP(c, hipStreamSynchronize(c->stream));
+  return KZG_OK;
+}
+
+template <class F>
+int fr_to_blob_t(Ctx* c, uint32_t log_n, const uint64_t* vals, size_t b, int bit_reversed, uint8_t* out_bytes,
+                 uint8_t* out_status) {
+  const size_t bytes = (b << log_n) * 32;
+  uint32_t *d_vals, *d_out;
+  uint8_t* d_status;
+  int rc = carve(c, c->io,
+                 [&](Carve& ws) { d_vals = ws.take(bytes);  d_out = ws.take(bytes);  d_status = ws.take<uint8_t>(b); });
+  if (rc) return rc;
+  {
+    ProfScope span(c, "blob_output");
+    KZG_HIP(c, hipMemcpyAsync(d_vals, vals, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = output_launch<F>(c, log_n, d_vals, b, bit_reversed, d_out, d_status))) return rc;
+    KZG_HIP(c, hipMemcpyAsync(out_bytes, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
     KZG_HIP(c, hipMemcpyAsync(out_status, d_status, b, hipMemcpyDeviceToHost, c->stream));
   }
   KZG_HIP(c, hipStreamSynchronize(c->stream));
@@ -157,6 +208,26 @@ int blob_to_fr_device(Ctx* c, uint32_t log_n, const void* d_blobs, size_t b, int
   ProfScope span(c, "blob_intake");
   return KZG_BY_FR(c, intake_launch, c, log_n, static_cast<const uint32_t*>(d_blobs), b, bit_reversed,
                    static_cast<uint32_t*>(d_vals), static_cast<uint8_t*>(d_status));
+}
+int blob_intake_launch(Ctx* c, uint32_t log_n, const uint32_t* d_blobs, size_t b, int bit_reversed, uint32_t* d_vals,
+                       uint8_t* d_status) {
+  return KZG_BY_FR(c, intake_launch, c, log_n, d_blobs, b, bit_reversed, d_vals, d_status);
+}
+int fr_to_blob(Ctx* c, uint32_t log_n, const uint64_t* vals, size_t b, int bit_reversed, uint8_t* out_bytes,
+               uint8_t* out_status) {
+  if (int rc = size_check(c, log_n, b, "kzg_fr_to_blob")) return rc;
+  if (b == 0) return KZG_OK;
+  return KZG_BY_FR(c, fr_to_blob_t, c, log_n, vals, b, bit_reversed, out_bytes, out_status);
+}
+int fr_to_blob_device(Ctx* c, uint32_t log_n, const void* d_vals, size_t b, int bit_reversed, void* d_bytes,
+                      void* d_status) {
+  if (int rc = size_check(c, log_n, b, "kzg_fr_to_blob_device")) return rc;
+  if (b == 0) return KZG_OK;
+  if (!aligned(d_vals, 32) || !aligned(d_bytes, 16))
+    return set_err(c, KZG_ERR_ARG, "kzg_fr_to_blob_device: misaligned device pointer");
+  ProfScope span(c, "blob_output");
+  return KZG_BY_FR(c, output_launch, c, log_n, static_cast<const uint32_t*>(d_vals), b, bit_reversed,
+                   static_cast<uint32_t*>(d_bytes), static_cast<uint8_t*>(d_status));
 }
 int blob_challenges(Ctx* c, uint32_t log_n, const uint8_t* blobs, const uint8_t* commitments, size_t b,
                     uint64_t* out_z) {

@@ -115,6 +115,13 @@ int verify_cosets(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const
                   const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
                   const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy, const uint8_t* proof_inf,
                   size_t K, const uint32_t* rho_words, uint64_t* out_xy, uint8_t* out_inf);
+// the same fold with the values as cells of 32-byte big-endian elements: an element >= r sets
+// *out_status and leaves both points at infinity
+int verify_cosets_bytes(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const uint32_t* w_words,
+                        const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
+                        const uint32_t* coset_idx, const uint8_t* cells, int bit_reversed, const uint64_t* proof_xy,
+                        const uint8_t* proof_inf, size_t K, const uint32_t* rho_words, uint64_t* out_xy,
+                        uint8_t* out_inf, uint8_t* out_status);
 
 // verify.hip: d_coef[j] = sum of d_r[d_perm[q]], q in [d_off[j], d_off[j + 1]): the per-commitment sums of the weights
 // over the cells grouped by commitment.  d_cpart: n_comm * ver_commsum_shares(n_comm) elements of scratch.  Two launches.
@@ -160,6 +167,14 @@ int blob_to_fr(Ctx* c, uint32_t log_n, const uint8_t* blobs, size_t b, int bit_r
                uint8_t* out_status);
 int blob_to_fr_device(Ctx* c, uint32_t log_n, const void* d_blobs, size_t b, int bit_reversed, void* d_vals,
                       void* d_status);
+int fr_to_blob(Ctx* c, uint32_t log_n, const uint64_t* vals, size_t b, int bit_reversed, uint8_t* out_bytes,
+               uint8_t* out_status);
+int fr_to_blob_device(Ctx* c, uint32_t log_n, const void* d_vals, size_t b, int bit_reversed, void* d_bytes,
+                      void* d_status);
+// the intake kernel alone, enqueued on the context's stream: nothing checked, log_n >= 0 (verify.hip: cells as bytes)
+__attribute__((visibility("hidden")))   // library-private: not in the exported symbol list
+int blob_intake_launch(Ctx* c, uint32_t log_n, const uint32_t* d_blobs, size_t b, int bit_reversed, uint32_t* d_vals,
+                       uint8_t* d_status);
 int blob_challenges(Ctx* c, uint32_t log_n, const uint8_t* blobs, const uint8_t* commitments, size_t b,
                     uint64_t* out_z);
 int blob_challenges_device(Ctx* c, uint32_t log_n, const void* d_blobs, const void* d_commitments, size_t b,

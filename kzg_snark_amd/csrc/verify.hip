@@ -12,7 +12,9 @@
 //             cells grouped by commitment (a counting sort of the small indices on the host, ver_commsum_kernel)
 //   values    ver_cell_kernel: tiles of max(l, 256) elements in LDS, a decimation-in-frequency inverse transform per
 //             cell (twiddles from the w table), then r_k l^-1 h_k^-j applied on the way back to memory;
-//             ver_colsum_kernel / ver_colsum_final_kernel add the cells up: T
+//             ver_colsum_kernel / ver_colsum_final_kernel add the cells up: T.  kzg_verify_cosets_bytes brings them as
+//             32-byte big-endian elements: uploaded once behind the pinned layout, written into the
+//             value array by the intake kernel of blob.hip; an element >= r is a verdict and nothing is folded
 //   proofs    imported as window-0 records (g1_import: coordinates < p, on the curve) of a key that holds NO
 //             other window; every scalar is cut into slices of win_bits - 1 bits (ver_slice_kernel) and each slice
 //             vector goes through the commit pipeline as one polynomial: a slice yields one digit, in window 0, without
@@ -187,10 +189,19 @@ XYZZ<C> recombine_slices(const uint64_t* xy, const uint8_t* inf, uint32_t ns, ui
   return acc;
 }
 
+// The values of the K claims, one of two forms: canonical limbs in natural order, or cells of 32-byte big-endian
+// elements that the intake kernel of blob.hip turns into the former on the device (status: their verdict)
+struct VerClaims {
+  const uint64_t* limbs;
+  const uint8_t* cells;
+  int bit_reversed;
+  uint8_t* status;
+};
+
 template <class C>
 int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const uint32_t* w_words,
                     const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
-                    const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy,
+                    const uint32_t* coset_idx, const VerClaims& claims, const uint64_t* proof_xy,
                     const uint8_t* proof_inf, size_t K, const uint32_t* rho_words, uint64_t* out_xy, uint8_t* out_inf) {
   using F = typename C::Fr;
   using Fd = Field<F>;
@@ -211,6 +222,7 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
     return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: w is not a primitive N-th root of unity");
   memset(out_xy, 0, 2 * PT_BYTES);
   out_inf[0] = out_inf[1] = 1;
+  if (claims.status) *claims.status = 0;
   if (K == 0) return KZG_OK;
   // the cells grouped by commitment: a counting sort of the indices (and their range check, cell by cell)
   const uint32_t n_cosets = 1u << (log_N - log_l);
@@ -224,10 +236,14 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
   const uint32_t log_e = std::max(log_l, VER_MIN_TILE_LOG);
   const uint32_t sum_threads = std::max<uint32_t>((uint32_t)l, VER_SUM_THREADS);
   VerifyWs d;
+  uint32_t* d_cells = nullptr;                       // the cells as bytes and their verdict, behind the pinned layout
+  uint8_t* d_status = nullptr;
   size_t total = 0;
   int rc = carve(c, c->ver_tmp, [&](Carve& ws) {
     d.layout(ws, K, n_comm, l, proof_inf != nullptr, comm_inf != nullptr, PT_BYTES, rb, POW_TAB, sum_threads,
              ver_commsum_shares(n_comm));
+    d_cells = ws.take_if<uint32_t>(claims.cells != nullptr, M * 32);
+    d_status = ws.take_if(claims.cells != nullptr, K);
   }, &total);
   if (rc) return rc;
 
@@ -247,12 +263,23 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
   uint32_t bad = 0;
   KZG_HIP(c, hipMemcpyAsync(&bad, d.bad, 4, hipMemcpyDeviceToHost, st));
   // the claims travel while the points are checked
-  KZG_HIP(c, hipMemcpyAsync(d.vals, values, M * 32, hipMemcpyHostToDevice, st));
+  std::vector<uint8_t> status(claims.cells ? K : 0);  // per cell, as the intake writes them
+  if (claims.cells) {
+    KZG_HIP(c, hipMemcpyAsync(d_cells, claims.cells, M * 32, hipMemcpyHostToDevice, st));
+    if ((rc = blob_intake_launch(c, log_l, d_cells, K, claims.bit_reversed, d.vals, d_status))) return rc;
+    KZG_HIP(c, hipMemcpyAsync(status.data(), d_status, K, hipMemcpyDeviceToHost, st));
+  } else {
+    KZG_HIP(c, hipMemcpyAsync(d.vals, claims.limbs, M * 32, hipMemcpyHostToDevice, st));
+  }
   KZG_HIP(c, hipMemcpyAsync(d.cidx, coset_idx, K * 4, hipMemcpyHostToDevice, st));
   KZG_HIP(c, hipMemcpyAsync(d.perm, perm.data(), K * 4, hipMemcpyHostToDevice, st));
   KZG_HIP(c, hipMemcpyAsync(d.off, off.data(), (n_comm + 1) * 4, hipMemcpyHostToDevice, st));
   KZG_HIP(c, hipStreamSynchronize(st));
   if (bad) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: a proof or commitment has a coordinate >= p or is not on the curve");
+  if (std::find(status.begin(), status.end(), 1) != status.end()) {   // an element >= r: a verdict, nothing is folded
+    *claims.status = 1;
+    return KZG_OK;
+  }
   if ((rc = srs_finish_windows(c, cs.get()))) return rc;
 
   // ---- weights and the fold of the values
@@ -347,8 +374,18 @@ int verify_cosets(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const
                   const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
                   const uint32_t* coset_idx, const uint64_t* values, const uint64_t* proof_xy, const uint8_t* proof_inf,
                   size_t K, const uint32_t* rho_words, uint64_t* out_xy, uint8_t* out_inf) {
+  const VerClaims claims{values, nullptr, 0, nullptr};
   return KZG_BY_CURVE(c, verify_cosets_t, c, mono, log_N, log_l, w_words, comm_xy, comm_inf, n_comm, comm_idx, coset_idx,
-                      values, proof_xy, proof_inf, K, rho_words, out_xy, out_inf);
+                      claims, proof_xy, proof_inf, K, rho_words, out_xy, out_inf);
+}
+int verify_cosets_bytes(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, const uint32_t* w_words,
+                        const uint64_t* comm_xy, const uint8_t* comm_inf, size_t n_comm, const uint32_t* comm_idx,
+                        const uint32_t* coset_idx, const uint8_t* cells, int bit_reversed, const uint64_t* proof_xy,
+                        const uint8_t* proof_inf, size_t K, const uint32_t* rho_words, uint64_t* out_xy,
+                        uint8_t* out_inf, uint8_t* out_status) {
+  const VerClaims claims{nullptr, cells, bit_reversed, out_status};
+  return KZG_BY_CURVE(c, verify_cosets_t, c, mono, log_N, log_l, w_words, comm_xy, comm_inf, n_comm, comm_idx, coset_idx,
+                      claims, proof_xy, proof_inf, K, rho_words, out_xy, out_inf);
 }
 
 }  // namespace kzg

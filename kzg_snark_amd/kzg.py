@@ -1324,3 +1324,297 @@ class KZG:
                                             inf[b:], rho)
         L_pt, R_pt = self._points(out_xy, out_inf)
         return self._verdict(L_pt, R_pt, rk, pairing, "verify_blob_kzg_proof_batch")
+
+    # ---- EIP-7594 cells as bytes: the spec's calls by name --------------------------------------------
+    #      The extended blob is ext[m] = p(w^(brp_N(m))), m < N; cell c is ext[l c .. l c + l), 32 big-endian bytes per
+    #      element.  brp_N(l c + t) = brp_l(t) C + brp_C(c), C = N/l: cell c is open_cosets' coset brp_C(c), element t
+    #      of a cell that coset's value brp_l(t).  The blob's own domain has the root w^(N/n).
+    _CELL_RHO_DOMAIN = b"RCKZGCBATCH__V1_"         # the domain of the cell batch's weight base (hashed here)
+
+    @staticmethod
+    def _brp(i, bits):
+        """i < 2^bits with its bits reversed"""
+        return int(format(i, f"0{bits}b")[::-1], 2) if bits else 0
+
+    def values_to_blob(self, values, n, bit_reversed=True):
+        """The inverse of blob_to_values: uint64[b, n, 4] canonical limbs (or b lists of n ints) -> b blobs (bytes) of
+        n elements of 32 big-endian bytes, element i the value bitrev(i) when bit_reversed (natural domain order in,
+        EIP-4844's order out).  Encoded and permuted on the device (kzg_fr_to_blob).  A value >= r raises ValueError
+        naming its row."""
+        log_n = self._blob_size(n)
+        if isinstance(values, np.ndarray) and values.dtype == np.uint64:
+            vals = np.ascontiguousarray(values)
+            if vals.size % (4 << log_n):
+                raise ValueError(f"values: {vals.size // 4} elements are no rows of {n}")
+            vals = vals.reshape(-1, 1 << log_n, 4)
+        else:
+            rows = [list(v) for v in values]
+            if any(len(v) != 1 << log_n for v in rows):
+                raise ValueError(f"every row needs {n} values")
+            flat = [int(y) for v in rows for y in v]
+            if any(y < 0 or y >> 256 for y in flat):
+                raise ValueError("a value does not fit 256 bits")
+            vals = (_native.ints_to_limbs(flat) if flat else np.zeros((0, 4), dtype=np.uint64)).reshape(-1, 1 << log_n, 4)
+        if not vals.shape[0]:
+            return []
+        with _bad_input_is_value_error():
+            out, status = self._context().fr_to_blob(vals, log_n, bit_reversed)
+        bad = np.flatnonzero(status)
+        if bad.size:
+            raise ValueError(f"row {int(bad[0])}: a value is not below the field modulus")
+        return [row.tobytes() for row in out]
+
+    def _cell_sizes(self, who, l, n, N, w):
+        """Host-side size checks of the cell calls: -> (n, l, N, log_N, w, w_n), w_n = w^(N/n) the blob's root.  N
+        defaults to 2n; the ranges are open_cosets' (l <= n/2, n <= N <= 4n)."""
+        l = 1 << self._log2_exact(l, "cell size")
+        if l < 2:
+            raise ValueError(f"{who}: a cell holds at least two elements")
+        n = self._domain_size(n)
+        if l > n // 2:
+            raise ValueError(f"{who}: cell size {l} exceeds n/2 = {n // 2}")
+        if l > (1 << self._COSET_MAX_LOG_L):
+            raise ValueError(f"{who}: cell size {l} exceeds 2^{self._COSET_MAX_LOG_L}")
+        N = 2 * n if N is None else int(N)
+        if N < n or N & (N - 1) or N > min(4 * n, 2 * self._DOMAIN_MAX):
+            raise ValueError(f"{who}: N = {N} is not a power of two in [n, min(4n, 2^21)]")
+        log_N, w = self._domain(N, w)
+        return n, l, N, log_N, w, pow(w, N // n, self.curve_order)
+
+    def _cells_key_n(self, who, ck_or_table, n, l):
+        """n of a call that takes a key or a coset table: the table's (a given n and l must agree), else the given one"""
+        if isinstance(ck_or_table, LagrangeKey):
+            raise TypeError(f"{who} needs a monomial key or a coset table, not a LagrangeKey")
+        if isinstance(ck_or_table, DomainTable):
+            return self._table_n(ck_or_table, n, 1 << self._log2_exact(l, "cell size"))
+        if n is None:
+            raise ValueError(f"{who}: n is needed with a key (a coset table carries its own)")
+        if len(ck_or_table) < int(n):
+            raise ValueError(f"commitment key of {len(ck_or_table)} points is shorter than the domain ({n})")
+        return n
+
+    def _blobs_to_coeffs(self, ctx, arr, n, w_n):
+        """b blobs (uint8[b, 32 n]) -> their coefficients, a device tensor int64[b, n, 4]: the intake and the inverse
+        transform over the blob's domain, on the device.  A blob with an element >= r raises ValueError."""
+        import torch
+        b, log_n = arr.shape[0], n.bit_length() - 1
+        dev = f"cuda:{ctx.device}"
+        d_coeffs = torch.empty((b, n, 4), dtype=torch.int64, device=dev)
+        d_status = torch.empty(b, dtype=torch.uint8, device=dev)
+        d_blobs = self._upload(ctx, arr)
+        with _bad_input_is_value_error():
+            ctx.blob_to_fr_device(d_blobs.data_ptr(), log_n, b, True, d_coeffs.data_ptr(), d_status.data_ptr())
+            ctx.ntt_device(d_coeffs.data_ptr(), log_n, _native.int_to_words(w_n), True, b)
+        ctx.synchronize()
+        bad = np.flatnonzero(d_status.cpu().numpy())
+        if bad.size:
+            raise self._first_bad_element(arr[int(bad[0])], int(bad[0]))
+        return d_coeffs
+
+    def _cells_of_coeffs(self, ctx, d_coeffs, b, n, l, N, w):
+        """The C = N/l cells of b resident coefficient vectors (the engine is idle: the caller has synchronised):
+        cells[j][c], bytes.  Zero-padded to N, one forward transform, then kzg_fr_to_blob_device with the
+        bit-reversed order: row j is cell 0 .. C - 1 of blob j one after the other."""
+        import torch
+        log_N = N.bit_length() - 1
+        dev = f"cuda:{ctx.device}"
+        d_ext = torch.zeros((b, N, 4), dtype=torch.int64, device=dev)
+        d_ext[:, :n] = d_coeffs
+        d_out = torch.empty((b, 32 * N), dtype=torch.uint8, device=dev)
+        d_status = torch.empty(b, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(ctx.device)              # the pad ran on torch's stream, the engine has its own
+        with _bad_input_is_value_error():
+            ctx.ntt_device(d_ext.data_ptr(), log_N, _native.int_to_words(w), False, b)
+            ctx.fr_to_blob_device(d_ext.data_ptr(), log_N, b, True, d_out.data_ptr(), d_status.data_ptr())
+        ctx.synchronize()
+        if d_status.cpu().numpy().any():
+            raise RuntimeError("a transform left a value that is not below the field modulus")
+        out = d_out.cpu().numpy()
+        size = 32 * l
+        return [[row[c * size:(c + 1) * size].tobytes() for c in range(N // l)] for row in out]
+
+    def _cell_proofs_of_coeffs(self, ctx, table, d_coeffs, b, n, l, log_N, w):
+        """proofs[j][c], compressed: the proof of cell c is open_cosets' proof of coset brp_C(c)"""
+        C = (1 << log_N) // l
+        xy, inf, _ = ctx.open_cosets(table.table, d_coeffs.data_ptr(), [n] * b, n, log_N, w, device=True, evals=False)
+        comp = ctx.g1_compress(xy.reshape(b * C, -1), inf.reshape(-1))
+        bits = C.bit_length() - 1
+        perm = [self._brp(c, bits) for c in range(C)]
+        return [[comp[j * C + i].tobytes() for i in perm] for j in range(b)]
+
+    def compute_cells(self, blobs, n, l, N=None, w=None):
+        """compute_cells of EIP-7594 for every blob: cells[j][c], C = N/l cells of 32 l bytes each (N defaults to 2n,
+        w to Fq.root_of_unity(N); a blob lives on the domain of w^(N/n)).  Every step stays on the device: intake,
+        inverse transform of size n, zero pad, forward transform of size N, kzg_fr_to_blob_device.  A blob with an
+        element >= r raises ValueError."""
+        n, l, N, _, w, w_n = self._cell_sizes("compute_cells", l, n, N, w)
+        arr = self._byte_rows(blobs, 32 * n, "blob")
+        if not arr.shape[0]:
+            return []
+        ctx = self._context()
+        d_coeffs = self._blobs_to_coeffs(ctx, arr, n, w_n)
+        return self._cells_of_coeffs(ctx, d_coeffs, arr.shape[0], n, l, N, w)
+
+    def compute_cells_and_kzg_proofs(self, ck_or_table, blobs, l, n=None, N=None, w=None):
+        """compute_cells_and_kzg_proofs of EIP-7594 for every blob: (cells, proofs), proofs[j][c] the compressed proof
+        of cell c.  compute_cells' chain, then kzg_open_cosets_device on the same resident coefficients (its values
+        are not requested) and kzg_g1_compress.  ck_or_table: a monomial key (n is then needed) or a coset table."""
+        who = "compute_cells_and_kzg_proofs"
+        n = self._cells_key_n(who, ck_or_table, n, l)
+        n, l, N, log_N, w, w_n = self._cell_sizes(who, l, n, N, w)
+        arr = self._byte_rows(blobs, 32 * n, "blob")
+        b = arr.shape[0]
+        if not b:
+            return [], []
+        table = self._coset_table_for(ck_or_table, n, l)
+        ctx = self._context()
+        d_coeffs = self._blobs_to_coeffs(ctx, arr, n, w_n)
+        cells = self._cells_of_coeffs(ctx, d_coeffs, b, n, l, N, w)
+        return cells, self._cell_proofs_of_coeffs(ctx, table, d_coeffs, b, n, l, log_N, w)
+
+    def _cell_indices(self, cell_indices, C, who):
+        idx = [int(i) for i in cell_indices]
+        if any(i < 0 or i >= C for i in idx):
+            raise ValueError(f"{who}: a cell index is outside [0, {C})")
+        return idx
+
+    def recover_cells_and_kzg_proofs(self, ck_or_table, cell_indices, cells, l, n=None, N=None, w=None):
+        """recover_cells_and_kzg_proofs of EIP-7594 for a batch: cells[j][k] (32 l bytes) is cell cell_indices[k] of
+        blob j, any K >= n/l distinct cells in any order, one index set for the batch -> (cells, proofs), all C cells
+        and all C proofs of each blob.  The bytes go through the device intake (log_n = log_l), then
+        kzg_recover_cosets_device, kzg_open_cosets_device, and the transform and kzg_fr_to_blob_device of
+        compute_cells.  ValueError: an element >= r (naming blob and cell), sizes, an index out of range or repeated,
+        fewer than n/l cells, and recover_cosets' for cells that lie on no polynomial of degree < n."""
+        who = "recover_cells_and_kzg_proofs"
+        n = self._cells_key_n(who, ck_or_table, n, l)
+        n, l, N, log_N, w, _ = self._cell_sizes(who, l, n, N, w)
+        C, log_l, log_n = N // l, l.bit_length() - 1, n.bit_length() - 1
+        idx = self._cell_indices(cell_indices, C, who)
+        K = len(idx)
+        if len(set(idx)) != K:
+            raise ValueError(f"{who}: a cell index is repeated")
+        if K * l < n:
+            raise ValueError(f"{who}: {K} cells of {l} values cannot determine a polynomial of degree < {n}")
+        b = len(cells)
+        if b < 1:
+            raise ValueError(f"{who} needs at least one blob")
+        rows = []
+        for j, blob_cells in enumerate(cells):
+            if len(blob_cells) != K:
+                raise ValueError(f"blob {j} has {len(blob_cells)} cells for {K} cell indices")
+            rows.append(self._byte_rows(blob_cells, 32 * l, f"blob {j}: cell"))
+        arr = np.ascontiguousarray(np.stack(rows)).reshape(b * K, 32 * l)
+        table = self._coset_table_for(ck_or_table, n, l)
+        ctx = self._context()
+        import torch
+        dev = f"cuda:{ctx.device}"
+        d_vals = torch.empty((b * K, l, 4), dtype=torch.int64, device=dev)
+        d_status = torch.empty(b * K, dtype=torch.uint8, device=dev)
+        d_coeffs = torch.empty((b, n, 4), dtype=torch.int64, device=dev)
+        d_cells = self._upload(ctx, arr)
+        with _bad_input_is_value_error():
+            ctx.blob_to_fr_device(d_cells.data_ptr(), log_l, b * K, True, d_vals.data_ptr(), d_status.data_ptr())
+        ctx.synchronize()
+        bad = np.flatnonzero(d_status.cpu().numpy())
+        if bad.size:
+            q = int(bad[0])
+            raise ValueError(f"blob {q // K}: cell {idx[q % K]} holds an element that is not below the field modulus")
+        bits = C.bit_length() - 1
+        coset_idx = np.asarray([self._brp(i, bits) for i in idx], dtype=np.uint32)
+        with _bad_input_is_value_error():
+            _, ok = ctx.recover_cosets(log_n, log_N, log_l, w, coset_idx, d_vals.data_ptr(), b,
+                                       d_coeffs=d_coeffs.data_ptr())
+        self._first_inconsistent(ok, n)
+        out = self._cells_of_coeffs(ctx, d_coeffs, b, n, l, N, w)
+        return out, self._cell_proofs_of_coeffs(ctx, table, d_coeffs, b, n, l, log_N, w)
+
+    def _cell_batch_rho(self, n, l, commitments, commitment_indices, cell_indices, cells, proofs):
+        """SHA-256("RCKZGCBATCH__V1_" | n | l | number of distinct commitments | K (8 bytes big-endian each) | the
+        distinct commitments | per cell: commitment index (8 bytes) | cell index (8 bytes) | the cell's 32 l bytes |
+        proof) mod r, on the host: one Merkle-Damgard chain has no parallel form.  Rows of bytes; indices: ints."""
+        import hashlib
+        h = hashlib.sha256(self._CELL_RHO_DOMAIN + int(n).to_bytes(8, "big") + int(l).to_bytes(8, "big")
+                           + len(commitments).to_bytes(8, "big") + len(cells).to_bytes(8, "big"))
+        for c in commitments:
+            h.update(bytes(c))
+        for ci, ki, cell, p in zip(commitment_indices, cell_indices, cells, proofs):
+            h.update(int(ci).to_bytes(8, "big") + int(ki).to_bytes(8, "big"))
+            h.update(cell)
+            h.update(bytes(p))
+        return int.from_bytes(h.digest(), "big") % self.curve_order
+
+    def verify_cell_kzg_proof_batch(self, ck, rk_l, commitments, cell_indices, cells, proofs, l, N, w=None,
+                                    pairing="device", n=None):
+        """verify_cell_kzg_proof_batch of EIP-7594: is cells[k] (32 l bytes) cell cell_indices[k] of the blob of
+        commitments[k], with proof proofs[k], for every k?  One compressed commitment per cell, deduplicated here in
+        order of first appearance; rk_l = [tau^l] G2 (coset_verification_key); n (the blob's size, part of the
+        challenge) defaults to N/2.  Commitments and proofs are decompressed with the subgroup test on the device
+        (enqueued before the batch challenge is hashed on the host, awaited after it); the cells go to
+        kzg_verify_cosets_bytes as bytes, which folds the claims with the weights rho^(k+1); two pairings as in
+        verify_cosets.  False, not an exception: an element >= r, a malformed point, a point off the curve or outside
+        the subgroup, a wrong proof.  ValueError: mismatched counts or sizes, an index out of range.  No cells: True."""
+        who = "verify_cell_kzg_proof_batch"
+        if pairing not in ("device", "host"):
+            raise ValueError(f"{who}: pairing must be \"device\" or \"host\", not {pairing!r}")
+        self._monomial_key(ck, who)
+        l = 1 << self._log2_exact(l, "cell size")
+        N = int(N)
+        if N < 2 or N & (N - 1) or N > self._VERIFY_MAX_N:
+            raise ValueError(f"N = {N} is not a power of two in [2, 2^21]")
+        if l > N // 2:
+            raise ValueError(f"cell size {l} exceeds N/2 = {N // 2}")
+        if l > (1 << self._COSET_MAX_LOG_L):
+            raise ValueError(f"cell size {l} exceeds 2^{self._COSET_MAX_LOG_L}")
+        n = N // 2 if n is None else int(n)
+        if n < l or n > N or n & (n - 1):
+            raise ValueError(f"n = {n} is not a power of two in [l, N]")
+        log_N, w = self._domain(N, w)
+        if len(ck) < l:
+            raise ValueError(f"commitment key of {len(ck)} points is shorter than the cell size {l}")
+        ctx = self._context()
+        G, C = ctx.g1_bytes, N // l
+        comm = self._byte_rows(commitments, G, "commitment")
+        prf = self._byte_rows(proofs, G, "proof")
+        arr = self._byte_rows(cells, 32 * l, "cell")
+        idx = self._cell_indices(cell_indices, C, who)
+        K = len(idx)
+        if comm.shape[0] != K or prf.shape[0] != K or arr.shape[0] != K:
+            raise ValueError("commitments, cell_indices, cells and proofs must describe the same number of cells")
+        if K > (1 << 21) or K * l > (1 << 24):
+            raise ValueError("at most 2^21 cells and 2^24 values per call")
+        if K == 0:
+            return True
+        first, comm_idx = {}, []
+        for row in comm:
+            comm_idx.append(first.setdefault(row.tobytes(), len(first)))
+        distinct = list(first)
+        if len(distinct) > (1 << 16):
+            raise ValueError("at most 2^16 distinct commitments per call")
+        n_comm = len(distinct)
+        points = np.concatenate([np.frombuffer(b"".join(distinct), dtype=np.uint8).reshape(n_comm, G), prf])
+        import torch
+        dev = f"cuda:{ctx.device}"
+        P = 2 * ctx.fp_limbs
+        d_xy = torch.empty((n_comm + K, P), dtype=torch.int64, device=dev)
+        d_inf = torch.empty(n_comm + K, dtype=torch.uint8, device=dev)
+        d_status = torch.empty(n_comm + K, dtype=torch.uint8, device=dev)
+        d_points = self._upload(ctx, points)
+        ctx.g1_decompress_device(d_points.data_ptr(), n_comm + K, True, d_xy.data_ptr(), d_inf.data_ptr(),
+                                 d_status.data_ptr())
+        rho = self._cell_batch_rho(n, l, distinct, comm_idx, idx, arr, prf)          # the device works meanwhile
+        ctx.synchronize()
+        if d_status.cpu().numpy().any():
+            return False
+        xy = np.ascontiguousarray(d_xy.cpu().numpy().view(np.uint64))
+        inf = d_inf.cpu().numpy()
+        bits = C.bit_length() - 1
+        coset_idx = np.asarray([self._brp(i, bits) for i in idx], dtype=np.uint32)
+        key = self._key(ck)
+        out_xy, out_inf, status = ctx.verify_cosets_bytes(key.srs, log_N, l.bit_length() - 1, w, xy[:n_comm],
+                                                          inf[:n_comm], np.asarray(comm_idx, dtype=np.uint32),
+                                                          coset_idx, arr, xy[n_comm:], inf[n_comm:], rho,
+                                                          bit_reversed=True)
+        if status:
+            return False
+        L_pt, R_pt = self._points(out_xy, out_inf)
+        return self._verdict(L_pt, R_pt, rk_l, pairing, who)
