@@ -457,6 +457,38 @@ int kzg_g1_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, 
 int kzg_srs_load_g1_compressed(kzg_ctx* ctx, const uint8_t* bytes, size_t n, int check_subgroup, kzg_srs** out);
 int kzg_srs_export_compressed(kzg_ctx* ctx, const kzg_srs* srs, size_t start, size_t count, uint8_t* out_bytes);
 
+/* ---- compressed G2 points and subgroup membership on the twist ---------------------------------------
+ * The G2 forms of the calls above.  A point is 4 * FP_LIMBS limbs, x.c0 | x.c1 | y.c0 | y.c1 (kzg_pairing_check's
+ * layout; x = x.c0 + x.c1 i).  Byte formats: big-endian x.c1 then x.c0, the flag bits of the G1 format in the top bits
+ * of byte 0.
+ *   BLS12-381  96 bytes, ZCash; infinity = 0xc0, then 95 zero bytes
+ *   BN254      64 bytes, gnark; infinity = 0x40, then 63 zero bytes
+ * "The larger y" is lexicographic, c1 first: y.c1 > (p - 1) / 2, or y.c1 = 0 and y.c0 > (p - 1) / 2.
+ * Status of a point, one byte each, first failure wins:
+ *   0 ok   1 bad encoding (the flags, a malformed infinity, x.c0 or x.c1 >= p)   2 x^3 + b' is not a square in Fp2
+ *   3 on the twist but outside the subgroup of prime order r (BOTH curves: BN254's twist has a cofactor too)
+ * The subgroup tests are exact and use the endomorphism psi (untwist, Frobenius, twist): psi(Q) = [u] Q on BLS12-381,
+ * [u + 1] Q + psi([u] Q) + psi^2([u] Q) = psi^3([2u] Q) on BN254: one multiplication by the 64-bit u instead of one
+ * by the 255-bit r.  Infinity passes.  A pairing check against a G2 point outside the subgroup proves nothing:
+ * kzg_pairing_check does not test membership, a caller with keys from an untrusted source runs them through here.
+ *   kzg_g2_compress        n affine points -> n blobs.  A coordinate >= p or a point off the twist is KZG_ERR_ARG;
+ *                          nothing is written then.
+ *   kzg_g2_decompress      n blobs -> affine points, infinity flags and statuses.  KZG_OK when it ran: the verdicts are
+ *                          in out_status.  A failed point decompresses to zeros with the flag 0.  check_subgroup = 0
+ *                          never reports 3.
+ *   kzg_g2_decompress_device   the same on device pointers (16-byte aligned; d_xy n * 4*FP_LIMBS limbs, d_inf and
+ *                          d_status n bytes), enqueued on the context's stream without synchronising.
+ *   kzg_g2_check_subgroup  statuses of n affine points: 0, 2 (a coordinate >= p or a point off the twist) or 3.
+ * n = 0 is KZG_OK with no work; more than 2^24 points per call is KZG_ERR_ARG.  Host pointers in and out and a
+ * synchronised stream, except for the _device form.  Profiling spans: "g2_decompress" (ONE per kzg_g2_decompress*),
+ * "g2_subgroup" (ONE per kzg_g2_check_subgroup). */
+int kzg_g2_compress(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_bytes);
+int kzg_g2_decompress(kzg_ctx* ctx, const uint8_t* bytes, size_t n, int check_subgroup, uint64_t* out_xy,
+                      uint8_t* out_inf, uint8_t* out_status);
+int kzg_g2_decompress_device(kzg_ctx* ctx, const void* d_bytes, size_t n, int check_subgroup, void* d_xy, void* d_inf,
+                             void* d_status);
+int kzg_g2_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status);
+
 /* ---- EIP-4844 blobs as bytes: device intake and SHA-256 challenges ---------------------------------
  * A blob is n = 2^log_n field elements of 32 big-endian bytes each; b blobs lie one after the other ([b][n][32]).
  *   kzg_blob_to_fr          every element checked < r and written as four canonical little-endian limbs:
@@ -548,8 +580,8 @@ int kzg_fr_eval_lagrange_batch_device(kzg_ctx* ctx, uint32_t log_n, const uint64
  *   0  the product is one      1  it is not
  *   2  a finite point of the equation has a coordinate >= p, is off the curve (G1) or off the twist (G2)
  * An equation whose points are all infinity has the product one.  Membership in the prime-order subgroups is NOT part
- * of these calls: kzg_g1_check_subgroup tests G1 points, G2 points (the verification keys) come from the caller's
- * setup.  Input outside the subgroups yields status 0 or 1, no error.
+ * of these calls: kzg_g1_check_subgroup tests G1 points and kzg_g2_check_subgroup G2 points (the verification keys of
+ * a setup that arrived as bytes).  Input outside the subgroups yields status 0 or 1, no error.
  *   kzg_pairing_check        the statuses alone: what a verifier needs after kzg_verify_cosets / kzg_verify_points,
  *                            one equation [(L, G2), (-R, [tau] G2)].
  *   kzg_pairing_product      also the value of every product raised to c = kzg_pairing_gt_multiple(curve) (the final
@@ -578,7 +610,8 @@ int kzg_pairing_gt_multiple(int curve);
  * the context's stream; its MSMs also report under the msm_* names), "recover_cosets" (ONE per kzg_recover_cosets*:
  * the product tree and every chunk), "g1_decompress" (ONE per kzg_g1_decompress*, and one per
  * kzg_srs_load_g1_compressed: the decoding, with the subgroup test when asked for), "g1_subgroup" (ONE per
- * kzg_g1_check_subgroup), "verify_points" (ONE per kzg_verify_points: the whole call), "eval_lagrange_batch" (ONE per
+ * kzg_g1_check_subgroup), "g2_decompress" (ONE per kzg_g2_decompress*), "g2_subgroup" (ONE per
+ * kzg_g2_check_subgroup), "verify_points" (ONE per kzg_verify_points: the whole call), "eval_lagrange_batch" (ONE per
  * kzg_fr_eval_lagrange_batch*: every chunk), "blob_intake" (ONE per kzg_blob_to_fr*), "blob_output" (ONE per kzg_fr_to_blob*), "blob_challenge" (ONE per
  * kzg_blob_challenges*) and "pairing" (ONE per kzg_pairing_check / kzg_pairing_product: copies and kernel).  kzg_prof_read synchronises the
  * stream and returns the accumulated milliseconds and span count of one name since the last kzg_prof_reset.

@@ -114,6 +114,10 @@ SIGNATURES = {
     "kzg_g1_decompress": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp]),
     "kzg_g1_decompress_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp]),
     "kzg_g1_check_subgroup": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "kzg_g2_compress": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "kzg_g2_decompress": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp]),
+    "kzg_g2_decompress_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp]),
+    "kzg_g2_check_subgroup": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "kzg_srs_load_g1_compressed": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_vp)]),
     "kzg_srs_export_compressed": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "kzg_recover_cosets_device": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
@@ -410,6 +414,48 @@ class Context:
         inf = _inf_arg(inf, n, "g1_check_subgroup: inf and xy")
         status = np.zeros(n, dtype=np.uint8)
         self._check(lib().kzg_g1_check_subgroup(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(status)))
+        return status
+
+    # ---- the G2 forms: points are uint64[n, 4*fp_limbs], x.c0 | x.c1 | y.c0 | y.c1 (pairing_check's layout)
+    @property
+    def g2_bytes(self):
+        """bytes of a compressed G2 point: 96 (bls12_381) or 64 (bn254)"""
+        return 16 * self.fp_limbs
+
+    def g2_compress(self, xy, inf=None):
+        """affine points (uint64[n, 4*fp_limbs], uint8[n] flags or None) -> uint8[n, g2_bytes]"""
+        xy = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, 4 * self.fp_limbs)
+        n = xy.shape[0]
+        inf = _inf_arg(inf, n, "g2_compress: inf and xy")
+        out = np.zeros((n, self.g2_bytes), dtype=np.uint8)
+        self._check(lib().kzg_g2_compress(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(out)))
+        return out
+
+    def g2_decompress(self, blobs, check_subgroup=True):
+        """uint8[n, g2_bytes] -> (xy uint64[n, 4*fp_limbs], inf uint8[n], status uint8[n]); status 0 ok, 1 bad
+        encoding, 2 no such point, 3 outside the subgroup.  A failed point is all zeros."""
+        blobs = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(-1, self.g2_bytes)
+        n = blobs.shape[0]
+        xy = np.zeros((n, 4 * self.fp_limbs), dtype=np.uint64)
+        inf = np.zeros(n, dtype=np.uint8)
+        status = np.zeros(n, dtype=np.uint8)
+        self._check(lib().kzg_g2_decompress(self._h, _as_vp(blobs), n, int(bool(check_subgroup)), _as_vp(xy),
+                                            _as_vp(inf), _as_vp(status)))
+        return xy, inf, status
+
+    def g2_decompress_device(self, d_bytes, n, check_subgroup, d_xy, d_inf, d_status):
+        """The same on device pointers, enqueued on the context's stream (no synchronisation)."""
+        self._check(lib().kzg_g2_decompress_device(self._h, _as_vp(d_bytes), int(n), int(bool(check_subgroup)),
+                                                   _as_vp(d_xy), _as_vp(d_inf), _as_vp(d_status)))
+
+    def g2_check_subgroup(self, xy, inf=None):
+        """status uint8[n] of affine points: 0 in the subgroup (infinity included), 2 a coordinate >= p or off the
+        twist, 3 on the twist but outside the subgroup"""
+        xy = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, 4 * self.fp_limbs)
+        n = xy.shape[0]
+        inf = _inf_arg(inf, n, "g2_check_subgroup: inf and xy")
+        status = np.zeros(n, dtype=np.uint8)
+        self._check(lib().kzg_g2_check_subgroup(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(status)))
         return status
 
     # ---- pairing-product checks
@@ -912,6 +958,19 @@ def g2_points_to_limbs(points, limbs):
     if not coords:
         return np.zeros((0, 4 * limbs), dtype=np.uint64), inf
     return np.ascontiguousarray(ints_to_limbs(coords, limbs).reshape(len(points), 4 * limbs)), inf
+
+
+def limbs_to_g2_points(xy, inf):
+    """affine G2 points in the C layout (x.c0 | x.c1 | y.c0 | y.c1 limbs per row, one infinity flag each) -> facade
+    tuples ((x0, x1), (y0, y1), (1, 0)), infinity ((1, 0), (1, 0), (0, 0))"""
+    out = []
+    for row, f in zip(np.atleast_2d(xy), np.atleast_1d(inf)):
+        if f:
+            out.append(((1, 0), (1, 0), (0, 0)))
+        else:
+            v = limbs_to_ints(row.reshape(4, -1))
+            out.append(((v[0], v[1]), (v[2], v[3]), (1, 0)))
+    return out
 
 
 def gt_to_tuple(gt_row, curve_type):

@@ -392,6 +392,28 @@ int kzg_g1_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, 
   return g1_check_subgroup(c, xy, inf, n, out_status);
 }
 
+int kzg_g2_compress(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_bytes) {
+  KZG_ENTER(n && (!xy || !out_bytes));
+  return g2_compress(c, xy, inf, n, out_bytes);
+}
+
+int kzg_g2_decompress(kzg_ctx* ctx, const uint8_t* bytes, size_t n, int check_subgroup, uint64_t* out_xy,
+                      uint8_t* out_inf, uint8_t* out_status) {
+  KZG_ENTER(n && (!bytes || !out_xy || !out_inf || !out_status));
+  return g2_decompress(c, bytes, n, check_subgroup, out_xy, out_inf, out_status);
+}
+
+int kzg_g2_decompress_device(kzg_ctx* ctx, const void* d_bytes, size_t n, int check_subgroup, void* d_xy, void* d_inf,
+                             void* d_status) {
+  KZG_ENTER(n && (!d_bytes || !d_xy || !d_inf || !d_status));
+  return g2_decompress_device(c, d_bytes, n, check_subgroup, d_xy, d_inf, d_status);
+}
+
+int kzg_g2_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status) {
+  KZG_ENTER(n && (!xy || !out_status));
+  return g2_check_subgroup(c, xy, inf, n, out_status);
+}
+
 int kzg_pairing_check(kzg_ctx* ctx, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
                       const uint8_t* g2_inf, size_t m, size_t k, uint8_t* out_status) {
   KZG_ENTER(m && (!g1_xy || !g2_xy || !out_status));

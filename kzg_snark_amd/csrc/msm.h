@@ -158,6 +158,13 @@ int g1_decompress(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, ui
 int g1_decompress_device(Ctx* c, const void* d_bytes, size_t n, int check_subgroup, void* d_xy, void* d_inf,
                          void* d_status);
 int g1_check_subgroup(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status);
+// g2_bytes.hip: the G2 forms (points are 4 * FP words: x.c0 | x.c1 | y.c0 | y.c1, kzg_pairing_check's layout)
+int g2_compress(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_bytes);
+int g2_decompress(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, uint64_t* out_xy, uint8_t* out_inf,
+                  uint8_t* out_status);
+int g2_decompress_device(Ctx* c, const void* d_bytes, size_t n, int check_subgroup, void* d_xy, void* d_inf,
+                         void* d_status);
+int g2_check_subgroup(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status);
 int srs_load_g1_compressed(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, Srs** out);
 int srs_export_compressed(Ctx* c, const Srs* s, size_t start, size_t count, uint8_t* out_bytes);
 

@@ -307,3 +307,113 @@ def decompress_g1(blob, cv, check_subgroup=True):
     if status != G1_OK:
         raise ValueError(f"compressed G1 point: {G1_STATUS_TEXT[status]}")
     return pt
+
+
+# ---- compressed G2 points and subgroup membership (single-point host helpers; the data-parallel forms are the
+# ---- kernels of csrc/g2_bytes.hip, which the tests compare against these) ----------------------------------------
+#   bls12_381  96 bytes, ZCash format: big-endian x.c1 then x.c0, the three flag bits of G1 in the top of byte 0;
+#              infinity is 0xc0 and 95 zero bytes
+#   bn254      64 bytes, gnark's format: big-endian x.c1 then x.c0, the two flag bits of G1 in the top of byte 0;
+#              infinity is 0x40 and 63 zero bytes
+# "larger y" is lexicographic, c1 first: y.c1 > (p - 1) / 2, or y.c1 = 0 and y.c0 > (p - 1) / 2.
+# Status of a blob, first failure wins (the per-point codes of kzg_g2_decompress):
+G2_OK, G2_BAD_ENCODING, G2_NOT_ON_CURVE, G2_NOT_IN_SUBGROUP = 0, 1, 2, 3
+G2_STATUS_TEXT = {G2_OK: "ok", G2_BAD_ENCODING: "bad encoding", G2_NOT_ON_CURVE: "x^3 + b' is not a square: no such point",
+                  G2_NOT_IN_SUBGROUP: "on the twist but outside the prime-order subgroup"}
+
+
+def g2_compressed_size(cv):
+    return 2 * g1_compressed_size(cv)
+
+
+def sqrt_fp2(a, p):
+    """A square root (x0, x1) of a = (a0, a1) in Fp2 = Fp[u]/(u^2 + 1), p = 3 (mod 4), or None when a is not a
+    square.  The complex method: with s = sqrt(a0^2 + a1^2) (the norm of a square is a square of Fp), one of
+    (a0 + s) / 2, (a0 - s) / 2 is a square d = x0^2 of Fp, and x1 = a1 / (2 x0).  a1 = 0: sqrt(a0) when a0 is a
+    residue, else sqrt(-a0) u."""
+    a0, a1 = a[0] % p, a[1] % p
+    if a1 == 0:
+        s = sqrt_fp(a0, p)
+        if s is not None:
+            return (s, 0)
+        return (0, sqrt_fp(p - a0, p))
+    s = sqrt_fp((a0 * a0 + a1 * a1) % p, p)
+    if s is None:
+        return None
+    half = (p + 1) // 2
+    x0 = sqrt_fp((a0 + s) * half % p, p)
+    if x0 is None:
+        x0 = sqrt_fp((a0 - s) * half % p, p)
+    x1 = a1 * pow(2 * x0, -1, p) % p
+    assert _fp2_mul((x0, x1), (x0, x1), p) == (a0, a1)
+    return (x0, x1)
+
+
+def _fp2_larger(y, p):
+    half = (p - 1) // 2
+    return y[1] > half or (y[1] == 0 and y[0] > half)
+
+
+def compress_g2(pt, cv):
+    size = g2_compressed_size(cv)
+    bls = cv.name == "bls12_381"
+    if pt[2] == (0, 0):
+        return bytes([0xc0 if bls else 0x40]) + bytes(size - 1)
+    x = (int(pt[0][0]) % cv.p, int(pt[0][1]) % cv.p)
+    y = (int(pt[1][0]) % cv.p, int(pt[1][1]) % cv.p)
+    larger = _fp2_larger(y, cv.p)
+    raw = bytearray(x[1].to_bytes(size // 2, "big") + x[0].to_bytes(size // 2, "big"))
+    raw[0] |= (0x80 | (0x20 if larger else 0)) if bls else (0xc0 if larger else 0x80)
+    return bytes(raw)
+
+
+def in_subgroup_g2(pt, cv):
+    """[r] Q = O, for a point on the twist (infinity included)."""
+    if pt[2] == (0, 0):
+        return True
+    return g2_group(cv).multiply((pt[0], pt[1], (1, 0)), cv.r)[2] == (0, 0)
+
+
+def decompress_g2_status(blob, cv, check_subgroup=True):
+    """(point or None, status) of one compressed G2 point."""
+    size = g2_compressed_size(cv)
+    blob = bytes(blob)
+    if len(blob) != size:
+        return None, G2_BAD_ENCODING
+    half = size // 2
+    inf = ((1, 0), (1, 0), (0, 0))
+    hi, x0 = int.from_bytes(blob[:half], "big"), int.from_bytes(blob[half:], "big")
+    if cv.name == "bls12_381":
+        flags, x1 = blob[0] >> 5, hi & ((1 << 381) - 1)
+        if not flags & 4:
+            return None, G2_BAD_ENCODING
+        if flags & 2:
+            return (inf, G2_OK) if flags == 6 and x1 == 0 and x0 == 0 else (None, G2_BAD_ENCODING)
+        larger = bool(flags & 1)
+    else:
+        flags, x1 = blob[0] >> 6, hi & ((1 << 254) - 1)
+        if flags == 0:
+            return None, G2_BAD_ENCODING
+        if flags == 1:
+            return (inf, G2_OK) if x1 == 0 and x0 == 0 else (None, G2_BAD_ENCODING)
+        larger = flags == 3
+    if x0 >= cv.p or x1 >= cv.p:
+        return None, G2_BAD_ENCODING
+    K = _Fp2(cv.p)
+    x = (x0, x1)
+    y = sqrt_fp2(K.add(K.mul(K.mul(x, x), x), cv.b2), cv.p)
+    if y is None:
+        return None, G2_NOT_ON_CURVE
+    if _fp2_larger(y, cv.p) != larger:
+        y = K.neg(y)
+    pt = (x, y, (1, 0))
+    if check_subgroup and not in_subgroup_g2(pt, cv):
+        return None, G2_NOT_IN_SUBGROUP
+    return pt, G2_OK
+
+
+def decompress_g2(blob, cv, check_subgroup=True):
+    pt, status = decompress_g2_status(blob, cv, check_subgroup)
+    if status != G2_OK:
+        raise ValueError(f"compressed G2 point: {G2_STATUS_TEXT[status]}")
+    return pt

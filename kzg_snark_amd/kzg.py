@@ -21,6 +21,7 @@ The reference returns un-normalised projective triples whose representative
 depends on py_ecc's operation order; equality there is `eq`, here plain `==` works
 too.  There is no CPU fallback for commit/open/setup: they raise
 _native.NativeUnavailable without the shared library and a GPU."""
+import secrets
 from collections.abc import Sequence
 from contextlib import contextmanager
 
@@ -116,6 +117,83 @@ class DomainTable:
 
     def __len__(self):
         return self.n
+
+
+def parse_trusted_setup(text, g1_size, g2_size):
+    """The text of a trusted-setup file (c-kzg-4844's trusted_setup.txt layout) -> (n1, n2, lagrange, g2, monomial),
+    the three sections as uint8 arrays [n1, g1_size], [n2, g2_size], [n1, g1_size] of compressed points, nothing
+    decoded.  Line 1: n1, line 2: n2 (decimal), then n1 + n2 + n1 lines of hex, one compressed point each: the G1
+    Lagrange points, the G2 powers, the G1 powers.  Blank lines and surrounding whitespace are skipped; n1 must be a
+    power of two.  Anything else raises ValueError naming the line (as counted in the file) or the section."""
+    lines = [(no, ln.strip()) for no, ln in enumerate(text.splitlines(), 1) if ln.strip()]
+    if len(lines) < 2:
+        raise ValueError("trusted setup: the file ends before the two counts (lines 1 and 2)")
+    counts = []
+    for (no, ln), what in zip(lines[:2], ("n1, the number of G1 points", "n2, the number of G2 points")):
+        if not ln.isdigit():
+            raise ValueError(f"trusted setup, line {no}: expected {what} in decimal, found {ln[:40]!r}")
+        counts.append(int(ln))
+    n1, n2 = counts
+    if n1 < 1 or n1 & (n1 - 1):
+        raise ValueError(f"trusted setup, line {lines[0][0]}: n1 = {n1} is not a power of two")
+    if n2 < 1:
+        raise ValueError(f"trusted setup, line {lines[1][0]}: n2 = {n2}: at least the G2 generator is needed")
+    body = lines[2:]
+    sections = (("G1 Lagrange", n1, g1_size), ("G2", n2, g2_size), ("G1 monomial", n1, g1_size))
+    want = 2 * n1 + n2
+    out, at = [], 0
+    for name, count, size in sections:
+        rows = body[at:at + count]
+        if len(rows) < count:
+            raise ValueError(f"trusted setup: the file is truncated in the {name} section: {len(rows)} of {count} "
+                             f"points ({len(body)} point lines where n1 = {n1}, n2 = {n2} announce {want})")
+        blob = bytearray()
+        for k, (no, ln) in enumerate(rows):
+            if len(ln) != 2 * size:
+                raise ValueError(f"trusted setup, line {no} ({name} section, point {k}): {len(ln)} hex digits, "
+                                 f"expected {2 * size}")
+            try:
+                blob += bytes.fromhex(ln)
+            except ValueError:
+                raise ValueError(f"trusted setup, line {no} ({name} section, point {k}): not hexadecimal") from None
+        out.append(np.frombuffer(bytes(blob), dtype=np.uint8).reshape(count, size))
+        at += count
+    if len(body) > want:
+        raise ValueError(f"trusted setup, line {body[want][0]}: {len(body) - want} lines more than the counts "
+                         f"n1 = {n1}, n2 = {n2} announce")
+    return n1, n2, out[0], out[1], out[2]
+
+
+def format_trusted_setup(lagrange, g2, monomial):
+    """The text parse_trusted_setup reads, from the three sections as arrays (or lists) of compressed points."""
+    rows = [bytes(b).hex() for sec in (lagrange, g2, monomial) for b in sec]
+    return "\n".join([str(len(monomial)), str(len(g2))] + rows) + "\n"
+
+
+def bit_reverse_rows(rows):
+    """rows[bitrev(i)] at i, for a power-of-two number of rows (its own inverse)"""
+    n = len(rows)
+    bits = n.bit_length() - 1
+    idx = [int(format(i, "0%db" % bits)[::-1], 2) if bits else 0 for i in range(n)]
+    return rows[idx]
+
+
+class TrustedSetup:
+    """What KZG.load_trusted_setup returns: .monomial (CommitmentKey [tau^i G1]), .lagrange (LagrangeKey over the
+    n1-th root of unity), .g2 (the points [tau^j G2]), .rk = g2[1] and .rk_l(l) = g2[l], the verification keys."""
+
+    def __init__(self, monomial, lagrange, g2):
+        self.monomial, self.lagrange, self.g2 = monomial, lagrange, list(g2)
+
+    @property
+    def rk(self):
+        return self.rk_l(1)
+
+    def rk_l(self, l):
+        l = int(l)
+        if not 0 <= l < len(self.g2):
+            raise ValueError(f"the setup holds {len(self.g2)} G2 powers: [tau^{l}] G2 needs at least {l + 1}")
+        return self.g2[l]
 
 
 class KZG:
@@ -351,6 +429,219 @@ class KZG:
         has cofactor 0x396c8c005555e1568c00aaab0000aaab; on bn254 every point of the curve is in the subgroup."""
         xy, inf = self._g1_arrays(points, "points")
         return self._context().g1_check_subgroup(xy, inf) == 0
+
+    # ---- the G2 forms (kzg_g2_*, DESIGN.md 4.14): the same argument and error conventions ------------------------------
+    def _g2_arrays(self, points, what):
+        """points: a list of G2 point tuples, or (xy uint64[n, 4L], inf uint8[n] | None) in the C layout -> (xy, inf)."""
+        L = (self._cv.p.bit_length() + 63) // 64
+        if isinstance(points, tuple) and len(points) == 2 and isinstance(points[0], np.ndarray):
+            xy = np.ascontiguousarray(points[0], dtype=np.uint64).reshape(-1, 4 * L)
+            inf = None if points[1] is None else np.ascontiguousarray(points[1], dtype=np.uint8).reshape(-1)
+            if inf is not None and inf.size != xy.shape[0]:
+                raise ValueError(f"{what}: {inf.size} infinity flags for {xy.shape[0]} points")
+            return xy, inf
+        return _native.g2_points_to_limbs([self._g2.normalize(pt) for pt in points], L)
+
+    def compress_g2(self, points):
+        """points: a list of G2 point tuples, or (xy, inf) arrays in the C layout -> list of bytes objects (96 bytes
+        each on bls12_381, ZCash's format; 64 on bn254, gnark's).  A point off the twist raises ValueError."""
+        xy, inf = self._g2_arrays(points, "points")
+        with _bad_input_is_value_error():
+            out = self._context().g2_compress(xy, inf)
+        return [row.tobytes() for row in out]
+
+    def decompress_g2(self, blobs, check_subgroup=True, strict=True):
+        """blobs: a list of bytes objects or a uint8[n, size] array -> list of G2 points.  strict: the first blob that
+        is malformed, names no point of the twist or (check_subgroup) a point outside the prime-order subgroup raises
+        ValueError with its index and the reason; strict=False returns (points, status) instead, status a uint8 array
+        (curve.G2_STATUS_TEXT) and None in place of a failed point."""
+        ctx = self._context()
+        if isinstance(blobs, np.ndarray):
+            arr = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(-1, ctx.g2_bytes)
+        else:
+            blobs = [bytes(b) for b in blobs]
+            for i, b in enumerate(blobs):
+                if len(b) != ctx.g2_bytes:
+                    raise ValueError(f"compressed G2 point {i}: {len(b)} bytes, expected {ctx.g2_bytes}")
+            arr = np.frombuffer(b"".join(blobs), dtype=np.uint8).reshape(len(blobs), ctx.g2_bytes)
+        xy, inf, status = ctx.g2_decompress(arr, check_subgroup)
+        bad = np.flatnonzero(status)
+        if strict and bad.size:
+            i = int(bad[0])
+            raise ValueError(f"compressed G2 point {i}: {_curve.G2_STATUS_TEXT[int(status[i])]}")
+        points = _native.limbs_to_g2_points(xy, inf)
+        if strict:
+            return points
+        for i in bad:
+            points[int(i)] = None
+        return points, status
+
+    def in_subgroup_g2(self, points):
+        """bool array: point i is on the twist AND in the subgroup of prime order (infinity: True).  The twists of
+        both curves have a cofactor: a random point of either twist is outside G2."""
+        xy, inf = self._g2_arrays(points, "points")
+        return self._context().g2_check_subgroup(xy, inf) == 0
+
+    # ---- trusted-setup files and keys checked on the device (DESIGN.md 4.14) --------------------------------------------
+    def setup_g2(self, count, tau):
+        """[tau^j] G2, j < count, on the host with curve.py: pure Python, one scalar multiplication per point -- for
+        tests and small ceremonies, NOT a data-parallel path (a real setup publishes its G2 powers; nobody knows tau)."""
+        tau = self._tau(tau)
+        out, t = [], 1
+        for _ in range(int(count)):
+            out.append(self.multiply(self.G2, t) if t else self.Z2)
+            t = t * tau % self.curve_order
+        return out
+
+    def _lagrange_of(self, key):
+        n = len(key)
+        log_n, w = self._domain(n, None)
+        ctx = self._context()
+        return LagrangeKey(ctx, ctx.srs_lagrange(key.srs, log_n, w), n, w)
+
+    def save_trusted_setup(self, path, ck, g2_points, lagrange_order="natural"):
+        """Writes a trusted-setup text file (parse_trusted_setup's layout) from a monomial key of power-of-two length
+        and a list of G2 points.  The Lagrange section is kzg_srs_lagrange of the key; every point is compressed on
+        the device.  lagrange_order="bit_reversed" writes the Lagrange section in bit-reversed order."""
+        if lagrange_order not in ("natural", "bit_reversed"):
+            raise ValueError(f"lagrange_order must be \"natural\" or \"bit_reversed\", not {lagrange_order!r}")
+        self._monomial_key(ck, "save_trusted_setup")
+        key = self._key(ck)
+        g2_points = list(g2_points)
+        if not g2_points:
+            raise ValueError("save_trusted_setup: at least one G2 point (the generator) is needed")
+        lag = self._lagrange_of(key)
+        try:
+            lag_blobs = lag.srs.export_compressed()
+        finally:
+            lag.srs.close()
+        if lagrange_order == "bit_reversed":
+            lag_blobs = bit_reverse_rows(lag_blobs)
+        text = format_trusted_setup(lag_blobs, self.compress_g2(g2_points), key.srs.export_compressed())
+        with open(path, "w") as f:
+            f.write(text)
+
+    def load_trusted_setup(self, path, check=True, check_subgroup=True, lagrange_order="natural", r=None):
+        """Reads a trusted-setup text file -> TrustedSetup.  The G1 sections are decompressed and expanded on the
+        device (kzg_srs_load_g1_compressed), the G2 section by kzg_g2_decompress; check_subgroup tests every point for
+        membership in its prime-order subgroup.  A point that fails raises ValueError naming the section, the index
+        and the status.  check: the three sections must describe ONE tau (check_key; r fixes its randomness),
+        else ValueError naming the part that failed.  lagrange_order="bit_reversed": the file's Lagrange section is
+        in bit-reversed order and is un-permuted on load."""
+        if lagrange_order not in ("natural", "bit_reversed"):
+            raise ValueError(f"lagrange_order must be \"natural\" or \"bit_reversed\", not {lagrange_order!r}")
+        ctx = self._context()
+        with open(path) as f:
+            n1, n2, lag_blobs, g2_blobs, mono_blobs = parse_trusted_setup(f.read(), ctx.g1_bytes, ctx.g2_bytes)
+        if lagrange_order == "bit_reversed":
+            lag_blobs = bit_reverse_rows(lag_blobs)
+        log_n, w = self._domain(n1, None)
+        srs = []
+        try:
+            for name, blobs in (("G1 monomial", mono_blobs), ("G1 Lagrange", lag_blobs)):
+                try:
+                    srs.append(ctx.srs_load_g1_compressed(blobs, check_subgroup))
+                except _native.NativeError as e:
+                    if e.code != -1:
+                        raise
+                    raise ValueError(f"trusted setup, {name} section: {e}") from e
+            xy, inf, status = ctx.g2_decompress(g2_blobs, check_subgroup)
+            bad = np.flatnonzero(status)
+            if bad.size:
+                i = int(bad[0])
+                raise ValueError(f"trusted setup, G2 section: point {i} has status {int(status[i])} "
+                                 f"({_curve.G2_STATUS_TEXT[int(status[i])]})")
+            setup = TrustedSetup(CommitmentKey(ctx, srs[0]), LagrangeKey(ctx, srs[1], n1, w),
+                                 _native.limbs_to_g2_points(xy, inf))
+            if check:
+                part = self._key_fault(setup.monomial, setup.g2, setup.lagrange, r)
+                if part is not None:
+                    raise ValueError(f"trusted setup: the sections do not describe one tau: {part}")
+        except Exception:
+            for h in srs:
+                h.close()
+            raise
+        return setup
+
+    _CHECK_KEY_PAIRS = 16
+
+    def check_key(self, ck, g2_points, lagrange=None, r=None):
+        """Do the pieces describe ONE tau -- ck = [tau^i G1], g2_points = [tau^j G2], lagrange (optional) the Lagrange
+        form of ck?  True iff (1) ck[0] and g2_points[0] are the generators, (2) G1 chain: for a random rho,
+        e(sum_{i<n-1} rho^i S_i, T_1) = e(sum_{i<n-1} rho^i S_{i+1}, G2) -- one commit of two polynomials against the
+        key and one device pairing check, (3) G2 chain: e([rho^j] S_1, T_j) = e([rho^j] G1, T_{j+1}) for every j, in
+        equations of at most 16 pairs with their own rho each, all in one kzg_pairing_check call, (4) the Lagrange key
+        equals kzg_srs_lagrange(ck) point by point.  rho: 128 random bits unless r fixes it.  Membership of the points
+        in their subgroups is the loader's business (check_subgroup), not this call's."""
+        return self._key_fault(ck, g2_points, lagrange, r) is None
+
+    def _key_fault(self, ck, g2_points, lagrange, r):
+        """None, or the name of the first of check_key's four conditions that fails"""
+        self._monomial_key(ck, "check_key")
+        key = self._key(ck)
+        ctx = self._context()
+        order = self.curve_order
+        g2 = [self._g2.normalize(pt) for pt in g2_points]
+        n, m = len(key), len(g2)
+        if m < 1:
+            raise ValueError("check_key: at least one G2 point is needed")
+        if (n > 1 or m > 1) and (n < 2 or m < 2):
+            raise ValueError("check_key: chaining the powers needs [tau] G1 and [tau] G2 (two points of each group)")
+
+        def fresh(e):
+            return (secrets.randbits(128) if r is None else (int(r) + e)) % order or 1
+
+        # (1) the generators
+        if not self.eq(key[0], self.G1):
+            return "the first G1 power is not the generator"
+        if not self._g2.eq(g2[0], self.G2):
+            return "the first G2 power is not the generator"
+        if n == 1:
+            return None
+        # (2) the G1 chain: the powers of rho on the device, two commitments, one pairing equation
+        rho = fresh(0)
+        import torch
+        d_ones = self._upload(ctx, np.tile(_native.int_to_words(1), (n - 1, 1)))
+        d_pows = torch.empty_like(d_ones)
+        ctx.vec_mul_powers(n - 1, d_ones.data_ptr(), rho, 1, d_pows.data_ptr())
+        ctx.synchronize()
+        pows = d_pows.cpu().numpy().view(np.uint64)
+        lo, hi = np.zeros((n, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        lo[:n - 1], hi[1:] = pows, pows
+        c_lo, c_hi = self.commit(key, [lo, hi])
+        equations = [[(c_lo, g2[1]), (self.neg(c_hi), self.G2)]]
+        # (3) the G2 chain, 8 links (16 pairs) per equation; pairs of infinities (skipped by the device) fill the rest
+        s1 = key[1]
+        links = self._CHECK_KEY_PAIRS // 2
+        for e, start in enumerate(range(0, m - 1, links), 1):
+            rho_e, wgt, eq = fresh(e), 1, []
+            for j in range(start, min(start + links, m - 1)):
+                eq += [(self.multiply(s1, wgt), g2[j]), (self.neg(self.multiply(self.G1, wgt)), g2[j + 1])]
+                wgt = wgt * rho_e % order
+            equations.append(eq)
+        k = max(len(eq) for eq in equations)
+        equations = [eq + [(self.Z1, self.G2)] * (k - len(eq)) for eq in equations]
+        verdicts = self.pairing_check(equations)
+        if not verdicts[0]:
+            return "the G1 powers are not a chain of powers of the tau of [tau] G2"
+        if not all(verdicts[1:]):
+            return "the G2 powers are not a chain of powers of the tau of [tau] G1"
+        # (4) the Lagrange key
+        if lagrange is not None:
+            if not isinstance(lagrange, LagrangeKey):
+                raise TypeError("check_key: lagrange must be a LagrangeKey")
+            if lagrange.n != n:
+                return "the Lagrange key has another length than the monomial key"
+            mine = self._lagrange_of(key)
+            try:
+                if mine.w != lagrange.w:
+                    return "the Lagrange key is over another root of unity"
+                (xa, ia), (xb, ib) = mine.srs.export(), lagrange.srs.export()
+                if not (np.array_equal(ia, ib) and np.array_equal(xa, xb)):
+                    return "the Lagrange points are not the Lagrange form of the G1 powers"
+            finally:
+                mine.srs.close()
+        return None
 
     def commit(self, ck, polynomials):
         """kzg.py:80-120."""
@@ -939,25 +1230,46 @@ class KZG:
         g2_xy, g2_inf = _native.g2_points_to_limbs([self._g2.normalize(pr[1]) for e in eqs for pr in e], L)
         return single, g1_xy, g1_inf, g2_xy, g2_inf, k
 
-    def pairing_check(self, pairs):
+    def _pairing_subgroups(self, g1_xy, g1_inf, g2_xy, g2_inf, k, who):
+        """check_subgroup=True of pairing_check / pairing_product: every G2 point through kzg_g2_check_subgroup and, on
+        bls12_381 (bn254's G1 has cofactor 1), every G1 point through kzg_g1_check_subgroup.  A point outside its
+        subgroup raises ValueError naming the equation and the pair; a malformed point is left to the pairing."""
+        ctx = self._context()
+        checks = [("G2", ctx.g2_check_subgroup(g2_xy, g2_inf))]
+        if self.curve_type == "bls12_381":
+            checks.append(("G1", ctx.g1_check_subgroup(g1_xy, g1_inf)))
+        for group, status in checks:
+            bad = np.flatnonzero(status == 3)
+            if bad.size:
+                i = int(bad[0])
+                raise ValueError(f"{who}: equation {i // k}, pair {i % k}: the {group} point is outside the "
+                                 f"prime-order subgroup")
+
+    def pairing_check(self, pairs, check_subgroup=False):
         """Is the product of e(P_i, Q_i) over the pairs (P_i in G1, Q_i in G2) of an equation one?  pairs: one equation
         as a list of (G1_point, G2_point) -> bool, or a list of equations (the same number of pairs each, at most 16)
         -> a list of bools, one wave of the device per equation.  A malformed point (a coordinate >= p, off its curve
-        or twist) gives False.  Membership in the prime-order subgroups is not tested (in_subgroup does it for G1)."""
+        or twist) gives False.  Membership in the prime-order subgroups is tested only with check_subgroup=True: a point
+        outside its subgroup then raises ValueError naming the equation and the pair (a pairing check against such a
+        point proves nothing)."""
         single, g1_xy, g1_inf, g2_xy, g2_inf, k = self._pairing_arrays(pairs, "pairing_check")
         if k == 0:
             return []
+        if check_subgroup:
+            self._pairing_subgroups(g1_xy, g1_inf, g2_xy, g2_inf, k, "pairing_check")
         status = self._context().pairing_check(g1_xy, g1_inf, g2_xy, g2_inf, k)
         out = [int(st) == 0 for st in status]
         return out[0] if single else out
 
-    def pairing_product(self, pairs):
+    def pairing_product(self, pairs, check_subgroup=False):
         """The value of the product: the 12-tuple pairing() returns, raised to c = _native.PAIRING_GT_MULTIPLE[curve] (1 on
         BN254, 3 on BLS12-381) -- for one equation, or a list of them for a list of equations.  ValueError for a
-        malformed point."""
+        malformed point; with check_subgroup=True also for a point outside its prime-order subgroup."""
         single, g1_xy, g1_inf, g2_xy, g2_inf, k = self._pairing_arrays(pairs, "pairing_product")
         if k == 0:
             return []
+        if check_subgroup:
+            self._pairing_subgroups(g1_xy, g1_inf, g2_xy, g2_inf, k, "pairing_product")
         gt, status = self._context().pairing_product(g1_xy, g1_inf, g2_xy, g2_inf, k)
         if (status == 2).any():
             raise ValueError(f"pairing_product: equation {int(np.flatnonzero(status == 2)[0])} has a malformed point")
