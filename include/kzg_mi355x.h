@@ -405,15 +405,35 @@ int kzg_recover_cosets_device(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint
  *   - it must be given _begin's z; another z is KZG_ERR_ARG and the slice stays held;
  *   - tuning changed after _begin (kzg_ctx_set_tuning) has no effect on it;
  *   - it does not consume the slice: it may be repeated, with the same result for the same carry.
- * The slice is KEPT across commits (pipelined ones too), key generation, kzg_fr_poly_eval, the kzg_fr_vec_*
- * primitives and kzg_ctx_set_tuning.  It is DROPPED by kzg_open, kzg_open_device[_async], kzg_open_coset[_device]
- * (they work in the same buffers; only an opening of nothing but empty polynomials leaves them alone) and by a
+ * The slice is KEPT across commits (pipelined ones too), key generation, kzg_fr_poly_eval[_batch], the kzg_fr_vec_*
+ * primitives and kzg_ctx_set_tuning.  It is DROPPED by kzg_open, kzg_open_device[_async], kzg_open_coset[_device],
+ * kzg_open_points[_device] (they work in the same buffers; only an opening of nothing but empty polynomials leaves them alone) and by a
  * _begin that fails: _finish is then KZG_ERR_ARG ("another opening has used the context"), as it is, with its own
  * message, on a context that never began. */
 int kzg_open_shard_begin(kzg_ctx* ctx, const void* d_polys, const size_t* lens, size_t k, size_t stride,
                          const uint64_t z[4], const uint64_t xi[4], uint64_t* chunk_eval_out);
 int kzg_open_shard_finish(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t z[4], const uint64_t carry[4],
                           int first_rank, uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out);
+
+/* ---- weighted sum of single-point quotients: the two proof points of a Shplonk opening ----------
+ * With Q_z[p] = (p - p(z)) / (X - z), the call commits
+ *     Q = sum_j Q_(z_j)[ sum_i w_ij p_i ],   j < t points, i < k polynomials (k, t <= 64),
+ * n = max lens coefficients wide: out_xy / out_inf = commit(Q), Q's n - 1 coefficients.  points: [t][4] canonical
+ * limbs; weights: [k][t][4], row i belongs to polynomial i.  Polynomials, lens and stride are those of kzg_open_device;
+ * KZG_ERR_DEGREE applies as it does there.  A zero weight skips its polynomial, a column of zero weights its point;
+ * z_j = 0 is a legal point (Q_0[p] is p shifted down by one) and points may repeat.  k = 0, t = 0 or nothing but
+ * empty polynomials give the point at infinity.
+ * d_quot (device, nullable): receives the n - 1 coefficients of Q as canonical words.  It may be a row of the same
+ * strided array above the k rows read, so that a second call can take Q as a further polynomial.
+ * The call works in the buffers of kzg_open_device: it DROPS a slice held for kzg_open_shard_finish exactly as a plain
+ * opening does.  Synchronises.  kzg_open_points takes the polynomials from host memory (d_quot stays a device
+ * pointer). */
+int kzg_open_points_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,
+                           size_t stride, const uint64_t* points, size_t t, const uint64_t* weights, void* d_quot,
+                           uint64_t* out_xy, uint8_t* out_inf);
+int kzg_open_points(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* polys, const size_t* lens, size_t k,
+                    size_t stride, const uint64_t* points, size_t t, const uint64_t* weights, void* d_quot,
+                    uint64_t* out_xy, uint8_t* out_inf);
 
 /* Sum of n affine G1 points, on the HOST (no context, no GPU): what every rank does with the partial commitments /
  * partial opening proofs the others computed over their coefficient ranges -- the group law is not an RCCL reduction
@@ -548,6 +568,12 @@ int kzg_fr_vec_mul_powers(kzg_ctx* ctx, size_t n, const void* d_a, const uint64_
 int kzg_fr_vec_inverse(kzg_ctx* ctx, size_t n, const void* d_a, void* d_out);
 int kzg_fr_vec_prefix_product(kzg_ctx* ctx, size_t n, const void* d_a, void* d_out);
 int kzg_fr_poly_eval(kzg_ctx* ctx, size_t n, const void* d_a, const uint64_t z[4], uint64_t out[4]);
+/* Every value p_i(z_j) of k device-resident polynomials (`stride` elements apart, lens[i] <= stride coefficients) at
+ * t points ([t][4] canonical limbs): out[i][j], [k][t][4] limbs in host memory.  k, t <= 64.  Each polynomial is read
+ * once for all points of a launch; one copy and one synchronisation end the call.  Works in buffers of its own (a
+ * slice held for kzg_open_shard_finish stays). */
+int kzg_fr_poly_eval_batch(kzg_ctx* ctx, const void* d_polys, const size_t* lens, size_t k, size_t stride,
+                           const uint64_t* points, size_t t, uint64_t* out);
 
 /* Barycentric evaluation of one value vector over H = {w^i} (len <= 2^log_n values, missing ones zero; longer is
  * KZG_ERR_DEGREE) at z, z in H included: p(z) of the interpolant.  Device-resident values; synchronises. */
@@ -602,6 +628,8 @@ int kzg_pairing_gt_multiple(int curve);
  * When enabled, the library brackets its kernels with HIP events on the stream each one runs on.
  * Span names: "ntt_pass", "msm_partition1", "msm_partition2", "msm_order", "msm_accumulate",
  * "msm_finalize", "msm_reduce", "open_poly" (ONE span per kzg_open*: combination, scan and division),
+ * "open_points_poly" (ONE per kzg_open_points*: the polynomial stage alone, not the MSM), "poly_eval_batch" (ONE per
+ * kzg_fr_poly_eval_batch),
  * "open_shard_poly" (one per kzg_open_shard_begin and one per _finish), "srs_lagrange" (one per Lagrange key
  * built), "open_evals_poly" (ONE per kzg_open_evals*: combination, value and quotient), "domain_table" (one per
  * kzg_domain_table_create), "open_domain" (ONE per kzg_open_domain*: every chunk, transform and copy), "coset_table"

@@ -70,6 +70,12 @@ SIGNATURES = {
     "kzg_fr_vec_inverse": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp]),
     "kzg_fr_vec_prefix_product": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp]),
     "kzg_fr_poly_eval": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "kzg_fr_poly_eval_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t,
+                                              _vp]),
+    "kzg_open_points_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t,
+                                              _vp, _vp, _vp, _vp]),
+    "kzg_open_points": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t,
+                                       _vp, _vp, _vp, _vp]),
     "kzg_prof_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "kzg_prof_reset": (ctypes.c_int, [_vp]),
     "kzg_prof_read": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
@@ -838,6 +844,34 @@ class Context:
         out = np.zeros(4, dtype=np.uint64)
         self._check(lib().kzg_fr_poly_eval(self._h, n, _as_vp(d_a), _fr(z), _as_vp(out)))
         return int.from_bytes(out.tobytes(), "little")
+
+    def poly_eval_batch(self, d_polys, lens, stride, points):
+        """p_i(z_j) for the device polynomials (rows of d_polys) at `points`: [k][t] ints, one synchronisation"""
+        k, t = len(lens), len(points)
+        if k == 0 or t == 0:
+            return [[0] * t for _ in range(k)]
+        lens_a = np.asarray(lens, dtype=np.uint64)
+        out = np.zeros((k, t, 4), dtype=np.uint64)
+        self._check(lib().kzg_fr_poly_eval_batch(self._h, _as_vp(d_polys), _as_vp(lens_a), k, stride,
+                                                 _as_vp(ints_to_limbs(points)), t, _as_vp(out)))
+        vals = limbs_to_ints(out.reshape(k * t, 4))
+        return [vals[i * t:(i + 1) * t] for i in range(k)]
+
+    def open_points(self, srs, polys, lens, stride, points, weights, d_quot=None, device=False):
+        """kzg_open_points[_device]: commit(sum_j Q_(z_j)[sum_i weights[i][j] p_i]) -> (out_xy, out_inf).  points: t
+        ints; weights: k rows of t ints; d_quot: device pointer that receives the quotient's coefficients, or None."""
+        k, t = len(lens), len(points)
+        lens_a = np.asarray(lens, dtype=np.uint64)
+        pts = ints_to_limbs(points) if t else np.zeros((1, 4), dtype=np.uint64)
+        flat = [w for row in weights for w in row]
+        if len(flat) != k * t:
+            raise ValueError("open_points: weights must be k rows of t values")
+        w = ints_to_limbs(flat) if flat else np.zeros((1, 4), dtype=np.uint64)
+        out_xy, out_inf, _ = result_buffers(self.fp_limbs)
+        fn = lib().kzg_open_points_device if device else lib().kzg_open_points
+        self._check(fn(self._h, srs._h, _as_vp(polys), _as_vp(lens_a), k, stride, _as_vp(pts), t, _as_vp(w),
+                       _as_vp(d_quot), _as_vp(out_xy), _as_vp(out_inf)))
+        return out_xy, out_inf
 
     # ---- sharded open (device pointers)
     def open_shard_begin(self, d_polys, lens, stride, z_words, xi_words):

@@ -577,6 +577,42 @@ int kzg_open(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* polys, const size
   return kzg_open_device(ctx, srs, d, lens, k, stride, z, xi, out_xy, out_inf, eval_out);
 }
 
+int kzg_open_points_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,
+                           size_t stride, const uint64_t* points, size_t t, const uint64_t* weights, void* d_quot,
+                           uint64_t* out_xy, uint8_t* out_inf) {
+  KZG_ENTER(!srs || !out_xy || !out_inf || (k && (!lens || !d_polys)) || (t && !points) || (k && t && !weights));
+  uint32_t* d_q = nullptr;
+  size_t qlen = 0;
+  int rc = open_points_quotient_device(c, static_cast<const uint32_t*>(d_polys), lens, k, stride,
+                                       reinterpret_cast<const uint32_t*>(points), t,
+                                       reinterpret_cast<const uint32_t*>(weights), &d_q, &qlen);
+  if (rc) return rc;
+  if (!d_q) {   // nothing but constants or empty polynomials: Q = 0
+    memset(out_xy, 0, (size_t)kzg_fp_limbs(c->curve) * 16);
+    *out_inf = 1;
+    return KZG_OK;
+  }
+  if (d_quot) KZG_HIP(c, hipMemcpyAsync(d_quot, d_q, qlen * 32, hipMemcpyDeviceToDevice, c->stream));
+  const size_t srs_n = srs->s->n;
+  if (qlen > srs_n) {   // the degree of Q decides, as in kzg_open_device
+    bool nz = false;
+    rc = device_any_nonzero(c, d_q, srs_n, qlen, &nz);
+    if (rc) return rc;
+    if (nz) return set_err(c, KZG_ERR_DEGREE, "witness polynomial longer than the commitment key");
+    qlen = srs_n;
+  }
+  return commit_device(c, srs->s, d_q, &qlen, 1, qlen ? qlen : 1, out_xy, out_inf);
+}
+
+int kzg_open_points(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* polys, const size_t* lens, size_t k,
+                    size_t stride, const uint64_t* points, size_t t, const uint64_t* weights, void* d_quot,
+                    uint64_t* out_xy, uint8_t* out_inf) {
+  KZG_ENTER(!srs || !out_xy || !out_inf || (k && (!lens || !polys)));
+  void* d = nullptr;
+  if (int rc = stage_host(c, polys, k * stride * 32, &d)) return rc;
+  return kzg_open_points_device(ctx, srs, d, lens, k, stride, points, t, weights, d_quot, out_xy, out_inf);
+}
+
 int kzg_open_shard_begin(kzg_ctx* ctx, const void* d_polys, const size_t* lens, size_t k, size_t stride,
                          const uint64_t z[4], const uint64_t xi[4], uint64_t* chunk_eval_out) {
   KZG_ENTER(!z || !xi || !chunk_eval_out || (k && (!lens || !d_polys)));
@@ -822,6 +858,14 @@ int kzg_fr_poly_eval(kzg_ctx* ctx, size_t n, const void* d_a, const uint64_t z[4
   KZG_ENTER(false);
   if (!z || !out || (n && !d_a)) return KZG_ERR_ARG;
   return fr_poly_eval(c, n, static_cast<const uint32_t*>(d_a), reinterpret_cast<const uint32_t*>(z), out);
+}
+
+int kzg_fr_poly_eval_batch(kzg_ctx* ctx, const void* d_polys, const size_t* lens, size_t k, size_t stride,
+                           const uint64_t* points, size_t t, uint64_t* out) {
+  KZG_ENTER(false);
+  if (k && t && (!d_polys || !lens || !points || !out)) return KZG_ERR_ARG;
+  return fr_poly_eval_batch(c, static_cast<const uint32_t*>(d_polys), lens, k, stride,
+                            reinterpret_cast<const uint32_t*>(points), t, out);
 }
 
 int kzg_fr_eval_lagrange(kzg_ctx* ctx, uint32_t log_n, const uint64_t w[4], size_t len, const void* d_vals,

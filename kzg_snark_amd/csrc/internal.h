@@ -85,7 +85,8 @@ struct Ctx {
   uint32_t ntt_lds_attr_set = 0;   // per ntt_pass_kernel instantiation: hipFuncAttributeMaxDynamicSharedMemorySize applies per device
   DevBuf ntt_scratch;     // pass-1 output of two-pass transforms
   DevBuf io;              // staging for the host-pointer entry points
-  DevBuf poly_tmp[4];     // open(): combined polynomial + suffix values; scratch of the vector primitives
+  DevBuf poly_tmp[4];     // open(): combined polynomial + suffix values; [1]: the point tables of kzg_open_points;
+                          // [2], [3]: scratch of the vector primitives and of kzg_fr_poly_eval[_batch]
   DevBuf scan_tmp;        // open(): chunk values, tile aggregates, power tables (open_slice holds their carve)
   DevBuf lagr_tmp;        // lagrange.hip: combined values, denominators, inverses, quotient, partial sums
   DevBuf dom_tmp;         // domain.hip: G1 transform buffers and the Fr vectors of one chunk of kzg_open_domain
@@ -167,6 +168,8 @@ int fr_vec_mul_powers(Ctx* c, size_t n, const uint32_t* a, const uint32_t* s, co
 int fr_vec_inverse(Ctx* c, size_t n, const uint32_t* a, uint32_t* out);
 int fr_vec_prefix_product(Ctx* c, size_t n, const uint32_t* a, uint32_t* out);
 int fr_poly_eval(Ctx* c, size_t n, const uint32_t* a, const uint32_t* z, uint64_t* out);
+int fr_poly_eval_batch(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
+                       const uint32_t* points, size_t t, uint64_t* out);
 
 // lagrange.hip (beside its table of w^i; not poly.hip, whose multiplier is built without field.h's chain pin):
 // d_tab <- the two-level power table of `base` (Montgomery form), POW_TAB entries of 32 bytes, read by fr_pow_lookup

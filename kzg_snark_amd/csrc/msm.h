@@ -100,6 +100,12 @@ void msm_free_work(Ctx* c);
 int open_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
                          const uint32_t* z_words, const uint32_t* xi_words, uint32_t** d_quot_out,
                          size_t* quot_len, uint64_t* eval_out, bool sync = true);
+// poly.hip: Q = sum_j Q_(z_j)[ sum_i w_ij p_i ].  points [t][8], weights [k][t][8] canonical words on
+// the host.  d_quot_out: max_len-1 coefficients (null: nothing to commit, Q = 0).  Enqueues; the host tables it
+// uploads have been copied when it returns.
+int open_points_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
+                                const uint32_t* points, size_t t, const uint32_t* weights, uint32_t** d_quot_out,
+                                size_t* quot_len);
 // poly.hip: coset opening.  combined = sum_i xi^(i+1) p_i; quotient (combined - rho) / (X^l - h^l), rho the remainder.
 // d_quot receives max(n - l, 0) coefficients; eval_out ([l][4], may be null) combined(h zeta^k).  Synchronises.
 // open_coset_check: the argument checks alone (log_l <= 12, h != 0, zeta a primitive l-th root, lens, key length).

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace kzg {
@@ -386,6 +387,272 @@ __global__ __launch_bounds__(TB) void tile_eval_kernel(uint32_t ntiles, const ui
   if (threadIdx.x == 0) store_words<F>(out_words, Fd::add(q0, load_limbs<F>(H)));
 }
 
+// =====================================================================================
+// The two passes for SEVERAL points at once (kzg_open_points, kzg_fr_poly_eval_batch):
+//   Q = sum_j Q_(z_j)[ sum_i w_ij p_i ],  Q_z[p] = (p - p(z)) / (X - z): the suffix values of the combination
+//   comb_j = sum_i w_ij p_i at z_j, added up over the points.
+// A launch takes up to MP points.  Pass 1 loads the (up to TILE_MAXK) coefficients of a position ONCE and forms every
+// comb_j from them, then runs the chunk / tile aggregates per point exactly as tile_combine_kernel does.  Pass 2 is one
+// launch per point, one after the other on the stream: each ADDS its point's suffix values into the one output vector
+// in place.  (A loop over the points inside one kernel was built first: every address derived from the thread index
+// became loop-invariant and stayed in registers across the body, 98-118 VGPRs against tile_fill_kernel's 71-84.)
+// The per-point tables (TileScanArgs, weights, z) do not fit the kernel arguments: they travel in a device buffer.
+// z_j = 0: the suffix values are comb_j itself; the point takes no part in the scan.
+// =====================================================================================
+constexpr uint32_t MP = 3;            // points per launch: 9 VGPRs of combination and 9 KiB of chunk sums each (a
+                                      // fourth takes the BLS12-381 kernel past 128 VGPRs: 3 waves per SIMD for 4)
+struct MultiPoint {                   // one point of one launch, Montgomery form
+  TileScanArgs ts;
+  uint32_t w[TILE_MAXK * FRN];        // weight of the launch's polynomial i at this point
+  uint32_t z[FRN];
+  uint32_t groups;                    // bit g: a polynomial of the g-th group of DOT_G has a non-zero weight here
+  uint32_t zero;                      // z = 0
+};
+struct MultiPolys {                   // the launch's polynomials: rows row[i] of the caller's array (a zero weight
+  const uint32_t* polys;              // everywhere drops a row before it gets here)
+  uint64_t stride;
+  uint32_t k;
+  uint32_t lens[TILE_MAXK];
+  uint32_t row[TILE_MAXK];
+};
+struct MultiCarve {                   // the scan buffers of the launch's points (TileShape's carve, per point)
+  uint32_t *G[MP], *H[MP], *A[MP], *zinv[MP], *W[MP];
+};
+
+// fn(integral_constant j) for j < MP: the points of a launch by constant index, so that acc[j] stays in registers
+template <class Fn, uint32_t... J>
+__device__ __forceinline__ void for_points(Fn&& fn, std::integer_sequence<uint32_t, J...>) {
+  (fn(std::integral_constant<uint32_t, J>{}), ...);
+}
+template <class Fn>
+__device__ __forceinline__ void for_points(Fn&& fn) {
+  for_points(fn, std::make_integer_sequence<uint32_t, MP>{});
+}
+// an element at an address that is the same in every lane, into scalar registers
+template <class F>
+__device__ __forceinline__ Fe<F> load_limbs_uniform(const uint32_t* p) {
+  Fe<F> r;
+#pragma unroll
+  for (int j = 0; j < F::N; ++j) r.l[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[j]);
+  return r;
+}
+
+// STORE = true (opening): the grid is one-dimensional, the k polynomials are combined per point.
+// STORE = false (batched evaluation): blockIdx.y is ONE polynomial, taken as it is for every point; only the tile
+// aggregates H[(poly0 + y) * hstride + b] and the W tables are written.
+template <class F, uint32_t TB, uint32_t ITER, bool STORE>
+__global__ __launch_bounds__(TB * SC / ITER) void tile_combine_multi_kernel(MultiPolys a, const MultiPoint* __restrict__ pts,
+                                                                            uint32_t np, MultiCarve cv, uint32_t* comb,
+                                                                            uint64_t comb_stride, uint32_t n,
+                                                                            uint32_t ntiles, uint32_t poly0,
+                                                                            uint32_t hstride) {
+  using Fd = Field<F>;
+  constexpr uint32_t T = TB * SC, TK = T / ITER;
+  static_assert(F::N == FRN && SC == 8 && TB % 64 == 0 && TB <= 256 && TK % 64 == 0 && TK >= TB && TK <= 1024, "tile layout");
+  __shared__ uint32_t hs[MP * TB * FRN];                    // chunk sums (lazy limbs), per point
+  __shared__ uint32_t zsh[MP * SC * FRN];
+  __shared__ uint32_t red[(TK / 8 + TK / 64) * FRN];
+  const uint32_t tid = threadIdx.x;
+#if KZG_TILE_PRIO
+  __builtin_amdgcn_s_setprio(KZG_TILE_PRIO);
+#endif
+  const uint32_t ntab = gridDim.x - ntiles;
+  if (blockIdx.x < ntab) {                                  // table workgroups, as in tile_combine_kernel
+    if (blockIdx.y) return;
+    const uint32_t t = blockIdx.x * TK + tid;
+#pragma unroll 1
+    for (uint32_t j = 0; j < np; ++j) {
+      if (pts[j].zero) continue;
+      if (STORE && t <= TB) store_limbs<F>(cv.zinv[j] + (size_t)t * F::N, pow_from_generators<F>(pts[j].ts.ginv, t));
+      if (t < ntiles) store_limbs<F>(cv.W[j] + (size_t)t * F::N, pow_from_generators<F>(pts[j].ts.gw, t + 1));
+    }
+    return;
+  }
+  const uint32_t b = blockIdx.x - ntab, base = b * T;
+  const uint32_t len = STORE ? n : a.lens[blockIdx.y];
+  if (base >= len) return;                                  // a tile above this polynomial's end (evaluation form)
+  const uint32_t* src = a.polys + a.stride * a.row[blockIdx.y] * 8;
+  for (uint32_t u = tid; u < np * SC * FRN; u += TK) zsh[u] = pts[u / (SC * FRN)].ts.zs[u % (SC * FRN)];
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t it = 0; it < ITER; ++it) {
+    const uint32_t i = it * TK + tid, t = base + i;
+    Fe<F> acc[MP];
+#pragma unroll
+    for (uint32_t j = 0; j < MP; ++j) acc[j] = Fd::zero();
+    if (t < len) {
+      if (STORE) {
+        for (uint32_t i0 = 0, grp = 0; i0 < a.k; i0 += DOT_G, ++grp) {
+          const uint32_t cnt = min(DOT_G, a.k - i0);
+          Fe<F> c[DOT_G];
+#pragma unroll
+          for (uint32_t g = 0; g < DOT_G; ++g) {
+            const uint32_t p = i0 + g;
+            const bool on = g < cnt && t < a.lens[g < cnt ? p : i0];         // shorter polynomials read as zero-padded
+            c[g] = on ? load_words<F>(a.polys + (a.stride * a.row[g < cnt ? p : i0] + t) * 8) : Fd::zero();
+          }
+          for_points([&](auto jc) {
+            constexpr uint32_t j = decltype(jc)::value;
+            if (j >= np || !((pts[j].groups >> grp) & 1u)) return;           // uniform: no weight of this group here
+            Fe<F> x[DOT_G];
+#pragma unroll
+            for (uint32_t g = 0; g < DOT_G; ++g) x[g] = load_limbs_uniform<F>(pts[j].w + (g < cnt ? i0 + g : i0) * F::N);
+            acc[j] = Fd::add(acc[j], dot_upto<F>(cnt, c, x));
+          });
+        }
+        for_points([&](auto jc) {
+          constexpr uint32_t j = decltype(jc)::value;
+          if (j < np) store_words<F>(comb + (comb_stride * j + t) * 8, acc[j]);
+        });
+      } else {
+        const Fe<F> cf = load_words<F>(src + (size_t)t * 8);
+#pragma unroll
+        for (uint32_t j = 0; j < MP; ++j) acc[j] = cf;
+      }
+    }
+    for_points([&](auto jc) {
+      constexpr uint32_t j = decltype(jc)::value;
+      if (j >= np || pts[j].zero) return;
+      const Fe<F> e = Fd::mul(acc[j], load_limbs<F>(zsh + (j * SC + (tid & (SC - 1))) * F::N));    // 0 beyond the end
+      Fe<F> s;
+#pragma unroll
+      for (int q = 0; q < F::N; ++q) s.l[q] = lane8_sum(e.l[q]);
+      if ((tid & 7) == 0) store_limbs<F>(hs + (j * TB + (i >> 3)) * F::N, s);
+    });
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t j = 0; j < np; ++j) {
+    if (pts[j].zero) continue;
+    Fe<F> g = Fd::zero();
+    if (tid < TB) {                                                           // whole waves: TB is a multiple of 64
+      const Fe<F> hq = Fd::reduce_wide(Fd::carry(load_limbs<F>(hs + (j * TB + tid) * F::N)));
+      const Fe<F> zq = Fd::mul(load_limbs<F>(pts[j].ts.zq_lo + (tid & 15) * F::N),
+                               load_limbs<F>(pts[j].ts.zq_hi + (tid >> 4) * F::N));
+      g = Fd::mul(hq, zq);
+      if (STORE) store_limbs<F>(cv.G[j] + ((size_t)b * TB + tid) * F::N, g);
+    }
+    const Fe<F> hb = block_sum<F, TK>(g, red);
+    if (tid == 0) store_limbs<F>(cv.H[j] + ((size_t)(poly0 + blockIdx.y) * hstride + b) * F::N, hb);
+  }
+}
+
+// Pass 2 for ONE point of a launch: out (S_0, S_1, ..: n elements) += the suffix values of comb at z -- tile_fill_kernel
+// whose last step adds to what `out` holds (add = 0: writes, nothing earlier is there).  The points of a launch follow
+// each other on the stream, so that the sum needs neither a buffer per point nor a pass of its own.  zero: z = 0, the
+// suffix values are comb itself.
+template <class F, uint32_t TB>
+__global__ __launch_bounds__(TB) void tile_fill_add_kernel(const uint32_t* comb, uint32_t n, uint32_t ntiles,
+                                                           const uint32_t* G, const uint32_t* H, const uint32_t* A,
+                                                           uint32_t nsuper, FrArg zarg, uint32_t zero,
+                                                           const uint32_t* zinv, const uint32_t* W, uint32_t add,
+                                                           uint32_t* out) {
+  using Fd = Field<F>;
+  constexpr uint32_t T = TB * SC, NWAVE = TB / 64;
+  __shared__ uint4 st[T * 2 + TB];                          // 32 B per coefficient + one pad quad per chunk
+  __shared__ uint32_t red[(TB / 8 + TB / 64) * FRN];
+  __shared__ uint32_t wsum[NWAVE * FRN];
+  __shared__ uint32_t qsh[FRN];
+#if KZG_TILE_PRIO
+  __builtin_amdgcn_s_setprio(KZG_TILE_PRIO);
+#endif
+  const uint32_t tid = threadIdx.x, b = blockIdx.x, e0 = b * T;
+  const uint4* gin = reinterpret_cast<const uint4*>(comb);
+  for (uint32_t i = tid; i < T * 2; i += TB) {
+    const uint32_t e = i >> 1;
+    if (e0 + e < n) st[i + (e >> SC_LOG)] = gin[(size_t)(e0 + e) * 2 + (i & 1)];
+  }
+  if (!zero) {
+    FrArg none{};
+    const Fe<F> q0 = tile_carry_sum<F, TB>(b, ntiles, H, A, nsuper, none, 0, W, red);
+    if (tid == 0) store_limbs<F>(qsh, q0);
+    // suffix sums of the tile's scaled chunk values: inclusive inside the wave by shuffles, the waves above from LDS
+    const uint32_t lane = tid & 63, wave = tid >> 6;
+    Fe<F> incl = load_limbs<F>(G + ((size_t)b * TB + tid) * F::N);
+#pragma unroll 1
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      Fe<F> t;
+#pragma unroll
+      for (int j = 0; j < F::N; ++j) t.l[j] = (uint32_t)__shfl_down((int)incl.l[j], d);
+      const Fe<F> s = Fd::add(incl, t);
+      incl = Fd::select(lane + d < 64, s, incl);
+    }
+    if (lane == 0) store_limbs<F>(wsum + wave * F::N, incl);
+    Fe<F> ex;                                               // sum over the chunks after this one
+#pragma unroll
+    for (int j = 0; j < F::N; ++j) {
+      const uint32_t t = (uint32_t)__shfl_down((int)incl.l[j], 1);
+      ex.l[j] = lane == 63 ? 0u : t;
+    }
+    __syncthreads();                                        // st, qsh, wsum complete
+    for (uint32_t w = wave + 1; w < NWAVE; ++w) ex = Fd::add(ex, load_limbs<F>(wsum + w * F::N));
+    Fe<F> acc = Fd::mul(Fd::add(ex, load_limbs<F>(qsh)), load_limbs<F>(zinv + (size_t)(tid + 1) * F::N));
+    const uint32_t j0 = e0 + tid * SC;
+    if (j0 < n) {
+      const Fe<F> z = arg_fe<F>(zarg);
+      for (uint32_t j = j0 + SC; j-- > j0;) {
+        if (j >= n) continue;                               // the chunk that holds the end: acc is zero up there
+        const uint32_t q = (j - e0) * 2 + tid;              // (j - e0) >> SC_LOG == tid
+        const uint4 lo = st[q], hi = st[q + 1];
+        const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        acc = Fd::add(Fd::from_words(w), Fd::mul(acc, z));
+        uint32_t o[8];
+        Fd::to_words(Fd::reduce(acc), o);
+        st[q] = make_uint4(o[0], o[1], o[2], o[3]);
+        st[q + 1] = make_uint4(o[4], o[5], o[6], o[7]);
+      }
+    }
+  }
+  __syncthreads();
+  uint4* gout = reinterpret_cast<uint4*>(out);
+  if (!add) {
+    for (uint32_t i = tid; i < T * 2; i += TB) {
+      const uint32_t e = i >> 1;
+      if (e0 + e < n) gout[(size_t)(e0 + e) * 2 + (i & 1)] = st[i + (e >> SC_LOG)];
+    }
+    return;
+  }
+  // whole elements, 32 contiguous bytes per lane: the tile's part of `out` was written by the launch before this one
+#pragma unroll 2
+  for (uint32_t e = tid; e < T; e += TB) {
+    if (e0 + e >= n) break;
+    const size_t o = (size_t)(e0 + e) * 2;
+    const uint4 lo = st[e * 2 + (e >> SC_LOG)], hi = st[e * 2 + 1 + (e >> SC_LOG)], plo = gout[o], phi = gout[o + 1];
+    const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const uint32_t y[8] = {plo.x, plo.y, plo.z, plo.w, phi.x, phi.y, phi.z, phi.w};
+    uint32_t r[8];
+    Fd::to_words(Fd::reduce(Fd::add(Fd::from_words(x), Fd::from_words(y))), r);
+    gout[o] = make_uint4(r[0], r[1], r[2], r[3]);
+    gout[o + 1] = make_uint4(r[4], r[5], r[6], r[7]);
+  }
+}
+
+// The values of a batched evaluation from the aggregates of pass 1: one workgroup per (polynomial, point).
+struct EvalBatchArgs {
+  const uint32_t* polys;
+  uint64_t stride;
+  uint32_t lens[MAXK];
+  uint32_t slot[MAXK];                // the point's place among the non-zero points, MAXK for z = 0
+};
+template <class F, uint32_t TB>
+__global__ __launch_bounds__(TB) void tile_eval_batch_kernel(EvalBatchArgs a, uint32_t k, const uint32_t* H,
+                                                             uint32_t hstride, const uint32_t* W, uint32_t wstride,
+                                                             uint32_t npts, uint32_t* out_words) {
+  using Fd = Field<F>;
+  __shared__ uint32_t red[(TB / 8 + TB / 64) * FRN];
+  const uint32_t i = blockIdx.x, j = blockIdx.y, len = a.lens[i], slot = a.slot[j];
+  uint32_t* o = out_words + ((size_t)i * npts + j) * 8;
+  if (len <= 1 || slot == MAXK) {                           // nothing, or the constant coefficient (poly_eval_t)
+    if (threadIdx.x < 8) o[threadIdx.x] = len ? a.polys[a.stride * i * 8 + threadIdx.x] : 0u;
+    return;
+  }
+  const uint32_t ntiles = (len + TB * SC - 1) / (TB * SC);
+  const uint32_t* Hij = H + ((size_t)slot * k + i) * hstride * F::N;
+  FrArg none{};
+  const Fe<F> q0 = tile_carry_sum<F, TB>(0, ntiles, Hij, nullptr, 0, none, 0, W + (size_t)slot * wstride * F::N, red);
+  if (threadIdx.x == 0) store_words<F>(o, Fd::add(q0, load_limbs<F>(Hij)));
+}
+
 // Buffer layout of poly_tmp[0] (canonical words, 8 per element), cap = n + 1:
 //   comb[0 .. cap)   combined polynomial
 //   eval             S_0
@@ -435,43 +702,57 @@ static uint32_t open_tile_threads(Ctx* c) {
   return msm_accumulate_in_flight(c) ? 128u : 256u;
 }
 
+// the counts of a scan over n coefficients in tiles of tb threads
+static void tile_counts(Ctx* c, size_t n, uint32_t tb, TileShape* s, uint32_t* ntab) {
+  const uint32_t T = tb * SC, tk = T / TILE_ITER;
+  s->tb = tb, s->n = n;
+  s->ntiles = (uint32_t)((n + T - 1) / T);
+  *ntab = (std::max(tb + 1, s->ntiles) + tk - 1) / tk;
+  const uint32_t direct_max = c->tune_open_direct_max > 0 ? (uint32_t)c->tune_open_direct_max : TILE_DIRECT_MAX;
+  s->nsuper = s->ntiles > direct_max ? (s->ntiles + SG - 1) / SG : 0;
+}
+// the powers of z != 0 that the two passes take from the host (one inversion), for tiles of tb threads
+template <class F>
+void tile_powers(const uint32_t* z_words, uint32_t tb, TileShape* s, TileScanArgs* ts) {
+  using Fd = Field<F>;
+  const Fe<F> z = Fd::to_mont(Fd::from_words(z_words));
+  memcpy(s->z, z.l, F::N * 4);
+  Fe<F> zj = Fd::one();
+  for (uint32_t j = 0; j < SC; ++j) { memcpy(&ts->zs[j * F::N], zj.l, F::N * 4); zj = Fd::mul(zj, z); }
+  const Fe<F> z8 = zj;
+  zj = Fd::one();
+  for (uint32_t j = 0; j < 16; ++j) { memcpy(&ts->zq_lo[j * F::N], zj.l, F::N * 4); zj = Fd::mul(zj, z8); }
+  const Fe<F> z128 = zj;
+  zj = Fd::one();
+  for (uint32_t j = 0; j < 16; ++j) { memcpy(&ts->zq_hi[j * F::N], zj.l, F::N * 4); zj = Fd::mul(zj, z128); }
+  Fe<F> g = z128;                                             // z^(8 * 16) -> z^(8 * tb) = z^T
+  for (uint32_t q = 16; q < tb; q <<= 1) g = Fd::mul(g, g);
+  for (uint32_t q = 0; q < TILE_GW; ++q) { memcpy(&ts->gw[q * F::N], g.l, F::N * 4); g = Fd::mul(g, g); }
+  g = Fd::inv(z);
+  memcpy(s->z_inv, g.l, F::N * 4);
+  for (uint32_t q = 0; q < SC_LOG; ++q) g = Fd::mul(g, g);    // z^-8
+  for (uint32_t q = 0; q < 9; ++q) { memcpy(&ts->ginv[q * F::N], g.l, F::N * 4); g = Fd::mul(g, g); }
+}
+// the carve of one scan's buffer at `base` (null: measure only); returns its words (with_chunks = false: no g)
+static size_t tile_carve(TileShape* s, uint32_t* base, bool with_chunks) {
+  const size_t chunk_words = with_chunks ? (size_t)s->ntiles * s->tb : 0;
+  s->G = base;
+  s->H = s->G + chunk_words * FRN;
+  s->A = s->H + (size_t)(s->ntiles + 1) * FRN;
+  s->zinv = s->A + (size_t)(s->nsuper + 1) * FRN;
+  s->W = s->zinv + (size_t)(s->tb + 1) * FRN;
+  return (chunk_words + (s->ntiles + 1) + (s->nsuper + 1) + (s->tb + 1) + s->ntiles) * FRN;
+}
+
 // the plan of a scan over n coefficients at z != 0 in tiles of tb threads, carved out of buf (with_chunks = false: no g)
 template <class F>
 int tile_plan(Ctx* c, size_t n, const uint32_t* z_words, uint32_t tb, DevBuf& buf, TileShape* s, TilePass1* p,
               bool with_chunks = true) {
-  using Fd = Field<F>;
-  const uint32_t T = tb * SC, tk = T / TILE_ITER;
-  s->tb = tb, s->n = n;
-  s->ntiles = (uint32_t)((n + T - 1) / T);
-  p->ntab = (std::max(tb + 1, s->ntiles) + tk - 1) / tk;
-  const uint32_t direct_max = c->tune_open_direct_max > 0 ? (uint32_t)c->tune_open_direct_max : TILE_DIRECT_MAX;
-  s->nsuper = s->ntiles > direct_max ? (s->ntiles + SG - 1) / SG : 0;
-  const Fe<F> z = Fd::to_mont(Fd::from_words(z_words));
-  memcpy(s->z, z.l, F::N * 4);
-  Fe<F> zj = Fd::one();
-  for (uint32_t j = 0; j < SC; ++j) { memcpy(&p->ts.zs[j * F::N], zj.l, F::N * 4); zj = Fd::mul(zj, z); }
-  const Fe<F> z8 = zj;
-  zj = Fd::one();
-  for (uint32_t j = 0; j < 16; ++j) { memcpy(&p->ts.zq_lo[j * F::N], zj.l, F::N * 4); zj = Fd::mul(zj, z8); }
-  const Fe<F> z128 = zj;
-  zj = Fd::one();
-  for (uint32_t j = 0; j < 16; ++j) { memcpy(&p->ts.zq_hi[j * F::N], zj.l, F::N * 4); zj = Fd::mul(zj, z128); }
-  Fe<F> g = z128;                                             // z^(8 * 16) -> z^(8 * tb) = z^T
-  for (uint32_t q = 16; q < tb; q <<= 1) g = Fd::mul(g, g);
-  for (uint32_t q = 0; q < TILE_GW; ++q) { memcpy(&p->ts.gw[q * F::N], g.l, F::N * 4); g = Fd::mul(g, g); }
-  g = Fd::inv(z);
-  memcpy(s->z_inv, g.l, F::N * 4);
-  for (uint32_t q = 0; q < SC_LOG; ++q) g = Fd::mul(g, g);    // z^-8
-  for (uint32_t q = 0; q < 9; ++q) { memcpy(&p->ts.ginv[q * F::N], g.l, F::N * 4); g = Fd::mul(g, g); }
-  const size_t chunk_words = with_chunks ? (size_t)s->ntiles * tb : 0;
-  const size_t words = (chunk_words + (s->ntiles + 1) + (s->nsuper + 1) + (tb + 1) + s->ntiles) * F::N;
-  int rc = ensure_buf(c, buf, words * 4);
+  tile_counts(c, n, tb, s, &p->ntab);
+  tile_powers<F>(z_words, tb, s, &p->ts);
+  int rc = ensure_buf(c, buf, tile_carve(s, nullptr, with_chunks) * 4);
   if (rc) return rc;
-  s->G = static_cast<uint32_t*>(buf.p);
-  s->H = s->G + chunk_words * F::N;
-  s->A = s->H + (size_t)(s->ntiles + 1) * F::N;
-  s->zinv = s->A + (size_t)(s->nsuper + 1) * F::N;
-  s->W = s->zinv + (size_t)(tb + 1) * F::N;
+  tile_carve(s, static_cast<uint32_t*>(buf.p), with_chunks);
   return KZG_OK;
 }
 
@@ -688,6 +969,130 @@ int open_shard_finish_t(Ctx* c, const uint32_t* z_words, const uint32_t* carry_w
   return KZG_OK;
 }
 
+// a point's tables (z != 0) for tiles of tb threads; weights and groups are the launch's to fill
+template <class F>
+MultiPoint multi_point(const uint32_t* z_words, uint32_t tb) {
+  MultiPoint m{};
+  m.zero = words_are_zero(z_words);
+  if (!m.zero) {
+    TileShape s;
+    tile_powers<F>(z_words, tb, &s, &m.ts);
+    memcpy(m.z, s.z, sizeof(m.z));
+  }
+  return m;
+}
+
+// Q = sum_j Q_(z_j)[ sum_i w_ij p_i ]: the vector S (n elements; Q's n - 1 coefficients are S_1 ..) in poly_tmp[0],
+// with the launch's MP combinations behind it; MP carves of scan_tmp; the launches' point tables in poly_tmp[1].
+// Polynomials that carry no weight and points whose weights are all zero never reach a launch.  More than TILE_MAXK
+// polynomials or MP points are further launches: the output is linear in both, so each pair of passes adds its part
+// to S in place.  ONE "open_points_poly" span per call.
+template <class F>
+int open_points_quotient_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
+                           const uint32_t* points, size_t t, const uint32_t* weights, uint32_t** d_quot_out,
+                           size_t* quot_len) {
+  using Fd = Field<F>;
+  *d_quot_out = nullptr;
+  *quot_len = 0;
+  if (t > MAXK) return set_err(c, KZG_ERR_ARG, "kzg_open_points: more than 64 points");
+  size_t n = 0;
+  int rc = check_open_args<F>(c, lens, k, stride, &n);
+  if (rc) return rc;
+  if (n <= 1) return KZG_OK;                     // a constant has the quotient 0 at every point
+  auto weight = [&](size_t i, size_t j) { return weights + (i * t + j) * 8; };
+  std::vector<uint32_t> pi, pj;
+  for (size_t i = 0; i < k; ++i) {
+    bool any = false;
+    for (size_t j = 0; j < t && !any; ++j) any = !words_are_zero(weight(i, j));
+    if (any && lens[i]) pi.push_back((uint32_t)i);
+  }
+  for (size_t j = 0; j < t; ++j) {
+    bool any = false;
+    for (size_t q = 0; q < pi.size() && !any; ++q) any = !words_are_zero(weight(pi[q], j));
+    if (any) pj.push_back((uint32_t)j);
+  }
+  const OpenBufs bufs = claim_open_bufs(c);
+  const uint32_t tb = open_tile_threads(c);
+  TileShape s0;
+  uint32_t ntab = 0;
+  tile_counts(c, n, tb, &s0, &ntab);
+  const size_t cap = n + 1, scan_words = tile_carve(&s0, nullptr, true);
+  if ((rc = ensure_buf(c, bufs.vec, (MP + 1) * cap * 32))) return rc;
+  if ((rc = ensure_buf(c, bufs.scan, MP * scan_words * 4))) return rc;
+  uint32_t* d_S = static_cast<uint32_t*>(bufs.vec.p);
+  uint32_t* d_comb = d_S + cap * 8;
+  MultiCarve cv{};
+  for (uint32_t q = 0; q < MP; ++q) {
+    TileShape s = s0;
+    tile_carve(&s, static_cast<uint32_t*>(bufs.scan.p) + q * scan_words, true);
+    cv.G[q] = s.G, cv.H[q] = s.H, cv.A[q] = s.A, cv.zinv[q] = s.zinv, cv.W[q] = s.W;
+  }
+  std::vector<MultiPoint> proto;
+  for (uint32_t j : pj) proto.push_back(multi_point<F>(points + (size_t)j * 8, tb));
+  struct Launch { MultiPolys polys; size_t first; uint32_t np; };
+  std::vector<Launch> launches;
+  std::vector<MultiPoint> table;
+  for (size_t i0 = 0; i0 < pi.size(); i0 += TILE_MAXK) {
+    const uint32_t kc = (uint32_t)std::min<size_t>(TILE_MAXK, pi.size() - i0);
+    for (size_t j0 = 0; j0 < pj.size(); j0 += MP) {
+      Launch L{};
+      L.polys.polys = d_polys, L.polys.stride = stride, L.polys.k = kc;
+      for (uint32_t q = 0; q < kc; ++q) L.polys.row[q] = pi[i0 + q], L.polys.lens[q] = (uint32_t)lens[pi[i0 + q]];
+      L.first = table.size();
+      for (size_t jj = j0; jj < std::min<size_t>(j0 + MP, pj.size()); ++jj) {
+        MultiPoint m = proto[jj];
+        for (uint32_t q = 0; q < kc; ++q) {
+          const uint32_t* w = weight(pi[i0 + q], pj[jj]);
+          if (words_are_zero(w)) continue;
+          m.groups |= 1u << (q / DOT_G);
+          const Fe<F> wm = Fd::to_mont(Fd::from_words(w));
+          memcpy(&m.w[q * F::N], wm.l, F::N * 4);
+        }
+        if (m.groups) table.push_back(m), ++L.np;
+      }
+      if (L.np) launches.push_back(L);
+    }
+  }
+  if (launches.empty()) {
+    KZG_HIP(c, hipMemsetAsync(d_S, 0, n * 32, c->stream));
+  } else {
+    if ((rc = ensure_buf(c, c->poly_tmp[1], table.size() * sizeof(MultiPoint)))) return rc;
+    const MultiPoint* d_table = static_cast<const MultiPoint*>(c->poly_tmp[1].p);
+    KZG_HIP(c, hipMemcpyAsync(c->poly_tmp[1].p, table.data(), table.size() * sizeof(MultiPoint), hipMemcpyHostToDevice,
+                              c->stream));
+    ProfScope ps(c, "open_points_poly");
+    for (size_t l = 0; l < launches.size() && !rc; ++l) {
+      const Launch& L = launches[l];
+      rc = by_tile_width(tb, [&](auto w) {
+        constexpr uint32_t TB = decltype(w)::value;
+        hipLaunchKernelGGL((tile_combine_multi_kernel<F, TB, TILE_ITER, true>), dim3(s0.ntiles + ntab),
+                           dim3(TB * SC / TILE_ITER), 0, c->stream, L.polys, d_table + L.first, L.np, cv, d_comb,
+                           (uint64_t)cap, (uint32_t)n, s0.ntiles, 0u, 0u);
+        KZG_HIP(c, hipGetLastError());
+        for (uint32_t q = 0; q < L.np && s0.nsuper; ++q)
+          if (!table[L.first + q].zero)
+            hipLaunchKernelGGL(tile_group_kernel<F>, dim3(s0.nsuper), dim3(64), 0, c->stream, cv.H[q], cv.W[q], s0.ntiles,
+                               cv.A[q]);
+        for (uint32_t q = 0; q < L.np; ++q) {      // one after the other: each adds to what the one before left
+          const MultiPoint& m = table[L.first + q];
+          FrArg z;
+          memcpy(z.l, m.z, sizeof(z.l));
+          hipLaunchKernelGGL((tile_fill_add_kernel<F, TB>), dim3(s0.ntiles), dim3(TB), 0, c->stream,
+                             d_comb + q * cap * 8, (uint32_t)n, s0.ntiles, cv.G[q], cv.H[q],
+                             s0.nsuper ? cv.A[q] : (const uint32_t*)nullptr, s0.nsuper, z, m.zero, cv.zinv[q], cv.W[q],
+                             (l || q) ? 1u : 0u, d_S);
+        }
+        return KZG_HIP_RC(c, hipGetLastError());
+      });
+    }
+    if (rc) return rc;
+  }
+  KZG_HIP(c, hipStreamSynchronize(c->stream));    // `table` has left the host
+  *d_quot_out = d_S + 8;
+  *quot_len = n - 1;
+  return KZG_OK;
+}
+
 // =====================================================================================
 // Coset opening: division by Z = X^l - a, a = h^l (l = 2^log_l).  With S_t = c_t + a S_(t+l) (zero beyond the end)
 // the quotient is q_t = S_(t+l) and the remainder rho_j = S_j (j < l).  Read as rows of l coefficients (row s holds
@@ -874,6 +1279,12 @@ int open_shard_begin_device(Ctx* c, const uint32_t* d_polys, const size_t* lens,
 int open_shard_finish_device(Ctx* c, const uint32_t* z_words, const uint32_t* carry_words, int first_rank,
                              uint32_t** d_vec_out, size_t* vec_len, uint64_t* eval_out) {
   return KZG_BY_FR(c, open_shard_finish_t, c, z_words, carry_words, first_rank, d_vec_out, vec_len, eval_out);
+}
+
+int open_points_quotient_device(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
+                                const uint32_t* points, size_t t, const uint32_t* weights, uint32_t** d_quot_out,
+                                size_t* quot_len) {
+  return KZG_BY_FR(c, open_points_quotient_t, c, d_polys, lens, k, stride, points, t, weights, d_quot_out, quot_len);
 }
 
 int open_coset_check(Ctx* c, const size_t* lens, size_t k, size_t stride, uint32_t log_l, const uint32_t* h_words,
@@ -1210,7 +1621,84 @@ int poly_eval_t(Ctx* c, size_t n, const uint32_t* a, const uint32_t* z_words, ui
   return KZG_OK;
 }
 
+// p_i(z_j) for k polynomials at t points: pass 1 without its stores over MP points at a time (a polynomial is read
+// once per launch, blockIdx.y picks it), then one workgroup per (polynomial, point) sums that pair's tile aggregates.
+// Buffers of its own, as poly_eval_t: the tables, W per point and H per (point, polynomial) in poly_tmp[2], the
+// values in poly_tmp[3].  n = 0, n = 1 and z = 0 as in poly_eval_t: nothing, or the constant coefficient.
+template <class F>
+int poly_eval_batch_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
+                      const uint32_t* points, size_t t, uint64_t* out) {
+  constexpr uint32_t TB = 256;
+  if (k > MAXK || t > MAXK) return set_err(c, KZG_ERR_ARG, "kzg_fr_poly_eval_batch: more than 64 polynomials or points");
+  if (!k || !t) return KZG_OK;
+  memset(out, 0, k * t * 32);
+  size_t n = 0;
+  EvalBatchArgs ea{};
+  ea.polys = d_polys, ea.stride = stride;
+  for (size_t i = 0; i < k; ++i) {
+    if (lens[i] > stride) return set_err(c, KZG_ERR_ARG, "kzg_fr_poly_eval_batch: lens[i] > stride");
+    n = std::max(n, lens[i]);
+    ea.lens[i] = (uint32_t)lens[i];
+  }
+  if (n >= (1ull << 31) - 1) return set_err(c, KZG_ERR_ARG, "vector too long");
+  if (n == 0) return KZG_OK;
+  std::vector<MultiPoint> table;
+  for (size_t j = 0; j < t; ++j) {
+    const MultiPoint m = multi_point<F>(points + j * 8, TB);
+    ea.slot[j] = m.zero ? MAXK : (uint32_t)table.size();
+    if (!m.zero) table.push_back(m);
+  }
+  TileShape s0;
+  uint32_t ntab = 0;
+  tile_counts(c, n, TB, &s0, &ntab);
+  const size_t nz = n > 1 ? table.size() : 0;        // points that need the scan
+  const uint32_t hstride = s0.ntiles + 1, wstride = s0.ntiles;
+  MultiPoint* d_table = nullptr;
+  uint32_t *d_H = nullptr, *d_W = nullptr;
+  int rc = carve(c, c->poly_tmp[2], [&](Carve& ws) {
+    d_table = ws.take<MultiPoint>((nz + 1) * sizeof(MultiPoint));
+    d_H = ws.take((nz * k * hstride + 1) * F::N * 4);
+    d_W = ws.take((nz * wstride + 1) * F::N * 4);
+  });
+  if (rc) return rc;
+  if ((rc = ensure_buf(c, c->poly_tmp[3], k * t * 32))) return rc;
+  uint32_t* d_val = static_cast<uint32_t*>(c->poly_tmp[3].p);
+  {
+    ProfScope ps(c, "poly_eval_batch");
+    if (nz) KZG_HIP(c, hipMemcpyAsync(d_table, table.data(), nz * sizeof(MultiPoint), hipMemcpyHostToDevice, c->stream));
+    for (size_t j0 = 0; j0 < nz; j0 += MP) {
+      const uint32_t np = (uint32_t)std::min<size_t>(MP, nz - j0);
+      MultiCarve cv{};
+      for (uint32_t q = 0; q < np; ++q) {
+        cv.H[q] = d_H + (j0 + q) * k * hstride * F::N;
+        cv.W[q] = d_W + (j0 + q) * wstride * F::N;
+      }
+      for (size_t i0 = 0; i0 < k; i0 += TILE_MAXK) {
+        MultiPolys mp{};
+        mp.polys = d_polys, mp.stride = stride, mp.k = (uint32_t)std::min<size_t>(TILE_MAXK, k - i0);
+        for (uint32_t q = 0; q < mp.k; ++q) mp.row[q] = (uint32_t)(i0 + q), mp.lens[q] = ea.lens[i0 + q];
+        // the W tables come from the first launch of a group of points
+        hipLaunchKernelGGL((tile_combine_multi_kernel<F, TB, TILE_ITER, false>), dim3(s0.ntiles + (i0 ? 0 : ntab), mp.k),
+                           dim3(TB * SC / TILE_ITER), 0, c->stream, mp, d_table + j0, np, cv, (uint32_t*)nullptr,
+                           (uint64_t)0, (uint32_t)n, s0.ntiles, (uint32_t)i0, hstride);
+        KZG_HIP(c, hipGetLastError());
+      }
+    }
+    hipLaunchKernelGGL((tile_eval_batch_kernel<F, TB>), dim3((uint32_t)k, (uint32_t)t), dim3(TB), 0, c->stream, ea,
+                       (uint32_t)k, d_H, hstride, d_W, wstride, (uint32_t)t, d_val);
+    KZG_HIP(c, hipGetLastError());
+  }
+  KZG_HIP(c, hipMemcpyAsync(out, d_val, k * t * 32, hipMemcpyDeviceToHost, c->stream));
+  KZG_HIP(c, hipStreamSynchronize(c->stream));
+  return KZG_OK;
+}
+
 }  // namespace
+
+int fr_poly_eval_batch(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k, size_t stride,
+                       const uint32_t* points, size_t t, uint64_t* out) {
+  return KZG_BY_FR(c, poly_eval_batch_t, c, d_polys, lens, k, stride, points, t, out);
+}
 
 int fr_vec_binary(Ctx* c, int op, size_t n, const uint32_t* a, const uint32_t* b, uint32_t* out) {
   return KZG_BY_FR(c, vec_binary_t, c, op, n, a, b, out);

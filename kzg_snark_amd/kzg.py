@@ -22,6 +22,7 @@ depends on py_ecc's operation order; equality there is `eq`, here plain `==` wor
 too.  There is no CPU fallback for commit/open/setup: they raise
 _native.NativeUnavailable without the shared library and a GPU."""
 import secrets
+from collections import namedtuple
 from collections.abc import Sequence
 from contextlib import contextmanager
 
@@ -46,6 +47,10 @@ def _lru_get(cache, key, capacity, fresh, make, close):
         close(cache.pop(next(iter(cache))))
     cache[key] = entry
     return entry
+
+
+# what open_multi returns: the two proof points, the challenge used and the values, evaluations[i] along point_sets[i]
+OpenMulti = namedtuple("OpenMulti", "W W2 zeta evaluations")
 
 
 @contextmanager
@@ -673,6 +678,136 @@ class KZG:
                     f"Polynomial degree exceeds maximum allowed degree {len(key) - 1}") from e   # via kzg.py:157 -> :103
             raise
         return self._points(xy, inf)[0]
+
+    # ---- Shplonk (Boneh-Drake-Fisch-Gabizon 2020, second scheme): any polynomials at any point sets, one proof of two
+    #      G1 points, two pairings.  With T the union of the sets S_i and Z_S = prod_(z in S) (X - z):
+    #        W  = commit( q ),  q = sum_i gamma^(i+1) (f_i - r_i) / Z_(S_i)        r_i: the interpolant of f_i on S_i
+    #        W' = commit( L / (X - zeta) ),  L = sum_i gamma^(i+1) Z_(T\S_i)(zeta) (f_i - r_i(zeta)) - Z_T(zeta) q
+    #      and the verifier checks e(F + zeta W', G2) = e(W', tau G2) for the commitment F of L.
+    _MULTI_MAX = 63                # polynomials (the second proof point takes q as one more) and points per opening
+
+    def evaluate_each(self, polynomials, points):
+        """values[i][j] = polynomials[i](points[j]) on the device: one kzg_fr_poly_eval_batch, one synchronisation.
+        At most 64 polynomials and 64 points."""
+        coeffs = [self._coeffs(p) for p in polynomials]
+        pts = [self._canon(z) for z in points]
+        if len(coeffs) > 64 or len(pts) > 64:
+            raise ValueError("evaluate_each: at most 64 polynomials and 64 points")
+        if not coeffs or not pts:
+            return [[] for _ in coeffs]
+        ctx = self._context()
+        arr, lens, stride = self._pack(coeffs)
+        d = self._upload(ctx, arr)
+        return ctx.poly_eval_batch(d.data_ptr(), lens, stride, pts)
+
+    def _point_sets(self, point_sets, k, who):
+        """-> (the sets as canonical ints, their de-duplicated union T in order of first appearance)"""
+        sets = [[self._canon(z) for z in S] for S in point_sets]
+        if len(sets) != k:
+            raise ValueError(f"{who}: {len(sets)} point sets for {k} polynomials")
+        for i, S in enumerate(sets):
+            if not S:
+                raise ValueError(f"{who}: point set {i} is empty")
+            if len(set(S)) != len(S):
+                raise ValueError(f"{who}: point set {i} repeats a point")
+        T = list(dict.fromkeys(z for S in sets for z in S))
+        if k > self._MULTI_MAX or len(T) > self._MULTI_MAX:
+            raise ValueError(f"{who}: at most {self._MULTI_MAX} polynomials and {self._MULTI_MAX} distinct points")
+        return sets, T
+
+    def _vanishing_at(self, points, x):
+        """prod_(z in points) (x - z)"""
+        acc = 1
+        for z in points:
+            acc = acc * (x - z) % self.curve_order
+        return acc
+
+    def open_multi(self, ck, polynomials, point_sets, gamma, zeta):
+        """One proof that polynomials[i] takes its values at every point of point_sets[i] (non-empty, no point twice).
+        zeta: a callable W -> challenge (Fiat-Shamir: zeta must depend on W), or a fixed value (tests).  Returns
+        OpenMulti(W, W2, zeta, evaluations) with evaluations[i][j] = polynomials[i](point_sets[i][j]).  The weights are
+        gamma^(i+1), as open's xi^(i+1): when every set is [z], W equals open(ck, polynomials, z, gamma)."""
+        r = self.curve_order
+        key = self._key(ck)
+        coeffs = [self._coeffs(p) for p in polynomials]
+        k = len(coeffs)
+        sets, T = self._point_sets(point_sets, k, "open_multi")
+        gamma = self._canon(gamma)
+        if k == 0:
+            return OpenMulti(self.Z1, self.Z1, self._canon(zeta(self.Z1) if callable(zeta) else zeta), [])
+        ctx = self._context()
+        arr, lens, stride = self._pack(coeffs)
+        rows = np.zeros((k + 1, stride, 4), dtype=np.uint64)         # row k: the quotient q, left there by the first call
+        rows[:k] = arr
+        d = self._upload(ctx, rows)
+        d_q = d.data_ptr() + k * stride * 32
+        values = ctx.poly_eval_batch(d.data_ptr(), lens, stride, T)
+        col = {z: j for j, z in enumerate(T)}
+        evaluations = [[values[i][col[z]] for z in S] for i, S in enumerate(sets)]
+        # W: sum over z in T of Q_z[ sum_i w_iz f_i ],  w_iz = gamma^(i+1) / prod_(m in S_i, m != z) (z - m)
+        weights, g, gpow = [[0] * len(T) for _ in range(k)], 1, []
+        for i, S in enumerate(sets):
+            g = g * gamma % r
+            gpow.append(g)
+            for z in S:
+                weights[i][col[z]] = g * pow(self._vanishing_at([m for m in S if m != z], z), -1, r) % r
+        try:
+            xy, inf = ctx.open_points(key.srs, d.data_ptr(), lens, stride, T, weights, d_quot=d_q, device=True)
+            W = self._points(xy, inf)[0]
+            zeta = self._canon(zeta(W) if callable(zeta) else zeta)
+            # W': one single-point quotient at zeta over the k polynomials and q; it does not depend on the constant
+            # term of L, so the r_i(zeta) are the verifier's alone
+            w2 = [[gpow[i] * self._vanishing_at([z for z in T if z not in S], zeta) % r] for i, S in enumerate(sets)]
+            w2.append([-self._vanishing_at(T, zeta) % r])
+            xy, inf = ctx.open_points(key.srs, d.data_ptr(), list(lens) + [max(max(lens) - 1, 0)], stride, [zeta], w2,
+                                      device=True)
+        except _native.NativeError as e:
+            if e.code == _native.KZG_ERR_DEGREE:
+                raise ValueError(f"Polynomial degree exceeds maximum allowed degree {len(key) - 1}") from e
+            raise
+        return OpenMulti(W, self._points(xy, inf)[0], zeta, evaluations)
+
+    def _multi_claim(self, commitments, sets, T, evaluations, W, gamma, zeta):
+        """F = sum_i gamma^(i+1) Z_(T\\S_i)(zeta) (C_i - r_i(zeta) G1) - Z_T(zeta) W, r_i the interpolant of the claimed
+        values on S_i (Lagrange's formula)"""
+        r = self.curve_order
+        parts, const, g = [], 0, 1
+        for C, S, vals in zip(commitments, sets, evaluations):
+            g = g * gamma % r
+            r_i = 0
+            for z, v in zip(S, vals):
+                others = [m for m in S if m != z]
+                r_i += int(v) * self._vanishing_at(others, zeta) * pow(self._vanishing_at(others, z), -1, r)
+            scale = g * self._vanishing_at([z for z in T if z not in S], zeta) % r
+            parts.append(self.multiply(C, scale))
+            const = (const + scale * r_i) % r
+        parts.append(self.multiply(self.G1, -const % r))
+        parts.append(self.multiply(W, -self._vanishing_at(T, zeta) % r))
+        return self._sum_g1(parts)
+
+    def check_multi(self, rk, commitments, point_sets, evaluations, proof, gamma, zeta, pairing="device"):
+        """Does `proof` -- open_multi's result, or the pair (W, W') -- show that the polynomial of commitments[i] takes
+        evaluations[i][j] at point_sets[i][j]?  e(F + zeta W', G2) == e(W', rk), rk = tau G2: two pairings whatever the
+        number of polynomials and points.  zeta: the challenge the prover used (re-derived from W by a Fiat-Shamir
+        caller).  A point off the curve: False.  pairing: as in verify_points."""
+        if pairing not in ("device", "host"):
+            raise ValueError(f"check_multi: pairing must be \"device\" or \"host\", not {pairing!r}")
+        commitments = list(commitments)
+        sets, T = self._point_sets(point_sets, len(commitments), "check_multi")
+        evaluations = [[self._canon(v) for v in vals] for vals in evaluations]
+        if len(evaluations) != len(sets) or any(len(v) != len(S) for v, S in zip(evaluations, sets)):
+            raise ValueError("check_multi: evaluations must follow point_sets")
+        W, W2 = (proof.W, proof.W2) if hasattr(proof, "W2") else proof
+        points = []
+        for pt in [*commitments, W, W2]:
+            pt = self._g1.normalize(tuple(int(c) for c in pt))
+            if not (0 <= pt[0] < self._cv.p and 0 <= pt[1] < self._cv.p and _curve.on_curve_g1(pt, self._cv)):
+                return False
+            points.append(pt)
+        *commitments, W, W2 = points
+        gamma, zeta = self._canon(gamma), self._canon(zeta)
+        F = self._multi_claim(commitments, sets, T, evaluations, W, gamma, zeta)
+        return self._verdict(self.add(F, self.multiply(W2, zeta)), W2, rk, pairing, "check_multi")
 
     # ---- verification (host; SURVEY.md 8f N3).  Both checks rest on one folded claim per opening:
     #      F = sum_i xi^(i+1) (C_i - v_i G1) commits to sum_i xi^(i+1) (p_i - v_i), which (X - z) divides iff the v_i are
