@@ -82,6 +82,8 @@ int kzg_ctx_synchronize(kzg_ctx* ctx);
  *   "open_direct_tiles"  tile count up to which every tile sums all tile aggregates above it (default 1024)
  *   "open_domain_chunk"  vectors per chunk of kzg_open_domain*, 1..1024 (default: as many as ~2 GiB of scratch holds)
  *   "open_cosets_chunk"  vectors per chunk of kzg_open_cosets*, 1..1024 (default: as many as ~2 GiB of scratch holds)
+ *   "open_cosets_group"  1 + log2 of the sub-tables that share one doubling chain in kzg_open_cosets*, 1..5, clipped to
+ *                        the table's log_l (default: min(l, 16) sub-tables, fewer while < 2^16 threads would run)
  *   "recover_chunk"      vectors per chunk of kzg_recover_cosets*, 1..1024 (default: as many as ~2 GiB of scratch holds)
  *   "eval_batch_chunk"   vectors per chunk of kzg_fr_eval_lagrange_batch*, 1..65535, the most one launch indexes
  *                        (default: as many as ~1 GiB of scratch holds, at most 65535) */

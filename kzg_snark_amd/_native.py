@@ -312,7 +312,8 @@ class Context:
 
     def set_tuning(self, key, value):
         """Fix a choice the library otherwise makes from what is resident ("ntt_tile_log", "open_tile_threads",
-        "open_direct_tiles", the "*_chunk" keys; 0 = the library's choice).  Results never depend on it."""
+        "open_direct_tiles", "open_cosets_group", the "*_chunk" keys; 0 = the library's choice).  Results never depend
+        on it."""
         self._check(lib().kzg_ctx_set_tuning(self._h, key.encode(), int(value)))
 
     # ---- measurement hooks

@@ -222,6 +222,9 @@ int kzg_ctx_set_tuning(kzg_ctx* ctx, const char* key, int64_t value) {
   } else if (k == "open_cosets_chunk") {
     if (value < 0 || value > 1024) return set_err(c, KZG_ERR_ARG, "open_cosets_chunk: 0 .. 1024");
     c->tune_open_cosets_chunk = (int)value;
+  } else if (k == "open_cosets_group") {
+    if (value < 0 || value > 5) return set_err(c, KZG_ERR_ARG, "open_cosets_group: 0 .. 5");
+    c->tune_open_cosets_group = (int)value;
   } else if (k == "recover_chunk") {
     if (value < 0 || value > 1024) return set_err(c, KZG_ERR_ARG, "recover_chunk: 0 .. 1024");
     c->tune_recover_chunk = (int)value;

@@ -476,8 +476,12 @@ int open_cosets_t(Ctx* c, const DomainTable* t, const uint32_t* polys, bool host
   const uint32_t log_L = log_N - log_l;                      // N/l proofs per vector
   const size_t L = (size_t)1 << log_L, NN = (size_t)1 << log_N;
   // Straus group: G = min(l, 16) terms share a doubling chain, fewer while that would leave < 2^16 threads busy
+  // (kzg_ctx_set_tuning "open_cosets_group" fixes log_g = value - 1 instead, clipped to log_l)
   uint32_t log_g = std::min<uint32_t>(log_l, 4);
-  while (log_g && ((std::min<size_t>(b, 64) * 2 * n) >> log_g) < ((size_t)1 << 16)) --log_g;
+  if (c->tune_open_cosets_group > 0)
+    log_g = std::min<uint32_t>(log_l, (uint32_t)c->tune_open_cosets_group - 1);
+  else
+    while (log_g && ((std::min<size_t>(b, 64) * 2 * n) >> log_g) < ((size_t)1 << 16)) --log_g;
   const uint32_t log_ng = log_l - log_g;
   const size_t xb = xyzz_bytes<C>(), pt_words = 2 * Fp::NW;
   const size_t part_pts = log_ng ? (size_t)mm << log_ng : 0;

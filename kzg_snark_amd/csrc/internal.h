@@ -109,6 +109,7 @@ struct Ctx {
   int tune_open_direct_max = 0;           // tiles up to which every tile sums all aggregates above it
   int tune_open_domain_chunk = 0;         // vectors per chunk of kzg_open_domain
   int tune_open_cosets_chunk = 0;         // vectors per chunk of kzg_open_cosets
+  int tune_open_cosets_group = 0;         // 1 + log2 of kzg_open_cosets' Straus group (1..5)
   int tune_recover_chunk = 0;             // vectors per chunk of kzg_recover_cosets
   int tune_eval_batch_chunk = 0;          // vectors per chunk of kzg_fr_eval_lagrange_batch
   int last_ntt_tile_log = 0;              // what the last transform used (kzg_prof_read "ntt_tile_log")

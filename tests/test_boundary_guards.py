@@ -152,10 +152,12 @@ def test_tuning_keys_and_values_are_checked():
     from kzg_snark_amd import _native
     ctx = _native.get_context("bls12_381")
     for key, bad in (("ntt_tile_log", 7), ("ntt_tile_log", 13), ("open_tile_threads", 64), ("open_tile_threads", 512),
-                     ("open_direct_tiles", -1), ("no_such_key", 1)):
-        with pytest.raises(_native.NativeError):
+                     ("open_direct_tiles", -1), ("open_cosets_group", -1), ("open_cosets_group", 6), ("no_such_key", 1)):
+        with pytest.raises(_native.NativeError) as e:
             ctx.set_tuning(key, bad)
-    for key, ok in (("ntt_tile_log", 10), ("open_tile_threads", 128), ("open_direct_tiles", 5)):
+        assert e.value.code == -1, (key, bad)                             # KZG_ERR_ARG
+    for key, ok in (("ntt_tile_log", 10), ("open_tile_threads", 128), ("open_direct_tiles", 5),
+                    ("open_cosets_group", 1), ("open_cosets_group", 5)):
         ctx.set_tuning(key, ok)
         ctx.set_tuning(key, 0)
 
