@@ -511,6 +511,40 @@ int kzg_g2_decompress_device(kzg_ctx* ctx, const void* d_bytes, size_t n, int ch
                              void* d_status);
 int kzg_g2_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status);
 
+/* ---- per-point scalar multiplication in G1 and G2 -------------------------------------------------
+ * out[i] = [k_i] P_i for n points, the products kept apart (kzg_commit* is their sum): what a participant of a
+ * powers-of-tau ceremony does to every section of a setup, cofactor clearing, the G2 powers of a setup.
+ * Points: canonical affine limbs and infinity flags (inf may be NULL: no point is infinity) -- G1 x | y (2*FP_LIMBS
+ * limbs), G2 x.c0 | x.c1 | y.c0 | y.c1 (4*FP_LIMBS limbs, kzg_pairing_check's layout).  Any point of the curve or of
+ * the twist is accepted, inside the prime-order subgroup or not.
+ * Scalars: `scalars` is n * 4 limbs, scalar i the 256-bit integer at limbs 4i .. 4i + 3 AS IT STANDS: it is not
+ * reduced modulo r ([r] Q is not infinity for Q outside the subgroup).  The _powers forms multiply point i by
+ * c0 * s^i mod r instead, formed on the device; s and c0 must be below r.
+ * The results are exact for every point and every scalar: the ladder's additions finish P + P, P + (-P) and infinite
+ * operands, which points of small order and scalars near multiples of r reach.
+ *   kzg_g1_mul_each / kzg_g2_mul_each      host pointers in and out, synchronised.
+ *   kzg_g1_mul_powers / kzg_g2_mul_powers  the same with the scalars c0 * s^i.
+ *   kzg_g1_mul_each_device  device pointers (16-byte aligned; d_inf may be NULL), enqueued on the context's stream
+ *                          without synchronising (the call waits for the stream only when its table has to grow).
+ *                          It cannot fail for a bad point: such a point's output is zeros with the flag 2.
+ *   kzg_srs_mul_powers     key handle -> new key handle: point i of `srs` times c0 * s^i, never through the host.
+ *                          `srs` may be a monomial or a Lagrange key; *out is a plain (monomial-tagged) key of the same
+ *                          length, the caller's to free.  Synchronises.
+ * A coordinate >= p, a point off its curve, or s or c0 >= r is KZG_ERR_ARG with the first offending index (or the
+ * argument's name) in kzg_last_error, and nothing is written.  n = 0 is KZG_OK with no work; more than 2^21 points per
+ * call is KZG_ERR_ARG.  Profiling spans: "g1_mul_each", "g2_mul_each" (ONE per call). */
+int kzg_g1_mul_each(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t* scalars,
+                    uint64_t* out_xy, uint8_t* out_inf);
+int kzg_g1_mul_each_device(kzg_ctx* ctx, const void* d_xy, const void* d_inf, size_t n, const void* d_scalars,
+                           void* d_out_xy, void* d_out_inf);
+int kzg_g1_mul_powers(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t s[4],
+                      const uint64_t c0[4], uint64_t* out_xy, uint8_t* out_inf);
+int kzg_srs_mul_powers(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t s[4], const uint64_t c0[4], kzg_srs** out);
+int kzg_g2_mul_each(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t* scalars,
+                    uint64_t* out_xy, uint8_t* out_inf);
+int kzg_g2_mul_powers(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t s[4],
+                      const uint64_t c0[4], uint64_t* out_xy, uint8_t* out_inf);
+
 /* ---- EIP-4844 blobs as bytes: device intake and SHA-256 challenges ---------------------------------
  * A blob is n = 2^log_n field elements of 32 big-endian bytes each; b blobs lie one after the other ([b][n][32]).
  *   kzg_blob_to_fr          every element checked < r and written as four canonical little-endian limbs:

@@ -124,6 +124,12 @@ SIGNATURES = {
     "kzg_g2_decompress": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp]),
     "kzg_g2_decompress_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp]),
     "kzg_g2_check_subgroup": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "kzg_g1_mul_each": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "kzg_g1_mul_each_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "kzg_g1_mul_powers": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
+    "kzg_srs_mul_powers": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
+    "kzg_g2_mul_each": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "kzg_g2_mul_powers": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
     "kzg_srs_load_g1_compressed": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_vp)]),
     "kzg_srs_export_compressed": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "kzg_recover_cosets_device": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
@@ -464,6 +470,55 @@ class Context:
         status = np.zeros(n, dtype=np.uint8)
         self._check(lib().kzg_g2_check_subgroup(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(status)))
         return status
+
+    # ---- per-point scalar multiplication: out[i] = [k_i] P_i, the products kept apart
+    G1_MUL_LANES = 256          # lanes per workgroup of g1_mul_each_kernel / g2_mul_each_kernel (csrc/g_mul.hip)
+    G2_MUL_LANES = 64
+
+    def _mul_each(self, group, xy, inf, scalars, s, c0):
+        """group 1 | 2; scalars uint64[n, 4] (each the 256-bit integer as it stands), or None for the power form
+        c0 * s^i mod r -> (xy, inf) of the products"""
+        width = 2 * group * self.fp_limbs
+        name = "g%d_mul_%s" % (group, "powers" if scalars is None else "each")
+        xy = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, width)
+        n = xy.shape[0]
+        inf = _inf_arg(inf, n, f"{name}: inf and xy")
+        out_xy, out_inf = np.zeros((n, width), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+        if scalars is None:
+            self._check(getattr(lib(), "kzg_" + name)(self._h, _as_vp(xy), _as_vp(inf), n, _fr(s), _fr(c0),
+                                                      _as_vp(out_xy), _as_vp(out_inf)))
+        else:
+            scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+            if scalars.shape[0] != n:
+                raise ValueError(f"{name}: {scalars.shape[0]} scalars for {n} points")
+            self._check(getattr(lib(), "kzg_" + name)(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(scalars),
+                                                      _as_vp(out_xy), _as_vp(out_inf)))
+        return out_xy, out_inf
+
+    def g1_mul_each(self, xy, inf, scalars):
+        """affine points (uint64[n, 2*fp_limbs], uint8[n] flags or None) and scalars uint64[n, 4] -> (xy, inf)"""
+        return self._mul_each(1, xy, inf, scalars, None, None)
+
+    def g1_mul_powers(self, xy, inf, s, c0=1):
+        """point i times c0 * s^i mod r (s, c0 ints below r), the scalars formed on the device"""
+        return self._mul_each(1, xy, inf, None, s, c0)
+
+    def g2_mul_each(self, xy, inf, scalars):
+        """the same for points of the twist, uint64[n, 4*fp_limbs] (x.c0 | x.c1 | y.c0 | y.c1)"""
+        return self._mul_each(2, xy, inf, scalars, None, None)
+
+    def g2_mul_powers(self, xy, inf, s, c0=1):
+        return self._mul_each(2, xy, inf, None, s, c0)
+
+    def g1_mul_each_device(self, d_xy, d_inf, n, d_scalars, d_out_xy, d_out_inf):
+        """The same on device pointers (d_inf may be None), enqueued on the context's stream (no synchronisation); a
+        point that is refused leaves zeros and the flag 2."""
+        self._check(lib().kzg_g1_mul_each_device(self._h, _as_vp(d_xy), _as_vp(d_inf), int(n), _as_vp(d_scalars),
+                                                 _as_vp(d_out_xy), _as_vp(d_out_inf)))
+
+    def srs_mul_powers(self, srs, s, c0=1):
+        """key handle -> new key handle: point i of `srs` (monomial or Lagrange) times c0 * s^i mod r; a plain key"""
+        return Srs(self, self._handle(lib().kzg_srs_mul_powers, srs._h, _fr(s), _fr(c0)), srs.n)
 
     # ---- pairing-product checks
     def _pairing_args(self, g1_xy, g1_inf, g2_xy, g2_inf, k, who):

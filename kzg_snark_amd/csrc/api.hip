@@ -161,7 +161,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
   ntt_free_domains(c);
   msm_free_work(c);
   for (DevBuf* b : {&c->ntt_scratch, &c->io, &c->scan_tmp, &c->lagr_tmp, &c->dom_tmp, &c->ver_tmp, &c->rec_tmp,
-                    &c->vpt_tmp, &c->pair_tmp,
+                    &c->vpt_tmp, &c->pair_tmp, &c->gmul_tmp,
                     &c->poly_tmp[0], &c->poly_tmp[1], &c->poly_tmp[2], &c->poly_tmp[3]})
     hipFree(b->p);
   hipFree(c->clk_probe);
@@ -415,6 +415,47 @@ int kzg_g2_decompress_device(kzg_ctx* ctx, const void* d_bytes, size_t n, int ch
 int kzg_g2_check_subgroup(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status) {
   KZG_ENTER(n && (!xy || !out_status));
   return g2_check_subgroup(c, xy, inf, n, out_status);
+}
+
+int kzg_g1_mul_each(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t* scalars,
+                    uint64_t* out_xy, uint8_t* out_inf) {
+  KZG_ENTER(n && (!xy || !scalars || !out_xy || !out_inf));
+  return g1_mul_each(c, xy, inf, n, reinterpret_cast<const uint32_t*>(scalars), nullptr, nullptr, out_xy, out_inf);
+}
+
+int kzg_g1_mul_each_device(kzg_ctx* ctx, const void* d_xy, const void* d_inf, size_t n, const void* d_scalars,
+                           void* d_out_xy, void* d_out_inf) {
+  KZG_ENTER(n && (!d_xy || !d_scalars || !d_out_xy || !d_out_inf));
+  return g1_mul_each_device(c, d_xy, d_inf, n, d_scalars, d_out_xy, d_out_inf);
+}
+
+int kzg_g1_mul_powers(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t s[4],
+                      const uint64_t c0[4], uint64_t* out_xy, uint8_t* out_inf) {
+  KZG_ENTER(!s || !c0 || (n && (!xy || !out_xy || !out_inf)));
+  return g1_mul_each(c, xy, inf, n, nullptr, reinterpret_cast<const uint32_t*>(s), reinterpret_cast<const uint32_t*>(c0),
+                     out_xy, out_inf);
+}
+
+int kzg_srs_mul_powers(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t s[4], const uint64_t c0[4], kzg_srs** out) {
+  KZG_ENTER(!srs || !s || !c0 || !out);
+  *out = nullptr;
+  if (srs->s->curve != c->curve) return set_err(c, KZG_ERR_ARG, "SRS belongs to another curve");
+  Srs* key = nullptr;
+  const int rc = srs_mul_powers(c, srs->s, reinterpret_cast<const uint32_t*>(s), reinterpret_cast<const uint32_t*>(c0), &key);
+  return adopt_srs(rc, key, out);
+}
+
+int kzg_g2_mul_each(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t* scalars,
+                    uint64_t* out_xy, uint8_t* out_inf) {
+  KZG_ENTER(n && (!xy || !scalars || !out_xy || !out_inf));
+  return g2_mul_each(c, xy, inf, n, reinterpret_cast<const uint32_t*>(scalars), nullptr, nullptr, out_xy, out_inf);
+}
+
+int kzg_g2_mul_powers(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t s[4],
+                      const uint64_t c0[4], uint64_t* out_xy, uint8_t* out_inf) {
+  KZG_ENTER(!s || !c0 || (n && (!xy || !out_xy || !out_inf)));
+  return g2_mul_each(c, xy, inf, n, nullptr, reinterpret_cast<const uint32_t*>(s), reinterpret_cast<const uint32_t*>(c0),
+                     out_xy, out_inf);
 }
 
 int kzg_pairing_check(kzg_ctx* ctx, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,

@@ -1,6 +1,6 @@
 // internal.h -- library-private declarations shared by the translation units of
 // libkzg_mi355x.so (api.hip, ntt.hip, msm.hip, msm_prep.hip, poly.hip, lagrange.hip, domain.hip, verify.hip,
-// recover.hip, g1_bytes.hip, verify_points.hip, blob.hip, pairing.hip): the context, error and profiling plumbing, the dispatch by curve (KZG_BY_CURVE,
+// recover.hip, g1_bytes.hip, verify_points.hip, blob.hip, pairing.hip, g2_bytes.hip, g_mul.hip): the context, error and profiling plumbing, the dispatch by curve (KZG_BY_CURVE,
 // KZG_BY_FR) and the entry points of ntt.hip and poly.hip.  Shared device helpers live in fr_util.h (one Fr element,
 // the power-table lookup), g1_util.h (word arrays, XYZZ points), g1_words.h (point <-> canonical words) and
 // srs_rec.h (key records); devmem.h owns device temporaries and carves the scratch buffers.
@@ -94,7 +94,8 @@ struct Ctx {
   DevBuf rec_tmp;         // recover.hip: power tables, the product tree, Z and its inverses, one chunk of vectors
   DevBuf vpt_tmp;         // verify_points.hip: staged claims, weights, power table, partial sums and partial points
   DevBuf pair_tmp;        // pairing.hip: staged points, flags, values and statuses of one kzg_pairing_* call
-  size_t ver_last_bytes = 0;              // what the last kzg_verify_cosets carved out of ver_tmp (kzg_prof_read)
+  DevBuf gmul_tmp;        // g_mul.hip: the lanes' tables of multiples, the power table, the staged arrays of one call
+  size_t ver_last_bytes = 0;             // what the last kzg_verify_cosets carved out of ver_tmp (kzg_prof_read)
   size_t vpt_last_bytes = 0;              // what the last kzg_verify_points carved out of vpt_tmp (kzg_prof_read)
   uint32_t ver_lds_attr_set = 0;          // per ver_cell_kernel instantiation, as ntt_lds_attr_set
   // kzg_fr_eval_lagrange_batch*: the vector lengths travel from this pinned array; the event marks the last copy out

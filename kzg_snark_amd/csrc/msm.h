@@ -171,6 +171,15 @@ int g2_decompress(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, ui
 int g2_decompress_device(Ctx* c, const void* d_bytes, size_t n, int check_subgroup, void* d_xy, void* d_inf,
                          void* d_status);
 int g2_check_subgroup(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* out_status);
+// g_mul.hip: per-point scalar multiplication; the contracts are those of the kzg_* entry points.
+// k: n x 8 words, or null for the power form c0 s^i (s, c0: 8 canonical words below r).  n = 0 does nothing.
+int g1_mul_each(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, const uint32_t* k, const uint32_t* s,
+                const uint32_t* c0, uint64_t* out_xy, uint8_t* out_inf);
+int g2_mul_each(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, const uint32_t* k, const uint32_t* s,
+                const uint32_t* c0, uint64_t* out_xy, uint8_t* out_inf);
+int g1_mul_each_device(Ctx* c, const void* d_xy, const void* d_inf, size_t n, const void* d_k, void* d_out_xy,
+                       void* d_out_inf);
+int srs_mul_powers(Ctx* c, const Srs* in, const uint32_t* s, const uint32_t* c0, Srs** out);
 int srs_load_g1_compressed(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, Srs** out);
 int srs_export_compressed(Ctx* c, const Srs* s, size_t start, size_t count, uint8_t* out_bytes);
 

@@ -15,6 +15,8 @@ commit and open -- executed by the gfx950 engine through the C ABI.
     compress_g1 / decompress_g1 / in_subgroup: 48- / 32-byte points and subgroup membership, on the device
     blob_to_kzg_commitment / compute_blob_kzg_proof / verify_blob_kzg_proof_batch: EIP-4844's calls, bytes in and out
     (blob_to_values / blob_challenges: the device intake of blob bytes and the SHA-256 challenges on their own)
+    multiply_each / multiply_each_g2 / scale_key: [k_i] P_i per point on the device, the products kept apart
+    unit_setup / contribute / verify_contribution / verify_contributions: a powers-of-tau ceremony on top of them
 
 Points are py_ecc-shaped 3-tuples, always normalised: (x, y, 1), infinity (1, 1, 0).
 The reference returns un-normalised projective triples whose representative
@@ -51,6 +53,8 @@ def _lru_get(cache, key, capacity, fresh, make, close):
 
 # what open_multi returns: the two proof points, the challenge used and the values, evaluations[i] along point_sets[i]
 OpenMulti = namedtuple("OpenMulti", "W W2 zeta evaluations")
+# what a participant publishes beside the new setup (KZG.contribute): [s] G2 and the new [tau] G1
+Contribution = namedtuple("Contribution", "pubkey tau_g1")
 
 
 @contextmanager
@@ -488,10 +492,14 @@ class KZG:
         return self._context().g2_check_subgroup(xy, inf) == 0
 
     # ---- trusted-setup files and keys checked on the device (DESIGN.md 4.14) --------------------------------------------
-    def setup_g2(self, count, tau):
+    def setup_g2(self, count, tau, device=False):
         """[tau^j] G2, j < count, on the host with curve.py: pure Python, one scalar multiplication per point -- for
-        tests and small ceremonies, NOT a data-parallel path (a real setup publishes its G2 powers; nobody knows tau)."""
+        tests and small ceremonies, NOT a data-parallel path (a real setup publishes its G2 powers; nobody knows tau).
+        device=True computes the same list on the device: kzg_g2_mul_powers on `count` copies of the generator."""
         tau = self._tau(tau)
+        if device:
+            xy, inf = self._g2_arrays([self.G2] * int(count), "setup_g2")
+            return _native.limbs_to_g2_points(*self._context().g2_mul_powers(xy, inf, tau, 1))
         out, t = [], 1
         for _ in range(int(count)):
             out.append(self.multiply(self.G2, t) if t else self.Z2)
@@ -503,6 +511,142 @@ class KZG:
         log_n, w = self._domain(n, None)
         ctx = self._context()
         return LagrangeKey(ctx, ctx.srs_lagrange(key.srs, log_n, w), n, w)
+
+    # ---- per-point scalar multiplication and setup contributions (kzg_g1_mul_* / kzg_g2_mul_*) ---------
+    @staticmethod
+    def _scalar_rows(scalars, n, who):
+        """n scalars, ints in [0, 2^256) taken as they stand (NOT reduced modulo r), as uint64[n, 4]"""
+        if isinstance(scalars, np.ndarray) and scalars.dtype == np.uint64:
+            rows = np.ascontiguousarray(scalars).reshape(-1, 4)
+        else:
+            ks = [int(k) for k in scalars]
+            for i, k in enumerate(ks):
+                if not 0 <= k < 1 << 256:
+                    raise ValueError(f"{who}: scalar {i} is not in [0, 2^256)")
+            rows = _native.ints_to_limbs(ks) if ks else np.zeros((0, 4), dtype=np.uint64)
+        if rows.shape[0] != n:
+            raise ValueError(f"{who}: {rows.shape[0]} scalars for {n} points")
+        return rows
+
+    def _multiply_each(self, group, points, scalars, who):
+        as_arrays = isinstance(points, tuple) and len(points) == 2 and isinstance(points[0], np.ndarray)
+        xy, inf = (self._g1_arrays if group == 1 else self._g2_arrays)(points, who)
+        rows = self._scalar_rows(scalars, xy.shape[0], who)
+        ctx = self._context()
+        with _bad_input_is_value_error():
+            out = (ctx.g1_mul_each if group == 1 else ctx.g2_mul_each)(xy, inf, rows)
+        if as_arrays:
+            return out
+        return self._points(*out) if group == 1 else _native.limbs_to_g2_points(*out)
+
+    def multiply_each(self, points, scalars):
+        """[k_i] P_i for every i, on the device, the products kept apart.  points: a list of G1 point tuples, or
+        (xy, inf) arrays in the C layout; the result is of the same kind.  scalars: ints in [0, 2^256), each taken as it
+        stands -- NOT reduced modulo r, so a point outside the prime-order subgroup is multiplied by the integer given
+        (multiply() reduces).  A point off the curve or with a coordinate >= p raises ValueError naming its index."""
+        return self._multiply_each(1, points, scalars, "multiply_each")
+
+    def multiply_each_g2(self, points, scalars):
+        """multiply_each for points of the twist (G2 tuples, or (xy, inf) arrays in kzg_pairing_check's layout)."""
+        return self._multiply_each(2, points, scalars, "multiply_each_g2")
+
+    def _below_order(self, v, who, name, least=0):
+        v = int(v)
+        if not least <= v < self.curve_order:
+            raise ValueError(f"{who}: {name} must be in [{least}, r)")
+        return v
+
+    def scale_key(self, ck, s, c0=1):
+        """The CommitmentKey whose point i is [c0 * s^i mod r] ck[i], computed on the device from key handle to key
+        handle (kzg_srs_mul_powers): what a contribution s does to a monomial key.  ck may be a LagrangeKey (its
+        points are scaled all the same); the result is a plain key.  s, c0: ints in [0, r)."""
+        s, c0 = self._below_order(s, "scale_key", "s"), self._below_order(c0, "scale_key", "c0")
+        key = self._key(ck)
+        with _bad_input_is_value_error():
+            return CommitmentKey(key._ctx, key._ctx.srs_mul_powers(key.srs, s, c0))
+
+    def unit_setup(self, n, n_g2):
+        """The TrustedSetup of tau = 1, where a ceremony starts: n copies of the G1 generator (n a power of two, at
+        least 2), n_g2 >= 2 copies of the G2 generator, the Lagrange key of the monomial one."""
+        n, n_g2 = int(n), int(n_g2)
+        if n < 2 or n & (n - 1) or n_g2 < 2:
+            raise ValueError("unit_setup: n must be a power of two >= 2 and n_g2 >= 2")
+        ctx = self._context()
+        xy, inf = _native.points_to_limbs([self.G1] * n, ctx.fp_limbs)
+        mono = CommitmentKey(ctx, ctx.srs_load_g1(xy, inf))
+        try:
+            return TrustedSetup(mono, self._lagrange_of(mono), [self.G2] * n_g2)
+        except Exception:
+            mono.srs.close()
+            raise
+
+    def contribute(self, setup, secret=None):
+        """One participant's step of a powers-of-tau ceremony: (new TrustedSetup, Contribution) with every power of
+        the old tau multiplied by the same power of a secret s, 1 <= s < r -- drawn from `secrets` when not given, and
+        not kept.  Monomial key: scale_key(setup.monomial, s); G2 powers: multiply_each_g2 by s^j; Lagrange key:
+        kzg_srs_lagrange of the new monomial key.  Contribution.pubkey = [s] G2 and .tau_g1 = the new [tau] G1 are what
+        verify_contribution needs besides the two setups."""
+        order = self.curve_order
+        s = secrets.randbelow(order - 1) + 1 if secret is None else self._below_order(secret, "contribute", "secret", 1)
+        if len(setup.monomial) < 2 or len(setup.g2) < 2:
+            raise ValueError("contribute: the setup needs [tau] G1 and [tau] G2 (two points of each group)")
+        opened = []
+        try:
+            mono = self.scale_key(setup.monomial, s)
+            opened.append(mono.srs)
+            powers, t = [], 1
+            for _ in setup.g2:
+                powers.append(t)
+                t = t * s % order
+            g2 = self.multiply_each_g2(list(setup.g2) + [self.G2], powers + [s])
+            lag = self._lagrange_of(mono)
+            opened.append(lag.srs)
+            return TrustedSetup(mono, lag, g2[:-1]), Contribution(g2[-1], mono[1])
+        except Exception:
+            for h in opened:
+                h.close()
+            raise
+
+    def verify_contribution(self, before, after, contribution, r=None, pairing="device"):
+        """Did one contribution turn `before` into `after`?  True iff pubkey and tau_g1 are finite points of their
+        prime-order subgroups, tau_g1 is after.monomial[1], e(tau_g1, G2) = e(before.monomial[1], pubkey) (the new tau
+        is the old one times the secret behind pubkey), `after` has the section lengths of `before`, and
+        check_key(after.monomial, after.g2, after.lagrange, r) passes (the sections of `after` describe ONE tau)."""
+        if len(before.monomial) < 2:
+            raise ValueError("verify_contribution: the setup needs [tau] G1")
+        pub, tau_g1 = self._g2.normalize(contribution.pubkey), self._g1.normalize(contribution.tau_g1)
+        if self._g2.is_inf(pub) or self._g1.is_inf(tau_g1):
+            return False
+        if not (self.in_subgroup_g2([pub])[0] and self.in_subgroup([tau_g1])[0]):
+            return False
+        if (len(after.monomial), len(after.g2), after.lagrange.n) != (len(before.monomial), len(before.g2), before.lagrange.n):
+            return False
+        if not self.eq(tau_g1, after.monomial[1]):
+            return False
+        if not self._verdict(tau_g1, before.monomial[1], pub, pairing, "verify_contribution"):
+            return False
+        return self.check_key(after.monomial, after.g2, after.lagrange, r)
+
+    def verify_contributions(self, first_tau_g1, contributions, pairing="device"):
+        """A coordinator's replay of a transcript: link i holds iff e(c_i.tau_g1, G2) = e(c_(i-1).tau_g1, c_i.pubkey),
+        c_(-1).tau_g1 = first_tau_g1 ([tau] G1 of the setup the chain starts from).  Returns the list of verdicts; with
+        pairing="device" all links are ONE kzg_pairing_check call, one equation per link.  A link with an infinite
+        point is False (its equation would hold for any partner).  Membership in the subgroups is verify_contribution's
+        business, or the loader's."""
+        if pairing not in ("device", "host"):
+            raise ValueError(f"verify_contributions: pairing must be \"device\" or \"host\", not {pairing!r}")
+        links, prev = [], self._g1.normalize(first_tau_g1)
+        for c in contributions:
+            links.append((self._g1.normalize(c.tau_g1), prev, self._g2.normalize(c.pubkey)))
+            prev = links[-1][0]
+        if not links:
+            return []
+        finite = [not (self._g1.is_inf(t) or self._g1.is_inf(p) or self._g2.is_inf(q)) for t, p, q in links]
+        if pairing == "device":
+            holds = self.pairing_check([[(t, self.G2), (self.neg(p), q)] for t, p, q in links])
+        else:
+            holds = [self.pairing(self.G2, t) == self.pairing(q, p) for t, p, q in links]
+        return [bool(f and h) for f, h in zip(finite, holds)]
 
     def save_trusted_setup(self, path, ck, g2_points, lagrange_order="natural"):
         """Writes a trusted-setup text file (parse_trusted_setup's layout) from a monomial key of power-of-two length
