@@ -198,7 +198,14 @@ int kzg_commit_flush(kzg_ctx* ctx);
 /* ---- KZG.open (kzg.py:122-159) -----------------------------------------------------------
  * combined = sum_i xi^(i+1) * polys[i]  (first polynomial scaled by xi, kzg.py:148-150);
  * witness = (combined - combined(z)) // (X - z); the proof is commit(witness).
- * eval_out (optional, 4 limbs) receives combined(z). */
+ * eval_out (optional, 4 limbs) receives combined(z).
+ * The witness's DEGREE is checked against the key, as the reference does through the commit of the witness
+ * (kzg.py:157 -> :103-106), not the lengths: with n = max lens the witness has n - 1 coefficients, and those from
+ * index kzg_srs_size(srs) on may be there as long as every one of them is zero -- literal trailing zeros of the
+ * inputs, or a combination whose high coefficients cancel exactly; they are then left out of the commitment.  One
+ * non-zero coefficient among them is KZG_ERR_DEGREE.  Only when n - 1 > kzg_srs_size(srs) are they looked at, on
+ * the device, which waits for the stream.  After KZG_ERR_DEGREE out_xy and out_inf are as the caller left them,
+ * eval_out is unspecified, nothing of the call is pending, and the context serves the next call as after any other. */
 int kzg_open(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* polys, const size_t* lens, size_t k, size_t stride,
              const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf, uint64_t* eval_out);
 int kzg_open_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,
@@ -208,7 +215,12 @@ int kzg_open_device(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const
 /* Pipelined form of kzg_open_device: the combine / evaluate / divide kernels and the MSM of the witness are only
  * enqueued (the MSM shares the commit pipeline's slots with kzg_commit_device_async); out_xy, out_inf and eval_out
  * (required, 4 limbs) are written when kzg_commit_flush() returns or a later call recycles the slot.  The input
- * polynomials may be overwritten by later work on the context's stream as soon as the call has returned. */
+ * polynomials may be overwritten by later work on the context's stream as soon as the call has returned.
+ * The degree rule is kzg_open's.  Its check (n - 1 > kzg_srs_size(srs) only) is the one thing that synchronises this
+ * form: the call waits for the context's stream, not for the pipeline.  KZG_ERR_DEGREE is returned by the call
+ * itself, before the MSM takes a slot: out_xy and out_inf are as the caller left them and are not written later
+ * (no flush touches them), eval_out is unspecified, and openings and commits enqueued before and after the refused
+ * call deliver their results as if it had not been made. */
 int kzg_open_device_async(kzg_ctx* ctx, const kzg_srs* srs, const void* d_polys, const size_t* lens, size_t k,
                           size_t stride, const uint64_t z[4], const uint64_t xi[4], uint64_t* out_xy, uint8_t* out_inf,
                           uint64_t* eval_out);
@@ -406,7 +418,11 @@ int kzg_recover_cosets_device(kzg_ctx* ctx, uint32_t log_n, uint32_t log_N, uint
  * length 0, is one).  _finish continues from exactly what _begin left:
  *   - it must be given _begin's z; another z is KZG_ERR_ARG and the slice stays held;
  *   - tuning changed after _begin (kzg_ctx_set_tuning) has no effect on it;
- *   - it does not consume the slice: it may be repeated, with the same result for the same carry.
+ *   - it does not consume the slice: it may be repeated, with the same result for the same carry;
+ *   - the slice's LENGTH is checked against the key shard, not its degree (a rank cannot know what the others hold):
+ *     more coefficients to commit than kzg_srs_size(srs) -- the slice's length, less one on the first rank -- is
+ *     KZG_ERR_DEGREE even when the top ones are zero.  The slice stays held: the call may be repeated with a shard
+ *     that is long enough.
  * The slice is KEPT across commits (pipelined ones too), key generation, kzg_fr_poly_eval[_batch], the kzg_fr_vec_*
  * primitives and kzg_ctx_set_tuning.  It is DROPPED by kzg_open, kzg_open_device[_async], kzg_open_coset[_device],
  * kzg_open_points[_device] (they work in the same buffers; only an opening of nothing but empty polynomials leaves them alone) and by a
@@ -422,11 +438,14 @@ int kzg_open_shard_finish(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t z[4],
  *     Q = sum_j Q_(z_j)[ sum_i w_ij p_i ],   j < t points, i < k polynomials (k, t <= 64),
  * n = max lens coefficients wide: out_xy / out_inf = commit(Q), Q's n - 1 coefficients.  points: [t][4] canonical
  * limbs; weights: [k][t][4], row i belongs to polynomial i.  Polynomials, lens and stride are those of kzg_open_device;
- * KZG_ERR_DEGREE applies as it does there.  A zero weight skips its polynomial, a column of zero weights its point;
+ * KZG_ERR_DEGREE applies as it does there: the degree of Q decides, so coefficients of Q beyond the key may be
+ * there when they are zero (a polynomial longer than the key that carries no weight, or a sum that cancels), and after
+ * an error out_xy / out_inf are as the caller left them.  A zero weight skips its polynomial, a column of zero weights its point;
  * z_j = 0 is a legal point (Q_0[p] is p shifted down by one) and points may repeat.  k = 0, t = 0 or nothing but
  * empty polynomials give the point at infinity.
- * d_quot (device, nullable): receives the n - 1 coefficients of Q as canonical words.  It may be a row of the same
- * strided array above the k rows read, so that a second call can take Q as a further polynomial.
+ * d_quot (device, nullable): receives the n - 1 coefficients of Q as canonical words, the zeros beyond the key
+ * included.  It may be a row of the same strided array above the k rows read, so that a second call can take Q as a
+ * further polynomial.  After an error (KZG_ERR_DEGREE too) what d_quot holds is unspecified.
  * The call works in the buffers of kzg_open_device: it DROPS a slice held for kzg_open_shard_finish exactly as a plain
  * opening does.  Synchronises.  kzg_open_points takes the polynomials from host memory (d_quot stays a device
  * pointer). */
