@@ -474,6 +474,8 @@ class Context:
     # ---- per-point scalar multiplication: out[i] = [k_i] P_i, the products kept apart
     G1_MUL_LANES = 256          # lanes per workgroup of g1_mul_each_kernel / g2_mul_each_kernel (csrc/g_mul.hip)
     G2_MUL_LANES = 64
+    G1_MUL_LAUNCH_LANES = 512 * 256     # lanes of one launch at the most (GM_LAUNCH_LANES1 / 2, csrc/g_mul.h): a longer
+    G2_MUL_LAUNCH_LANES = 256 * 64      # call is split evenly over the fewest launches, all over one table
 
     def _mul_each(self, group, xy, inf, scalars, s, c0):
         """group 1 | 2; scalars uint64[n, 4] (each the 256-bit integer as it stands), or None for the power form

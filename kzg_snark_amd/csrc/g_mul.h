@@ -1,6 +1,7 @@
 // g_mul.h -- ONE scalar multiplication [k] P, for a point of G1's curve (Ec<C> / XYZZ<C>) and for a point of the twist
 // (G2Bytes<C>::J), the arithmetic behind kzg_g1_mul_* / kzg_g2_mul_* (DESIGN.md 4.16).  Shared by the kernels of
-// g_mul.hip and the host (tests/shim/g_mul_shim.cpp compiles this text with g++): nothing here is device-only.
+// g_mul.hip and the host (tests/shim/g_mul_shim.cpp compiles this text with g++): nothing here is device-only.  At the
+// end: how a call is cut into launches (GmPlan) and where a lane's table entries lie, for the same two readers.
 //
 // The scalar is eight 32-bit words and means the 256-bit integer AS GIVEN: it is not reduced modulo r, so a point
 // outside the prime-order subgroup is multiplied by k itself ([r] Q != O there; cofactor clearing is a call of this).
@@ -161,5 +162,36 @@ template <class F>
 static KZG_HD bool gmul_scalar_below(const uint32_t* k) {
   return words_below_p<F>(k);
 }
+
+// ---- the launches of a call and a lane's column of the table (g_mul.hip; tests/test_g_mul_host.py through the shim) --
+constexpr uint32_t GM_TB1 = 256;                          // lanes per workgroup, G1
+constexpr uint32_t GM_TB2 = 64;                           // lanes per workgroup, G2: one wave
+constexpr uint32_t GM_LAUNCH_LANES1 = 512 * GM_TB1;       // two workgroups per CU
+constexpr uint32_t GM_LAUNCH_LANES2 = 256 * GM_TB2;       // one wave per CU
+constexpr size_t GM_MAX_POINTS = (size_t)1 << 21;         // the power table's largest exponent
+
+// the lanes of a call split evenly over the fewest launches of at most `cap` lanes (whole workgroups)
+struct GmPlan {
+  uint32_t blocks, launch_blocks;
+  GmPlan(size_t n, uint32_t tb, uint32_t cap) {
+    blocks = (uint32_t)((n + tb - 1) / tb);
+    const uint32_t cap_blocks = cap / tb, launches = (blocks + cap_blocks - 1) / cap_blocks;
+    launch_blocks = launches ? (blocks + launches - 1) / launches : 0;
+  }
+};
+
+// the table of a launch of `slots` lanes: entry e is `pieces` vectors, piece q of entry e of lane `slot` at
+// (e * pieces + q) * slots + slot -- a wave's lanes are adjacent.  The index is 32 bits wide: a table has fewer than
+// 2^25 vectors.  gm_entry_index is piece 0 of an entry, gm_piece_index piece q from it.
+static KZG_HD uint32_t gm_entry_index(int e, int pieces, uint32_t slots, uint32_t slot) {
+  return (uint32_t)(e * pieces) * slots + slot;
+}
+static KZG_HD uint32_t gm_piece_index(uint32_t entry_idx, int q, uint32_t slots) { return entry_idx + (uint32_t)q * slots; }
+// pieces of a table entry: an XYZZ point of G1's curve is 4 N limbs in pieces of 16 bytes, a Jacobian point of the twist
+// 6 N limbs (N is odd) in pieces of 8 bytes
+template <class C> constexpr int gm_g1_pieces() { return C::Fp::N; }
+template <class C> constexpr int gm_g2_pieces() { return 3 * C::Fp::N; }
+template <class C> constexpr size_t g1_column_bytes() { return (size_t)GMUL_TABLE * 4 * C::Fp::N * 4; }
+template <class C> constexpr size_t g2_column_bytes() { return (size_t)GMUL_TABLE * 6 * C::Fp::N * 4; }
 
 }  // namespace kzg

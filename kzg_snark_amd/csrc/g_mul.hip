@@ -27,11 +27,7 @@ namespace kzg {
 
 namespace {
 
-constexpr uint32_t GM_TB1 = 256;                          // lanes per workgroup, G1
-constexpr uint32_t GM_TB2 = 64;                           // lanes per workgroup, G2: one wave
-constexpr uint32_t GM_LAUNCH_LANES1 = 512 * GM_TB1;       // two workgroups per CU
-constexpr uint32_t GM_LAUNCH_LANES2 = 256 * GM_TB2;       // one wave per CU
-constexpr size_t GM_MAX_POINTS = (size_t)1 << 21;         // the power table's largest exponent
+// GM_TB1 / GM_TB2 (lanes per workgroup), GM_LAUNCH_LANES1 / 2 (lanes per launch) and GM_MAX_POINTS: g_mul.h
 constexpr uint32_t GM_NONE = 0xffffffffu;                 // *bad while every point is good
 constexpr uint8_t GM_FLAG_BAD = 2;                        // out_inf of a point that was refused
 
@@ -53,9 +49,8 @@ __device__ __forceinline__ void gm_scalar(const GmScalars& sc, uint32_t i, uint3
   }
 }
 
-// a lane's column of the table: entry e is PIECES vectors V, piece q of entry e of lane `slot` at
-// (e * PIECES + q) * slots + slot -- a wave's lanes are adjacent.  The index is 32 bits wide (a table has fewer than
-// 2^25 vectors) and the entry's first index is hidden from the optimiser behind an empty asm: the table phase stores
+// a lane's column of the table: entry e is PIECES vectors V at the indices of g_mul.h's gm_entry_index /
+// gm_piece_index.  The entry's first index is hidden from the optimiser behind an empty asm: the table phase stores
 // entry `it`, the loop's own counter, and strength reduction would otherwise keep one 64-bit address PER PIECE alive
 // across the whole ladder, in registers the G2 lanes do not have (hundreds of bytes of scratch memory).
 template <class V, int PIECES>
@@ -63,14 +58,14 @@ struct GmColumn {
   V* tab;
   uint32_t slots, slot;
   __device__ __forceinline__ uint32_t entry(int e) const {
-    uint32_t idx = (uint32_t)(e * PIECES) * slots + slot;
+    uint32_t idx = gm_entry_index(e, PIECES, slots, slot);
     asm volatile("" : "+v"(idx));
     return idx;
   }
-  __device__ __forceinline__ V& at(uint32_t entry_idx, int q) const { return tab[entry_idx + (uint32_t)q * slots]; }
+  __device__ __forceinline__ V& at(uint32_t entry_idx, int q) const { return tab[gm_piece_index(entry_idx, q, slots)]; }
 };
 template <class C>
-struct G1Tab : GmColumn<uint4, C::Fp::N> {
+struct G1Tab : GmColumn<uint4, gm_g1_pieces<C>()> {
   static constexpr int N = C::Fp::N;
   __device__ __forceinline__ void store(int e, const XYZZ<C>& v) const {
     uint32_t w[4 * N];
@@ -96,7 +91,7 @@ struct G1Tab : GmColumn<uint4, C::Fp::N> {
 };
 // a Jacobian point of the twist is 6 N limbs (N is odd): 3 N pieces of 8 bytes
 template <class C>
-struct G2Tab : GmColumn<uint2, 3 * C::Fp::N> {
+struct G2Tab : GmColumn<uint2, gm_g2_pieces<C>()> {
   static constexpr int N = C::Fp::N;
   __device__ __forceinline__ void store(int e, const Jac2<C>& v) const {
     uint32_t w[6 * N];
@@ -126,8 +121,6 @@ struct G2Tab : GmColumn<uint2, 3 * C::Fp::N> {
     return r;
   }
 };
-template <class C> constexpr size_t g1_column_bytes() { return (size_t)GMUL_TABLE * 4 * C::Fp::N * 4; }
-template <class C> constexpr size_t g2_column_bytes() { return (size_t)GMUL_TABLE * 6 * C::Fp::N * 4; }
 
 // out[i] = [k_i] P_i, i = first + the lane's index in the launch, i < n.  Points: recs (window-0 records) or xy / inf
 // (inf may be null).  Output: out_recs (records) or out_xy / out_inf.  A point that is refused leaves zeros, the flag
@@ -207,16 +200,6 @@ __global__ __launch_bounds__(GM_TB2) void g2_mul_each_kernel(uint32_t n, uint32_
 }
 
 // ---- host side --------------------------------------------------------------------------------------
-
-// the lanes of a call split evenly over the fewest launches of at most `cap` lanes (whole workgroups)
-struct GmPlan {
-  uint32_t blocks, launch_blocks;
-  GmPlan(size_t n, uint32_t tb, uint32_t cap) {
-    blocks = (uint32_t)((n + tb - 1) / tb);
-    const uint32_t cap_blocks = cap / tb, launches = (blocks + cap_blocks - 1) / cap_blocks;
-    launch_blocks = launches ? (blocks + launches - 1) / launches : 0;
-  }
-};
 
 // what a call keeps in the context's buffer: the table, the first refused index and -- power form -- the power table
 // and -- host-pointer forms -- the staged arrays

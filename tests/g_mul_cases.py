@@ -9,6 +9,8 @@ import random
 import subprocess
 from functools import lru_cache
 
+import numpy as np
+
 from g2_bytes_cases import CURVE_IDS, INF2, fp_words, g2_generator, point_value, random_twist_point, value_point
 from kzg_snark_amd import curve as C
 
@@ -142,11 +144,123 @@ def words(v, n):
     return [(v >> (32 * i)) & 0xffffffff for i in range(n)]
 
 
+# ---- outputs with guard bytes behind them (the GPU tests through the C ABI) -----------------------------------------
+
+GUARD = 0xA5
+PAD = 192                     # guard bytes behind every output
+
+
+def guarded(nbytes):
+    return np.full(nbytes + PAD, GUARD, dtype=np.uint8)
+
+
+def guard_ok(a, nbytes):
+    return bool((a[nbytes:] == GUARD).all())
+
+
+def vp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
 @lru_cache(maxsize=None)
 def build_shim():
     so = os.path.join(SHIM_DIR, "libg_mul_shim.so")
     subprocess.run(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", SHIM_SRC, "-o", so], check=True)
     return ctypes.CDLL(so)
+
+
+def shim_consts(lib):
+    """{group: (lanes per workgroup, lanes per launch)} and the largest n of a call, as csrc/g_mul.h states them"""
+    lib.gm_const.restype = ctypes.c_uint64
+    v = [int(lib.gm_const(i)) for i in range(5)]
+    return {1: (v[0], v[2]), 2: (v[1], v[3])}, v[4]
+
+
+def shim_plan(lib, n, g):
+    """GmPlan of a call of n points of group g -> (blocks, launch_blocks)"""
+    blocks, launch_blocks = U32(), U32()
+    lib.gm_plan(ctypes.c_uint64(n), g, ctypes.byref(blocks), ctypes.byref(launch_blocks))
+    return blocks.value, launch_blocks.value
+
+
+def shim_table(lib, name, g, grid, launch_blocks):
+    """a launch of `grid` workgroups over the table of a plan -> (pieces per entry, the largest index the launch touches
+    by the kernels' 32-bit arithmetic, the vectors allocated for launch_blocks)"""
+    pieces, top, vectors = U32(), U32(), ctypes.c_uint64()
+    assert lib.gm_table(CURVE_IDS[name], g, grid, launch_blocks, ctypes.byref(pieces), ctypes.byref(top),
+                        ctypes.byref(vectors)) == 0
+    return pieces.value, top.value, vectors.value
+
+
+def launches(lib, n, g):
+    """[(first lane, end lane)] of the launches of a call of n points, as g_mul.hip's drivers loop: b0 = 0, launch_blocks,
+    ... below blocks, each of min(launch_blocks, blocks - b0) workgroups (the last range ends at n)"""
+    tb = shim_consts(lib)[0][g][0]
+    blocks, launch_blocks = shim_plan(lib, n, g)
+    out, b0 = [], 0
+    while b0 < blocks:
+        grid = min(launch_blocks, blocks - b0)
+        out.append((b0 * tb, min(n, (b0 + grid) * tb)))
+        b0 += launch_blocks
+    return out
+
+
+# ---- inputs of calls of more than one launch (tests/test_g_mul_launches_gpu.py): arrays, no group operation per lane --
+
+def random_rows(seed, n, limbs=4):
+    """n seeded random rows of `limbs` 64-bit limbs"""
+    return np.frombuffer(np.random.default_rng(seed).bytes(8 * limbs * n), dtype=np.uint64).reshape(n, limbs).copy()
+
+
+def edge_lanes(spans, n, offsets, rng, extra):
+    """the lanes `offsets` away from every launch start, lane n - 1 and `extra` seeded lanes, those of [0, n) sorted"""
+    lanes = {f + d for f, _ in spans for d in offsets} | {n - 1} | {rng.randrange(n) for _ in range(extra)}
+    return sorted(i for i in lanes if 0 <= i < n)
+
+
+def each_scalars(name, n, spans, seed):
+    """(uint64[n, 4], the lanes that were overwritten): seeded 256-bit integers, NOT reduced, with 0, r, r - 1 and
+    2^256 - 1 in turn at lanes first - 1, first, first + 1 of every launch, at n - 1 and at a few seeded lanes"""
+    from kzg_snark_amd import _native
+    r = C.CURVES[name].r
+    k = random_rows(seed, n)
+    lanes = edge_lanes(spans, n, (-1, 0, 1), random.Random(seed), 8)
+    special = [0, r, r - 1, (1 << 256) - 1]
+    k[lanes] = _native.ints_to_limbs([special[j % 4] for j in range(len(lanes))])
+    return k, lanes
+
+
+def rho_rows(seed, n):
+    """n seeded random coefficients below 2^253 (below r on both curves) as canonical limbs"""
+    rho = random_rows(seed, n)
+    rho[:, 3] >>= np.uint64(3)
+    return rho
+
+
+@lru_cache(maxsize=None)
+def g2_pool(name):
+    """(8 points, 12 scalars, the 96 products, product of point a and scalar b at a * 12 + b): infinity, G, -G, three
+    random points of the subgroup, the point outside the subgroup and the one of small prime order; 0, 1, the
+    neighbourhood of r, 2r - 4, 2^256 - 1, 2^255 and four random 256-bit values"""
+    cv, G = C.CURVES[name], group(name, 2)
+    pts = [pt for pt, _ in points(name, 2)]
+    what = [w for _, w in points(name, 2)]
+    assert len(pts) == 8 and what[0] == "infinity" and what[6] == "outside the subgroup" and what[7].startswith("order ")
+    rng = random.Random(0xc2 + CURVE_IDS[name])
+    r = cv.r
+    ks = [0, 1, r - 1, r, r + 1, 2 * r - 4, (1 << 256) - 1, 1 << 255] + [rng.getrandbits(256) for _ in range(4)]
+    return pts, ks, [G.normalize(G.multiply(pt, k)) for pt in pts for k in ks]
+
+
+def odd_order_scalar(name):
+    """(s, m): s of odd multiplicative order m modulo r, so that s^i = s^(i mod m) and s^2048 has order m as well"""
+    r = C.CURVES[name].r
+    base, m = {"bls12_381": (2, 33), "bn254": (5, 39)}[name]
+    assert (r - 1) % m == 0
+    s = pow(base, (r - 1) // m, r)
+    assert pow(s, m, r) == 1 and all(pow(s, m // q, r) != 1 for q in (3, 11, 13) if m % q == 0)
+    assert m % 2 == 1 and math.gcd(2048, m) == 1
+    return s, m
 
 
 def shim_mul(lib, name, g, pt, k):

@@ -1,6 +1,6 @@
 // Host-only test shim: kzg_snark_amd/csrc/g_mul.h (the text the gfx950 kernels of g_mul.hip compile) behind a tiny C
 // interface, so tests/test_g_mul_host.py can check [k] P in both groups of both curves against curve.py's group law
-// without a GPU.  With -DG_MUL_SHIM_MAIN it is a program of its own that replays a file of cases (the sanitizer run).
+// without a GPU, and the launch plan and table indices of g_mul.hip's drivers.  With -DG_MUL_SHIM_MAIN it is a program of its own that replays a file of cases (the sanitizer run).
 // Test infrastructure only.
 #include <stdio.h>
 #include <string.h>
@@ -35,6 +35,36 @@ extern "C" int gm_mul(int curve, int group, const uint32_t* xy, int inf, const u
   if (curve == 1) return group == 1 ? do_g1<Bls12_381>(xy, inf, k, out, out_inf) : do_g2<Bls12_381>(xy, inf, k, out, out_inf);
   return -1;
 }
+// ---- the launches of a call (GmPlan) and the table's index arithmetic, as g_mul.hip uses them ----------------------
+// 0 / 1: lanes per workgroup of G1 / G2, 2 / 3: lanes per launch, 4: the largest n
+extern "C" uint64_t gm_const(int which) {
+  const uint64_t v[] = {GM_TB1, GM_TB2, GM_LAUNCH_LANES1, GM_LAUNCH_LANES2, GM_MAX_POINTS};
+  return which >= 0 && which < 5 ? v[which] : 0;
+}
+extern "C" void gm_plan(uint64_t n, int group, uint32_t* blocks, uint32_t* launch_blocks) {
+  const GmPlan plan((size_t)n, group == 1 ? GM_TB1 : GM_TB2, group == 1 ? GM_LAUNCH_LANES1 : GM_LAUNCH_LANES2);
+  *blocks = plan.blocks;
+  *launch_blocks = plan.launch_blocks;
+}
+template <class C>
+static void table_of(int group, uint32_t g, uint32_t launch_blocks, uint32_t* pieces, uint32_t* top, uint64_t* vectors) {
+  const uint32_t tb = group == 1 ? GM_TB1 : GM_TB2, slots = g * tb;
+  const int p = group == 1 ? gm_g1_pieces<C>() : gm_g2_pieces<C>();
+  *pieces = (uint32_t)p;
+  // the last piece of the last entry of the last lane, by the kernels' own 32-bit arithmetic
+  *top = gm_piece_index(gm_entry_index(GMUL_TABLE - 1, p, slots, slots - 1), p - 1, slots);
+  // what the host drivers allocate for launches of at most launch_blocks workgroups, in vectors (G1: 16 bytes, G2: 8)
+  *vectors = (group == 1 ? g1_column_bytes<C>() / 16 : g2_column_bytes<C>() / 8) * tb * launch_blocks;
+}
+// a launch of g >= 1 workgroups over a table allocated for launch_blocks: pieces per entry, the largest index it touches,
+// the vectors allocated.  0 ok, -1 no such curve
+extern "C" int gm_table(int curve, int group, uint32_t g, uint32_t launch_blocks, uint32_t* pieces, uint32_t* top,
+                        uint64_t* vectors) {
+  if (curve == 0) return table_of<Bn254>(group, g, launch_blocks, pieces, top, vectors), 0;
+  if (curve == 1) return table_of<Bls12_381>(group, g, launch_blocks, pieces, top, vectors), 0;
+  return -1;
+}
+
 // one case of a replay file, 32-bit words: curve, group (1 | 2), inf, the point (48 words, the unused tail zero), the
 // scalar (8), the expected flag, the expected point (48)
 constexpr int GM_POINT_WORDS = 48;

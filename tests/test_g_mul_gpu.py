@@ -1,19 +1,17 @@
 """GPU tests of the per-point scalar multiplication (csrc/g_mul.hip through the C ABI and the facade): out[i] = [k_i] P_i
 in G1 and G2 of both curves.  Every expected point comes from curve.Group.multiply, exact for any point and integer
 (KZG.multiply reduces modulo r and is not the reference).  B1 / B2 are the workgroup sizes of the two kernels."""
-import ctypes
 import random
 
 import numpy as np
 import pytest
 
 import g_mul_cases as gm
+from g_mul_cases import guard_ok, guarded, vp
 
 pytestmark = pytest.mark.gpu
 
 CURVES = gm.CURVES
-GUARD = 0xA5
-PAD = 192                     # guard bytes behind every output
 
 
 @pytest.fixture(scope="module")
@@ -25,18 +23,6 @@ def kzgs():
 @pytest.fixture(scope="module")
 def lanes(native):
     return native.Context.G1_MUL_LANES, native.Context.G2_MUL_LANES
-
-
-def guarded(nbytes):
-    return np.full(nbytes + PAD, GUARD, dtype=np.uint8)
-
-
-def guard_ok(a, nbytes):
-    return bool((a[nbytes:] == GUARD).all())
-
-
-def vp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 _POOL = {}

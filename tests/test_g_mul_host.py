@@ -1,6 +1,7 @@
 """Per-point scalar multiplication on the CPU: csrc/g_mul.h -- the text the gfx950 kernels of g_mul.hip compile -- built
 for the host (tests/shim/g_mul_shim.cpp) against curve.Group.multiply on the whole case list of g_mul_cases.py, both
-groups, both curves, word for word; the case list itself; the same shim as a program under the sanitizers."""
+groups, both curves, word for word; the case list itself; the same shim as a program under the sanitizers; the launch
+plan and the table indices that g_mul.hip's drivers and kernels take from that header."""
 import os
 import re
 import subprocess
@@ -74,6 +75,75 @@ def test_points_that_are_not_points_are_refused(name):
         assert gm.shim_mul(lib, name, g, off, 5)[0] == 1
         if (gen[0] if g == 1 else gen[0][0]) + cv.p < 1 << (32 * gm.fp_words(cv)):
             assert gm.shim_mul(lib, name, g, big, 5)[0] == 1
+
+
+def plan_sizes(tb, cap, limit):
+    ns = {0, 1, tb - 1, tb, tb + 1, limit}
+    ns |= {c * cap + d for c in range(1, 17) for d in (-tb - 1, -tb, -1, 0, 1, tb, tb + 1)}
+    return sorted({min(max(n, 0), limit) for n in ns})
+
+
+def test_the_shim_states_the_constants_of_the_python_layer():
+    from kzg_snark_amd import _native
+    consts, limit = gm.shim_consts(gm.build_shim())
+    ctx = _native.Context
+    assert consts == {1: (ctx.G1_MUL_LANES, ctx.G1_MUL_LAUNCH_LANES), 2: (ctx.G2_MUL_LANES, ctx.G2_MUL_LAUNCH_LANES)}
+    assert limit == 1 << 21
+
+
+@pytest.mark.parametrize("g", [1, 2])
+def test_the_plan_covers_every_block_once_in_the_fewest_launches(g):
+    """GmPlan (csrc/g_mul.h) as the drivers of g_mul.hip loop over it: launches b0 = 0, launch_blocks, ... of
+    min(launch_blocks, blocks - b0) workgroups."""
+    lib = gm.build_shim()
+    consts, limit = gm.shim_consts(lib)
+    tb, cap = consts[g]
+    assert cap % tb == 0
+    cap_blocks = cap // tb
+    sizes = plan_sizes(tb, cap, limit)
+    assert {0, 1, cap, cap + 1, 2 * cap + 1, limit} <= set(sizes)
+    for n in sizes:
+        blocks, launch_blocks = gm.shim_plan(lib, n, g)
+        assert blocks == -(-n // tb), n
+        grids, b0 = [], 0
+        while b0 < blocks:
+            assert launch_blocks > 0, n
+            grids.append((b0, min(launch_blocks, blocks - b0)))
+            b0 += launch_blocks
+        # [0, blocks) exactly once and in order, no launch empty or above the cap, and no launch more than needed
+        at = 0
+        for b0, grid in grids:
+            assert b0 == at and 1 <= grid <= cap_blocks, (n, grids)
+            at += grid
+        assert at == blocks, (n, grids)
+        assert len(grids) == -(-blocks // cap_blocks), (n, grids)
+        if n == 0:
+            assert grids == [] and launch_blocks == 0
+        # the same ranges in lanes, as the GPU tests take them
+        assert gm.launches(lib, n, g) == [(b0 * tb, min(n, (b0 + grid) * tb)) for b0, grid in grids]
+
+
+@pytest.mark.parametrize("g", [1, 2])
+@pytest.mark.parametrize("name", gm.CURVES)
+def test_every_launch_grid_stays_inside_the_table_and_below_2_pow_25(name, g):
+    """The largest index of a launch -- entry 7, last piece, last slot, slots = grid * TB -- by the kernels' own 32-bit
+    arithmetic (gm_entry_index / gm_piece_index): equal to the same index in Python integers (nothing wrapped), inside
+    what the drivers allocate for launch_blocks workgroups, and below the 2^25 vectors csrc/g_mul.h promises."""
+    lib = gm.build_shim()
+    consts, limit = gm.shim_consts(lib)
+    tb, cap = consts[g]
+    seen = set()
+    for n in plan_sizes(tb, cap, limit):
+        launch_blocks = gm.shim_plan(lib, n, g)[1]
+        if launch_blocks in seen:
+            continue
+        seen.add(launch_blocks)
+        for grid in range(1, launch_blocks + 1):
+            pieces, top, vectors = gm.shim_table(lib, name, g, grid, launch_blocks)
+            assert vectors == 8 * pieces * tb * launch_blocks
+            assert top == 8 * pieces * grid * tb - 1, (n, grid)
+            assert top < vectors and top < 1 << 25, (n, grid)
+    assert cap // tb in seen and 1 in seen
 
 
 def test_the_case_list_under_address_and_undefined_behaviour_sanitizers(tmp_path):

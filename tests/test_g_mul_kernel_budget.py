@@ -50,3 +50,4 @@ def test_once_per_curve_no_scratch_and_within_the_stated_registers(kernels, kern
     # the workgroup sizes the Python layer states are the kernels'
     from kzg_snark_amd import _native
     assert (_native.Context.G1_MUL_LANES, _native.Context.G2_MUL_LANES) == (256, 64)
+    assert (_native.Context.G1_MUL_LAUNCH_LANES, _native.Context.G2_MUL_LAUNCH_LANES) == (131072, 16384)
