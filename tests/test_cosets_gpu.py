@@ -7,6 +7,7 @@ import random
 import numpy as np
 import pytest
 
+from coset_scan_profiles import coset_divide
 from oracle import c_oracle
 from oracle import py_oracle as O
 
@@ -50,15 +51,6 @@ def points(native, L, xy, inf):
 
 def one_point(native, L, xy, inf):
     return None if inf[0] else tuple(native.limbs_to_ints(np.asarray(xy).reshape(2, L)))
-
-
-def coset_divide(coeffs, l, a, r):
-    """(quotient, remainder) of p by X^l - a: S_t = c_t + a S_(t+l), q_t = S_(t+l), rho_j = S_j"""
-    c = [int(x) % r for x in coeffs]
-    S = c + [0] * l
-    for t in range(len(c) - 1, -1, -1):
-        S[t] = (c[t] + a * S[t + l]) % r
-    return [S[t + l] for t in range(max(len(c) - l, 0))], [S[j] for j in range(l)]
 
 
 def coset_interpolate(values, h, zeta, r):
