@@ -564,6 +564,28 @@ int kzg_g2_mul_each(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t
 int kzg_g2_mul_powers(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t s[4],
                       const uint64_t c0[4], uint64_t* out_xy, uint8_t* out_inf);
 
+/* ---- linear combinations in G2 -----------------------------------------------------------------------
+ * out = sum_i [k_i] Q_i for n points of the twist, as ONE point: a commitment in G2, a random linear combination of
+ * verification keys, the two folds of a setup's G2 chain.  The products of kzg_g2_mul_each summed on the device: no
+ * per-point inversion and no per-point result on the host.
+ * Points and scalars: exactly those of kzg_g2_mul_each / kzg_g2_mul_powers -- canonical affine limbs
+ * x.c0 | x.c1 | y.c0 | y.c1 with optional infinity flags, any point of the twist inside the prime-order subgroup or
+ * not; `scalars` n * 4 limbs, each the 256-bit integer AS IT STANDS (not reduced modulo r), or -- _powers -- the
+ * scalars c0 * s^i mod r formed on the device, s and c0 below r (s = 0 gives c0, 0, 0, ...).
+ * The sum is exact for every input: every addition of the sum finishes P + P, P + (-P) and infinite operands, which
+ * equal points with equal scalars, a point and its negative, and points of small order all reach.
+ *   kzg_g2_lincomb         host pointers in and out, synchronised.  out_xy: 4*FP_LIMBS limbs, zeros when the sum is
+ *                          infinity; *out_inf: 1 for infinity, else 0.
+ *   kzg_g2_lincomb_powers  the same with the scalars c0 * s^i.
+ * A coordinate >= p or a point off the twist is KZG_ERR_ARG with the smallest offending index in kzg_last_error; s or
+ * c0 >= r is KZG_ERR_ARG naming the argument, before any work; more than 2^21 points per call is KZG_ERR_ARG.  A call
+ * that fails writes nothing to out_xy and out_inf.  n = 0 is KZG_OK and the sum is infinity.  Profiling span:
+ * "g2_lincomb" (ONE per call, copies in and out included). */
+int kzg_g2_lincomb(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t* scalars,
+                   uint64_t* out_xy, uint8_t* out_inf);
+int kzg_g2_lincomb_powers(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t s[4],
+                          const uint64_t c0[4], uint64_t* out_xy, uint8_t* out_inf);
+
 /* ---- EIP-4844 blobs as bytes: device intake and SHA-256 challenges ---------------------------------
  * A blob is n = 2^log_n field elements of 32 big-endian bytes each; b blobs lie one after the other ([b][n][32]).
  *   kzg_blob_to_fr          every element checked < r and written as four canonical little-endian limbs:

@@ -130,6 +130,8 @@ SIGNATURES = {
     "kzg_srs_mul_powers": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
     "kzg_g2_mul_each": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "kzg_g2_mul_powers": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
+    "kzg_g2_lincomb": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "kzg_g2_lincomb_powers": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
     "kzg_srs_load_g1_compressed": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_vp)]),
     "kzg_srs_export_compressed": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "kzg_recover_cosets_device": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
@@ -511,6 +513,39 @@ class Context:
 
     def g2_mul_powers(self, xy, inf, s, c0=1):
         return self._mul_each(2, xy, inf, None, s, c0)
+
+    # ---- linear combinations in G2: sum_i [k_i] Q_i as one point
+    G2_LINCOMB_LANES = 64               # lanes per workgroup of g2_lincomb_kernel (GL_TB, csrc/g2_lincomb.h): one wave
+    G2_LINCOMB_LAUNCH_LANES = 1024 * 64     # lanes of one launch at the most (GL_LAUNCH_LANES), all over one table
+    G2_LINCOMB_FOLD_LANES = 64          # lanes per workgroup of g2_lincomb_fold_kernel (GL_FOLD_TB)
+    G2_LINCOMB_FOLD_SPAN = 256          # points one workgroup of the fold adds (GL_FOLD_SPAN)
+
+    def _g2_lincomb(self, xy, inf, scalars, s, c0):
+        width = 4 * self.fp_limbs
+        name = "g2_lincomb" if s is None else "g2_lincomb_powers"
+        xy = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, width)
+        n = xy.shape[0]
+        inf = _inf_arg(inf, n, f"{name}: inf and xy")
+        out_xy, out_inf = np.zeros(width, dtype=np.uint64), np.zeros(1, dtype=np.uint8)
+        if s is None:
+            scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+            if scalars.shape[0] != n:
+                raise ValueError(f"{name}: {scalars.shape[0]} scalars for {n} points")
+            self._check(lib().kzg_g2_lincomb(self._h, _as_vp(xy), _as_vp(inf), n, _as_vp(scalars), _as_vp(out_xy),
+                                             _as_vp(out_inf)))
+        else:
+            self._check(lib().kzg_g2_lincomb_powers(self._h, _as_vp(xy), _as_vp(inf), n, _fr(s), _fr(c0),
+                                                    _as_vp(out_xy), _as_vp(out_inf)))
+        return out_xy, out_inf
+
+    def g2_lincomb(self, xy, inf, scalars):
+        """points of the twist (uint64[n, 4*fp_limbs], uint8[n] flags or None) and scalars uint64[n, 4], each the 256-bit
+        integer as it stands -> (xy uint64[4*fp_limbs], inf uint8[1]) of the ONE point sum_i [k_i] Q_i; n = 0: infinity"""
+        return self._g2_lincomb(xy, inf, scalars, None, None)
+
+    def g2_lincomb_powers(self, xy, inf, s, c0=1):
+        """the same with the scalars c0 * s^i mod r (s, c0 ints below r), formed on the device"""
+        return self._g2_lincomb(xy, inf, None, s, c0)
 
     def g1_mul_each_device(self, d_xy, d_inf, n, d_scalars, d_out_xy, d_out_inf):
         """The same on device pointers (d_inf may be None), enqueued on the context's stream (no synchronisation); a

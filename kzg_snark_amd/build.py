@@ -16,7 +16,7 @@ LIBDIR = os.environ.get("KZG_BUILD_DIR") or os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libkzg_mi355x.so")
 SOURCES = ["api.hip", "ntt.hip", "msm.hip", "msm_prep.hip", "poly.hip", "lagrange.hip", "domain.hip",
            "verify.hip", "recover.hip", "g1_bytes.hip", "verify_points.hip", "blob.hip", "pairing.hip", "g2_bytes.hip",
-           "g_mul.hip"]
+           "g_mul.hip", "g2_lincomb.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fgpu-rdc" if False else "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result", "-Wno-pass-failed"]

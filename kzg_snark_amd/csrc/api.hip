@@ -458,6 +458,19 @@ int kzg_g2_mul_powers(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size
                      out_xy, out_inf);
 }
 
+int kzg_g2_lincomb(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t* scalars,
+                   uint64_t* out_xy, uint8_t* out_inf) {
+  KZG_ENTER(!out_xy || !out_inf || (n && (!xy || !scalars)));
+  return g2_lincomb(c, xy, inf, n, reinterpret_cast<const uint32_t*>(scalars), nullptr, nullptr, out_xy, out_inf);
+}
+
+int kzg_g2_lincomb_powers(kzg_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, const uint64_t s[4],
+                          const uint64_t c0[4], uint64_t* out_xy, uint8_t* out_inf) {
+  KZG_ENTER(!s || !c0 || !out_xy || !out_inf || (n && !xy));
+  return g2_lincomb(c, xy, inf, n, nullptr, reinterpret_cast<const uint32_t*>(s), reinterpret_cast<const uint32_t*>(c0),
+                    out_xy, out_inf);
+}
+
 int kzg_pairing_check(kzg_ctx* ctx, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
                       const uint8_t* g2_inf, size_t m, size_t k, uint8_t* out_status) {
   KZG_ENTER(m && (!g1_xy || !g2_xy || !out_status));

@@ -22,105 +22,13 @@
 #include "msm.h"
 #include "srs_rec.h"
 #include "g_mul.h"
+#include "g_mul_dev.h"
 
 namespace kzg {
 
+// the scalars of a launch (GmScalars), a lane's column of the table (G1Tab / G2Tab) and the argument checks of a call:
+// g_mul_dev.h, shared with g2_lincomb.hip
 namespace {
-
-// GM_TB1 / GM_TB2 (lanes per workgroup), GM_LAUNCH_LANES1 / 2 (lanes per launch) and GM_MAX_POINTS: g_mul.h
-constexpr uint32_t GM_NONE = 0xffffffffu;                 // *bad while every point is good
-constexpr uint8_t GM_FLAG_BAD = 2;                        // out_inf of a point that was refused
-
-// the scalars of a launch: k != null: n x 8 words; else c0 s^i with s^i from the power table
-struct GmScalars {
-  const uint32_t* k;
-  const uint32_t* ptab;
-  FrArg c0;                                               // Montgomery form
-};
-
-template <class C>
-__device__ __forceinline__ void gm_scalar(const GmScalars& sc, uint32_t i, uint32_t* k) {
-  using Fr = typename C::Fr;
-  if (sc.k) {
-    ld_words<8>(sc.k + (size_t)i * 8, k);
-  } else {
-    const Fe<Fr> v = Field<Fr>::mul(fr_pow_lookup<Fr>(sc.ptab, i), arg_fe<Fr>(sc.c0));
-    Field<Fr>::to_words(Field<Fr>::from_mont(v), k);
-  }
-}
-
-// a lane's column of the table: entry e is PIECES vectors V at the indices of g_mul.h's gm_entry_index /
-// gm_piece_index.  The entry's first index is hidden from the optimiser behind an empty asm: the table phase stores
-// entry `it`, the loop's own counter, and strength reduction would otherwise keep one 64-bit address PER PIECE alive
-// across the whole ladder, in registers the G2 lanes do not have (hundreds of bytes of scratch memory).
-template <class V, int PIECES>
-struct GmColumn {
-  V* tab;
-  uint32_t slots, slot;
-  __device__ __forceinline__ uint32_t entry(int e) const {
-    uint32_t idx = gm_entry_index(e, PIECES, slots, slot);
-    asm volatile("" : "+v"(idx));
-    return idx;
-  }
-  __device__ __forceinline__ V& at(uint32_t entry_idx, int q) const { return tab[gm_piece_index(entry_idx, q, slots)]; }
-};
-template <class C>
-struct G1Tab : GmColumn<uint4, gm_g1_pieces<C>()> {
-  static constexpr int N = C::Fp::N;
-  __device__ __forceinline__ void store(int e, const XYZZ<C>& v) const {
-    uint32_t w[4 * N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) { w[j] = v.x.l[j]; w[N + j] = v.y.l[j]; w[2 * N + j] = v.zz.l[j]; w[3 * N + j] = v.zzz.l[j]; }
-    const uint32_t at0 = this->entry(e);
-#pragma unroll
-    for (int q = 0; q < N; ++q) this->at(at0, q) = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-  }
-  __device__ __forceinline__ XYZZ<C> load(int e) const {
-    uint32_t w[4 * N];
-    const uint32_t at0 = this->entry(e);
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-      const uint4 v = this->at(at0, q);
-      w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-    }
-    XYZZ<C> r;
-#pragma unroll
-    for (int j = 0; j < N; ++j) { r.x.l[j] = w[j]; r.y.l[j] = w[N + j]; r.zz.l[j] = w[2 * N + j]; r.zzz.l[j] = w[3 * N + j]; }
-    return r;
-  }
-};
-// a Jacobian point of the twist is 6 N limbs (N is odd): 3 N pieces of 8 bytes
-template <class C>
-struct G2Tab : GmColumn<uint2, gm_g2_pieces<C>()> {
-  static constexpr int N = C::Fp::N;
-  __device__ __forceinline__ void store(int e, const Jac2<C>& v) const {
-    uint32_t w[6 * N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      w[j] = v.x.c0.l[j]; w[N + j] = v.x.c1.l[j]; w[2 * N + j] = v.y.c0.l[j]; w[3 * N + j] = v.y.c1.l[j];
-      w[4 * N + j] = v.z.c0.l[j]; w[5 * N + j] = v.z.c1.l[j];
-    }
-    const uint32_t at0 = this->entry(e);
-#pragma unroll
-    for (int q = 0; q < 3 * N; ++q) this->at(at0, q) = make_uint2(w[2 * q], w[2 * q + 1]);
-  }
-  __device__ __forceinline__ Jac2<C> load(int e) const {
-    uint32_t w[6 * N];
-    const uint32_t at0 = this->entry(e);
-#pragma unroll
-    for (int q = 0; q < 3 * N; ++q) {
-      const uint2 v = this->at(at0, q);
-      w[2 * q] = v.x; w[2 * q + 1] = v.y;
-    }
-    Jac2<C> r;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      r.x.c0.l[j] = w[j]; r.x.c1.l[j] = w[N + j]; r.y.c0.l[j] = w[2 * N + j]; r.y.c1.l[j] = w[3 * N + j];
-      r.z.c0.l[j] = w[4 * N + j]; r.z.c1.l[j] = w[5 * N + j];
-    }
-    return r;
-  }
-};
 
 // out[i] = [k_i] P_i, i = first + the lane's index in the launch, i < n.  Points: recs (window-0 records) or xy / inf
 // (inf may be null).  Output: out_recs (records) or out_xy / out_inf.  A point that is refused leaves zeros, the flag
@@ -218,28 +126,6 @@ struct GmWs {
 };
 
 template <class C>
-int check_scalar(Ctx* c, const uint32_t* v, const char* who, const char* name) {
-  if (gmul_scalar_below<typename C::Fr>(v)) return KZG_OK;
-  const std::string msg = std::string(who) + ": " + name + " is not below the group order r";
-  return set_err(c, KZG_ERR_ARG, msg.c_str());
-}
-
-// the scalars of a launch from a call's arguments; the power form checks s and c0 and enqueues the table's launch
-template <class C>
-int scalars_of(Ctx* c, const uint32_t* d_k, const uint32_t* s, const uint32_t* c0, uint32_t* d_ptab, const char* who,
-               GmScalars* sc) {
-  using Fr = typename C::Fr;
-  sc->k = d_k;
-  sc->ptab = d_ptab;
-  sc->c0 = FrArg{};
-  if (d_k) return KZG_OK;
-  if (int rc = check_scalar<C>(c, s, who, "s")) return rc;
-  if (int rc = check_scalar<C>(c, c0, who, "c0")) return rc;
-  sc->c0 = fr_arg<Fr>(mont_from_words<Fr>(c0));
-  return fr_pow_table(c, fr_arg<Fr>(mont_from_words<Fr>(s)), d_ptab);
-}
-
-template <class C>
 int g1_launches(Ctx* c, size_t n, const GmPlan& plan, const uint32_t* d_xy, const uint8_t* d_inf, const uint32_t* recs,
                 const GmScalars& sc, void* d_tab, uint32_t* d_out_xy, uint8_t* d_out_inf, uint32_t* d_out_recs,
                 uint32_t* d_bad) {
@@ -263,12 +149,6 @@ int g2_launches(Ctx* c, size_t n, const GmPlan& plan, const uint32_t* d_xy, cons
     KZG_HIP(c, hipGetLastError());
   }
   return KZG_OK;
-}
-
-int refuse(Ctx* c, const char* who, uint32_t index, const char* curve) {
-  const std::string msg = std::string(who) + ": point " + std::to_string(index) + " has a coordinate >= p or is not on the " +
-                          curve;
-  return set_err(c, KZG_ERR_ARG, msg.c_str());
 }
 
 // the host-pointer forms of both groups: stage, launch, wait, report or copy out.  k: n x 8 words, or null with s, c0
@@ -341,13 +221,6 @@ int srs_mul_powers_t(Ctx* c, const Srs* in, const uint32_t* s, const uint32_t* c
   return KZG_OK;
 }
 
-int size_check(Ctx* c, size_t n, const char* who) {
-  if (n > GM_MAX_POINTS) {
-    const std::string msg = std::string(who) + ": more than 2^21 points";
-    return set_err(c, KZG_ERR_ARG, msg.c_str());
-  }
-  return KZG_OK;
-}
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <class C> int g1_host(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, const uint32_t* k, const uint32_t* s,

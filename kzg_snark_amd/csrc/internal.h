@@ -94,7 +94,7 @@ struct Ctx {
   DevBuf rec_tmp;         // recover.hip: power tables, the product tree, Z and its inverses, one chunk of vectors
   DevBuf vpt_tmp;         // verify_points.hip: staged claims, weights, power table, partial sums and partial points
   DevBuf pair_tmp;        // pairing.hip: staged points, flags, values and statuses of one kzg_pairing_* call
-  DevBuf gmul_tmp;        // g_mul.hip: the lanes' tables of multiples, the power table, the staged arrays of one call
+  DevBuf gmul_tmp;        // g_mul.hip, g2_lincomb.hip: the lanes' tables of multiples, the power table, the staged arrays of one call
   size_t ver_last_bytes = 0;             // what the last kzg_verify_cosets carved out of ver_tmp (kzg_prof_read)
   size_t vpt_last_bytes = 0;              // what the last kzg_verify_points carved out of vpt_tmp (kzg_prof_read)
   uint32_t ver_lds_attr_set = 0;          // per ver_cell_kernel instantiation, as ntt_lds_attr_set

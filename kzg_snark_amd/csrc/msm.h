@@ -180,6 +180,10 @@ int g2_mul_each(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, const 
 int g1_mul_each_device(Ctx* c, const void* d_xy, const void* d_inf, size_t n, const void* d_k, void* d_out_xy,
                        void* d_out_inf);
 int srs_mul_powers(Ctx* c, const Srs* in, const uint32_t* s, const uint32_t* c0, Srs** out);
+// g2_lincomb.hip: the sum of the products on the twist as one point.  s == null: k is n x 8 words;
+// else the power form c0 s^i.  n = 0 is infinity.
+int g2_lincomb(Ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, const uint32_t* k, const uint32_t* s,
+               const uint32_t* c0, uint64_t* out_xy, uint8_t* out_inf);
 int srs_load_g1_compressed(Ctx* c, const uint8_t* bytes, size_t n, int check_subgroup, Srs** out);
 int srs_export_compressed(Ctx* c, const Srs* s, size_t start, size_t count, uint8_t* out_bytes);
 

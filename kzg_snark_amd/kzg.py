@@ -550,6 +550,43 @@ class KZG:
         """multiply_each for points of the twist (G2 tuples, or (xy, inf) arrays in kzg_pairing_check's layout)."""
         return self._multiply_each(2, points, scalars, "multiply_each_g2")
 
+    def lincomb_g2(self, points, scalars):
+        """sum_i [k_i] Q_i as ONE point of the twist, on the device (kzg_g2_lincomb).  points: a list of
+        G2 point tuples, or (xy, inf) arrays in kzg_pairing_check's layout; scalars: ints in [0, 2^256), each taken as
+        it stands -- NOT reduced modulo r.  The sum is exact for every point of the twist, in the subgroup or not.  No
+        points give infinity.  A point off the twist or with a coordinate >= p raises ValueError naming its index."""
+        xy, inf = self._g2_arrays(points, "lincomb_g2")
+        rows = self._scalar_rows(scalars, xy.shape[0], "lincomb_g2")
+        with _bad_input_is_value_error():
+            out_xy, out_inf = self._context().g2_lincomb(xy, inf, rows)
+        return _native.limbs_to_g2_points(out_xy.reshape(1, -1), out_inf)[0]
+
+    def commit_g2(self, g2_powers, polynomials):
+        """The commitments in G2: sum_j c_j [tau^j] G2 for every polynomial, one kzg_g2_lincomb call each.  g2_powers:
+        the G2 section of a setup (a list of G2 point tuples, or (xy, inf) arrays).  Polynomials, their canonical
+        coefficients and the degree rule are commit's."""
+        xy, inf = self._g2_arrays(g2_powers, "commit_g2")
+        max_degree = xy.shape[0] - 1
+        coeffs = [self._coeffs(p) for p in polynomials]
+        for c in coeffs:
+            if len(c) - 1 > max_degree:
+                raise ValueError(
+                    f"Polynomial degree {len(c) - 1} exceeds maximum allowed degree {max_degree}")   # kzg.py:103-106
+        ctx = self._context()
+        out = []
+        for c in coeffs:
+            rows = c if isinstance(c, np.ndarray) else self._scalar_rows(c, len(c), "commit_g2")
+            with _bad_input_is_value_error():
+                out_xy, out_inf = ctx.g2_lincomb(xy[:len(c)], None if inf is None else inf[:len(c)], rows)
+            out.append(_native.limbs_to_g2_points(out_xy.reshape(1, -1), out_inf)[0])
+        return out
+
+    @staticmethod
+    def _g2_chain(g2_chain, who):
+        if g2_chain not in ("links", "fold"):
+            raise ValueError(f"{who}: g2_chain must be \"links\" or \"fold\", not {g2_chain!r}")
+        return g2_chain
+
     def _below_order(self, v, who, name, least=0):
         v = int(v)
         if not least <= v < self.curve_order:
@@ -607,11 +644,13 @@ class KZG:
                 h.close()
             raise
 
-    def verify_contribution(self, before, after, contribution, r=None, pairing="device"):
+    def verify_contribution(self, before, after, contribution, r=None, pairing="device", g2_chain="links"):
         """Did one contribution turn `before` into `after`?  True iff pubkey and tau_g1 are finite points of their
         prime-order subgroups, tau_g1 is after.monomial[1], e(tau_g1, G2) = e(before.monomial[1], pubkey) (the new tau
         is the old one times the secret behind pubkey), `after` has the section lengths of `before`, and
-        check_key(after.monomial, after.g2, after.lagrange, r) passes (the sections of `after` describe ONE tau)."""
+        check_key(after.monomial, after.g2, after.lagrange, r) passes (the sections of `after` describe ONE tau).
+        g2_chain: check_key's."""
+        self._g2_chain(g2_chain, "verify_contribution")
         if len(before.monomial) < 2:
             raise ValueError("verify_contribution: the setup needs [tau] G1")
         pub, tau_g1 = self._g2.normalize(contribution.pubkey), self._g1.normalize(contribution.tau_g1)
@@ -625,14 +664,16 @@ class KZG:
             return False
         if not self._verdict(tau_g1, before.monomial[1], pub, pairing, "verify_contribution"):
             return False
-        return self.check_key(after.monomial, after.g2, after.lagrange, r)
+        return self.check_key(after.monomial, after.g2, after.lagrange, r, g2_chain=g2_chain)
 
-    def verify_contributions(self, first_tau_g1, contributions, pairing="device"):
+    def verify_contributions(self, first_tau_g1, contributions, pairing="device", g2_chain="links"):
         """A coordinator's replay of a transcript: link i holds iff e(c_i.tau_g1, G2) = e(c_(i-1).tau_g1, c_i.pubkey),
         c_(-1).tau_g1 = first_tau_g1 ([tau] G1 of the setup the chain starts from).  Returns the list of verdicts; with
         pairing="device" all links are ONE kzg_pairing_check call, one equation per link.  A link with an infinite
         point is False (its equation would hold for any partner).  Membership in the subgroups is verify_contribution's
-        business, or the loader's."""
+        business, or the loader's.  g2_chain is check_key's keyword, taken (and checked) so that a coordinator passes one
+        set of options to every call of a replay; the links themselves hold no chain of G2 powers."""
+        self._g2_chain(g2_chain, "verify_contributions")
         if pairing not in ("device", "host"):
             raise ValueError(f"verify_contributions: pairing must be \"device\" or \"host\", not {pairing!r}")
         links, prev = [], self._g1.normalize(first_tau_g1)
@@ -670,15 +711,17 @@ class KZG:
         with open(path, "w") as f:
             f.write(text)
 
-    def load_trusted_setup(self, path, check=True, check_subgroup=True, lagrange_order="natural", r=None):
+    def load_trusted_setup(self, path, check=True, check_subgroup=True, lagrange_order="natural", r=None,
+                           g2_chain="links"):
         """Reads a trusted-setup text file -> TrustedSetup.  The G1 sections are decompressed and expanded on the
         device (kzg_srs_load_g1_compressed), the G2 section by kzg_g2_decompress; check_subgroup tests every point for
         membership in its prime-order subgroup.  A point that fails raises ValueError naming the section, the index
         and the status.  check: the three sections must describe ONE tau (check_key; r fixes its randomness),
         else ValueError naming the part that failed.  lagrange_order="bit_reversed": the file's Lagrange section is
-        in bit-reversed order and is un-permuted on load."""
+        in bit-reversed order and is un-permuted on load.  g2_chain: check_key's."""
         if lagrange_order not in ("natural", "bit_reversed"):
             raise ValueError(f"lagrange_order must be \"natural\" or \"bit_reversed\", not {lagrange_order!r}")
+        self._g2_chain(g2_chain, "load_trusted_setup")
         ctx = self._context()
         with open(path) as f:
             n1, n2, lag_blobs, g2_blobs, mono_blobs = parse_trusted_setup(f.read(), ctx.g1_bytes, ctx.g2_bytes)
@@ -703,7 +746,7 @@ class KZG:
             setup = TrustedSetup(CommitmentKey(ctx, srs[0]), LagrangeKey(ctx, srs[1], n1, w),
                                  _native.limbs_to_g2_points(xy, inf))
             if check:
-                part = self._key_fault(setup.monomial, setup.g2, setup.lagrange, r)
+                part = self._key_fault(setup.monomial, setup.g2, setup.lagrange, r, g2_chain)
                 if part is not None:
                     raise ValueError(f"trusted setup: the sections do not describe one tau: {part}")
         except Exception:
@@ -714,18 +757,23 @@ class KZG:
 
     _CHECK_KEY_PAIRS = 16
 
-    def check_key(self, ck, g2_points, lagrange=None, r=None):
+    def check_key(self, ck, g2_points, lagrange=None, r=None, g2_chain="links"):
         """Do the pieces describe ONE tau -- ck = [tau^i G1], g2_points = [tau^j G2], lagrange (optional) the Lagrange
         form of ck?  True iff (1) ck[0] and g2_points[0] are the generators, (2) G1 chain: for a random rho,
         e(sum_{i<n-1} rho^i S_i, T_1) = e(sum_{i<n-1} rho^i S_{i+1}, G2) -- one commit of two polynomials against the
         key and one device pairing check, (3) G2 chain: e([rho^j] S_1, T_j) = e([rho^j] G1, T_{j+1}) for every j, in
         equations of at most 16 pairs with their own rho each, all in one kzg_pairing_check call, (4) the Lagrange key
         equals kzg_srs_lagrange(ck) point by point.  rho: 128 random bits unless r fixes it.  Membership of the points
-        in their subgroups is the loader's business (check_subgroup), not this call's."""
-        return self._key_fault(ck, g2_points, lagrange, r) is None
+        in their subgroups is the loader's business (check_subgroup), not this call's.
+        g2_chain="fold" replaces (3) by the G2 image of (2): for one rho, e(S_1, sum_{j<m-1} rho^j T_j) =
+        e(G1, sum_{j<m-1} rho^j T_{j+1}), the two sums by kzg_g2_lincomb_powers on the device and the equation in the
+        same kzg_pairing_check call as (2)'s -- no host multiplication and two equations whatever m is.  The verdict
+        and the name of a failing condition are those of "links"."""
+        return self._key_fault(ck, g2_points, lagrange, r, g2_chain) is None
 
-    def _key_fault(self, ck, g2_points, lagrange, r):
+    def _key_fault(self, ck, g2_points, lagrange, r, g2_chain="links"):
         """None, or the name of the first of check_key's four conditions that fails"""
+        self._g2_chain(g2_chain, "check_key")
         self._monomial_key(ck, "check_key")
         key = self._key(ck)
         ctx = self._context()
@@ -762,7 +810,20 @@ class KZG:
         # (3) the G2 chain, 8 links (16 pairs) per equation; pairs of infinities (skipped by the device) fill the rest
         s1 = key[1]
         links = self._CHECK_KEY_PAIRS // 2
-        for e, start in enumerate(range(0, m - 1, links), 1):
+        if g2_chain == "fold":
+            # both sums on the device, one equation; a G2 power that is no point of the twist fails the chain, as the
+            # pairing check of "links" would say
+            xy, inf = self._g2_arrays(g2, "check_key")
+            rho_1 = fresh(1)
+            try:
+                lo_hi = [ctx.g2_lincomb_powers(xy[a:a + m - 1], inf[a:a + m - 1], rho_1, 1) for a in (0, 1)]
+            except _native.NativeError as e:
+                if e.code != -1:
+                    raise
+                return "the G2 powers are not a chain of powers of the tau of [tau] G1"
+            a_pt, b_pt = (_native.limbs_to_g2_points(o_xy.reshape(1, -1), o_inf)[0] for o_xy, o_inf in lo_hi)
+            equations.append([(s1, a_pt), (self.neg(self.G1), b_pt)])
+        for e, start in enumerate(range(0, m - 1, links) if g2_chain == "links" else (), 1):
             rho_e, wgt, eq = fresh(e), 1, []
             for j in range(start, min(start + links, m - 1)):
                 eq += [(self.multiply(s1, wgt), g2[j]), (self.neg(self.multiply(self.G1, wgt)), g2[j + 1])]
