@@ -191,6 +191,44 @@ __device__ __forceinline__ Fe<F> pow_from_generators(const uint32_t* g, uint32_t
   return p;
 }
 
+// The steps of pass 1 that are the same for one point (tile_combine_kernel) and for several (tile_combine_multi_kernel,
+// below), per point.
+// Entry t of the two tables pass 2 reads: zinv[t] = z^(-8t) (t <= TB; ZINV = false: not wanted) and W[t] = z^(T(t+1))
+// (t < ntiles), each a chain of <= 20 products over the host's generator powers.
+template <class F, uint32_t TB, bool ZINV = true>
+__device__ __forceinline__ void tile_table_entry(uint32_t t, uint32_t ntiles, const uint32_t* ginv, const uint32_t* gw,
+                                                 uint32_t* zinv, uint32_t* W) {
+  if (ZINV && t <= TB) store_limbs<F>(zinv + (size_t)t * F::N, pow_from_generators<F>(ginv, t));
+  if (t < ntiles) store_limbs<F>(W + (size_t)t * F::N, pow_from_generators<F>(gw, t + 1));
+}
+// A coefficient's term of its chunk sum, c z^(pos mod 8) (0 beyond the end), added across the chunk's 8 lanes; the
+// sum stays in lazy limbs (8 limbs of 29 bits are below 2^32) and goes to h, the chunk's place in LDS.
+template <class F>
+__device__ __forceinline__ void tile_chunk_sum(const Fe<F>& cf, const Fe<F>& zr, uint32_t* h) {
+  const Fe<F> e = Field<F>::mul(cf, zr);
+  Fe<F> s;
+#pragma unroll
+  for (int j = 0; j < F::N; ++j) s.l[j] = lane8_sum(e.l[j]);
+  if ((threadIdx.x & 7) == 0) store_limbs<F>(h, s);
+}
+// The chunk sums hs of tile b (complete in LDS) -> g_q = h_q z^(8q), to G[b TB + q] if STORE, and their sum, the
+// tile's aggregate, to Hb.  All TK threads of the workgroup call it; red as for block_sum<TK>.
+template <class F, uint32_t TB, uint32_t TK, bool STORE>
+__device__ __forceinline__ void tile_aggregate(const uint32_t* hs, const uint32_t* zq_lo, const uint32_t* zq_hi,
+                                               uint32_t b, uint32_t* G, uint32_t* Hb, uint32_t* red) {
+  using Fd = Field<F>;
+  const uint32_t tid = threadIdx.x;
+  Fe<F> g = Fd::zero();
+  if (tid < TB) {                                                             // whole waves: TB is a multiple of 64
+    const Fe<F> hq = Fd::reduce_wide(Fd::carry(load_limbs<F>(hs + tid * F::N)));
+    const Fe<F> zq = Fd::mul(load_limbs<F>(zq_lo + (tid & 15) * F::N), load_limbs<F>(zq_hi + (tid >> 4) * F::N));
+    g = Fd::mul(hq, zq);
+    if (STORE) store_limbs<F>(G + ((size_t)b * TB + tid) * F::N, g);
+  }
+  const Fe<F> hb = block_sum<F, TK>(g, red);
+  if (tid == 0) store_limbs<F>(Hb, hb);
+}
+
 // TB chunks (T = 8 TB coefficients) per tile, TK = T / ITER threads per workgroup: the kernel waits for memory, so the
 // coefficients of a tile are spread over MORE threads than the fill uses (2 waves per SIMD at one thread per chunk:
 // 77 us for the 2^20 x 6 combination; profiles/r04a_open_kernel_stats.csv), each taking ITER strided elements.
@@ -211,9 +249,7 @@ __global__ __launch_bounds__(TB * SC / ITER) void tile_combine_kernel(TileLincom
 #endif
   const uint32_t ntab = gridDim.x - ntiles;
   if (blockIdx.x < ntab) {       // table workgroups (nothing of pass 1 reads these): FIRST in the grid, so that their
-    const uint32_t t = blockIdx.x * TK + tid;               // chains of <= 20 products start at once and end early
-    if (t <= TB) store_limbs<F>(zinv + (size_t)t * F::N, pow_from_generators<F>(ts.ginv, t));
-    if (t < ntiles) store_limbs<F>(W + (size_t)t * F::N, pow_from_generators<F>(ts.gw, t + 1));
+    tile_table_entry<F, TB>(blockIdx.x * TK + tid, ntiles, ts.ginv, ts.gw, zinv, W);      // chains start at once and end early
     return;
   }
   const uint32_t b = blockIdx.x - ntab, base = b * T;
@@ -240,22 +276,10 @@ __global__ __launch_bounds__(TB * SC / ITER) void tile_combine_kernel(TileLincom
       }
       if (STORE) store_words<F>(comb + (size_t)t * 8, acc);
     }
-    const Fe<F> e = Fd::mul(acc, zr);                                         // 0 beyond the end
-    Fe<F> s;
-#pragma unroll
-    for (int j = 0; j < F::N; ++j) s.l[j] = lane8_sum(e.l[j]);
-    if ((tid & 7) == 0) store_limbs<F>(hs + (i >> 3) * F::N, s);
+    tile_chunk_sum<F>(acc, zr, hs + (i >> 3) * F::N);
   }
   __syncthreads();
-  Fe<F> g = Fd::zero();
-  if (tid < TB) {                                                             // whole waves: TB is a multiple of 64
-    const Fe<F> hq = Fd::reduce_wide(Fd::carry(load_limbs<F>(hs + tid * F::N)));
-    const Fe<F> zq = Fd::mul(load_limbs<F>(ts.zq_lo + (tid & 15) * F::N), load_limbs<F>(ts.zq_hi + (tid >> 4) * F::N));
-    g = Fd::mul(hq, zq);
-    if (STORE) store_limbs<F>(G + ((size_t)b * TB + tid) * F::N, g);
-  }
-  const Fe<F> hb = block_sum<F, TK>(g, red);
-  if (tid == 0) store_limbs<F>(H + (size_t)b * F::N, hb);
+  tile_aggregate<F, TB, TK, STORE>(hs, ts.zq_lo, ts.zq_hi, b, G, H + (size_t)b * F::N, red);
 }
 
 // A[s] = sum_(i < 64) H[64 s + i] z^(T i): one wave per group of tiles
@@ -307,11 +331,16 @@ __device__ __forceinline__ Fe<F> tile_carry_sum(uint32_t b, uint32_t ntiles, con
   return block_sum<F, TB>(acc, red);
 }
 
+// Pass 2 for one point: out (S_0, S_1, ..: n elements) = the suffix values of comb at z, or, with `add`, what `out`
+// holds plus them (kzg_open_points: the points of a call follow each other on the stream, so that their sum needs
+// neither a buffer per point nor a pass of its own).  has_hv: hv is the aggregate of a virtual tile above the last one
+// (sharded open).  zero: z = 0, the suffix values are comb itself and no table is read.
 template <class F, uint32_t TB>
 __global__ __launch_bounds__(TB) void tile_fill_kernel(const uint32_t* comb, uint32_t n, uint32_t ntiles,
                                                        const uint32_t* G, const uint32_t* H, const uint32_t* A,
                                                        uint32_t nsuper, FrArg hv, uint32_t has_hv, FrArg zarg,
-                                                       const uint32_t* zinv, const uint32_t* W, uint32_t* S_base) {
+                                                       uint32_t zero, const uint32_t* zinv, const uint32_t* W,
+                                                       uint32_t add, uint32_t* out) {
   using Fd = Field<F>;
   constexpr uint32_t T = TB * SC, NWAVE = TB / 64;
   __shared__ uint4 st[T * 2 + TB];                          // 32 B per coefficient + one pad quad per chunk
@@ -327,77 +356,103 @@ __global__ __launch_bounds__(TB) void tile_fill_kernel(const uint32_t* comb, uin
     const uint32_t e = i >> 1;
     if (e0 + e < n) st[i + (e >> SC_LOG)] = gin[(size_t)(e0 + e) * 2 + (i & 1)];
   }
-  const Fe<F> q0 = tile_carry_sum<F, TB>(b, ntiles, H, A, nsuper, hv, has_hv, W, red);
-  if (tid == 0) store_limbs<F>(qsh, q0);
-  // suffix sums of the tile's scaled chunk values: inclusive inside the wave by shuffles, the waves above from LDS
-  const uint32_t lane = tid & 63, wave = tid >> 6;
-  Fe<F> incl = load_limbs<F>(G + ((size_t)b * TB + tid) * F::N);
+  if (!zero) {
+    const Fe<F> q0 = tile_carry_sum<F, TB>(b, ntiles, H, A, nsuper, hv, has_hv, W, red);
+    if (tid == 0) store_limbs<F>(qsh, q0);
+    // suffix sums of the tile's scaled chunk values: inclusive inside the wave by shuffles, the waves above from LDS
+    const uint32_t lane = tid & 63, wave = tid >> 6;
+    Fe<F> incl = load_limbs<F>(G + ((size_t)b * TB + tid) * F::N);
 #pragma unroll 1
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    Fe<F> t;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      Fe<F> t;
 #pragma unroll
-    for (int j = 0; j < F::N; ++j) t.l[j] = (uint32_t)__shfl_down((int)incl.l[j], d);
-    const Fe<F> s = Fd::add(incl, t);
-    incl = Fd::select(lane + d < 64, s, incl);
-  }
-  if (lane == 0) store_limbs<F>(wsum + wave * F::N, incl);
-  Fe<F> ex;                                                 // sum over the chunks after this one
+      for (int j = 0; j < F::N; ++j) t.l[j] = (uint32_t)__shfl_down((int)incl.l[j], d);
+      const Fe<F> s = Fd::add(incl, t);
+      incl = Fd::select(lane + d < 64, s, incl);
+    }
+    if (lane == 0) store_limbs<F>(wsum + wave * F::N, incl);
+    Fe<F> ex;                                               // sum over the chunks after this one
 #pragma unroll
-  for (int j = 0; j < F::N; ++j) {
-    const uint32_t t = (uint32_t)__shfl_down((int)incl.l[j], 1);
-    ex.l[j] = lane == 63 ? 0u : t;
-  }
-  __syncthreads();                                          // st, qsh, wsum complete
-  for (uint32_t w = wave + 1; w < NWAVE; ++w) ex = Fd::add(ex, load_limbs<F>(wsum + w * F::N));
-  Fe<F> acc = Fd::mul(Fd::add(ex, load_limbs<F>(qsh)), load_limbs<F>(zinv + (size_t)(tid + 1) * F::N));
-  const uint32_t j0 = e0 + tid * SC;
-  if (j0 < n) {
-    const Fe<F> z = arg_fe<F>(zarg);
-    for (uint32_t j = j0 + SC; j-- > j0;) {
-      if (j >= n) {                                         // the chunk that holds the end: zero coefficients above it
-        if (has_hv) acc = Fd::mul(acc, z);
-        continue;
+    for (int j = 0; j < F::N; ++j) {
+      const uint32_t t = (uint32_t)__shfl_down((int)incl.l[j], 1);
+      ex.l[j] = lane == 63 ? 0u : t;
+    }
+    __syncthreads();                                        // st, qsh, wsum complete
+    for (uint32_t w = wave + 1; w < NWAVE; ++w) ex = Fd::add(ex, load_limbs<F>(wsum + w * F::N));
+    Fe<F> acc = Fd::mul(Fd::add(ex, load_limbs<F>(qsh)), load_limbs<F>(zinv + (size_t)(tid + 1) * F::N));
+    const uint32_t j0 = e0 + tid * SC;
+    if (j0 < n) {
+      const Fe<F> z = arg_fe<F>(zarg);
+      for (uint32_t j = j0 + SC; j-- > j0;) {
+        if (j >= n) {                                       // the chunk that holds the end: zero coefficients above it,
+          if (has_hv) acc = Fd::mul(acc, z);                // and acc is zero up there without a carry
+          continue;
+        }
+        const uint32_t q = (j - e0) * 2 + tid;              // (j - e0) >> SC_LOG == tid
+        const uint4 lo = st[q], hi = st[q + 1];
+        const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        acc = Fd::add(Fd::from_words(w), Fd::mul(acc, z));
+        uint32_t o[8];
+        Fd::to_words(Fd::reduce(acc), o);
+        st[q] = make_uint4(o[0], o[1], o[2], o[3]);
+        st[q + 1] = make_uint4(o[4], o[5], o[6], o[7]);
       }
-      const uint32_t q = (j - e0) * 2 + tid;                // (j - e0) >> SC_LOG == tid
-      const uint4 lo = st[q], hi = st[q + 1];
-      const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-      acc = Fd::add(Fd::from_words(w), Fd::mul(acc, z));
-      uint32_t o[8];
-      Fd::to_words(Fd::reduce(acc), o);
-      st[q] = make_uint4(o[0], o[1], o[2], o[3]);
-      st[q + 1] = make_uint4(o[4], o[5], o[6], o[7]);
     }
   }
   __syncthreads();
-  uint4* gout = reinterpret_cast<uint4*>(S_base);
-  for (uint32_t i = tid; i < T * 2; i += TB) {
-    const uint32_t e = i >> 1;
-    if (e0 + e < n) gout[(size_t)(e0 + e) * 2 + (i & 1)] = st[i + (e >> SC_LOG)];
+  uint4* gout = reinterpret_cast<uint4*>(out);
+  if (!add) {
+    for (uint32_t i = tid; i < T * 2; i += TB) {
+      const uint32_t e = i >> 1;
+      if (e0 + e < n) gout[(size_t)(e0 + e) * 2 + (i & 1)] = st[i + (e >> SC_LOG)];
+    }
+    return;
+  }
+  // whole elements, 32 contiguous bytes per lane: the tile's part of `out` was written by the launch before this one
+#pragma unroll 2
+  for (uint32_t e = tid; e < T; e += TB) {
+    if (e0 + e >= n) break;
+    const size_t o = (size_t)(e0 + e) * 2;
+    const uint4 lo = st[e * 2 + (e >> SC_LOG)], hi = st[e * 2 + 1 + (e >> SC_LOG)], plo = gout[o], phi = gout[o + 1];
+    const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const uint32_t y[8] = {plo.x, plo.y, plo.z, plo.w, phi.x, phi.y, phi.z, phi.w};
+    uint32_t r[8];
+    Fd::to_words(Fd::reduce(Fd::add(Fd::from_words(x), Fd::from_words(y))), r);
+    gout[o] = make_uint4(r[0], r[1], r[2], r[3]);
+    gout[o + 1] = make_uint4(r[4], r[5], r[6], r[7]);
   }
 }
 
-// S_0 alone (the slice evaluation of a sharded open): H_0 + sum_k H_(1+k) W[k]
+// S_0 = H_0 + sum_k H_(1+k) W[k] from the aggregates of pass 1, to out_words; all TB threads of the workgroup call it
+template <class F, uint32_t TB>
+__device__ __forceinline__ void tile_store_s0(uint32_t ntiles, const uint32_t* H, const uint32_t* A, uint32_t nsuper,
+                                              const uint32_t* W, uint32_t* red, uint32_t* out_words) {
+  FrArg none{};
+  const Fe<F> q0 = tile_carry_sum<F, TB>(0, ntiles, H, A, nsuper, none, 0, W, red);
+  if (threadIdx.x == 0) store_words<F>(out_words, Field<F>::add(q0, load_limbs<F>(H)));
+}
+
+// S_0 alone (the slice evaluation of a sharded open)
 template <class F, uint32_t TB>
 __global__ __launch_bounds__(TB) void tile_eval_kernel(uint32_t ntiles, const uint32_t* H, const uint32_t* A,
                                                        uint32_t nsuper, const uint32_t* W, uint32_t* out_words) {
-  using Fd = Field<F>;
   __shared__ uint32_t red[(TB / 8 + TB / 64) * FRN];
-  FrArg none{};
-  const Fe<F> q0 = tile_carry_sum<F, TB>(0, ntiles, H, A, nsuper, none, 0, W, red);
-  if (threadIdx.x == 0) store_words<F>(out_words, Fd::add(q0, load_limbs<F>(H)));
+  tile_store_s0<F, TB>(ntiles, H, A, nsuper, W, red, out_words);
 }
 
 // =====================================================================================
 // The two passes for SEVERAL points at once (kzg_open_points, kzg_fr_poly_eval_batch):
 //   Q = sum_j Q_(z_j)[ sum_i w_ij p_i ],  Q_z[p] = (p - p(z)) / (X - z): the suffix values of the combination
 //   comb_j = sum_i w_ij p_i at z_j, added up over the points.
-// A launch takes up to MP points.  Pass 1 loads the (up to TILE_MAXK) coefficients of a position ONCE and forms every
-// comb_j from them, then runs the chunk / tile aggregates per point exactly as tile_combine_kernel does.  Pass 2 is one
-// launch per point, one after the other on the stream: each ADDS its point's suffix values into the one output vector
-// in place.  (A loop over the points inside one kernel was built first: every address derived from the thread index
-// became loop-invariant and stayed in registers across the body, 98-118 VGPRs against tile_fill_kernel's 71-84.)
+// A launch takes up to MP points.  Pass 1 (tile_combine_multi_kernel) differs from tile_combine_kernel in its
+// combination alone: it loads the (up to TILE_MAXK) coefficients of a position ONCE and forms every comb_j from them;
+// the tables, the chunk sums and the tile aggregates are the steps above (tile_table_entry, tile_chunk_sum,
+// tile_aggregate), taken per point.  Pass 2 is tile_fill_kernel itself, one launch per point, one after the other on
+// the stream: each but the call's first ADDS its point's suffix values into the one output vector in place.  (A loop
+// over the points inside one kernel was built first: every address derived from the thread index became loop-invariant
+// and stayed in registers across the body, 98-118 VGPRs against tile_fill_kernel's 71-84.)
 // The per-point tables (TileScanArgs, weights, z) do not fit the kernel arguments: they travel in a device buffer.
-// z_j = 0: the suffix values are comb_j itself; the point takes no part in the scan.
+// z_j = 0: the suffix values are comb_j itself; the point takes no part in the scan (tile_fill_kernel's `zero`).
 // =====================================================================================
 constexpr uint32_t MP = 3;            // points per launch: 9 VGPRs of combination and 9 KiB of chunk sums each (a
                                       // fourth takes the BLS12-381 kernel past 128 VGPRs: 3 waves per SIMD for 4)
@@ -415,7 +470,8 @@ struct MultiPolys {                   // the launch's polynomials: rows row[i] o
   uint32_t lens[TILE_MAXK];
   uint32_t row[TILE_MAXK];
 };
-struct MultiCarve {                   // the scan buffers of the launch's points (TileShape's carve, per point)
+struct MultiCarve {                   // the scan buffers of a launch's points as the kernel takes them: from the
+                                      // points' TileShapes (launch_tile_combine_multi)
   uint32_t *G[MP], *H[MP], *A[MP], *zinv[MP], *W[MP];
 };
 
@@ -457,15 +513,12 @@ __global__ __launch_bounds__(TB * SC / ITER) void tile_combine_multi_kernel(Mult
   __builtin_amdgcn_s_setprio(KZG_TILE_PRIO);
 #endif
   const uint32_t ntab = gridDim.x - ntiles;
-  if (blockIdx.x < ntab) {                                  // table workgroups, as in tile_combine_kernel
+  if (blockIdx.x < ntab) {                                  // table workgroups, for every point that is scanned
     if (blockIdx.y) return;
-    const uint32_t t = blockIdx.x * TK + tid;
 #pragma unroll 1
-    for (uint32_t j = 0; j < np; ++j) {
-      if (pts[j].zero) continue;
-      if (STORE && t <= TB) store_limbs<F>(cv.zinv[j] + (size_t)t * F::N, pow_from_generators<F>(pts[j].ts.ginv, t));
-      if (t < ntiles) store_limbs<F>(cv.W[j] + (size_t)t * F::N, pow_from_generators<F>(pts[j].ts.gw, t + 1));
-    }
+    for (uint32_t j = 0; j < np; ++j)
+      if (!pts[j].zero)
+        tile_table_entry<F, TB, STORE>(blockIdx.x * TK + tid, ntiles, pts[j].ts.ginv, pts[j].ts.gw, cv.zinv[j], cv.W[j]);
     return;
   }
   const uint32_t b = blockIdx.x - ntab, base = b * T;
@@ -513,118 +566,15 @@ __global__ __launch_bounds__(TB * SC / ITER) void tile_combine_multi_kernel(Mult
     for_points([&](auto jc) {
       constexpr uint32_t j = decltype(jc)::value;
       if (j >= np || pts[j].zero) return;
-      const Fe<F> e = Fd::mul(acc[j], load_limbs<F>(zsh + (j * SC + (tid & (SC - 1))) * F::N));    // 0 beyond the end
-      Fe<F> s;
-#pragma unroll
-      for (int q = 0; q < F::N; ++q) s.l[q] = lane8_sum(e.l[q]);
-      if ((tid & 7) == 0) store_limbs<F>(hs + (j * TB + (i >> 3)) * F::N, s);
+      tile_chunk_sum<F>(acc[j], load_limbs<F>(zsh + (j * SC + (tid & (SC - 1))) * F::N), hs + (j * TB + (i >> 3)) * F::N);
     });
   }
   __syncthreads();
 #pragma unroll 1
-  for (uint32_t j = 0; j < np; ++j) {
-    if (pts[j].zero) continue;
-    Fe<F> g = Fd::zero();
-    if (tid < TB) {                                                           // whole waves: TB is a multiple of 64
-      const Fe<F> hq = Fd::reduce_wide(Fd::carry(load_limbs<F>(hs + (j * TB + tid) * F::N)));
-      const Fe<F> zq = Fd::mul(load_limbs<F>(pts[j].ts.zq_lo + (tid & 15) * F::N),
-                               load_limbs<F>(pts[j].ts.zq_hi + (tid >> 4) * F::N));
-      g = Fd::mul(hq, zq);
-      if (STORE) store_limbs<F>(cv.G[j] + ((size_t)b * TB + tid) * F::N, g);
-    }
-    const Fe<F> hb = block_sum<F, TK>(g, red);
-    if (tid == 0) store_limbs<F>(cv.H[j] + ((size_t)(poly0 + blockIdx.y) * hstride + b) * F::N, hb);
-  }
-}
-
-// Pass 2 for ONE point of a launch: out (S_0, S_1, ..: n elements) += the suffix values of comb at z -- tile_fill_kernel
-// whose last step adds to what `out` holds (add = 0: writes, nothing earlier is there).  The points of a launch follow
-// each other on the stream, so that the sum needs neither a buffer per point nor a pass of its own.  zero: z = 0, the
-// suffix values are comb itself.
-template <class F, uint32_t TB>
-__global__ __launch_bounds__(TB) void tile_fill_add_kernel(const uint32_t* comb, uint32_t n, uint32_t ntiles,
-                                                           const uint32_t* G, const uint32_t* H, const uint32_t* A,
-                                                           uint32_t nsuper, FrArg zarg, uint32_t zero,
-                                                           const uint32_t* zinv, const uint32_t* W, uint32_t add,
-                                                           uint32_t* out) {
-  using Fd = Field<F>;
-  constexpr uint32_t T = TB * SC, NWAVE = TB / 64;
-  __shared__ uint4 st[T * 2 + TB];                          // 32 B per coefficient + one pad quad per chunk
-  __shared__ uint32_t red[(TB / 8 + TB / 64) * FRN];
-  __shared__ uint32_t wsum[NWAVE * FRN];
-  __shared__ uint32_t qsh[FRN];
-#if KZG_TILE_PRIO
-  __builtin_amdgcn_s_setprio(KZG_TILE_PRIO);
-#endif
-  const uint32_t tid = threadIdx.x, b = blockIdx.x, e0 = b * T;
-  const uint4* gin = reinterpret_cast<const uint4*>(comb);
-  for (uint32_t i = tid; i < T * 2; i += TB) {
-    const uint32_t e = i >> 1;
-    if (e0 + e < n) st[i + (e >> SC_LOG)] = gin[(size_t)(e0 + e) * 2 + (i & 1)];
-  }
-  if (!zero) {
-    FrArg none{};
-    const Fe<F> q0 = tile_carry_sum<F, TB>(b, ntiles, H, A, nsuper, none, 0, W, red);
-    if (tid == 0) store_limbs<F>(qsh, q0);
-    // suffix sums of the tile's scaled chunk values: inclusive inside the wave by shuffles, the waves above from LDS
-    const uint32_t lane = tid & 63, wave = tid >> 6;
-    Fe<F> incl = load_limbs<F>(G + ((size_t)b * TB + tid) * F::N);
-#pragma unroll 1
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      Fe<F> t;
-#pragma unroll
-      for (int j = 0; j < F::N; ++j) t.l[j] = (uint32_t)__shfl_down((int)incl.l[j], d);
-      const Fe<F> s = Fd::add(incl, t);
-      incl = Fd::select(lane + d < 64, s, incl);
-    }
-    if (lane == 0) store_limbs<F>(wsum + wave * F::N, incl);
-    Fe<F> ex;                                               // sum over the chunks after this one
-#pragma unroll
-    for (int j = 0; j < F::N; ++j) {
-      const uint32_t t = (uint32_t)__shfl_down((int)incl.l[j], 1);
-      ex.l[j] = lane == 63 ? 0u : t;
-    }
-    __syncthreads();                                        // st, qsh, wsum complete
-    for (uint32_t w = wave + 1; w < NWAVE; ++w) ex = Fd::add(ex, load_limbs<F>(wsum + w * F::N));
-    Fe<F> acc = Fd::mul(Fd::add(ex, load_limbs<F>(qsh)), load_limbs<F>(zinv + (size_t)(tid + 1) * F::N));
-    const uint32_t j0 = e0 + tid * SC;
-    if (j0 < n) {
-      const Fe<F> z = arg_fe<F>(zarg);
-      for (uint32_t j = j0 + SC; j-- > j0;) {
-        if (j >= n) continue;                               // the chunk that holds the end: acc is zero up there
-        const uint32_t q = (j - e0) * 2 + tid;              // (j - e0) >> SC_LOG == tid
-        const uint4 lo = st[q], hi = st[q + 1];
-        const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        acc = Fd::add(Fd::from_words(w), Fd::mul(acc, z));
-        uint32_t o[8];
-        Fd::to_words(Fd::reduce(acc), o);
-        st[q] = make_uint4(o[0], o[1], o[2], o[3]);
-        st[q + 1] = make_uint4(o[4], o[5], o[6], o[7]);
-      }
-    }
-  }
-  __syncthreads();
-  uint4* gout = reinterpret_cast<uint4*>(out);
-  if (!add) {
-    for (uint32_t i = tid; i < T * 2; i += TB) {
-      const uint32_t e = i >> 1;
-      if (e0 + e < n) gout[(size_t)(e0 + e) * 2 + (i & 1)] = st[i + (e >> SC_LOG)];
-    }
-    return;
-  }
-  // whole elements, 32 contiguous bytes per lane: the tile's part of `out` was written by the launch before this one
-#pragma unroll 2
-  for (uint32_t e = tid; e < T; e += TB) {
-    if (e0 + e >= n) break;
-    const size_t o = (size_t)(e0 + e) * 2;
-    const uint4 lo = st[e * 2 + (e >> SC_LOG)], hi = st[e * 2 + 1 + (e >> SC_LOG)], plo = gout[o], phi = gout[o + 1];
-    const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const uint32_t y[8] = {plo.x, plo.y, plo.z, plo.w, phi.x, phi.y, phi.z, phi.w};
-    uint32_t r[8];
-    Fd::to_words(Fd::reduce(Fd::add(Fd::from_words(x), Fd::from_words(y))), r);
-    gout[o] = make_uint4(r[0], r[1], r[2], r[3]);
-    gout[o + 1] = make_uint4(r[4], r[5], r[6], r[7]);
-  }
+  for (uint32_t j = 0; j < np; ++j)
+    if (!pts[j].zero)
+      tile_aggregate<F, TB, TK, STORE>(hs + j * TB * F::N, pts[j].ts.zq_lo, pts[j].ts.zq_hi, b, cv.G[j],
+                                       cv.H[j] + ((size_t)(poly0 + blockIdx.y) * hstride + b) * F::N, red);
 }
 
 // The values of a batched evaluation from the aggregates of pass 1: one workgroup per (polynomial, point).
@@ -638,7 +588,6 @@ template <class F, uint32_t TB>
 __global__ __launch_bounds__(TB) void tile_eval_batch_kernel(EvalBatchArgs a, uint32_t k, const uint32_t* H,
                                                              uint32_t hstride, const uint32_t* W, uint32_t wstride,
                                                              uint32_t npts, uint32_t* out_words) {
-  using Fd = Field<F>;
   __shared__ uint32_t red[(TB / 8 + TB / 64) * FRN];
   const uint32_t i = blockIdx.x, j = blockIdx.y, len = a.lens[i], slot = a.slot[j];
   uint32_t* o = out_words + ((size_t)i * npts + j) * 8;
@@ -648,9 +597,7 @@ __global__ __launch_bounds__(TB) void tile_eval_batch_kernel(EvalBatchArgs a, ui
   }
   const uint32_t ntiles = (len + TB * SC - 1) / (TB * SC);
   const uint32_t* Hij = H + ((size_t)slot * k + i) * hstride * F::N;
-  FrArg none{};
-  const Fe<F> q0 = tile_carry_sum<F, TB>(0, ntiles, Hij, nullptr, 0, none, 0, W + (size_t)slot * wstride * F::N, red);
-  if (threadIdx.x == 0) store_words<F>(o, Fd::add(q0, load_limbs<F>(Hij)));
+  tile_store_s0<F, TB>(ntiles, Hij, nullptr, 0, W + (size_t)slot * wstride * F::N, red, o);
 }
 
 // Buffer layout of poly_tmp[0] (canonical words, 8 per element), cap = n + 1:
@@ -790,6 +737,12 @@ int launch_lincomb(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_t k
   return KZG_HIP_RC(c, hipGetLastError());
 }
 
+// the aggregates of groups of 64 tiles, where the scan sums in two levels (after pass 1: reads H and W)
+template <class F>
+int launch_tile_group(Ctx* c, const TileShape& s) {
+  if (s.nsuper) hipLaunchKernelGGL(tile_group_kernel<F>, dim3(s.nsuper), dim3(64), 0, c->stream, s.H, s.W, s.ntiles, s.A);
+  return KZG_HIP_RC(c, hipGetLastError());
+}
 // pass 1: combination + chunk / tile aggregates + tables.  STORE = false: the aggregates and tables alone.
 template <class F, uint32_t TB, bool STORE = true>
 int launch_tile_combine(Ctx* c, const TileShape& s, const TilePass1& p, const TileLincomb& la, uint32_t* d_comb) {
@@ -797,8 +750,7 @@ int launch_tile_combine(Ctx* c, const TileShape& s, const TilePass1& p, const Ti
                      dim3(TB * SC / TILE_ITER), 0, c->stream, la, p.ts, d_comb, (uint32_t)s.n, s.ntiles,
                      STORE ? s.G : (uint32_t*)nullptr, s.H, s.zinv, s.W);
   KZG_HIP(c, hipGetLastError());
-  if (s.nsuper) hipLaunchKernelGGL(tile_group_kernel<F>, dim3(s.nsuper), dim3(64), 0, c->stream, s.H, s.W, s.ntiles, s.A);
-  return KZG_HIP_RC(c, hipGetLastError());
+  return launch_tile_group<F>(c, s);
 }
 // pass 1 of an opening.  More than TILE_MAXK polynomials are combined first and pass 1 then runs over the combination
 // itself (weight one).
@@ -811,14 +763,16 @@ int launch_open_combine(Ctx* c, const TileShape& s, const TilePass1& p, const ui
   return rc ? rc : launch_tile_combine<F, TB>(c, s, p, lincomb_of_one<F>(d_comb, s.n), d_comb);
 }
 
-// pass 2.  hv: the aggregate of a virtual tile above the last one (sharded open), or null
+// pass 2.  hv: the aggregate of a virtual tile above the last one (sharded open), or null.  zero: s.z is 0 and d_S
+// takes d_comb as it is; add: d_S keeps what it holds and the suffix values are added to it (kzg_open_points).
 template <class F, uint32_t TB>
-int launch_tile_fill(Ctx* c, const TileShape& s, const uint32_t* d_comb, const FrArg* hv, uint32_t* d_S) {
+int launch_tile_fill(Ctx* c, const TileShape& s, const uint32_t* d_comb, const FrArg* hv, uint32_t* d_S,
+                     bool zero = false, bool add = false) {
   FrArg none{}, z;
   memcpy(z.l, s.z, sizeof(z.l));
   hipLaunchKernelGGL((tile_fill_kernel<F, TB>), dim3(s.ntiles), dim3(TB), 0, c->stream, d_comb, (uint32_t)s.n, s.ntiles,
                      s.G, s.H, s.nsuper ? s.A : (const uint32_t*)nullptr, s.nsuper, hv ? *hv : none, hv ? 1u : 0u, z,
-                     s.zinv, s.W, d_S);
+                     zero ? 1u : 0u, s.zinv, s.W, add ? 1u : 0u, d_S);
   return KZG_HIP_RC(c, hipGetLastError());
 }
 
@@ -969,6 +923,24 @@ int open_shard_finish_t(Ctx* c, const uint32_t* z_words, const uint32_t* carry_w
   return KZG_OK;
 }
 
+// pass 1 for the np <= MP points whose scan buffers are shapes[0 .. np) and whose tables are d_pts[0 .. np): the
+// opening's form (STORE: d_comb takes the np combinations, comb_stride elements apart) or the evaluation's (one
+// polynomial per blockIdx.y; its aggregates to H[(poly0 + y) * hstride ..]).  ntab = 0: the tables are there already.
+template <class F, uint32_t TB, bool STORE>
+int launch_tile_combine_multi(Ctx* c, const TileShape* shapes, uint32_t np, uint32_t ntab, const MultiPolys& polys,
+                              const MultiPoint* d_pts, uint32_t* d_comb, size_t comb_stride, uint32_t poly0,
+                              uint32_t hstride) {
+  MultiCarve cv{};
+  for (uint32_t q = 0; q < np; ++q) {
+    const TileShape& s = shapes[q];
+    cv.G[q] = s.G, cv.H[q] = s.H, cv.A[q] = s.A, cv.zinv[q] = s.zinv, cv.W[q] = s.W;
+  }
+  hipLaunchKernelGGL((tile_combine_multi_kernel<F, TB, TILE_ITER, STORE>), dim3(shapes[0].ntiles + ntab, STORE ? 1 : polys.k),
+                     dim3(TB * SC / TILE_ITER), 0, c->stream, polys, d_pts, np, cv, d_comb, (uint64_t)comb_stride,
+                     (uint32_t)shapes[0].n, shapes[0].ntiles, poly0, hstride);
+  return KZG_HIP_RC(c, hipGetLastError());
+}
+
 // a point's tables (z != 0) for tiles of tb threads; weights and groups are the launch's to fill
 template <class F>
 MultiPoint multi_point(const uint32_t* z_words, uint32_t tb) {
@@ -1013,19 +985,17 @@ int open_points_quotient_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, 
   }
   const OpenBufs bufs = claim_open_bufs(c);
   const uint32_t tb = open_tile_threads(c);
-  TileShape s0;
+  TileShape shapes[MP];                          // the scan of a launch's q-th point; its z is the launch's to fill
   uint32_t ntab = 0;
-  tile_counts(c, n, tb, &s0, &ntab);
-  const size_t cap = n + 1, scan_words = tile_carve(&s0, nullptr, true);
+  tile_counts(c, n, tb, &shapes[0], &ntab);
+  const size_t cap = n + 1, scan_words = tile_carve(&shapes[0], nullptr, true);
   if ((rc = ensure_buf(c, bufs.vec, (MP + 1) * cap * 32))) return rc;
   if ((rc = ensure_buf(c, bufs.scan, MP * scan_words * 4))) return rc;
   uint32_t* d_S = static_cast<uint32_t*>(bufs.vec.p);
   uint32_t* d_comb = d_S + cap * 8;
-  MultiCarve cv{};
   for (uint32_t q = 0; q < MP; ++q) {
-    TileShape s = s0;
-    tile_carve(&s, static_cast<uint32_t*>(bufs.scan.p) + q * scan_words, true);
-    cv.G[q] = s.G, cv.H[q] = s.H, cv.A[q] = s.A, cv.zinv[q] = s.zinv, cv.W[q] = s.W;
+    shapes[q] = shapes[0];
+    tile_carve(&shapes[q], static_cast<uint32_t*>(bufs.scan.p) + q * scan_words, true);
   }
   std::vector<MultiPoint> proto;
   for (uint32_t j : pj) proto.push_back(multi_point<F>(points + (size_t)j * 8, tb));
@@ -1063,26 +1033,16 @@ int open_points_quotient_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, 
     ProfScope ps(c, "open_points_poly");
     for (size_t l = 0; l < launches.size() && !rc; ++l) {
       const Launch& L = launches[l];
+      const MultiPoint* pts = &table[L.first];
       rc = by_tile_width(tb, [&](auto w) {
-        constexpr uint32_t TB = decltype(w)::value;
-        hipLaunchKernelGGL((tile_combine_multi_kernel<F, TB, TILE_ITER, true>), dim3(s0.ntiles + ntab),
-                           dim3(TB * SC / TILE_ITER), 0, c->stream, L.polys, d_table + L.first, L.np, cv, d_comb,
-                           (uint64_t)cap, (uint32_t)n, s0.ntiles, 0u, 0u);
-        KZG_HIP(c, hipGetLastError());
-        for (uint32_t q = 0; q < L.np && s0.nsuper; ++q)
-          if (!table[L.first + q].zero)
-            hipLaunchKernelGGL(tile_group_kernel<F>, dim3(s0.nsuper), dim3(64), 0, c->stream, cv.H[q], cv.W[q], s0.ntiles,
-                               cv.A[q]);
-        for (uint32_t q = 0; q < L.np; ++q) {      // one after the other: each adds to what the one before left
-          const MultiPoint& m = table[L.first + q];
-          FrArg z;
-          memcpy(z.l, m.z, sizeof(z.l));
-          hipLaunchKernelGGL((tile_fill_add_kernel<F, TB>), dim3(s0.ntiles), dim3(TB), 0, c->stream,
-                             d_comb + q * cap * 8, (uint32_t)n, s0.ntiles, cv.G[q], cv.H[q],
-                             s0.nsuper ? cv.A[q] : (const uint32_t*)nullptr, s0.nsuper, z, m.zero, cv.zinv[q], cv.W[q],
-                             (l || q) ? 1u : 0u, d_S);
+        int r = launch_tile_combine_multi<F, w, true>(c, shapes, L.np, ntab, L.polys, d_table + L.first, d_comb, cap, 0, 0);
+        for (uint32_t q = 0; q < L.np && !r; ++q)
+          if (!pts[q].zero) r = launch_tile_group<F>(c, shapes[q]);
+        for (uint32_t q = 0; q < L.np && !r; ++q) {      // one after the other: each adds to what the one before left
+          memcpy(shapes[q].z, pts[q].z, sizeof(pts[q].z));
+          r = launch_tile_fill<F, w>(c, shapes[q], d_comb + q * cap * 8, nullptr, d_S, pts[q].zero, l || q);
         }
-        return KZG_HIP_RC(c, hipGetLastError());
+        return r;
       });
     }
     if (rc) return rc;
@@ -1668,20 +1628,20 @@ int poly_eval_batch_t(Ctx* c, const uint32_t* d_polys, const size_t* lens, size_
     if (nz) KZG_HIP(c, hipMemcpyAsync(d_table, table.data(), nz * sizeof(MultiPoint), hipMemcpyHostToDevice, c->stream));
     for (size_t j0 = 0; j0 < nz; j0 += MP) {
       const uint32_t np = (uint32_t)std::min<size_t>(MP, nz - j0);
-      MultiCarve cv{};
+      TileShape shapes[MP];                        // no chunk values, no groups: H per (point, polynomial), W per point
       for (uint32_t q = 0; q < np; ++q) {
-        cv.H[q] = d_H + (j0 + q) * k * hstride * F::N;
-        cv.W[q] = d_W + (j0 + q) * wstride * F::N;
+        shapes[q] = s0;
+        shapes[q].H = d_H + (j0 + q) * k * hstride * F::N;
+        shapes[q].W = d_W + (j0 + q) * wstride * F::N;
       }
       for (size_t i0 = 0; i0 < k; i0 += TILE_MAXK) {
         MultiPolys mp{};
         mp.polys = d_polys, mp.stride = stride, mp.k = (uint32_t)std::min<size_t>(TILE_MAXK, k - i0);
         for (uint32_t q = 0; q < mp.k; ++q) mp.row[q] = (uint32_t)(i0 + q), mp.lens[q] = ea.lens[i0 + q];
         // the W tables come from the first launch of a group of points
-        hipLaunchKernelGGL((tile_combine_multi_kernel<F, TB, TILE_ITER, false>), dim3(s0.ntiles + (i0 ? 0 : ntab), mp.k),
-                           dim3(TB * SC / TILE_ITER), 0, c->stream, mp, d_table + j0, np, cv, (uint32_t*)nullptr,
-                           (uint64_t)0, (uint32_t)n, s0.ntiles, (uint32_t)i0, hstride);
-        KZG_HIP(c, hipGetLastError());
+        if ((rc = launch_tile_combine_multi<F, TB, false>(c, shapes, np, i0 ? 0 : ntab, mp, d_table + j0, nullptr, 0,
+                                                          (uint32_t)i0, hstride)))
+          return rc;
       }
     }
     hipLaunchKernelGGL((tile_eval_batch_kernel<F, TB>), dim3((uint32_t)k, (uint32_t)t), dim3(TB), 0, c->stream, ea,

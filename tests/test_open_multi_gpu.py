@@ -123,6 +123,37 @@ def test_open_points_and_eval_batch_at_the_scan_edges(envs, curve, tb):
         ctx.set_tuning("open_tile_threads", 0)
 
 
+@pytest.mark.parametrize("tb", [0, 128])
+@pytest.mark.parametrize("curve", CURVES)
+def test_open_points_with_a_zero_point_first(envs, curve, tb):
+    """z = 0 where shapes() never puts it, in the kernel the plain opening runs too: the call's only point (the fill
+    copies the combination and writes), and the first point both of the call and of its second launch of 3 points (there
+    the fill copies and adds to what the first launch left).  k = 2, every weight non-zero, so that no point drops out;
+    n = 9 ends inside a chunk, n = T + 1 has a second tile of one coefficient.  The quotient coefficient by
+    coefficient against the exact restatement."""
+    env = envs[curve]
+    native, ctx, r = env.native, env.ctx, env.r
+    T = 1024 if tb == 128 else 2048
+    rng = random.Random(123 + tb)
+    try:
+        ctx.set_tuning("open_tile_threads", tb)
+        for n in (9, T + 1):
+            polys = [[rng.randrange(r) for _ in range(n)], [r - 1] * (n - 2)]
+            d, dl, stride = upload(native, polys, extra_rows=1, pad=3)
+            for t in (1, 4):
+                points = [rng.randrange(1, r) for _ in range(t)]
+                points[0] = points[-1] = 0
+                weights = [[rng.randrange(1, r) for _ in range(t)] for _ in polys]
+                want = quotient_points(polys, points, weights, r)
+                xy, inf = ctx.open_points(env.key, d.data_ptr(), dl, stride, points, weights,
+                                          d_quot=d.data_ptr() + 2 * stride * 32, device=True)
+                assert row_ints(native, d, 2, n - 1) == want, ("quotient", n, t)
+                assert row_ints(native, d, 2, stride)[n - 1:] == [0] * (stride - n + 1), ("beyond the quotient", n, t)
+                assert env.point(xy, inf) == env.commitment(want), ("point", n, t)
+    finally:
+        ctx.set_tuning("open_tile_threads", 0)
+
+
 @pytest.mark.parametrize("curve", CURVES)
 def test_open_points_host_twin_and_empty_inputs(envs, curve):
     env = envs[curve]
