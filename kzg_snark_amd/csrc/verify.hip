@@ -21,6 +21,8 @@
 //             a carry.  sum_s 2^(s (win_bits - 1)) P_s is finished on the host.
 //   short     [T(tau)] is a commit of l scalars against the monomial key, the commitment term a commit of n_comm
 //             scalars against a key loaded from the commitments.
+//   plan      tile size and count, the grid cap, the threads of the column sum, the shares of a commitment sum and the
+//             slices are decided in one place, VerPlan (ver_layout.h), which the host tests read through their shim.
 // Fr kernels: <= 128 VGPRs, no scratch; elements travel as 8 canonical words (values in standard form, table entries
 // and factors in Montgomery form, so a product of the two is in standard form again).
 #include <cstring>
@@ -36,10 +38,6 @@
 namespace kzg {
 
 namespace {
-
-constexpr uint32_t VER_MIN_TILE_LOG = 8;                        // ver_cell_kernel: tile of max(l, 256) elements
-constexpr uint32_t VER_SUM_THREADS = 1u << 15;                  // ver_colsum_kernel: threads (a multiple of every l)
-constexpr uint32_t VER_COMM_SPLIT = 64;                         // ver_commsum_kernel: workgroups per commitment when few
 
 // r_k = rho^(k+1) and s_k = r_k w^(i_k l), canonical words
 template <class F>
@@ -232,20 +230,22 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
     if (coset_idx[k] >= n_cosets) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: coset index out of range");
   if (k_bad < K) return set_err(c, KZG_ERR_ARG, "kzg_verify_cosets: commitment index out of range");
 
-  const size_t M = K << log_l, rb = srs_rec_bytes(c->curve);
-  const uint32_t log_e = std::max(log_l, VER_MIN_TILE_LOG);
-  const uint32_t sum_threads = std::max<uint32_t>((uint32_t)l, VER_SUM_THREADS);
+  Srs pv;                                            // the proofs as a key of one window; its records after the carve
+  srs_window0_view(c, nullptr, K, &pv);
+  const VerPlan plan(K, log_l, n_comm, (uint32_t)pv.win_bits, F::BITS);
+  const size_t M = plan.M, rb = srs_rec_bytes(c->curve);
   VerifyWs d;
   uint32_t* d_cells = nullptr;                       // the cells as bytes and their verdict, behind the pinned layout
   uint8_t* d_status = nullptr;
   size_t total = 0;
   int rc = carve(c, c->ver_tmp, [&](Carve& ws) {
-    d.layout(ws, K, n_comm, l, proof_inf != nullptr, comm_inf != nullptr, PT_BYTES, rb, POW_TAB, sum_threads,
-             ver_commsum_shares(n_comm));
+    d.layout(ws, K, n_comm, l, proof_inf != nullptr, comm_inf != nullptr, PT_BYTES, rb, POW_TAB, plan.sum_threads,
+             plan.shares);
     d_cells = ws.take_if<uint32_t>(claims.cells != nullptr, M * 32);
     d_status = ws.take_if(claims.cells != nullptr, K);
   }, &total);
   if (rc) return rc;
+  pv.recs = d.recs;
 
   SrsPtr cs;                                         // the commitments as a key of their own (all windows)
   if ((rc = srs_create(c, n_comm, &cs))) return rc;
@@ -290,26 +290,21 @@ int verify_cosets_t(Ctx* c, const Srs* mono, uint32_t log_N, uint32_t log_l, con
   hipLaunchKernelGGL(ver_weights_kernel<F>, k_grid, dim3(256), 0, st, (uint32_t)K, log_l, d.cidx, d.wtab, d.rtab, d.r,
                      d.s);
   KZG_HIP(c, hipGetLastError());
-  const size_t lds_bytes = (size_t)32 << log_e;
-  if (lds_bytes > 64 * 1024 && !c->ver_lds_attr_set) {   // > 64 KiB of dynamic LDS (gfx950: 160 KiB per CU); per device
+  if (plan.lds_bytes > 64 * 1024 && !c->ver_lds_attr_set) {   // > 64 KiB of dynamic LDS (gfx950: 160 KiB per CU); per device
     KZG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(ver_cell_kernel<F>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     c->ver_lds_attr_set = 1;
   }
-  const size_t ntiles = (M + ((size_t)1 << log_e) - 1) >> log_e;
-  hipLaunchKernelGGL(ver_cell_kernel<F>, dim3((uint32_t)std::min<size_t>(ntiles, 4096)), dim3(256), lds_bytes, st,
-                     (uint32_t)K, log_l, log_N, log_e, d.cidx, d.wtab, d.rtab, fr_arg<F>(Fd::reduce(inv_pow2<F>(log_l))),
-                     d.vals);
-  hipLaunchKernelGGL(ver_colsum_kernel<F>, dim3(sum_threads / 256), dim3(256), 0, st, M, d.vals, d.part);
-  hipLaunchKernelGGL(ver_colsum_final_kernel<F>, dim3((uint32_t)l), dim3(64), 0, st, (uint32_t)l,
-                     sum_threads >> log_l, d.part, d.T);
+  hipLaunchKernelGGL(ver_cell_kernel<F>, dim3(plan.cell_grid), dim3(256), plan.lds_bytes, st, (uint32_t)K, log_l, log_N,
+                     plan.log_e, d.cidx, d.wtab, d.rtab, fr_arg<F>(Fd::reduce(inv_pow2<F>(log_l))), d.vals);
+  hipLaunchKernelGGL(ver_colsum_kernel<F>, dim3(plan.sum_threads / 256), dim3(256), 0, st, M, d.vals, d.part);
+  hipLaunchKernelGGL(ver_colsum_final_kernel<F>, dim3((uint32_t)l), dim3(64), 0, st, (uint32_t)l, plan.sum_cnt, d.part,
+                     d.T);
   KZG_HIP(c, hipGetLastError());
   if ((rc = ver_commitment_sums(c, d.r, d.perm, d.off, n_comm, d.cpart, d.coef))) return rc;
 
   // ---- the MSMs: 2 x ns slice vectors over the proofs, T over the key, the weights over the commitments
-  Srs pv;
-  srs_window0_view(c, d.recs, K, &pv);
-  const uint32_t sb = (uint32_t)pv.win_bits - 1, ns = (F::BITS + sb - 1) / sb;
+  const uint32_t sb = plan.slice_bits, ns = plan.slices;
   std::vector<uint64_t> h_xy((size_t)(2 * ns + 2) * PW64);
   std::vector<uint8_t> h_inf(2 * ns + 2);
   for (uint32_t v = 0; v < 2 && rc == KZG_OK; ++v) {
@@ -361,7 +356,7 @@ int column_sums_t(Ctx* c, uint32_t cols, uint32_t cnt, const uint32_t* d_part, u
 
 }  // namespace
 
-size_t ver_commsum_shares(size_t n_comm) { return n_comm >= VER_COMM_SPLIT ? 1 : VER_COMM_SPLIT; }
+size_t ver_commsum_shares(size_t n_comm) { return ver_shares(n_comm); }
 int ver_commitment_sums(Ctx* c, const uint32_t* d_r, const uint32_t* d_perm, const uint32_t* d_off, size_t n_comm,
                         uint32_t* d_cpart, uint32_t* d_coef) {
   return KZG_BY_FR(c, commitment_sums_t, c, d_r, d_perm, d_off, n_comm, d_cpart, d_coef);

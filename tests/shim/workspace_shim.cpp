@@ -1,7 +1,9 @@
 // csrc/devmem.h and csrc/ver_layout.h on the CPU: a program of its own over a counting hipMalloc / hipFree defined
 // here (no HIP library is linked).  Without arguments it checks the owners, the carve and the counting sort and
 // prints "no violations"; `verify ...` / `points ...` print the offsets of one workspace layout for the sizes given
-// (tests/test_workspace_host.py compares them with the arithmetic restated there).
+// (tests/test_workspace_host.py compares them with the arithmetic restated there); `plan ...` prints the launch plan
+// of kzg_verify_cosets (VerPlan) for one call (tests/test_verify_scalars_host.py: each shape of the exact-point tests
+// reaches the regime it is there for).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -166,7 +168,14 @@ int main(int argc, char** argv) {
     });
   }
 #undef P
-  if (argc != 1) { printf("usage: workspace_shim [verify ... | points ...]\n"); return 2; }
+  if (argc == 7 && !strcmp(argv[1], "plan")) {           // K log_l n_comm win_bits fr_bits: "name value" per field
+    const VerPlan p(v[0], (uint32_t)v[1], v[2], (uint32_t)v[3], (uint32_t)v[4]);
+    printf("M %zu\nlog_e %u\nntiles %zu\nlds_bytes %zu\ncell_grid %u\nsum_threads %u\nsum_cnt %u\nshares %u\n"
+           "slice_bits %u\nslices %u\n", p.M, p.log_e, p.ntiles, p.lds_bytes, p.cell_grid, p.sum_threads, p.sum_cnt,
+           p.shares, p.slice_bits, p.slices);
+    return 0;
+  }
+  if (argc != 1) { printf("usage: workspace_shim [verify ... | points ... | plan ...]\n"); return 2; }
   check_owners();
   check_carve();
   check_sort();
