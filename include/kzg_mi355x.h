@@ -630,7 +630,8 @@ int kzg_blob_challenges_device(kzg_ctx* ctx, uint32_t log_n, const void* d_blobs
  * What the reference's callers do with Sage's dense polynomials between the transforms and the
  * commitments (plonk/prover.py:243-316: accumulator ratios, products, division by Z_H on a coset),
  * as passes over device-resident vectors of canonical 32-byte elements.  All enqueue on the context's
- * stream; out may alias an input for the element-wise ones.
+ * stream; out may alias an input for the element-wise ones (vec_op, vec_lincomb, vec_mul_powers,
+ * vec_inverse: the same pointer, not a partial overlap).  vec_prefix_product: out must not overlap d_a.
  *   vec_op          out[i] = a[i] (+ | - | *) b[i]            op: 0 add, 1 sub, 2 mul
  *   vec_lincomb     out[i] = sum_j scalars[j] * p_j[i]         (p_j of lens[j] < n read as zero-padded)
  *   vec_mul_powers  out[i] = a[i] * c0 * s^i                   (coset shift of a coefficient vector)

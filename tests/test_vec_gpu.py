@@ -48,7 +48,10 @@ def test_vector_primitives(native, curve, n):
     ctx.vec_inverse(n, inpl.data_ptr(), inpl.data_ptr())
     ctx.synchronize()
     assert host(native, inpl) == [pow(x, -1, r) if x else 0 for x in a]
-    if n >= 33:                                            # a whole chunk of zeros, and zeros at chunk borders
+    if n >= 33:                                            # zeros in many batches: the batch kernel strides, so the
+                                                           # elements 0 .. 32 are the FIRST elements of 33 different
+                                                           # threads, never a whole batch of several.  Whole batches
+                                                           # of zeros: tests/test_vec_edges_gpu.py, test_inverse_batches
         az = list(a)
         for i in list(range(0, 32)) + [32, n - 1]:
             az[i] = 0
